@@ -2,8 +2,13 @@
 """bench.py -- the headline measurement: cell.direction.frequency updates/s of one diffuse-transfer
 iteration on a 256^3 uniform grid, and the sweep kernel's achieved fraction of the HBM roofline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 256] [--nnu 8] [--ndir 96]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 256] [--nnu 8] [--ndir 96] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times K steps and prints the line.  --full adds what takes time of its own beyond the
+timed steps: the CPU baseline below.  --dump-outputs DIR writes, after the timed steps, the J of the last step as
+DIR/J.npy (DIR/J_rank<r>.npy per rank for N > 1): float64 [groups][cells], the whole array where it fits in 32 MB, else
+the same seeded sample of cells every run (sorted, at most 32 MB), so that two builds can be compared output for output.
 
 A step is one full source iteration of the hot path on inputs already resident in HBM:
 new opacities are handed to the library (device-to-device, including the two layout transposes the
@@ -29,7 +34,8 @@ reduce-scatter over the direction slices comes first).  --exchange gather assemb
 The JSON line also carries
   roofline    : sweep kernel: `achieved` = algorithmic bytes (24 B per update) / HIP-event time of its launches; `frac` = HBM bytes the
                 counters saw (a committed --measure-traffic record of the same configuration) / the same time / peak
-  cpu_baseline: the reference's own compiled transport (oracle/_ref) or the C oracle, on the host cores
+  cpu_baseline: the reference's own compiled transport (oracle/_ref) or the C oracle, on the host cores (--full only)
+The roofline figures come from the timed steps' own launch records and a committed counter record: a plain run has them too.
 """
 from __future__ import annotations
 
@@ -93,7 +99,37 @@ def parse():
                     help="collect this configuration's HBM traffic and SQ counters with rocprofv3 --pmc passes of this script (child "
                          "processes, a few minutes) and write profiles/pmc_traffic.json, which later runs of the same configuration quote")
     ap.add_argument("--cpu-n", type=int, default=0, help="grid size of the CPU sample (default: --n)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what a plain run leaves out: the CPU baseline (minutes of host work)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's J (or a fixed, seeded sample of its cells) as DIR/*.npy")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+DUMP_BYTES = 32 << 20   # per array written by --dump-outputs
+DUMP_SEED = 20240611    # the cells sampled from an output too large to write whole
+
+
+def dump_outputs(directory, arrays):
+    """arrays: name -> [rows][cells] float64 (torch tensor, on any device, or ndarray).  An array larger than DUMP_BYTES is cut to
+    the same seeded, sorted choice of cells (columns) for a given shape, so that two runs or two builds line up cell for cell."""
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in arrays.items():
+        rows, cols = arr.shape
+        keep = max(1, DUMP_BYTES // (8 * rows))
+        if cols > keep:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(cols, size=keep, replace=False))
+            if isinstance(arr, np.ndarray):
+                arr = arr[:, idx]
+            else:
+                import torch
+                arr = arr.index_select(1, torch.from_numpy(idx).to(arr.device))
+        if not isinstance(arr, np.ndarray):
+            arr = arr.cpu().numpy()
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 def directions(total: int):
@@ -234,6 +270,8 @@ def in_process(a):
     for _ in range(a.steps):
         eng.iterate_into(kappa, phi, theta, w, uvb, J)
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"J": J})
     out = {"metric": "cell·dir·ν updates/sec per iteration through the host-array boundary (PCIe-inclusive), one process over N devices",
            "value": n ** 3 * nnu * a.ndir * a.steps / elapsed, "unit": "updates/s", "n_gpus": nd, "steps": a.steps, "warmup": a.warmup,
            "ms_per_step": elapsed / a.steps * 1e3, "higher_is_better": True, "scaling": "strong", "dtype": "f64", "data": "synthetic",
@@ -343,16 +381,19 @@ def main():
         eng.transport_device(phi, theta, w, uvb, J.data_ptr(), stream)
         if timed:
             ev[1].record()
+        result = J   # what the caller of a step holds at its end
         if world > 1:
             Jx = J.cpu() if a.rehearse_on_one_gpu else J   # rehearsal: gloo moves host tensors
             if shard is None:
                 dist.all_reduce(Jx)
+                result = Jx
             elif a.exchange == "gather":
-                shard.combine(Jx, out=None if a.rehearse_on_one_gpu else J_full)
+                result = shard.combine(Jx, out=None if a.rehearse_on_one_gpu else J_full)
             else:
-                shard.exchange(Jx)
+                result = shard.exchange(Jx)
         if timed:
             ev[2].record()
+        return result
 
     def fence():
         if world > 1:
@@ -365,7 +406,7 @@ def main():
     launch_ms, launch_updates, compute_ms, collective_ms = 0.0, 0, 0.0, 0.0
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        step(timed=True)
+        result = step(timed=True)
         # the launch records of a sweep are read after the sweep has drained; the next sweep starts with a stream
         # synchronise anyway (it rewrites device tables), so this adds no bubble of its own
         torch.cuda.synchronize()
@@ -380,6 +421,8 @@ def main():
         t = torch.tensor([elapsed, compute_ms, collective_ms], dtype=torch.float64, device="cpu" if a.rehearse_on_one_gpu else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, compute_ms, collective_ms = (float(x) for x in t.tolist())
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"J" if world == 1 else f"J_rank{rank}": result})
 
     updates_per_step = ncell * total_dirs * nnu
     value = updates_per_step * a.steps / elapsed
@@ -431,7 +474,7 @@ def main():
                              "(traffic; FETCH_SIZE doubled per the guide, + WRITE_SIZE) / the same HIP-event time: what the memory "
                              "system delivered.  null where no committed counter pass matches this configuration (options, sharding)."},
     }
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cn = a.cpu_n or n
         if cn == n:
             k3 = kappa_host[:3]

@@ -31,7 +31,9 @@ def test_library_exports_every_declared_symbol(rt):
     from radiativetransfer_amd import _lib
     names = header_functions()
     assert len(names) >= 19
-    lib = C.CDLL(_lib.LIB_PATH)
+    # through the package's loader: a bare CDLL here would map the system HIP runtime ahead of torch's, and every later test
+    # in this process that opens a device would find none
+    lib = _lib.load()
     for name in names:
         assert hasattr(lib, name), f"libftte.so does not export {name}"
     # and the Python binding table covers exactly the header

@@ -91,40 +91,26 @@ def test_config1_plumbing_case_bitwise(golden):
     assert np.array_equal(J, g["J"])
 
 
-def test_lifted_driver_and_restated_driver_agree(tmp_path):
+def test_lifted_driver_and_restated_driver_agree(golden):
     """oracle/_ref/ref_harness has two routes through a direction: the reference's own driver lines lifted from
     equiSources.f90:1393-1801 (what every golden is made with), and ref_harness.f90's own sequence of the same steps.  Same
-    bits, on a uniform and on a refined cell array -- wherever the harness binary exists (it is built from /root/reference)."""
+    bits, on a uniform and on a refined cell array: both routes' J as the harness gave them (tests/golden/driver_routes.npz,
+    tests/golden/make_golden_routes.py), and -- wherever the harness binary has been built -- as it gives them again."""
     import os
-    import struct
-    import subprocess
-    from radiativetransfer_amd import synthetic
-    harness = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "ref_harness")
-    if not os.path.exists(harness):
-        pytest.skip("oracle/_ref/ref_harness has not been built here")
-    phi, theta, w = O.healpix_directions(2)
-    uvb = synthetic.frequency_groups(3)[2]
-    cases = []
-    kap, _, _ = synthetic.uniform_workload(12, 3, seed=8, tau_median=0.4)
-    cases.append((12, np.zeros(12 ** 3, np.int32), kap))
-    level = synthetic.refine_levels(6, [(2, 2, 3), (5, 1, 4)], depth=2)
-    cases.append((6, level, 2.0 * synthetic.frequency_groups(3)[1][:, None] * synthetic.lognormal_density(len(level), seed=3)[None, :]))
-    for n, level, kappa in cases:
-        out = []
-        for flag in (16, 0):
-            case, res = tmp_path / f"case{flag}.bin", tmp_path / f"out{flag}.bin"
-            with open(case, "wb") as f:
-                f.write(struct.pack("<4i", n, len(level), len(phi), flag))
-                f.write(struct.pack("<d", 1.0))
-                f.write(np.asarray(uvb, "<f8").tobytes())
-                f.write(np.asarray(level, "<i4").tobytes())
-                f.write(np.ascontiguousarray(kappa, "<f8").tobytes())
-                for a in (phi, theta, w):
-                    f.write(np.asarray(a, "<f8").tobytes())
-            subprocess.check_call([harness, str(case), str(res)], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-            out.append(np.fromfile(res, "<f8").reshape(3, len(level)))
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+    import make_golden_routes as R
+    g = golden("driver_routes")
+    phi, theta, w, uvb = R.directions()
+    assert all(np.array_equal(a, g[k]) for a, k in ((phi, "phi"), (theta, "theta"), (w, "w"), (uvb, "uvb")))
+    live = os.path.exists(R.M.HARNESS)
+    for c, (n, level, kappa) in enumerate(R.cases()):
+        assert n == int(g[f"n{c}"]) and np.array_equal(level, g[f"level{c}"]) and np.array_equal(kappa, g[f"kappa{c}"])
+        out = [g[f"J{c}_lifted"], g[f"J{c}_restated"]]
+        if live:
+            assert np.array_equal(R.run(n, level, kappa, True), out[0]) and np.array_equal(R.run(n, level, kappa, False), out[1])
         assert np.array_equal(out[0], out[1])
-        assert np.array_equal(out[0], O.sweep_tree(n, level, kappa, 1.0, phi, theta, w, uvb))
+        assert np.array_equal(out[0], O.sweep_tree(n, level, kappa, R.BOX, phi, theta, w, uvb))
 
 
 def test_transparent_box_gives_inflow(golden):
