@@ -318,7 +318,12 @@ int ftte_host_unregister(ftte_ctx *ctx, void *ptr);
  * (boxes around clusters of refined cells, of the izone that has most) and "hybrid_passes" (passes their forests are swept in), 0
  * when the last sweep did not take the hybrid path; "fine_block": fine cells a side of the refined block that plan sweeps with bricks of
  * its own (0: none); "brick_form": the form of the brick kernel the last uniform-grid sweep of the
- * brick engine took (option "team": 0 or 2; -1 before the first); "devices"; of a multi-device context also "frequency_slices",
+ * brick engine took (option "team": 0 or 2; -1 before the first); "brick_dataflow": how that sweep was launched (0 a launch per
+ * stage, 1 one launch with flags, 2 the same with write-through stores, 3 persistent workgroups with a queue per XCD; the form
+ * option "dataflow" asks for falls back to 1 or 0 where the XCD census or the grid size does not allow it; -1 before the first);
+ * "brick_groups" and "brick_accumulators" (also "_0", "_1", "_2" per memory layout): direction groups of the current brick plan and
+ * the J accumulators they share (0 without a plan), "brick_chunk" (layers per brick of that plan) and "brick_queue_mix" (the
+ * option "queue_mix" the persistent form's queues were laid out by; -1 when the plan has no queues); "devices"; of a multi-device context also "frequency_slices",
  * "direction_slices" and "multi_rccl" (1: the last direction-split sweep was summed over RCCL), "rccl_loadable", "rccl_selftest" (runs the
  * direction sum's RCCL calls on a clique of one rank, the first device: 1 = the piece came back unchanged; negative = it could not
  * run), the rest from its first device.

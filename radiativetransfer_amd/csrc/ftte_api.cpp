@@ -496,6 +496,9 @@ long long ftte_counter(const ftte_ctx *c, const char *name)
     if (!std::strcmp(name, "hybrid_passes")) return (c->hplan.valid && c->hplan.worthwhile) ? c->hplan.npass : 0;
     if (!std::strcmp(name, "fine_block")) return (c->hplan.valid && c->hplan.worthwhile && c->hplan.fine.active) ? c->hplan.fine.n : 0;
     if (!std::strcmp(name, "brick_form")) return c->last_brick_form;
+    if (!std::strcmp(name, "brick_dataflow")) return c->last_brick_dataflow;
+    if (!std::strcmp(name, "brick_chunk")) return c->bplan.valid ? c->bplan.chunk : 0;
+    if (!std::strcmp(name, "brick_queue_mix")) return (c->bplan.valid && c->bplan.persistent) ? c->bplan.qmix : -1;
     if (!std::strcmp(name, "brick_groups")) return c->bplan.valid ? (long long)c->bplan.groups.size() : 0;
     if (!std::strcmp(name, "brick_accumulators")) return c->bplan.valid ? c->bplan.nacc[0] + c->bplan.nacc[1] + c->bplan.nacc[2] : 0;
     if (!std::strcmp(name, "brick_accumulators_0")) return c->bplan.valid ? c->bplan.nacc[0] : 0;

@@ -1275,18 +1275,49 @@ int launch_point_trace(const TraceRec &T, hipStream_t stream)
 // ------------------------------------------------------------------------------------------------
 struct ChemEq { double k1, k2, k3, k4, k5, k6, nh, nhe, kr24, kr25, kr26; };
 
-__device__ __forceinline__ double chem_residual(const ChemEq &q, double de, double &HeI)
+template <bool kIeee> __device__ __forceinline__ double chem_div(double a, double b) { return kIeee ? a / b : FTTE_DIV(a, b); }
+
+template <bool kIeee> __device__ __forceinline__ double chem_residual_as(const ChemEq &q, double de, double &HeI, double &HX)
 {
     // :3592-3596 (repeated at :3600-3604 and :3618-3622)
-    // (the divisions through FTTE_DIV: the instruction sequence of an IEEE fp64 division without its range handling -- every
-    // denominator here is a positive normal number far from the ends of the range: k de with de >= 1e-30, 1 + ..., -X/Y - 2 --,
-    // same bits, a quarter fewer instructions; six divisions per evaluation, some forty evaluations per cell)
     const double X = q.k3 * de + q.kr26, Y = q.k4 * de;
-    const double XY = FTTE_DIV(X, Y);
-    const double HII = FTTE_DIV(q.nh, 1. + FTTE_DIV(q.k2 * de, q.k1 * de + q.kr24));
-    HeI = FTTE_DIV(de - HII - 2. * q.nhe, XY - 2. - FTTE_DIV(2. * X, Y));
-    const double HeII = FTTE_DIV(HeI * X, Y);
+    const double XY = chem_div<kIeee>(X, Y);
+    const double HII = chem_div<kIeee>(q.nh, 1. + chem_div<kIeee>(q.k2 * de, q.k1 * de + q.kr24));
+    HeI = chem_div<kIeee>(de - HII - 2. * q.nhe, XY - 2. - chem_div<kIeee>(2. * X, Y));
+    HX = HeI * X;
+    const double HeII = chem_div<kIeee>(HX, Y);
     return q.k3 * HeI * de + q.k6 * (q.nhe - HeI - HeII) * de + q.kr26 * HeI - HeII * (q.k4 * de + q.k5 * de + q.kr25);
+}
+
+// The residual's six divisions through FTTE_DIV, the trimmed sequence of ftte_math.h (a quarter fewer instructions, some forty
+// evaluations per cell), where that gives IEEE's quotient; the plain division where it might not.  `tame` (per cell,
+// chem_tame): every operand that depends on the rate coefficients lies in [2^-250, 2^250] for every de of the bracket -- then
+// every divisor, and every quotient but the last, is far from both ends of the range.  Left to check per evaluation: the last
+// numerator, HeI X (too small: HeII near the underflow), and NaN from an overflowing quotient.  Any lane outside takes the whole
+// wavefront through IEEE division, which gives the same bits in the lanes that did not need it.
+__device__ __forceinline__ double chem_residual(const ChemEq &q, double de, double &HeI, bool tame)
+{
+    double HX;
+    if (!FTTE_ANY(!tame)) {
+        double h;
+        const double r = chem_residual_as<false>(q, de, h, HX);
+        if (!FTTE_ANY(!(r == r) || (HX != 0. && fabs(HX) < 0x1p-700))) { HeI = h; return r; }
+    }
+    return chem_residual_as<true>(q, de, HeI, HX);
+}
+
+// Whether the divisors and numerators of chem_residual that depend on the rate coefficients stay in [2^-250, 2^250] over the
+// bracket [de1, de2] (each is a non-decreasing function of de when the coefficients are not negative, so its ends bound it), X
+// either there or 0 throughout, and nh, nhe there too.  False for a table whose coefficients vanish or come close to it where
+// nothing else ionises the cell: k1 de + kr24 or k4 de is then subnormal or 0 at de = 1e-30, where the trimmed division
+// returns NaN and IEEE's carries on with inf and 0.
+__device__ __forceinline__ bool chem_tame(const ChemEq &q, double de1, double de2)
+{
+    const auto in = [](double v) { return v >= 0x1p-250 && v <= 0x1p250; };
+    const double X1 = q.k3 * de1 + q.kr26, X2 = q.k3 * de2 + q.kr26;
+    return q.k1 >= 0. && q.k2 >= 0. && q.k3 >= 0. && q.k4 >= 0. && in(q.nh) && in(q.nhe) && in(q.k1 * de1 + q.kr24) &&
+           in(q.k1 * de2 + q.kr24) && in(q.k2 * de1) && in(q.k2 * de2) && in(q.k4 * de1) && in(q.k4 * de2) &&
+           ((X1 == 0. && X2 == 0.) || (in(X1) && in(X2)));
 }
 
 __global__ void __launch_bounds__(256) rate_equations_kernel(const ChemRec R)
@@ -1344,15 +1375,16 @@ __global__ void __launch_bounds__(256) rate_equations_kernel(const ChemRec R)
 
     // bisection on the electron density, :3589-3633
     double de1 = (double)1.e-30f, de2 = q.nh + 2. * q.nhe;
-    double res1 = chem_residual(q, de1, HeI);
+    const bool tame = chem_tame(q, de1, de2);
+    double res1 = chem_residual(q, de1, HeI, tame);
     double de = de2;
-    (void)chem_residual(q, de2, HeI);
+    (void)chem_residual(q, de2, HeI, tame);
     double HeIprev = -1.;
     unsigned steps = 0;
     while (fabs(HeI - HeIprev) / q.nhe > 1.e-10 && steps < 4096u) {
         HeIprev = HeI;
         de = 0.5 * (de1 + de2);
-        const double res = chem_residual(q, de, HeI);
+        const double res = chem_residual(q, de, HeI, tame);
         const bool opposite = (res > 0. && res1 < 0.) || (res < 0. && res1 > 0.); // :5044-5058
         if (opposite) de2 = de;
         else { de1 = de; res1 = res; }

@@ -32,10 +32,14 @@
 #define FTTE_FMAX(a, b) __builtin_fmax((a), (b))
 #define FTTE_FREXP(a, pe) __builtin_frexp((a), (pe))
 #if defined(__HIP_DEVICE_COMPILE__)
-/* a/b correctly rounded, for normal-range operands: v_rcp_f64 seed, two Newton steps, quotient, one residual
- * correction -- the instruction sequence hipcc itself emits for an IEEE fp64 division, minus the
- * v_div_scale / v_div_fixup range handling that 0.29 <= a <= 1, 0.34 <= b < 1e300 never needs (lanes outside
- * that range discard the result).  Same bits as the host's `/`: checked by the bitwise parity tests. */
+/* a/b correctly rounded away from the ends of the range: v_rcp_f64 seed, two Newton steps, quotient, one residual
+ * correction -- the instruction sequence hipcc itself emits for an IEEE fp64 division, minus the v_div_scale /
+ * v_div_fixup range handling.  That handling changes nothing -- the result is IEEE's -- when b is finite with
+ * 2^-1022 <= |b| <= 2^1021 (b and 1/b normal), a is 0 or 2^-969 <= |a|, and the quotient is normal and below 2^767.
+ * Outside that it is not IEEE's: a zero or subnormal b gives NaN (not +-inf), a quotient near the underflow can be
+ * off in its last bits.  Callers keep their operands inside (the attenuation pair: 0.29 <= a <= 1, 0.34 <= b < 1e300,
+ * lanes outside discard the result) or check them (chem_residual).  Same bits as the host's `/` there: checked by
+ * the bitwise parity tests. */
 __device__ __forceinline__ double ftte_div(double a, double b)
 {
     double y = __builtin_amdgcn_rcp(b);

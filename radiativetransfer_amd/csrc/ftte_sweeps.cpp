@@ -656,6 +656,8 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
                 FTTE_HIP(c, hipGetDeviceProperties(&prop, c->device));
                 persistent = (int)std::min<size_t>((size_t)prop.multiProcessorCount * 16, P.queue.size());
             }
+            c->last_brick_form = 0;
+            c->last_brick_dataflow = P.persistent ? 3 : c->dataflow == 2 ? 2 : 1;
             const int lrc = launch_brick(L, P.max_dirs, c->brick_waves, stream, false, persistent);
             if (lrc) return fail(c, lrc == -1 ? FTTE_ERR_ARG : FTTE_ERR_NO_DEVICE, "brick kernel launch failed");
             FTTE_HIP(c, hipMemcpyAsync(c->h_berror, c->d_bsync, sizeof(uint32_t) * kSyncWords, hipMemcpyDeviceToHost, stream));
@@ -705,6 +707,7 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
                 L.atomic_acc = c->atomic_acc;
                 const int form = brick_form(c, nnu);
                 c->last_brick_form = form;
+                c->last_brick_dataflow = 0;
                 const int lrc = form == 2 ? launch_brick_pair(L, P.max_dirs, c->pair_waves, q) : launch_brick(L, P.max_dirs, c->brick_waves, q);
                 if (lrc) return fail(c, lrc == -1 ? FTTE_ERR_ARG : FTTE_ERR_NO_DEVICE, "brick kernel launch failed");
             }

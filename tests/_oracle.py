@@ -126,6 +126,40 @@ def sweep_uniform(n, kappa, box, phi, theta, w, uvb, eta=None, src=None, arith=A
     return (J, noise) if with_noise else J
 
 
+def oracle_threads():
+    """Threads sweep_uniform_parallel may use: the CPUs this process may run on, at most 16."""
+    return max(1, min(16, len(os.sched_getaffinity(0))))
+
+
+def sweep_uniform_parallel(n, kappa, box, phi, theta, w, uvb, arith=ARITH_REFERENCE, threads=None):
+    """sweep_uniform spread over threads (the library has no mutable globals; ctypes lets go of the GIL during the call).
+    Split by frequency group first -- groups never meet, so that alone gives the bits of one call; with fewer groups than
+    threads each group's directions are also cut into blocks of consecutive directions, swept apart and added in block order
+    -- one call's J to the rounding of that sum (SUM_RTOL)."""
+    from concurrent.futures import ThreadPoolExecutor
+    lib()                                   # built and loaded once, before the threads
+    kappa = _f64(kappa)
+    nnu = kappa.shape[0]
+    phi, theta, w, uvb = map(_f64, (phi, theta, w, uvb))
+    threads = oracle_threads() if threads is None else max(1, min(int(threads), oracle_threads()))
+    nblk = max(1, min(len(phi), threads // nnu if nnu < threads else 1))
+    cuts = [len(phi) * b // nblk for b in range(nblk + 1)]
+    jobs = [(g, cuts[b], cuts[b + 1]) for g in range(nnu) for b in range(nblk)]
+
+    def one(job):
+        g, lo, hi = job
+        return sweep_uniform(n, kappa[g:g + 1], box, phi[lo:hi], theta[lo:hi], w[lo:hi], uvb[g:g + 1], arith=arith)[0]
+
+    with ThreadPoolExecutor(max_workers=min(threads, len(jobs))) as pool:
+        parts = list(pool.map(one, jobs))
+    J = np.empty_like(kappa)
+    for g in range(nnu):
+        J[g] = parts[g * nblk]
+        for b in range(1, nblk):
+            J[g] += parts[g * nblk + b]
+    return J
+
+
 def sweep_tree(n, level, kappa, box, phi, theta, w, uvb, eta=None, src=None, arith=ARITH_REFERENCE, order=ORDER_SERIAL,
                with_noise=False):
     kappa = _f64(kappa)

@@ -244,3 +244,71 @@ def test_assign_uvb_radiation_against_reference(stellar, golden):
     assert np.array_equal(J, g["J"])
     J5 = stellar.assign_uvb_radiation(np.arange(1, 6) * 1e-22, float(g["threshold"]))   # any number of groups
     assert J5.shape[0] == 5 and np.array_equal(J5[4] > 0, g["J"][0] > 0)
+
+
+@pytest.mark.parametrize("coefficient", ["k1", "k4"])
+def test_vanishing_rate_coefficients_where_nothing_ionises_bitwise(golden, coefficient):
+    """The residual's divisors k1 de + kr24 and k4 de at the bottom of the range: a rate table whose collisional ionisation of HI
+    (k1) or recombination of HeII (k4) is zero or below 1e-278 at the lowest temperatures -- the reference accepts any table --
+    in cells that nothing ionises (no transfer J: run_uvb off; every cell shielded, so the uniform background does not reach it;
+    no point rates): kr24 = kr26 = 0, and at the bisection's lower end (de = 1e-30) the divisor is subnormal or zero.  IEEE
+    division carries on with inf and 0 there; the library's species and bisection steps equal the oracle's bit for bit in a
+    field where the oracle converges in every cell, and in a field that holds cells on rows where the coefficient is exactly 0
+    (0/0 in the fractions: the reference stops), the library stops at the same first cell."""
+    import radiativetransfer_amd as rt
+    g = golden("chem_uvb_refined")
+    n = 16
+    nc = n ** 3
+    box = 2.5e23
+    mp, mn, psi = float(np.float32(1.6726231e-24)), float(np.float32(1.67492728e-24)), float(np.float32(0.76))
+    logtem0, logtem9, dlogtem = float(g["logtem0"]), float(g["logtem9"]), float(g["dlogtem"])
+    uniform, threshold = np.array([3e-14, 1e-16, 2e-14]), 1e300      # mfp < threshold everywhere: shielded
+    rows, zero_rows = 1000, 100                                     # 1 K .. 40 K; the last 100 rows (27.5 K ..) exactly 0
+    rng = np.random.default_rng(3)
+    k = np.array(g["k"], dtype=np.float64, copy=True)
+    r = {"k1": 0, "k4": 3}[coefficient]
+    k[r, :rows] = 10 ** rng.uniform(-300, -279, rows)
+    k[r, rows - zero_rows:rows] = 0.0
+    if coefficient == "k4":
+        k[2, :rows] = 0.0          # and no collisional ionisation of HeI there (X = 0): with k3 = 1e-20 HeII runs out of [0, 1]
+    table = (logtem0, logtem9, dlogtem, k)
+
+    def oracle(rho, tgas, start):
+        return O.solve_rate_equations(1 if len(rho) == 1 else n, np.zeros(len(rho), np.int32), box, rho, tgas, *start, None, False, None,
+                                      None, uniform, threshold, *table)
+
+    # candidates below the zero rows; the cells of the first field are those the oracle takes through
+    m = 3 * nc
+    rho = 10 ** rng.uniform(-30, -16, m)
+    nh, nhe = psi * rho / mp, (1 - psi) * rho / (2 * (mp + mn))
+    tgas = np.exp(logtem0 + rng.uniform(0, (rows - zero_rows - 1) * dlogtem, m))
+    start = (nh * 10 ** rng.uniform(-3, 0, m), nhe * 10 ** rng.uniform(-3, -0.5, m), nhe * 10 ** rng.uniform(-3, -0.5, m))
+    converges = np.array([oracle(rho[i:i + 1], tgas[i:i + 1], [a[i:i + 1] for a in start])[3] == 0 for i in range(m)])
+    keep = np.flatnonzero(converges)[:nc]
+    assert keep.size == nc
+    rho, tgas, start = rho[keep], tgas[keep], tuple(a[keep] for a in start)
+
+    def device(rho, tgas, start):
+        with rt.StellarTransfer() as st:
+            st.set_uniform_grid(n, box)
+            st.set_rate_coefficients(*table)
+            st.set_medium(*start, rho, None, 0)
+            st.set_temperature(tgas)
+            st.solve_rate_equations(False, None, None, uniform, threshold)
+            return st.medium(), st.rate_equation_steps()
+
+    ref = oracle(rho, tgas, start)
+    assert ref[3] == 0 and ref[4] > 0
+    (HI, HeI, HeII), steps = device(rho, tgas, start)
+    bad = np.flatnonzero((HI != ref[0]) | (HeI != ref[1]) | (HeII != ref[2]))
+    assert bad.size == 0, f"{bad.size} of {nc} cells differ, first {bad[:5]}: HI {HI[bad[:3]]} vs {ref[0][bad[:3]]}"
+    assert steps == ref[4]
+    # cells on the zero rows from cell 1000 on: the reference stops at the first of them
+    hot = np.arange(1000, nc, 397)
+    tgas2 = tgas.copy()
+    tgas2[hot] = np.exp(logtem0 + (rows - zero_rows / 2) * dlogtem)
+    ref = oracle(rho, tgas2, start)
+    assert ref[3] == 1 + hot[0]
+    with pytest.raises(rt.FtteError) as err:
+        device(rho, tgas2, start)
+    assert err.value.status == "FTTE_ERR_RATES" and f"cell {ref[3] - 1} " in str(err.value)

@@ -78,8 +78,6 @@ def test_multi_device_context_on_a_refined_cell_array_with_a_source_function_and
         e.set_source_function(None)
         J_plain = e.iterate_into(0.5 * kappa, phi, theta, w, uvb, np.empty_like(kappa))   # new opacities and the sweep in one call
     assert np.allclose(J_plain, O.sweep_tree(n, level, 0.5 * kappa, 1.0, phi, theta, w, uvb, arith=O.ARITH_DEVICE), rtol=SUM_RTOL, atol=0)
-    return
-    assert np.allclose(J_plain, O.sweep_tree(n, level, kappa, 1.0, phi, theta, w, uvb, arith=O.ARITH_DEVICE), rtol=SUM_RTOL, atol=0)
 
 
 def test_what_a_multi_device_context_refuses_and_how_it_fails():
