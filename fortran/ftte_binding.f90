@@ -271,6 +271,25 @@ module ftte_binding
        real(c_double), intent(out) :: HI(*), HeI(*), HeII(*)
      end function ftte_get_medium
 
+     ! equiSources.f90:1008-1022: initialIonizationEquilibrium `passes` times per leaf (the reference: 2) on the device-resident
+     ! medium; neutral_fraction = neutralHydrogenMass / totalHydrogenMass of the result (what :1022 prints)
+     integer(c_int) function ftte_initial_ionization_equilibrium(ctx, uniform, self_shielding_threshold, passes, neutral_fraction) &
+          bind(C, name='ftte_initial_ionization_equilibrium')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       real(c_double), intent(in) :: uniform(3)
+       real(c_double), value :: self_shielding_threshold
+       integer(c_int), value :: passes
+       real(c_double), intent(out) :: neutral_fraction
+     end function ftte_initial_ionization_equilibrium
+
+     ! computeMass (equiSources.f90:4369-4393) over the device-resident medium [msun]
+     integer(c_int) function ftte_hydrogen_mass(ctx, neutral_msun, total_msun) bind(C, name='ftte_hydrogen_mass')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       real(c_double), intent(out) :: neutral_msun, total_msun
+     end function ftte_hydrogen_mass
+
      integer(c_int) function ftte_compute_opacities(ctx, nnu, beta) bind(C, name='ftte_compute_opacities')
        import :: c_ptr, c_int, c_double
        type(c_ptr), value :: ctx

@@ -1,13 +1,17 @@
-! ftte_rate_equations.f90 -- the drop-in for the chemistry step: what replaces the solveRateEquations calls of the loop
-! equiSources.f90:1824-1831 in the reference driver (computeMass stays where it is).
+! ftte_rate_equations.f90 -- the drop-ins for the chemistry: what replaces the start-up equilibrium equiSources.f90:1008-1022,
+! the solveRateEquations calls of the loop :1824-1831 and the loop's computeMass calls in the reference driver.
 !
 ! Compiled TOGETHER WITH the reference (module `definitions`); this repository compiles it only as an interface check
 ! against oracle/_ref/definitions.mod (fortran/Makefile: target `dropin-check`).
 !
-!   call ftteSolveRateEquations(nx, runUVBTransfer)
+!   call ftteInitialIonizationEquilibrium(nx)        ! replaces :1008-1022 (both passes, computeMass, the printed fraction)
+!   call ftteSolveRateEquations(nx, runUVBTransfer)  ! replaces the solveRateEquations calls of :1824-1831
+!   call ftteComputeMass(nx)                         ! replaces the computeMass calls of :1824-1831
 !
 ! On entry the leaves hold rho, tgas, HI, HeI, HeII, krate24..26 (the point-source block) and Jmean1..3 (the diffuse
-! block); on return HI, HeI, HeII are the reference's new equilibrium values.
+! block); on return HI, HeI, HeII are the reference's new equilibrium values.  ftteInitialIonizationEquilibrium and
+! ftteComputeMass set neutralHydrogenMass and totalHydrogenMass.  ftteComputeMass works on the medium the last of the
+! other two left on the device (the tree's HI and rho unchanged since); before either has run it takes the tree.
 module ftte_rate_equations
 
   use, intrinsic :: iso_c_binding
@@ -17,6 +21,7 @@ module ftte_rate_equations
 
   type(c_ptr), save, private :: ctx = c_null_ptr
   integer(c_int64_t), private :: cursor
+  logical, save, private :: resident = .false.   ! the context's medium is the tree's
 
 contains
 
@@ -79,7 +84,81 @@ contains
           enddo
        enddo
     enddo
+    resident = .true.
   end subroutine ftteSolveRateEquations
+
+  ! the tree's leaves -> the context: grid, rate coefficients, medium with rho, temperature; f(ncell,11) as gatherState fills it
+  subroutine loadTree(nx, f)
+    integer, intent(in) :: nx
+    real(c_double), allocatable, intent(out) :: f(:,:)
+    integer(c_int64_t) :: ncell
+    integer(c_int32_t), allocatable :: lev(:)
+    integer :: i, j, k
+
+    if (.not. c_associated(ctx)) call ftteCheck(c_null_ptr, ftte_create(ctx, 1, c_null_ptr), 'ftte_create')
+    ncell = 0
+    do i = 1, nx
+       do j = 1, nx
+          do k = 1, nx
+             call countChemCells(baseGrid%cell(i,j,k), ncell)
+          enddo
+       enddo
+    enddo
+    allocate(lev(ncell), f(ncell,11))
+    cursor = 0
+    do i = 1, nx
+       do j = 1, nx
+          do k = 1, nx
+             call gatherState(baseGrid%cell(i,j,k), 0, lev, f)
+          enddo
+       enddo
+    enddo
+    call ftteCheck(ctx, ftte_set_grid(ctx, nx, nx, nx, ncell, lev, physicalBoxSize), 'ftte_set_grid')
+    call ftteCheck(ctx, ftte_set_rate_coefficients(ctx, nratec, logtem0, logtem9, dlogtem, k1a, k2a, k3a, k4a, k5a, k6a), &
+         'ftte_set_rate_coefficients')
+    call ftteCheck(ctx, ftte_set_medium(ctx, f(:,3), f(:,4), f(:,5), f(:,1), f(:,1), 0), 'ftte_set_medium')
+    call ftteCheck(ctx, ftte_set_temperature(ctx, f(:,2)), 'ftte_set_temperature')
+  end subroutine loadTree
+
+  ! equiSources.f90:1008-1022: initialIonizationEquilibrium twice for every leaf, computeMass, the printed neutral fraction
+  subroutine ftteInitialIonizationEquilibrium(nx)
+    integer, intent(in) :: nx
+    real(c_double), allocatable :: f(:,:)
+    real(c_double) :: uniform(3), fraction
+    integer :: i, j, k
+
+    print*, 'computing ionization equilibrium'
+    call loadTree(nx, f)
+    uniform = (/ uniformQuasar*quasar%ksi24 + uniformStellar*stellar%ksi24, &
+                 uniformQuasar*quasar%ksi25 + uniformStellar*stellar%ksi25, &
+                 uniformQuasar*quasar%ksi26 + uniformStellar*stellar%ksi26 /)
+    call ftteCheck(ctx, ftte_initial_ionization_equilibrium(ctx, uniform, selfShieldingThreshold, 2, fraction), &
+         'ftte_initial_ionization_equilibrium')
+    call ftteCheck(ctx, ftte_get_medium(ctx, f(:,3), f(:,4), f(:,5)), 'ftte_get_medium')
+    cursor = 0
+    do i = 1, nx
+       do j = 1, nx
+          do k = 1, nx
+             call scatterState(baseGrid%cell(i,j,k), f)
+          enddo
+       enddo
+    enddo
+    resident = .true.
+    call ftteCheck(ctx, ftte_hydrogen_mass(ctx, neutralHydrogenMass, totalHydrogenMass), 'ftte_hydrogen_mass')
+    write(*,'("ionization equilibrium:", es18.8)') neutralHydrogenMass/totalHydrogenMass
+  end subroutine ftteInitialIonizationEquilibrium
+
+  ! computeMass (equiSources.f90:4369-4393) over every leaf: neutralHydrogenMass, totalHydrogenMass [msun]
+  subroutine ftteComputeMass(nx)
+    integer, intent(in) :: nx
+    real(c_double), allocatable :: f(:,:)
+
+    if (.not. resident) then
+       call loadTree(nx, f)
+       resident = .true.
+    endif
+    call ftteCheck(ctx, ftte_hydrogen_mass(ctx, neutralHydrogenMass, totalHydrogenMass), 'ftte_hydrogen_mass')
+  end subroutine ftteComputeMass
 
   recursive subroutine countChemCells(c, total)
     type(zoneType) :: c

@@ -274,8 +274,23 @@ int ftte_compute_opacities(ftte_ctx *ctx, int nnu, const double *beta);
  * HeII 1.58e-18) of the device-resident medium is at least the threshold, else 0.  J[nnu][ncell]. */
 int ftte_assign_uvb_radiation(ftte_ctx *ctx, int nnu, const double *uvb, double self_shielding_threshold, double *J);
 int ftte_assign_uvb_radiation_device(ftte_ctx *ctx, int nnu, const double *uvb, double self_shielding_threshold, double *J_dev);
-/* bisection steps of the last ftte_solve_rate_equations*, summed over the cells */
+/* bisection steps of the last ftte_solve_rate_equations* or ftte_initial_ionization_equilibrium, summed over the cells (and
+ * over the passes of the latter) */
 long long ftte_rate_equation_steps(const ftte_ctx *ctx);
+/* The start-up ionisation equilibrium, equiSources.f90:1008-1022: initialIonizationEquilibrium (:3679-3868) `passes` times
+ * for every leaf (the reference: 2), each pass starting from the last one's HI, HeI, HeII, on the device-resident medium.
+ * Preconditions those of ftte_solve_rate_equations (rate coefficients, temperature, a medium with rho).  The rates are the
+ * uniform background's alone, uniform[3] as there, where the Lyman-limit mean free path is at least self_shielding_threshold
+ * (:3731-3743); unlike solveRateEquations the bracket starts at 1.e-20, its lower residual is never updated, and the
+ * bisection runs until HeI stops changing.  neutral_fraction (may be NULL): neutralHydrogenMass / totalHydrogenMass of
+ * computeMass over the result, what :1022 prints.  FTTE_ERR_RATES (first failing cell named, medium unchanged) where the
+ * reference stops (:3809-3818, :3832-3843) or where the bisection does not settle in 4096 steps. */
+int ftte_initial_ionization_equilibrium(ftte_ctx *ctx, const double *uniform, double self_shielding_threshold, int passes,
+                                        double *neutral_fraction);
+/* computeMass (equiSources.f90:4369-4393) over the device-resident medium: neutralHydrogenMass = sum HI mh cs^3 / msun and
+ * totalHydrogenMass = sum psi rho cs^3 / msun [msun], cs the leaf's size; the ratio is the loop's `time` line (:1820-1834).
+ * Every term is the reference's; the sums are deterministic (a fixed order, not the reference's sequential one). */
+int ftte_hydrogen_mass(ftte_ctx *ctx, double *neutral_msun, double *total_msun);
 
 /* ---- grid ingest (no device needed) -----------------------------------------------------------------
  * What the reference does between reading its grid file and the first transfer (equiSources.f90:427-618,

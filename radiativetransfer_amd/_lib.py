@@ -73,6 +73,8 @@ SIGNATURES = {
     "ftte_assign_uvb_radiation": (C.c_int, [_vp, C.c_int, _dp, C.c_double, _dp]),
     "ftte_assign_uvb_radiation_device": (C.c_int, [_vp, C.c_int, _dp, C.c_double, _vp]),
     "ftte_rate_equation_steps": (C.c_longlong, [_vp]),
+    "ftte_initial_ionization_equilibrium": (C.c_int, [_vp, _dp, C.c_double, C.c_int, _dp]),
+    "ftte_hydrogen_mass": (C.c_int, [_vp, _dp, _dp]),
     "ftte_point_ray_steps": (C.c_longlong, [_vp]),
     "ftte_rmax": (C.c_int, [_dp]),
     "ftte_uvb_beta_table": (C.c_int, [C.c_int, C.c_double, _dp, _dp, _dp, _dp]),

@@ -491,3 +491,18 @@ class StellarTransfer(DiffuseTransfer):
 
     def rate_equation_steps(self) -> int:
         return int(self._lib.ftte_rate_equation_steps(self._ctx))
+
+    # -- the start-up equilibrium (equiSources.f90:1008-1022) and computeMass (:4369-4393)
+    def initial_ionization_equilibrium(self, uniform, threshold: float, passes: int = 2) -> float:
+        """initialIonizationEquilibrium `passes` times per leaf on the device-resident medium, uniform[3] the background rates
+        behind the self-shielding threshold.  Returns neutralHydrogenMass / totalHydrogenMass of the result."""
+        uniform = _f64(uniform).reshape(3)
+        frac = C.c_double()
+        self._ok(self._lib.ftte_initial_ionization_equilibrium(self._ctx, _dp(uniform), float(threshold), int(passes), C.byref(frac)))
+        return frac.value
+
+    def hydrogen_mass(self) -> Tuple[float, float]:
+        """(neutralHydrogenMass, totalHydrogenMass) [msun] of the device-resident medium."""
+        neutral, total = C.c_double(), C.c_double()
+        self._ok(self._lib.ftte_hydrogen_mass(self._ctx, C.byref(neutral), C.byref(total)))
+        return neutral.value, total.value

@@ -119,6 +119,7 @@ int ftte_destroy(ftte_ctx *c)
     c->drop_chem_grid();
     if (c->chem_k) (void)hipFree(c->chem_k);
     if (c->chem_counters) (void)hipFree(c->chem_counters);
+    if (c->chem_mass) (void)hipFree(c->chem_mass);
     for (auto &t : c->timing) {
         (void)hipEventDestroy(t.start); (void)hipEventDestroy(t.stop);
         for (auto &e : t.first) (void)hipEventDestroy(e);
@@ -881,6 +882,99 @@ int ftte_solve_rate_equations_device(ftte_ctx *c, int run_uvb_transfer, const do
 {
     return solve_rates(c, run_uvb_transfer, J_dev, true, ksi, uniform, self_shielding_threshold, use_point_rates, max_change,
                        "ftte_solve_rate_equations_device");
+}
+
+// computeMass over the leaves of HI (the medium's or a candidate's): the two totals [msun], deterministic
+static int hydrogen_mass(ftte_ctx *c, const double *HI_dev, double *neutral, double *total, const char *who)
+{
+    PointState &P = c->point;
+    const size_t nc = (size_t)c->ncell;
+    if (!c->chem_level) {
+        FTTE_HIP(c, hipMalloc((void **)&c->chem_level, nc));
+        FTTE_HIP(c, hipMemcpyAsync(c->chem_level, c->leaf_level.data(), nc, hipMemcpyHostToDevice, c->stream));
+    }
+    if (!c->chem_mass) FTTE_HIP(c, hipMalloc((void **)&c->chem_mass, sizeof(double) * kMassParts));
+    if (launch_hydrogen_mass(c->chem_level, HI_dev, P.medium[3], (long)nc, c->n, c->box, c->chem_mass, c->stream))
+        return fail(c, FTTE_ERR_NO_DEVICE, std::string(who) + ": kernel launch failed");
+    double out[2];
+    FTTE_HIP(c, hipMemcpyAsync(out, c->chem_mass + 2 * kMassBlocks, sizeof out, hipMemcpyDeviceToHost, c->stream));
+    FTTE_HIP(c, hipStreamSynchronize(c->stream));
+    *neutral = out[0];
+    *total = out[1];
+    return FTTE_OK;
+}
+
+int ftte_initial_ionization_equilibrium(ftte_ctx *c, const double *uniform, double threshold, int passes, double *neutral_fraction)
+{
+    const char *who = "ftte_initial_ionization_equilibrium";
+    if (c && c->multi) return check_ready(c, false); // (refuses: a multi-device context routes the diffuse sweep only)
+    int rc = check_ready(c, false);
+    if (rc) return rc;
+    PointState &P = c->point;
+    if (!c->chem_k) return fail(c, FTTE_ERR_STATE, std::string(who) + ": no rate coefficients (ftte_set_rate_coefficients)");
+    if (!c->chem_temperature_set) return fail(c, FTTE_ERR_STATE, std::string(who) + ": no temperature (ftte_set_temperature)");
+    if (!P.medium_ready || P.medium_cells != c->ncell || !P.rho_given)
+        return fail(c, FTTE_ERR_STATE, std::string(who) + ": no medium with density (ftte_set_medium with rho)");
+    if (!uniform) return fail(c, FTTE_ERR_ARG, std::string(who) + ": the uniform-background update needs the background rates");
+    if (passes < 1) return fail(c, FTTE_ERR_ARG, std::string(who) + ": passes must be at least 1");
+    FTTE_HIP(c, hipSetDevice(c->device));
+    const size_t nc = (size_t)c->ncell;
+    if (!c->chem_level) {
+        FTTE_HIP(c, hipMalloc((void **)&c->chem_level, nc));
+        FTTE_HIP(c, hipMemcpyAsync(c->chem_level, c->leaf_level.data(), nc, hipMemcpyHostToDevice, c->stream));
+    }
+    if (!c->chem_out) FTTE_HIP(c, hipMalloc((void **)&c->chem_out, sizeof(double) * 3 * nc));
+    if (!c->chem_counters) FTTE_HIP(c, hipMalloc((void **)&c->chem_counters, sizeof(unsigned long long) * 4));
+    const unsigned long long init[4] = {~0ull, 0ull, 0ull, 0ull};
+    FTTE_HIP(c, hipMemcpyAsync(c->chem_counters, init, sizeof init, hipMemcpyHostToDevice, c->stream));
+
+    ChemRec R;
+    std::memset(&R, 0, sizeof R);
+    R.level = c->chem_level;
+    R.rho = P.medium[3]; R.logtem = c->chem_logtem;
+    R.HI = P.medium[0]; R.HeI = P.medium[1]; R.HeII = P.medium[2];
+    R.HI_out = c->chem_out; R.HeI_out = c->chem_out + nc; R.HeII_out = c->chem_out + 2 * nc;
+    R.k = c->chem_k;
+    R.ncell = c->ncell; R.n = c->n; R.nratec = c->chem_nratec; R.passes = passes;
+    R.box = c->box; R.logtem0 = c->chem_logtem0; R.logtem9 = c->chem_logtem9; R.dlogtem = c->chem_dlogtem;
+    std::memcpy(R.uniform, uniform, sizeof R.uniform);
+    R.threshold = threshold;
+    R.first_bad = c->chem_counters; R.max_change = c->chem_counters + 1; R.steps = c->chem_counters + 2;
+    if (launch_initial_equilibrium(R, c->stream)) return fail(c, FTTE_ERR_NO_DEVICE, std::string(who) + ": kernel launch failed");
+    unsigned long long out[4];
+    FTTE_HIP(c, hipMemcpyAsync(out, c->chem_counters, sizeof out, hipMemcpyDeviceToHost, c->stream));
+    FTTE_HIP(c, hipStreamSynchronize(c->stream));
+    if (out[0] != ~0ull) {
+        // the reference prints the species of the cell and stops (equiSources.f90:3809-3818, :3832-3843); the state is left as it was
+        return fail(c, FTTE_ERR_RATES, std::string(who) + ": species fraction outside [0, 1] or no convergence in cell " +
+                                           std::to_string(out[0]) + " (0-based cell-array index)");
+    }
+    for (int f = 0; f < 3; ++f)
+        FTTE_HIP(c, hipMemcpyAsync(P.medium[f], c->chem_out + f * nc, sizeof(double) * nc, hipMemcpyDeviceToDevice, c->stream));
+    P.packed_ready = false; // the tracer's packed copy of the medium is stale now
+    FTTE_HIP(c, hipStreamSynchronize(c->stream));
+    c->chem_steps = (long long)out[2];
+    if (neutral_fraction) {
+        // equiSources.f90:1020-1022
+        double neutral = 0., total = 0.;
+        if ((rc = hydrogen_mass(c, P.medium[0], &neutral, &total, who))) return rc;
+        *neutral_fraction = neutral / total;
+    }
+    return FTTE_OK;
+}
+
+int ftte_hydrogen_mass(ftte_ctx *c, double *neutral_msun, double *total_msun)
+{
+    const char *who = "ftte_hydrogen_mass";
+    if (c && c->multi) return check_ready(c, false); // (refuses: a multi-device context routes the diffuse sweep only)
+    int rc = check_ready(c, false);
+    if (rc) return rc;
+    if (!neutral_msun || !total_msun) return fail(c, FTTE_ERR_ARG, std::string(who) + ": bad argument");
+    PointState &P = c->point;
+    if (!P.medium_ready || P.medium_cells != c->ncell || !P.rho_given)
+        return fail(c, FTTE_ERR_STATE, std::string(who) + ": no medium with density (ftte_set_medium with rho)");
+    FTTE_HIP(c, hipSetDevice(c->device));
+    return hydrogen_mass(c, P.medium[0], neutral_msun, total_msun, who);
 }
 
 int ftte_get_medium(ftte_ctx *c, double *HI, double *HeI, double *HeII)

@@ -306,6 +306,7 @@ struct ftte_ctx {
     double *chem_out = nullptr, *chem_J = nullptr; // [3][ncell] each
     unsigned long long *chem_counters = nullptr;   // first bad cell, bits of the largest change, bisection steps
     long long chem_steps = 0;
+    double *chem_mass = nullptr;     // computeMass: per-workgroup partial sums, then the two totals (kMassParts)
 
     void drop_chem_grid()
     {

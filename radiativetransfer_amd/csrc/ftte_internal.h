@@ -286,7 +286,7 @@ struct ChemRec {
     const double *J;           // [3][ncell] or nullptr (uniform background)
     const double *k;           // [6][nratec] rate coefficients k1a..k6a
     int64_t ncell;
-    int32_t n, nratec, run_uvb, pad;
+    int32_t n, nratec, run_uvb, passes; // passes: initial_equilibrium_kernel only
     double box, logtem0, logtem9, dlogtem;
     double ksi[9];             // [group][ksi24, ksi25, ksi26]
     double uniform[3];         // uniformQuasar * quasar%ksi + uniformStellar * stellar%ksi, per reaction

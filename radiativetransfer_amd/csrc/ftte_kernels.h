@@ -51,6 +51,13 @@ int launch_repack_rates(double *planes, double *packed, long ncell, bool to_pack
 
 // ionisation equilibrium of every leaf (solveRateEquations)
 int launch_rate_equations(const ChemRec &R, hipStream_t stream);
+// the start-up equilibrium (initialIonizationEquilibrium), R.passes times per leaf; R.krate, R.J, R.run_uvb, R.ksi unused
+int launch_initial_equilibrium(const ChemRec &R, hipStream_t stream);
+// computeMass over the leaves: part[kMassParts]; the neutral and the total hydrogen mass [msun] land in part[2 kMassBlocks], [+1]
+constexpr int kMassBlocks = 1024;
+constexpr int kMassParts = 2 * kMassBlocks + 2;
+int launch_hydrogen_mass(const int8_t *level, const double *HI, const double *rho, long ncell, int n, double box, double *part,
+                         hipStream_t stream);
 int launch_thin_limit(const double *HI, const double *HeI, const double *HeII, const double *rho, const double *uvb, double threshold,
                       double *J, long ncell, int nnu, hipStream_t stream);
 

@@ -1463,6 +1463,167 @@ int launch_rate_equations(const ChemRec &R, hipStream_t stream)
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The start-up ionisation equilibrium, initialIonizationEquilibrium (equiSources.f90:3679-3868), `passes` times per leaf
+// (the reference: twice, :1016), the next pass starting from the last one's HI, HeI, HeII -- in registers, since the routine
+// reads nothing outside its own cell.  The residual is solveRateEquations' (chem_residual_as, IEEE divisions throughout); what
+// differs from rate_equations_kernel is spelled out at each place.  R.krate, R.J, R.run_uvb are not used: the rates are the
+// uniform background's behind the self-shielding test alone (:3731-3743).
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) initial_equilibrium_kernel(const ChemRec R)
+{
+    __shared__ unsigned long long blk_steps[4], blk_bad[4];
+    unsigned long long my_steps = 0ull, my_bad = ~0ull;
+    const double psi = (double)0.76f, mp = (double)1.6726231e-24f, mn = (double)1.67492728e-24f; // definitionsModule.f90:25-28, 261
+    const double mh = mp, mhe = 2. * (mp + mn), pi = (double)3.141592654f;
+    for (long c = (long)blockIdx.x * blockDim.x + threadIdx.x; c < R.ncell; c += (long)gridDim.x * blockDim.x) {
+    const double rho = R.rho[c];
+    ChemEq q;
+    q.nh = psi * rho / mh;
+    q.nhe = (1. - psi) * rho / mhe;
+    // rate coefficients at this temperature (:3747-3766): the same in every pass
+    double logtem = R.logtem[c];
+    logtem = fmax(logtem, R.logtem0);
+    logtem = fmin(logtem, R.logtem9);
+    int ix = (int)((logtem - R.logtem0) / R.dlogtem) + 1;
+    ix = ix < 1 ? 1 : ix;
+    ix = ix > R.nratec - 1 ? R.nratec - 1 : ix;
+    const double t1 = R.logtem0 + (double)(ix - 1) * R.dlogtem, t2 = R.logtem0 + (double)ix * R.dlogtem, tdef = t2 - t1;
+    double kk[6];
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+        const double *ka = R.k + (size_t)r * R.nratec;
+        kk[r] = ka[ix - 1] + (logtem - t1) * (ka[ix] - ka[ix - 1]) / tdef;
+    }
+    q.k1 = kk[0]; q.k2 = kk[1]; q.k3 = kk[2]; q.k4 = kk[3]; q.k5 = kk[4]; q.k6 = kk[5];
+
+    double cHI = R.HI[c], cHeI = R.HeI[c], cHeII = R.HeII[c]; // currentCell%HI, %HeI, %HeII on entry to the pass
+    bool ok = true;
+    for (int pass = 0; pass < R.passes && ok; ++pass) {
+        // :3710-3726.  HII is dead (de is reassigned before use).  Of the HeIII clip only this survives: currentCell%HeI and
+        // %HeII are overwritten at the end, so the local HeII = 0 of the inner branch is its one effect, and that branch tests
+        // the REASSIGNED currentCell%HeII = nhe - HeI0 (unlike :3504-3513)
+        double HI = fmin(cHI, q.nh), HeI = cHeI;
+        const double HeII = (q.nhe - cHeI - cHeII < 0. && q.nhe - cHeI < 0.) ? 0. : cHeII;
+        // uniform background only, behind the self-shielding test (:3731-3743); HI clipped, HeI unclipped
+        const double mfp = 1. / (HI * (double)6.3e-18f + HeI * (double)7.42e-18f + HeII * (double)1.58e-18f);
+        const bool lit = mfp >= R.threshold;
+        q.kr24 = lit ? 4. * pi * R.uniform[0] : 0.;
+        q.kr25 = lit ? 4. * pi * R.uniform[1] : 0.;
+        q.kr26 = lit ? 4. * pi * R.uniform[2] : 0.;
+        // bisection, :3771-3807: bracket from a default-real 1.e-20, res1 taken once at de1 and never updated, run until HeI
+        // stops changing at all
+        double de1 = (double)1.e-20f, de2 = q.nh + 2. * q.nhe;
+        double HX;
+        const double res1 = chem_residual_as<true>(q, de1, HeI, HX);
+        (void)chem_residual_as<true>(q, de2, HeI, HX);
+        double de = de2, HeIprev = -1.;
+        unsigned steps = 0;
+        while (HeI != HeIprev && steps < 4096u) { // (the reference loops forever on a NaN HeI: capped, and a failure)
+            HeIprev = HeI;
+            de = 0.5 * (de1 + de2);
+            const double res = chem_residual_as<true>(q, de, HeI, HX);
+            const bool opposite = (res > 0. && res1 < 0.) || (res < 0. && res1 > 0.); // :5044-5058
+            if (opposite) de2 = de;
+            else de1 = de;
+            ++steps;
+        }
+        my_steps += (unsigned long long)steps;
+        // :3808-3818: HIprev, HeIIprev are HI, HeII (unchanged inside the loop) once the loop has run, -1 if it has not
+        const double HIprev = steps ? HI : -1., HeIIprev = steps ? HeII : -1.;
+        const bool converged = HeI == HeIprev && !(HIprev != HI) && !(HeIIprev != HeII);
+        // :3820-3823
+        const double X = q.k3 * de + q.kr26, Y = q.k4 * de;
+        const double HII = q.nh / (1. + q.k2 * de / (q.k1 * de + q.kr24));
+        HI = q.k2 * HII * de / (q.k1 * de + q.kr24);
+        // :3832-3843
+        ok = converged && (HI / q.nh >= 0. && HI / q.nh <= 1.) && (HeI / q.nhe >= 0. && HeI / q.nhe <= 1.);
+        cHI = HI; cHeI = HeI; cHeII = HeI * X / Y;
+    }
+    if (!ok) my_bad = (unsigned long long)c < my_bad ? (unsigned long long)c : my_bad;
+    else { R.HI_out[c] = cHI; R.HeI_out[c] = cHeI; R.HeII_out[c] = cHeII; }
+    }
+    // wavefront, then workgroup, then one atomic each (as rate_equations_kernel)
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long os = __shfl_xor(my_steps, off), ob = __shfl_xor(my_bad, off);
+        my_steps += os;
+        my_bad = ob < my_bad ? ob : my_bad;
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { blk_steps[wave] = my_steps; blk_bad[wave] = my_bad; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; ++k) {
+            my_steps += blk_steps[k];
+            my_bad = blk_bad[k] < my_bad ? blk_bad[k] : my_bad;
+        }
+        if (my_bad != ~0ull) atomicMin(R.first_bad, my_bad);
+        if (my_steps) atomicAdd(R.steps, my_steps);
+    }
+}
+
+int launch_initial_equilibrium(const ChemRec &R, hipStream_t stream)
+{
+    if (R.ncell <= 0) return 0;
+    if (R.passes < 1) return -1;
+    const long blocks = (R.ncell + 255) / 256;
+    hipLaunchKernelGGL(initial_equilibrium_kernel, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, stream, R);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// computeMass (equiSources.f90:4369-4393) per leaf: HI mh cs3/msun and psi rho cs3/msun, cs3 the cube of the cell's size, each
+// term with the reference's operations in its order.  The sums are the code's own and deterministic: every thread adds its
+// cells in grid-stride order, the workgroup folds its 256 sums as a fixed tree, and mass_total_kernel adds the workgroups'
+// partial sums in a fixed order too.  No floating-point atomics.
+__device__ __forceinline__ void tree_sum_256(double *a, double *b)
+{
+    for (int w = 128; w > 0; w >>= 1) {
+        __syncthreads();
+        if ((int)threadIdx.x < w) { a[threadIdx.x] += a[threadIdx.x + w]; b[threadIdx.x] += b[threadIdx.x + w]; }
+    }
+    __syncthreads();
+}
+
+__global__ void __launch_bounds__(256) hydrogen_mass_kernel(const int8_t *__restrict__ level, const double *__restrict__ HI,
+                                                            const double *__restrict__ rho, long ncell, int n, double box,
+                                                            double *__restrict__ part)
+{
+    __shared__ double sn[256], st[256];
+    const double psi = (double)0.76f, mh = (double)1.6726231e-24f, msun = (double)1.98892e33f; // definitionsModule.f90:25-29, 261
+    double an = 0., at = 0.;
+    for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < ncell; c += (long)gridDim.x * 256) {
+        const double size = box / (double)((float)(1 << level[c]) * (float)n);
+        const double cs3 = size * size * size;
+        an += HI[c] * mh * cs3 / msun;
+        at += psi * rho[c] * cs3 / msun;
+    }
+    sn[threadIdx.x] = an; st[threadIdx.x] = at;
+    tree_sum_256(sn, st);
+    if (threadIdx.x == 0) { part[blockIdx.x] = sn[0]; part[kMassBlocks + blockIdx.x] = st[0]; }
+}
+
+__global__ void __launch_bounds__(256) mass_total_kernel(double *part, int nblocks)
+{
+    __shared__ double sn[256], st[256];
+    double an = 0., at = 0.;
+    for (int b = threadIdx.x; b < nblocks; b += 256) { an += part[b]; at += part[kMassBlocks + b]; }
+    sn[threadIdx.x] = an; st[threadIdx.x] = at;
+    tree_sum_256(sn, st);
+    if (threadIdx.x == 0) { part[2 * kMassBlocks] = sn[0]; part[2 * kMassBlocks + 1] = st[0]; }
+}
+
+int launch_hydrogen_mass(const int8_t *level, const double *HI, const double *rho, long ncell, int n, double box, double *part,
+                         hipStream_t stream)
+{
+    if (ncell < 1 || n < 1 || !part) return -1;
+    const long want = (ncell + 255) / 256;
+    const int blocks = (int)(want < kMassBlocks ? want : kMassBlocks);
+    hipLaunchKernelGGL(hydrogen_mass_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, level, HI, rho, ncell, n, box, part);
+    if (hipGetLastError() != hipSuccess) return -2;
+    hipLaunchKernelGGL(mass_total_kernel, dim3(1), dim3(256), 0, stream, part, blocks);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
 // kappa[g][c] = HI[c]*beta[0][g] + HeI[c]*beta[1][g] + HeII[c]*beta[2][g]   (equiSources.f90:4977-4980)
 __global__ void __launch_bounds__(256) opacity_kernel(const double *__restrict__ HI, const double *__restrict__ HeI,
                                                       const double *__restrict__ HeII, const double *__restrict__ beta,
