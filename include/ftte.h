@@ -338,7 +338,9 @@ int ftte_host_unregister(ftte_ctx *ctx, void *ptr);
  * option "dataflow" asks for falls back to 1 or 0 where the XCD census or the grid size does not allow it; -1 before the first);
  * "brick_groups" and "brick_accumulators" (also "_0", "_1", "_2" per memory layout): direction groups of the current brick plan and
  * the J accumulators they share (0 without a plan), "brick_chunk" (layers per brick of that plan) and "brick_queue_mix" (the
- * option "queue_mix" the persistent form's queues were laid out by; -1 when the plan has no queues); "devices"; of a multi-device context also "frequency_slices",
+ * option "queue_mix" the persistent form's queues were laid out by; -1 when the plan has no queues); "brick_stages" (stages of that
+ * plan), "merge_points" and "merge_blocks" (its block-wise merge: points and 32^3-cell blocks), "merge_stage_K" and "merge_final_K"
+ * (the stage after which point K runs, the blocks final by then); "devices"; of a multi-device context also "frequency_slices",
  * "direction_slices" and "multi_rccl" (1: the last direction-split sweep was summed over RCCL), "rccl_loadable", "rccl_selftest" (runs the
  * direction sum's RCCL calls on a clique of one rank, the first device: 1 = the piece came back unchanged; negative = it could not
  * run), the rest from its first device.
@@ -358,6 +360,8 @@ long long ftte_counter(const ftte_ctx *ctx, const char *name);
  *                   write-through stores, 3 one launch of persistent workgroups with a task queue per XCD
  *     "tiled"       bricks: 1 = opacities and accumulators stored brick by brick (a brick's layer in one piece; grids of whole
  *                   bricks), 2 = the whole brick in one piece; same results, measured without gain; 0 = in frames (default)
+ *     "merge_overlap" bricks: 1 (default) = J merged block by block (32^3 cells) while the last stages run, 0 = one merge after
+ *                   the last stage; same results
  *     "team"        bricks: 0 = one wavefront per brick, 2 = two wavefronts per
  *                   brick, four rows each ("pair_waves": workgroups per SIMD that form is compiled for, 2..4); -1 (default):
  *                   2 with up to four frequency groups on this GPU, else 0

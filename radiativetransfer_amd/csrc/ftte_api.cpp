@@ -78,6 +78,7 @@ int ftte_destroy(ftte_ctx *c)
     if (c->h_berror) (void)hipHostFree(c->h_berror);
     if (c->d_blayers) (void)hipFree(c->d_blayers);
     if (c->d_bgroups) (void)hipFree(c->d_bgroups);
+    if (c->d_mblocks) (void)hipFree(c->d_mblocks);
     if (c->d_btasks) (void)hipFree(c->d_btasks);
     if (c->d_faces) (void)hipFree(c->d_faces);
     if (c->d_layers) (void)hipFree(c->d_layers);
@@ -107,6 +108,7 @@ int ftte_destroy(ftte_ctx *c)
     for (auto &q : c->lane_stream) (void)hipStreamDestroy(q);
     for (auto &e : c->pipe_up) (void)hipEventDestroy(e);
     for (auto &e : c->lane_done) (void)hipEventDestroy(e);
+    for (auto &e : c->ev_merge_point) (void)hipEventDestroy(e);
     if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
     for (auto &e : c->ev_combine) if (e) (void)hipEventDestroy(e);
     if (c->host_J_dev) (void)hipFree(c->host_J_dev);
@@ -220,16 +222,18 @@ int ftte_set_opacity_device(ftte_ctx *c, int nnu, const double *kappa_dev)
     FTTE_HIP(c, hipSetDevice(c->device));
     if ((rc = wait_sweep(c))) return rc;
     if ((rc = ensure_kappa(c, nnu))) return rc;
-    // A uniform grid whose last sweep used all three layouts (the copies are there): the copy and the two transposes in one pass
-    // over the caller's array.  Else the copy alone; the sweep makes what it needs.
-    const bool all_three = !c->use_forest && c->kappa[1] && c->kappa[2] && c->kappa_ready[1] && c->kappa_ready[2] && c->nnu == nnu && !c->tiled_opt;
-    if (all_three) {
-        if (launch_set_layouts(kappa_dev, c->kappa[0], c->kappa[1], c->kappa[2], c->n, nnu, (long)c->ncell, c->stream))
+    // A uniform grid whose last sweep used the transposed layout 2 (the copy is there): the copy and the transposes in one pass over
+    // the caller's array, layout 1 too where the last sweep used it (the tile engine; the brick engine marches layout 1 through
+    // layout 0).  Else the copy alone; the sweep makes what it needs.
+    const bool same = !c->use_forest && c->nnu == nnu && !c->tiled_opt;
+    const bool with2 = same && c->kappa[2] && c->kappa_ready[2], with1 = with2 && c->kappa[1] && c->kappa_ready[1];
+    if (with2) {
+        if (launch_set_layouts(kappa_dev, c->kappa[0], with1 ? c->kappa[1] : nullptr, c->kappa[2], c->n, nnu, (long)c->ncell, c->stream))
             return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
     } else FTTE_HIP(c, hipMemcpyAsync(c->kappa[0], kappa_dev, sizeof(double) * nnu * c->ncell, hipMemcpyDeviceToDevice, c->stream));
     FTTE_HIP(c, hipStreamSynchronize(c->stream)); // the sweep may run on another stream: the copies must have landed
     c->nnu = nnu;
-    c->kappa_ready[0] = true; c->kappa_ready[1] = c->kappa_ready[2] = all_three; c->kappa_ready[3] = false;
+    c->kappa_ready[0] = true; c->kappa_ready[1] = with1; c->kappa_ready[2] = with2; c->kappa_ready[3] = false;
     ++c->n_kappa_sets;
     return FTTE_OK;
 }
@@ -357,6 +361,9 @@ int ftte_set_option(ftte_ctx *c, const char *key, int value)
     } else if (!std::strcmp(key, "dataflow")) {
         if (value < 0 || value > 3) return fail(c, FTTE_ERR_ARG, "dataflow must be 0 (a launch per stage), 1 (one launch, bricks wait for each other), 2 (the same with write-through stores) or 3 (persistent workgroups, a task queue per XCD)");
         c->dataflow = value;
+    } else if (!std::strcmp(key, "merge_overlap")) {
+        if (value != 0 && value != 1) return fail(c, FTTE_ERR_ARG, "merge_overlap must be 0 (the brick sweep merges J after its last stage) or 1 (block by block as the stages finish them)");
+        c->merge_overlap = value;
     } else if (!std::strcmp(key, "lanes")) {
         if (value < 1 || value > 16) return fail(c, FTTE_ERR_ARG, "lanes (streams the brick sweep spreads its frequency groups over) must be 1..16");
         c->lanes = value;
@@ -505,6 +512,15 @@ long long ftte_counter(const ftte_ctx *c, const char *name)
     if (!std::strcmp(name, "brick_accumulators_0")) return c->bplan.valid ? c->bplan.nacc[0] : 0;
     if (!std::strcmp(name, "brick_accumulators_1")) return c->bplan.valid ? c->bplan.nacc[1] : 0;
     if (!std::strcmp(name, "brick_accumulators_2")) return c->bplan.valid ? c->bplan.nacc[2] : 0;
+    if (!std::strcmp(name, "brick_stages")) return c->bplan.valid ? c->bplan.nstages : 0;
+    if (!std::strcmp(name, "merge_points")) return c->bplan.valid ? (long long)c->bplan.merge_stage.size() : 0;
+    if (!std::strcmp(name, "merge_blocks")) return c->bplan.valid ? (long long)c->bplan.merge_blocks.size() : 0;
+    if (!std::strncmp(name, "merge_stage_", 12) || !std::strncmp(name, "merge_final_", 12)) { // merge point k: its stage, blocks final by then
+        char *end = nullptr;
+        const long k = std::strtol(name + 12, &end, 10);
+        if (!c->bplan.valid || end == name + 12 || *end || k < 0 || k >= (long)c->bplan.merge_stage.size()) return -1;
+        return name[6] == 's' ? c->bplan.merge_stage[(size_t)k] : (long long)c->bplan.merge_off[(size_t)k + 1];
+    }
     return -1;
 }
 

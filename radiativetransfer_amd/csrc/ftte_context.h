@@ -97,6 +97,13 @@ struct BrickPlan {
     int ntu = 0, ntv = 0, nti = 0, up = 0, vp = 0, max_dirs = 0;
     int64_t face_elems = 0, vface_off = 0, iface_off = 0;
     int nacc[3] = {0, 0, 0};
+    // Merge blocks (option "merge_overlap", stages on one lane of groups): kMergeBlock^3 cells aligned with merge_kernel's tiles.
+    // Merge point m runs after stage merge_stage[m] and sums the blocks merge_blocks[merge_off[m] .. merge_off[m + 1]) (block id
+    // (bi * nmb + bj) * nmb + bk, bi along ic): those whose last writer is in a stage after merge_stage[m - 1] and not after merge_stage[m].
+    int nmb = 0;
+    std::vector<int32_t> merge_blocks;
+    std::vector<int> merge_stage;
+    std::vector<size_t> merge_off;
 };
 
 struct LaunchTiming {
@@ -213,6 +220,11 @@ struct ftte_ctx {
     // partial merges run beside the sweeps of the next layout on their own (non-blocking) stream
     hipStream_t merge_stream = nullptr;
     hipEvent_t ev_layout_done = nullptr, ev_merge_done = nullptr, ev_layouts_ready = nullptr;
+    // brick sweep, option "merge_overlap" (1 = default): J merged block by block on merge_stream as the stages finish the blocks
+    // (BrickPlan::merge_blocks), behind ev_merge_point[lane * points + m] of each lane; 0 = one merge after the last stage
+    int merge_overlap = 1;
+    std::vector<hipEvent_t> ev_merge_point;
+    int32_t *d_mblocks = nullptr; size_t d_mblocks_cap = 0;
     // end of the last sweep on whatever stream the caller gave it: the setters and the next sweep wait for it before they
     // overwrite what that sweep reads
     hipEvent_t ev_sweep_done = nullptr;

@@ -60,6 +60,7 @@ static_assert(sizeof(WorkItem) == 12, "WorkItem must be 12 bytes");
 
 constexpr int kMaxSlots = 16; // directions of one tile-kernel launch
 constexpr int kMaxAcc = 32;   // J accumulators per memory layout (tile kernel: one per slot; bricks: one per group)
+constexpr int kMergeBlock = 32; // cells a side of a merge block (BrickPlan::merge_blocks): one 32 x 32 tile of merge_kernel per ic plane
 
 struct LaunchRec {
     DirRec dir[kMaxSlots];

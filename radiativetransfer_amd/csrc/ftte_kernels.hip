@@ -440,8 +440,8 @@ __global__ void __launch_bounds__(256) to_layout2_kernel(const double *__restric
 }
 
 // The caller's opacities (cell-array order) into the library's three copies in ONE pass: dst0 as they come, dst1[jc][ic][kc] the
-// same rows elsewhere, dst2[kc][ic][jc] each ic plane transposed through LDS.  Read once, written three times (a copy and two
-// transposes read them three times).
+// same rows elsewhere (skipped when dst1 is null), dst2[kc][ic][jc] each ic plane transposed through LDS.  Read once, written three
+// times (a copy and two transposes read them three times).
 __global__ void __launch_bounds__(256) set_layouts_kernel(const double *__restrict__ src, double *__restrict__ dst0, double *__restrict__ dst1,
                                                           double *__restrict__ dst2, int n, long group_stride)
 {
@@ -456,7 +456,7 @@ __global__ void __launch_bounds__(256) set_layouts_kernel(const double *__restri
             const double v = src[base + ((long)ic * n + j0 + r) * n + k0 + tx];
             tile[r][tx] = v;
             dst0[base + ((long)ic * n + j0 + r) * n + k0 + tx] = v;
-            dst1[base + ((long)(j0 + r) * n + ic) * n + k0 + tx] = v;
+            if (dst1) dst1[base + ((long)(j0 + r) * n + ic) * n + k0 + tx] = v;
         }
     __syncthreads();
     for (int r = ty; r < 32; r += 8)
@@ -497,14 +497,29 @@ struct MergeRec {
 // leaf_of_base != nullptr (hybrid sweep of a refined cell array): the accumulators are arrays over the BASE cells (group stride
 // n^3) and J is in cell-array order (group stride j_stride): element (ic, jc, kc) goes to its leaf, refined base cells are skipped.
 // tiled: the accumulators are in brick order (tiled_index)
+// blocks != nullptr: only the merge blocks listed there (kMergeBlock^3 cells, id (bi * nmb + bj) * nmb + bk): blockIdx.x the list entry,
+// blockIdx.y the ic plane inside the block, blockIdx.z the group; the same sums per cell as the merge of the whole grid
 template <bool tiled>
 __global__ void __launch_bounds__(256) merge_kernel(const MergeRec M, double *__restrict__ J, int n, long group_stride, int accumulate,
-                                                    const int32_t *__restrict__ leaf_of_base, long j_stride, int tchunk)
+                                                    const int32_t *__restrict__ leaf_of_base, long j_stride, int tchunk,
+                                                    const int32_t *__restrict__ blocks, int nmb)
 {
+    static_assert(kMergeBlock == 32, "a merge block is one tile per ic plane");
     __shared__ double tile[32][33];
-    const long g = blockIdx.z / n;
-    const int ic = blockIdx.z % n;
-    const int j0 = blockIdx.y * 32, k0 = blockIdx.x * 32;
+    long g;
+    int ic, j0, k0;
+    if (blocks) {
+        const int b = blocks[blockIdx.x];
+        const int bi = b / (nmb * nmb), bj = (b / nmb) % nmb, bk = b % nmb;
+        g = blockIdx.z;
+        ic = bi * kMergeBlock + (int)blockIdx.y;
+        j0 = bj * kMergeBlock; k0 = bk * kMergeBlock;
+        if (ic >= n) return; // (the whole workgroup: a ragged last block)
+    } else {
+        g = blockIdx.z / n;
+        ic = blockIdx.z % n;
+        j0 = blockIdx.y * 32; k0 = blockIdx.x * 32;
+    }
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
     double sum[4] = {0.0, 0.0, 0.0, 0.0};
     bool have = false;
@@ -589,8 +604,22 @@ int launch_merge(const double *const *acc, const int *layout, int count, double 
     M.count = count;
     for (int a = 0; a < count; ++a) { M.acc[a] = acc[a]; M.layout[a] = layout[a]; }
     const dim3 grid((n + 31) / 32, (n + 31) / 32, n * nnu);
-    if (tiled) hipLaunchKernelGGL(merge_kernel<true>, grid, dim3(256), 0, stream, M, J, n, group_stride, accumulate ? 1 : 0, leaf_of_base, j_stride, tchunk);
-    else hipLaunchKernelGGL(merge_kernel<false>, grid, dim3(256), 0, stream, M, J, n, group_stride, accumulate ? 1 : 0, leaf_of_base, j_stride, tchunk);
+    if (tiled) hipLaunchKernelGGL(merge_kernel<true>, grid, dim3(256), 0, stream, M, J, n, group_stride, accumulate ? 1 : 0, leaf_of_base, j_stride, tchunk, nullptr, 0);
+    else hipLaunchKernelGGL(merge_kernel<false>, grid, dim3(256), 0, stream, M, J, n, group_stride, accumulate ? 1 : 0, leaf_of_base, j_stride, tchunk, nullptr, 0);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int launch_merge_blocks(const double *const *acc, const int *layout, int count, double *J, int n, int nnu, long group_stride,
+                        const int32_t *blocks, int nblocks, int nmb, hipStream_t stream, bool tiled, int tchunk)
+{
+    if (count > 3 * kMaxAcc || nmb != (n + kMergeBlock - 1) / kMergeBlock) return -1;
+    if (nblocks == 0 || nnu == 0) return 0;
+    MergeRec M;
+    M.count = count;
+    for (int a = 0; a < count; ++a) { M.acc[a] = acc[a]; M.layout[a] = layout[a]; }
+    const dim3 grid(nblocks, kMergeBlock, nnu);
+    if (tiled) hipLaunchKernelGGL(merge_kernel<true>, grid, dim3(256), 0, stream, M, J, n, group_stride, 0, nullptr, 0l, tchunk, blocks, nmb);
+    else hipLaunchKernelGGL(merge_kernel<false>, grid, dim3(256), 0, stream, M, J, n, group_stride, 0, nullptr, 0l, tchunk, blocks, nmb);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

@@ -449,6 +449,59 @@ int build_brick_plan(ftte_ctx *c, int ndir, const double *phi, const double *the
             for (int k = 0; k < kBrickDeps; ++k)
                 if (P.deps[q * kBrickDeps + k] >= (int32_t)q) return fail(c, FTTE_ERR_STATE, "brick plan: a dependency does not precede its brick");
     }
+    // Merge blocks: the stage of the last task that writes into each kMergeBlock^3 block of cells, in any accumulator.  A brick holds,
+    // along the storage axes (ic, jc, kc) of its layout, the layers chunk * ti + 1 .. of the march axis, the rows kBrickRows * tv + 1 ..
+    // of the middle one and the columns 64 tu + 1 .. of the contiguous one, each counted from the far end where the frame mirrors it.
+    // The blocks are then cut into merge points: after the stages by which half, three quarters, ... of them are final, and after the
+    // last stage.  (Points from an eighth of the blocks on: 0.3 ms per 256^3 x 8 x 96 step slower -- the early merges only take
+    // bandwidth from wide stages -- and three points: 0.1 ms slower; profiles/README.md.)
+    P.nmb = 0; P.merge_blocks.clear(); P.merge_stage.clear(); P.merge_off.clear();
+    if (!P.dataflow && P.glanes == 1 && !P.tasks.empty()) {
+        const int nmb = (n + kMergeBlock - 1) / kMergeBlock;
+        const size_t nblk = (size_t)nmb * nmb * nmb;
+        P.nmb = nmb;
+        std::vector<int> last(nblk, nstages - 1); // (every block is written; the default only keeps a gap safe)
+        std::vector<char> seen(nblk, 0);
+        for (int st = 0; st < nstages; ++st)
+            for (size_t q = P.stage_off[(size_t)st]; q < P.stage_off[(size_t)st + 1]; ++q) {
+                const BrickTask &T = P.tasks[q];
+                const BrickPlan::Group &G = P.groups[(size_t)T.group];
+                const DirPlan &D0 = P.dirs[G.dirs[0]];
+                const int march_c = G.layout, fast_c = march_c == 2 ? 1 : 2, mid_c = march_c == 0 ? 1 : 0;
+                int lo[3], hi[3];
+                auto span = [&](int axis, int first, int len, bool mirror) { // cells first .. first + len - 1 (0-based) of the frame axis
+                    const int a = first, b = std::min(first + len, n) - 1;
+                    lo[axis] = (mirror ? n - 1 - b : a) / kMergeBlock;
+                    hi[axis] = (mirror ? n - 1 - a : b) / kMergeBlock;
+                };
+                span(march_c, chunk * (T.ti & (kBrickAccumulate - 1)), chunk, D0.si < 0);
+                span(mid_c, kBrickRows * T.tv, kBrickRows, D0.sv < 0);
+                span(fast_c, 64 * T.tu, 64, D0.su < 0);
+                for (int bi = lo[0]; bi <= hi[0]; ++bi)
+                    for (int bj = lo[1]; bj <= hi[1]; ++bj)
+                        for (int bk = lo[2]; bk <= hi[2]; ++bk) {
+                            const size_t b = ((size_t)bi * nmb + bj) * nmb + bk;
+                            last[b] = seen[b] ? std::max(last[b], st) : st;
+                            seen[b] = 1;
+                        }
+            }
+        std::vector<int32_t> order(nblk);
+        for (size_t b = 0; b < nblk; ++b) order[b] = (int32_t)b;
+        std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return last[(size_t)x] < last[(size_t)y]; });
+        static const double kFrac[] = {4. / 8, 6. / 8, 7. / 8, 15. / 16, 31. / 32, 1.};
+        P.merge_off.push_back(0);
+        for (double f : kFrac) {
+            const size_t want = std::min(nblk, std::max<size_t>(1, (size_t)std::ceil(f * (double)nblk)));
+            const int st = f >= 1. ? nstages - 1 : last[(size_t)order[want - 1]];
+            if (!P.merge_stage.empty() && st <= P.merge_stage.back()) continue;
+            size_t end = P.merge_off.back();
+            while (end < nblk && last[(size_t)order[end]] <= st) ++end;
+            if (end == P.merge_off.back() && st != nstages - 1) continue;
+            P.merge_stage.push_back(st);
+            P.merge_off.push_back(end);
+        }
+        P.merge_blocks = std::move(order);
+    }
     P.persistent = false;
     if (P.dataflow && want_dataflow == 3 && !P.tasks.empty()) {
         // Queues.  What a brick waits for belongs to its own frequency group and to the groups of directions that share its

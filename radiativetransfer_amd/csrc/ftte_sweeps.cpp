@@ -475,6 +475,10 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
     const bool tiled = c->tiled_opt && !pipe && !c->emit_mode && n % 64 == 0 && n % kBrickRows == 0 &&
                        (c->tiled_opt == 1 || n % P.chunk == 0);
     const int tchunk = tiled && c->tiled_opt == 2 ? P.chunk : 0; // 2: a whole brick in one piece
+    // Layout 1 ([jc][ic][kc]) holds the rows of layout 0 ([ic][jc][kc]) in another order: its groups march along jc through the
+    // layout-0 frame itself (BrickGroup si = +-n, sv = +-n^2), read kappa[0] and leave their accumulators in layout-0 order.  Only
+    // layout 2, whose march runs along the contiguous axis, needs a transposed copy.  (Brick order keeps its own copy per layout.)
+    auto frame = [tiled](int l) { return l == 1 && !tiled ? 0 : l; };
     // accumulators and the opacity in the layouts the groups march through
     for (int l = 0; l < 3; ++l) {
         for (int s = 0; s < P.nacc[l]; ++s)
@@ -487,7 +491,7 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
                 c->kappa_tiled_from[l] = c->n_kappa_sets;
                 c->kappa_tiled_chunk[l] = tchunk;
             }
-        } else if (P.nacc[l] && !c->kappa_ready[l]) {
+        } else if (P.nacc[l] && frame(l) == l && !c->kappa_ready[l]) {
             if (!c->kappa[l]) FTTE_HIP(c, hipMalloc((void **)&c->kappa[l], sizeof(double) * c->kappa_cap));
             if (!lane_ends) {
                 if (launch_to_layout(l, c->kappa[0], c->kappa[l], n, nnu, (long)c->ncell, stream))
@@ -495,7 +499,7 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
                 c->kappa_ready[l] = true;
             } else lane_layout[l] = true;
         }
-        if (P.nacc[l] && c->emit_mode && !c->emis_ready[l]) {
+        if (P.nacc[l] && frame(l) == l && c->emit_mode && !c->emis_ready[l]) {
             if (!c->emis[l]) FTTE_HIP(c, hipMalloc((void **)&c->emis[l], sizeof(double) * c->kappa_cap));
             if (launch_to_layout(l, c->emis[0], c->emis[l], n, nnu, (long)c->ncell, stream))
                 return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
@@ -516,6 +520,10 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
             if ((rc = ensure(c, &c->d_bdeps, &c->d_bdeps_cap, P.deps.size()))) return rc;
             FTTE_HIP(c, hipMemcpy(c->d_bdeps, P.deps.data(), sizeof(int32_t) * P.deps.size(), hipMemcpyHostToDevice));
         }
+        if (!P.merge_blocks.empty()) {
+            if ((rc = ensure(c, &c->d_mblocks, &c->d_mblocks_cap, P.merge_blocks.size()))) return rc;
+            FTTE_HIP(c, hipMemcpy(c->d_mblocks, P.merge_blocks.data(), sizeof(int32_t) * P.merge_blocks.size(), hipMemcpyHostToDevice));
+        }
         c->bplan_uploaded = true;
         c->bqueue_uploaded = false;
     }
@@ -526,10 +534,16 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
         for (size_t g = 0; g < P.groups.size(); ++g) {
             const BrickPlan::Group &H = P.groups[g];
             const DirPlan &D0 = P.dirs[H.dirs[0]];
-            G[g].kappa = tiled ? c->kappa_tiled[H.layout] : c->kappa[H.layout];
-            G[g].emis = c->emit_mode ? c->emis[H.layout] : nullptr;
+            G[g].kappa = tiled ? c->kappa_tiled[H.layout] : c->kappa[frame(H.layout)];
+            G[g].emis = c->emit_mode ? c->emis[frame(H.layout)] : nullptr;
             G[g].J = c->acc[H.layout][H.acc];
             G[g].org = D0.org; G[g].si = D0.si; G[g].sv = D0.sv; G[g].su = D0.su;
+            if (frame(H.layout) != H.layout) { // march (jc) stride n, rows (ic) n^2 apart; a mirrored axis enters from its far end
+                const int64_t nn = (int64_t)n * n;
+                G[g].si = D0.si > 0 ? n : -n;
+                G[g].sv = (int32_t)(D0.sv > 0 ? nn : -nn);
+                G[g].org = -1 + (D0.sv > 0 ? -nn : n * nn) + (D0.si > 0 ? -(int64_t)n : nn);
+            }
             if (tiled) { // cell (brick tu, tv; row r; lane; layer i) at org + i * si + tu * bu + tv * bv + r * sv + lane (63 - lane mirrored)
                 const int64_t ntu = n / 64, ntv = n / kBrickRows, piece = 64 * kBrickRows;
                 G[g].sv = D0.sv > 0 ? 64 : -64;
@@ -585,6 +599,14 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
         c->lane_stream.push_back(q); c->lane_done.push_back(e);
     }
     if (!c->ev_fork) FTTE_HIP(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+    // (the plan has merge blocks only for stages on one lane of groups; with host arrays every lane merges its own after its stages)
+    const bool overlap = c->merge_overlap && !lane_ends && !P.dataflow && P.glanes == 1 && !P.groups.empty() && !P.merge_stage.empty();
+    const size_t npoints = overlap ? P.merge_stage.size() : 0;
+    while (c->ev_merge_point.size() < (size_t)nlanes * npoints) {
+        hipEvent_t e;
+        FTTE_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        c->ev_merge_point.push_back(e);
+    }
     while (c->timing.size() < 1) {
         LaunchTiming t;
         FTTE_HIP(c, hipEventCreate(&t.start));
@@ -688,8 +710,19 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
                         return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
                 FTTE_HIP(c, hipEventRecord(T.first[(size_t)lane], q));
             }
-            for (size_t st = 0; st < nstages; ++st) {
-                if (off[st + 1] == off[st]) continue;
+            for (size_t st = 0, mp = 0; st < nstages; ++st) {
+                // (after the stage: this lane's part of the blocks merge point mp waits for, recorded even behind an empty stage)
+                auto merge_point = [&]() -> int {
+                    if (overlap && mp < npoints && (size_t)P.merge_stage[mp] == st) {
+                        FTTE_HIP(c, hipEventRecord(c->ev_merge_point[(size_t)lane * npoints + mp], q));
+                        ++mp;
+                    }
+                    return FTTE_OK;
+                };
+                if (off[st + 1] == off[st]) {
+                    if ((rc = merge_point())) return rc;
+                    continue;
+                }
                 BrickLaunch L;
                 std::memset(&L, 0, sizeof L);
                 L.groups = c->d_bgroups;
@@ -710,13 +743,14 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
                 c->last_brick_dataflow = 0;
                 const int lrc = form == 2 ? launch_brick_pair(L, P.max_dirs, c->pair_waves, q) : launch_brick(L, P.max_dirs, c->brick_waves, q);
                 if (lrc) return fail(c, lrc == -1 ? FTTE_ERR_ARG : FTTE_ERR_NO_DEVICE, "brick kernel launch failed");
+                if ((rc = merge_point())) return rc;
             }
             if (lane_ends) { // this lane's J: merged as soon as its stages are done, and on its way back (pinned arrays) behind that
                 FTTE_HIP(c, hipEventRecord(T.last[(size_t)lane], q));
                 const double *accs[3 * kMaxAcc];
                 int layouts[3 * kMaxAcc], count = 0;
                 for (int l = 0; l < 3; ++l)
-                    for (int s2 = 0; s2 < P.nacc[l]; ++s2) { accs[count] = c->acc[l][s2] + slice0; layouts[count++] = l; }
+                    for (int s2 = 0; s2 < P.nacc[l]; ++s2) { accs[count] = c->acc[l][s2] + slice0; layouts[count++] = frame(l); }
                 if (launch_merge(accs, layouts, count, J_dev + slice0, n, nu1 - nu0, (long)c->ncell, false, q, nullptr, 0, tiled, tchunk))
                     return fail(c, FTTE_ERR_NO_DEVICE, "merge kernel launch failed");
                 if (pipe && is_registered(c, pipe->J + slice0, slice_bytes))
@@ -746,11 +780,31 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
         c->timing_used = 1;
     }
     // J = the groups' accumulators, layout after layout
-    if (!lane_ends || P.groups.empty()) {
+    if (overlap) {
+        // block by block as the stages finish them: merge point after merge point, each lane's frequency groups behind that lane's
+        // stage; the caller's stream goes on once the last blocks are in
         const double *accs[3 * kMaxAcc];
         int layouts[3 * kMaxAcc], count = 0;
         for (int l = 0; l < 3; ++l)
-            for (int s = 0; s < P.nacc[l]; ++s) { accs[count] = c->acc[l][s]; layouts[count++] = l; }
+            for (int s = 0; s < P.nacc[l]; ++s) { accs[count] = c->acc[l][s]; layouts[count++] = frame(l); }
+        for (size_t mp = 0; mp < npoints; ++mp)
+            for (int lane = 0; lane < nlanes; ++lane) {
+                const int nu0 = (int)((int64_t)nnu * lane / nulanes), nu1 = (int)((int64_t)nnu * (lane + 1) / nulanes);
+                const size_t slice0 = (size_t)nu0 * c->ncell;
+                const double *lane_accs[3 * kMaxAcc];
+                for (int a = 0; a < count; ++a) lane_accs[a] = accs[a] + slice0;
+                FTTE_HIP(c, hipStreamWaitEvent(c->merge_stream, c->ev_merge_point[(size_t)lane * npoints + mp], 0));
+                if (launch_merge_blocks(lane_accs, layouts, count, J_dev + slice0, n, nu1 - nu0, (long)c->ncell, c->d_mblocks + P.merge_off[mp],
+                                        (int)(P.merge_off[mp + 1] - P.merge_off[mp]), P.nmb, c->merge_stream, tiled, tchunk))
+                    return fail(c, FTTE_ERR_NO_DEVICE, "merge kernel launch failed");
+            }
+        FTTE_HIP(c, hipEventRecord(c->ev_merge_done, c->merge_stream));
+        FTTE_HIP(c, hipStreamWaitEvent(stream, c->ev_merge_done, 0));
+    } else if (!lane_ends || P.groups.empty()) {
+        const double *accs[3 * kMaxAcc];
+        int layouts[3 * kMaxAcc], count = 0;
+        for (int l = 0; l < 3; ++l)
+            for (int s = 0; s < P.nacc[l]; ++s) { accs[count] = c->acc[l][s]; layouts[count++] = frame(l); }
         if (count) {
             if (launch_merge(accs, layouts, count, J_dev, n, nnu, (long)c->ncell, false, stream, nullptr, 0, tiled, tchunk))
                 return fail(c, FTTE_ERR_NO_DEVICE, "merge kernel launch failed");
