@@ -97,13 +97,13 @@ __device__ __forceinline__ double brick_segment(const ftte_consts &K, double lea
     return ftte_segment_emit(&K, &I, kap * dpath, x, 0.0);              // the reference's emissivity term and its log-mean
 }
 
-template <int SHAPE, int EMIT, int RW = kBrickRows>
+template <int SHAPE, int EMIT, int RW = kBrickRows, bool VUVB = false>
 __device__ __forceinline__ void brick_step(const ftte_consts &K, double lead, double (&cur)[RW], const double (&kap)[RW],
                                            const double (&xs)[EMIT ? RW : 1],
                                            double (&Jacc)[RW], bool third_first, double d0, double d1, double d2,
                                            double w, double uvb, gcbyte *uin, gbyte *uout, gcbyte *vin, gbyte *vout, int lane, bool through = false,
                                            bool same_launch = false, int take_lane = 0, int hand_lane = 63, bool active = true,
-                                           const double *carry_in = nullptr, double *carry_out = nullptr)
+                                           const double *carry_in = nullptr, double *carry_out = nullptr, gcbyte *vuvb = nullptr)
 {
     // take_lane / hand_lane / active: a brick that sweeps only the lanes take_lane .. hand_lane (hybrid sweep of a refined cell
     // array: the others belong to the segment forest).  The rays waiting in `uin` then enter lane take_lane, lane hand_lane hands
@@ -126,7 +126,11 @@ __device__ __forceinline__ void brick_step(const ftte_consts &K, double lead, do
             }
         }
     }
-    if (HAS_V && vin) carry = same_launch ? fresh(vin + 8 * lane) : *(gcdouble *)(vin + 8 * lane);
+    // VUVB: vuvb is where the inflow lies in memory (brick_kernel<..., WHOLE>).  A brick at the domain's lower v-face then loads its
+    // inflow from there: one load on either path, whose wait the compiler can count, instead of a load on one path and a register on
+    // the other
+    if (HAS_V && VUVB) carry = *(gcdouble *)(vin ? vin + 8 * lane : vuvb);
+    else if (HAS_V && vin) carry = same_launch ? fresh(vin + 8 * lane) : *(gcdouble *)(vin + 8 * lane);
     if (HAS_V && carry_in) carry = carry_in[lane]; // pair kernel: the wavefront below left it in LDS
     const bool hands_u = HAS_U && uout != nullptr && lane == hand_lane;
 
@@ -204,7 +208,9 @@ __device__ __forceinline__ void brick_step(const ftte_consts &K, double lead, do
 // the segment forest cuts through; where the box's u-faces lie inside a brick, rays cross them through two face rings of their own.
 // FLOW: 0 a launch per stage; 1 one launch, a workgroup per brick, tickets from one counter (cross-XCD hand-overs: write-through
 // stores or an L2 write-back per brick); 2 one launch of persistent workgroups, a queue per XCD (BrickLaunch::queue).
-template <int WAVES, int EMIT, int FLOW, bool MASKED = false>
+// WHOLE: every brick whole (n a multiple of 64 and of kBrickRows), no atomic_acc, no ablate bits (launch_brick decides).  The
+// layer loop then holds no option the compiler has to branch around, and every wait in it is counted: see the loop below.
+template <int WAVES, int EMIT, int FLOW, bool MASKED = false, bool WHOLE = false>
 __global__ void __launch_bounds__(64, WAVES) brick_kernel(const BrickLaunch L)
 {
     extern __shared__ double state[]; // [slot][row][lane]: the rays of the directions that are not in registers
@@ -265,8 +271,10 @@ __global__ void __launch_bounds__(64, WAVES) brick_kernel(const BrickLaunch L)
     const int tv_field = uniform((int)T.tv);
     const int tv = MASKED ? tv_field & kBrickTvMask : tv_field, box = MASKED ? (tv_field >> kBrickBoxShift) & kBrickBoxMask : 0;
     const int ti = uniform((int)T.ti) & (kBrickAccumulate - 1);
-    const bool accumulate = (uniform((int)T.ti) & kBrickAccumulate) != 0 && !(L.pad2_ & 4);
-    const bool atomic_acc = L.atomic_acc != 0 && !through;
+    static_assert(!WHOLE || (EMIT == 0 && FLOW == 0 && !MASKED), "the whole-brick form is the plain stage launch");
+    // (pad2_: diagnostic option "ablate", below)
+    const bool accumulate = (uniform((int)T.ti) & kBrickAccumulate) != 0 && (WHOLE || !(L.pad2_ & 4));
+    const bool atomic_acc = !WHOLE && L.atomic_acc != 0 && !through;
     cgroup *G = (cgroup *)(L.groups + (MASKED ? group_field & kBrickGroupMask : group_field));
     const int n = L.n, chunk = L.chunk, up = L.up, vp = L.vp;
     const int ndir = G->ndir;
@@ -287,7 +295,7 @@ __global__ void __launch_bounds__(64, WAVES) brick_kernel(const BrickLaunch L)
     const int cuc = cu < n ? cu : n;
     const bool tiled = L.tiled != 0; // brick-ordered kappa and J (BrickLaunch::tiled): the lane's place in its row of the brick
     const unsigned off0 = tiled ? 8u * (unsigned)(mirror_u ? 63 - lane : lane) : 8u * (unsigned)(mirror_u ? n + 1 - cuc : cuc);
-    const bool own_lane = cu <= n && (!MASKED || (lane >= lane_lo && lane <= lane_hi));
+    const bool own_lane = WHOLE || (cu <= n && (!MASKED || (lane >= lane_lo && lane <= lane_hi)));
     const long row_bytes = 8l * sv;
     const int i0 = ti * chunk + 1;
     const int i1 = (i0 + chunk - 1 < n) ? i0 + chunk - 1 : n;
@@ -295,7 +303,7 @@ __global__ void __launch_bounds__(64, WAVES) brick_kernel(const BrickLaunch L)
     // (pad2_: diagnostic option "ablate" -- WRONG RESULTS, timing only: bit 0 no rays taken from the left and from below, bit 1 none
     // handed to the right and above, bit 2 no earlier J read, bit 3 no rays taken from or left for the chunks before and after,
     // bit 4 the opacities of a brick's first layer for all its layers, bit 5 no J stored)
-    const int ablate = L.pad2_;
+    const int ablate = WHOLE ? 0 : L.pad2_;
     const bool sub = !MASKED && L.sub != 0; // a sub-grid with neighbours all round (BrickLaunch::sub): rings at its faces too
     const bool has_u_in = (tu > 0 || lane_lo > 0 || sub) && !(ablate & 1), has_u_out = (64 * (tu + 1) < n || lane_hi < 63 || sub) && !(ablate & 2);
     const bool has_v_in = (tv > 0 || sub) && !(ablate & 1), has_v_out = (R * (tv + 1) < n || sub) && !(ablate & 2);
@@ -372,89 +380,187 @@ __global__ void __launch_bounds__(64, WAVES) brick_kernel(const BrickLaunch L)
     double kap_next[R];
     // (row addresses are walked with scalar additions; the rows a ragged last brick lacks repeat its last row's address for loads
     // and are skipped by stores)
-    const int nrows = n - cv0 + 1 < R ? n - cv0 + 1 : R;
+    const int nrows = WHOLE || n - cv0 + 1 >= R ? R : n - cv0 + 1;
     const long row0 = tiled ? 8l * ((long)tu * G->bu + (long)tv * G->bv + (long)ti * G->bi) : cv0 * row_bytes;
     load_rows<R, false>(kap_next, kbase + 8l * i0 * si + row0, off0, row_bytes, nrows);
     double cur[R];
-    // rays entering the brick's bottom: the inflow, or what the chunk below left
-    {
-        gcdouble *f = (gcdouble *)(G->dir[p0].faces + fnu);
+    if constexpr (WHOLE) {
+        // Whole bricks: every wait in the layer loop is counted (tools/brick_isa.py, tests/test_brick_isa.py).  vmcnt counts loads
+        // and stores together, in issue order, and where the compiler cannot count it waits for everything outstanding:
+        //  * a value the options choose between a register and a load (the rays entering from the chunk below or from the brick
+        //    below, at the domain's faces the inflow) is always loaded, at the domain's faces from uvb's own place in memory;
+        //  * the prologue's loads are retired once, before the loop: no pending load enters it through its header;
+        //  * the opacities are double-buffered by unrolling the loop by two, without copies: a layer's are waited for at their first
+        //    use, by a count that leaves the next layer's loads and the earlier layer's J stores in flight.
+        // (uvb's address passes through an empty asm: the compiler otherwise knows the value there from the scalar load of uvb above
+        // and takes the register instead, which brings the branch back)
+        gcdouble *uvb_at = (gcdouble *)L.uvb + nu;
+        asm volatile("" : "+s"(uvb_at));
+        const long ist = has_i_in ? (long)up : 0l;
+        {
+            gcdouble *f = has_i_in ? (gcdouble *)(G->dir[p0].faces + fnu) + i_in : uvb_at;
 #pragma unroll
-        for (int r = 0; r < R; ++r) cur[r] = !has_i_in ? uvb : FLOW == 2 ? fresh((gcbyte *)&f[i_in + (long)r * up]) : f[i_in + (long)r * up];
-    }
-    for (int k = 0; k + 1 < ndir; ++k) {
-        int d = p0 + 1 + k;
-        d = d >= ndir ? d - ndir : d;
-        gcdouble *f = (gcdouble *)(G->dir[d].faces + fnu);
-        // (all eight loads in flight, then the eight LDS stores: left to itself the compiler pairs them, load, load, wait, store,
-        // wait, store -- four round trips to memory per direction where one will do, and a brick is a short thing)
-        double parked[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) parked[r] = !has_i_in ? uvb : FLOW == 2 ? fresh((gcbyte *)&f[i_in + (long)r * up]) : f[i_in + (long)r * up];
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int r = 0; r < R; ++r) state[(k * R + r) * 64 + lane] = parked[r];
-    }
-    for (int i = i0; i <= i1; ++i) {
-        const int il = i - i0;
-        double kap[R], xs[EMIT ? R : 1], Jacc[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) { kap[r] = kap_next[r]; Jacc[r] = 0.0; if (EMIT) { const int row = (cv0 + r < n) ? cv0 + r : n; xs[r] = *(gcdouble *)(xbase + 8l * i * si + row * row_bytes + off0); } }
-        gbyte *jplane = jbase + 8l * i * si;
-        const long rstep = here(row_bytes); // (per layer: the seven steps of a ragged brick are then not kept, and spilled, for the whole run)
-        // what the groups before this one left in these cells: read now and added to (the wavefront waits for it at its first sum), or
-        // -- BrickLaunch::atomic_acc -- left where it is and added to by the memory system when the layer's sums are stored
-        if (accumulate && !atomic_acc) load_rows<R, true>(Jacc, (gcbyte *)jplane + row0, off0, rstep, nrows);
-        if (i < i1 && !(ablate & 16)) load_rows<R, false>(kap_next, kbase + 8l * (i + 1) * si + row0, off0, rstep, nrows);
-        for (int j = 0; j < ndir; ++j) {
-            int d = p0 + j;
+            for (int r = 0; r < R; ++r) cur[r] = f[r * ist];
+        }
+        for (int k = 0; k + 1 < ndir; ++k) {
+            int d = p0 + 1 + k;
             d = d >= ndir ? d - ndir : d;
-            if (j) { // direction d leaves slot j - 1, the one just done takes its place
+            gcdouble *f = has_i_in ? (gcdouble *)(G->dir[d].faces + fnu) + i_in : uvb_at;
+            double parked[R]; // (the loads together, then the LDS stores: below)
 #pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const double parked = state[((j - 1) * R + r) * 64 + lane];
-                    state[((j - 1) * R + r) * 64 + lane] = cur[r];
-                    cur[r] = parked;
+            for (int r = 0; r < R; ++r) parked[r] = f[r * ist];
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int r = 0; r < R; ++r) state[(k * R + r) * 64 + lane] = parked[r];
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) asm volatile("" ::"v"(kap_next[r]), "v"(cur[r])); // the one drain before the loop
+        double kap_odd[R];
+        // layer i with its opacities in kap; the next layer's go to kn (the last layer loads its own again rather than branch)
+        auto layer = [&](const int i, const double(&kap)[R], double(&kn)[R]) __attribute__((always_inline)) {
+            const int il = i - i0;
+            const double xs[1] = {0.0};
+            double Jacc[R];
+            gbyte *jplane = jbase + 8l * i * si;
+            const long rstep = here(row_bytes);
+            if (accumulate) load_rows<R, true>(Jacc, (gcbyte *)jplane + row0, off0, rstep, R);
+            else {
+#pragma unroll
+                for (int r = 0; r < R; ++r) Jacc[r] = 0.0;
+            }
+            load_rows<R, false>(kn, kbase + 8l * (i < i1 ? i + 1 : i) * si + row0, off0, rstep, R);
+            for (int j = 0; j < ndir; ++j) {
+                int d = p0 + j;
+                d = d >= ndir ? d - ndir : d;
+                if (j) {
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        const double parked = state[((j - 1) * R + r) * 64 + lane];
+                        state[((j - 1) * R + r) * 64 + lane] = cur[r];
+                        cur[r] = parked;
+                    }
+                }
+                clayer *rp = (clayer *)(G->dir[d].layers) + (i - 1);
+                const double d0 = rp->dpath[0], d1 = rp->dpath[1], d2 = rp->dpath[2];
+                const int rc = rp->info & 7;
+                const double w = G->dir[d].w;
+                gbyte *f = (gbyte *)(G->dir[d].faces + fnu);
+                gcbyte *uin = has_u_in ? (gcbyte *)f + 8 * (u_in + (long)il * uw) : nullptr;
+                gbyte *uout = has_u_out ? f + 8 * (u_out + (long)il * uw) : nullptr;
+                gcbyte *vin = has_v_in ? (gcbyte *)f + 8 * (v_in + (long)il * up) : nullptr;
+                gbyte *vout = has_v_out ? f + 8 * (v_out + (long)il * up) : nullptr;
+                gcbyte *vb = (gcbyte *)uvb_at;
+                const bool third_first = rc == RC_THREE_U_SWAP || rc == RC_THREE_V_SWAP;
+                switch (rc) {
+                case RC_ONE: brick_step<RC_ONE, 0, R, true>(L.math, lead, cur, kap, xs, Jacc, false, d0, d1, d2, w, uvb, uin, uout, vin, vout, lane, false, false, 0, 63, true, nullptr, nullptr, vb); break;
+                case RC_TWO_U: brick_step<RC_TWO_U, 0, R, true>(L.math, lead, cur, kap, xs, Jacc, false, d0, d1, d2, w, uvb, uin, uout, vin, vout, lane, false, false, 0, 63, true, nullptr, nullptr, vb); break;
+                case RC_TWO_V: brick_step<RC_TWO_V, 0, R, true>(L.math, lead, cur, kap, xs, Jacc, false, d0, d1, d2, w, uvb, uin, uout, vin, vout, lane, false, false, 0, 63, true, nullptr, nullptr, vb); break;
+                case RC_THREE_U:
+                case RC_THREE_U_SWAP:
+                    brick_step<RC_THREE_U, 0, R, true>(L.math, lead, cur, kap, xs, Jacc, third_first, d0, d1, d2, w, uvb, uin, uout, vin, vout, lane, false, false, 0, 63, true, nullptr, nullptr, vb);
+                    break;
+                default:
+                    brick_step<RC_THREE_V, 0, R, true>(L.math, lead, cur, kap, xs, Jacc, third_first, d0, d1, d2, w, uvb, uin, uout, vin, vout, lane, false, false, 0, 63, true, nullptr, nullptr, vb);
+                    break;
                 }
             }
-            clayer *rp = (clayer *)(G->dir[d].layers) + (i - 1);
-            const double d0 = rp->dpath[0], d1 = rp->dpath[1], d2 = rp->dpath[2];
-            const int rc = rp->info & 7;
-            const double w = G->dir[d].w;
-            gbyte *f = (gbyte *)(G->dir[d].faces + fnu);
-            gcbyte *uin = has_u_in ? (gcbyte *)f + 8 * (u_in + (long)il * uw) : nullptr;
-            gbyte *uout = has_u_out ? f + 8 * (u_out + (long)il * uw) : nullptr;
-            gcbyte *vin = has_v_in ? (gcbyte *)f + 8 * (v_in + (long)il * up) : nullptr;
-            gbyte *vout = has_v_out ? f + 8 * (v_out + (long)il * up) : nullptr;
-            const bool third_first = rc == RC_THREE_U_SWAP || rc == RC_THREE_V_SWAP;
-            switch (rc) {
-            case RC_ONE: brick_step<RC_ONE, EMIT>(L.math, lead, cur, kap, xs, Jacc, false, d0, d1, d2, w, uvb, uin, uout, vin, vout, lane, through, FLOW != 0, lane_lo, lane_hi, !MASKED || own_lane); break;
-            case RC_TWO_U: brick_step<RC_TWO_U, EMIT>(L.math, lead, cur, kap, xs, Jacc, false, d0, d1, d2, w, uvb, uin, uout, vin, vout, lane, through, FLOW != 0, lane_lo, lane_hi, !MASKED || own_lane); break;
-            case RC_TWO_V: brick_step<RC_TWO_V, EMIT>(L.math, lead, cur, kap, xs, Jacc, false, d0, d1, d2, w, uvb, uin, uout, vin, vout, lane, through, FLOW != 0, lane_lo, lane_hi, !MASKED || own_lane); break;
-            case RC_THREE_U:
-            case RC_THREE_U_SWAP:
-                brick_step<RC_THREE_U, EMIT>(L.math, lead, cur, kap, xs, Jacc, third_first, d0, d1, d2, w, uvb, uin, uout, vin, vout, lane, through, FLOW != 0, lane_lo, lane_hi, !MASKED || own_lane);
-                break;
-            default:
-                brick_step<RC_THREE_V, EMIT>(L.math, lead, cur, kap, xs, Jacc, third_first, d0, d1, d2, w, uvb, uin, uout, vin, vout, lane, through, FLOW != 0, lane_lo, lane_hi, !MASKED || own_lane);
-                break;
-            }
-        }
-        p0 = p0 ? p0 - 1 : ndir - 1;
-        // the group's contribution to J of this layer's cells: stored once, read only by the merge
-        if (own_lane && !(ablate & 32)) {
+            p0 = p0 ? p0 - 1 : ndir - 1;
             gbyte *jrow = jplane + row0;
             const unsigned off = here(off0);
 #pragma unroll
             for (int r = 0; r < R; ++r) {
-                if (r < nrows) {
-                    if (through) __hip_atomic_store((double *)(jrow + off0), Jacc[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    else if (accumulate && atomic_acc) (void)__builtin_amdgcn_global_atomic_fadd_f64((gdouble *)lane_address(jrow, off), Jacc[r]);
-                    else __builtin_nontemporal_store(Jacc[r], (gdouble *)lane_address(jrow, off));
-                }
+                __builtin_nontemporal_store(Jacc[r], (gdouble *)lane_address(jrow, off));
                 jrow += rstep;
             }
+        };
+        for (int i = i0;; i += 2) {
+            layer(i, kap_next, kap_odd);
+            if (i == i1) break;
+            layer(i + 1, kap_odd, kap_next);
+            if (i + 1 == i1) break;
         }
+    } else {
+        // rays entering the brick's bottom: the inflow, or what the chunk below left
+        {
+            gcdouble *f = (gcdouble *)(G->dir[p0].faces + fnu);
+#pragma unroll
+            for (int r = 0; r < R; ++r) cur[r] = !has_i_in ? uvb : FLOW == 2 ? fresh((gcbyte *)&f[i_in + (long)r * up]) : f[i_in + (long)r * up];
+        }
+        for (int k = 0; k + 1 < ndir; ++k) {
+            int d = p0 + 1 + k;
+            d = d >= ndir ? d - ndir : d;
+            gcdouble *f = (gcdouble *)(G->dir[d].faces + fnu);
+            // (all eight loads in flight, then the eight LDS stores: left to itself the compiler pairs them, load, load, wait, store,
+            // wait, store -- four round trips to memory per direction where one will do, and a brick is a short thing)
+            double parked[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) parked[r] = !has_i_in ? uvb : FLOW == 2 ? fresh((gcbyte *)&f[i_in + (long)r * up]) : f[i_in + (long)r * up];
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int r = 0; r < R; ++r) state[(k * R + r) * 64 + lane] = parked[r];
+        }
+        for (int i = i0; i <= i1; ++i) {
+            const int il = i - i0;
+            double kap[R], xs[EMIT ? R : 1], Jacc[R];
+#pragma unroll
+            for (int r = 0; r < R; ++r) { kap[r] = kap_next[r]; Jacc[r] = 0.0; if (EMIT) { const int row = (cv0 + r < n) ? cv0 + r : n; xs[r] = *(gcdouble *)(xbase + 8l * i * si + row * row_bytes + off0); } }
+            gbyte *jplane = jbase + 8l * i * si;
+            const long rstep = here(row_bytes); // (per layer: the seven steps of a ragged brick are then not kept, and spilled, for the whole run)
+            // what the groups before this one left in these cells: read now and added to (the wavefront waits for it at its first sum), or
+            // -- BrickLaunch::atomic_acc -- left where it is and added to by the memory system when the layer's sums are stored
+            if (accumulate && !atomic_acc) load_rows<R, true>(Jacc, (gcbyte *)jplane + row0, off0, rstep, nrows);
+            if (i < i1 && !(ablate & 16)) load_rows<R, false>(kap_next, kbase + 8l * (i + 1) * si + row0, off0, rstep, nrows);
+            for (int j = 0; j < ndir; ++j) {
+                int d = p0 + j;
+                d = d >= ndir ? d - ndir : d;
+                if (j) { // direction d leaves slot j - 1, the one just done takes its place
+#pragma unroll
+                    for (int r = 0; r < R; ++r) {
+                        const double parked = state[((j - 1) * R + r) * 64 + lane];
+                        state[((j - 1) * R + r) * 64 + lane] = cur[r];
+                        cur[r] = parked;
+                    }
+                }
+                clayer *rp = (clayer *)(G->dir[d].layers) + (i - 1);
+                const double d0 = rp->dpath[0], d1 = rp->dpath[1], d2 = rp->dpath[2];
+                const int rc = rp->info & 7;
+                const double w = G->dir[d].w;
+                gbyte *f = (gbyte *)(G->dir[d].faces + fnu);
+                gcbyte *uin = has_u_in ? (gcbyte *)f + 8 * (u_in + (long)il * uw) : nullptr;
+                gbyte *uout = has_u_out ? f + 8 * (u_out + (long)il * uw) : nullptr;
+                gcbyte *vin = has_v_in ? (gcbyte *)f + 8 * (v_in + (long)il * up) : nullptr;
+                gbyte *vout = has_v_out ? f + 8 * (v_out + (long)il * up) : nullptr;
+                const bool third_first = rc == RC_THREE_U_SWAP || rc == RC_THREE_V_SWAP;
+                switch (rc) {
+                case RC_ONE: brick_step<RC_ONE, EMIT>(L.math, lead, cur, kap, xs, Jacc, false, d0, d1, d2, w, uvb, uin, uout, vin, vout, lane, through, FLOW != 0, lane_lo, lane_hi, !MASKED || own_lane); break;
+                case RC_TWO_U: brick_step<RC_TWO_U, EMIT>(L.math, lead, cur, kap, xs, Jacc, false, d0, d1, d2, w, uvb, uin, uout, vin, vout, lane, through, FLOW != 0, lane_lo, lane_hi, !MASKED || own_lane); break;
+                case RC_TWO_V: brick_step<RC_TWO_V, EMIT>(L.math, lead, cur, kap, xs, Jacc, false, d0, d1, d2, w, uvb, uin, uout, vin, vout, lane, through, FLOW != 0, lane_lo, lane_hi, !MASKED || own_lane); break;
+                case RC_THREE_U:
+                case RC_THREE_U_SWAP:
+                    brick_step<RC_THREE_U, EMIT>(L.math, lead, cur, kap, xs, Jacc, third_first, d0, d1, d2, w, uvb, uin, uout, vin, vout, lane, through, FLOW != 0, lane_lo, lane_hi, !MASKED || own_lane);
+                    break;
+                default:
+                    brick_step<RC_THREE_V, EMIT>(L.math, lead, cur, kap, xs, Jacc, third_first, d0, d1, d2, w, uvb, uin, uout, vin, vout, lane, through, FLOW != 0, lane_lo, lane_hi, !MASKED || own_lane);
+                    break;
+                }
+            }
+            p0 = p0 ? p0 - 1 : ndir - 1;
+            // the group's contribution to J of this layer's cells: stored once, read only by the merge
+            if (own_lane && !(ablate & 32)) {
+                gbyte *jrow = jplane + row0;
+                const unsigned off = here(off0);
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    if (r < nrows) {
+                        if (through) __hip_atomic_store((double *)(jrow + off0), Jacc[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        else if (accumulate && atomic_acc) (void)__builtin_amdgcn_global_atomic_fadd_f64((gdouble *)lane_address(jrow, off), Jacc[r]);
+                        else __builtin_nontemporal_store(Jacc[r], (gdouble *)lane_address(jrow, off));
+                    }
+                    jrow += rstep;
+                }
+            }
+        }
+
     }
 
     if (has_i_out) { // p0 is in registers, p0 + 1 + k in slot k
@@ -721,7 +827,11 @@ int launch_brick(const BrickLaunch &L, int max_dirs, int waves, hipStream_t stre
     else switch (waves) {
     case 2: hipLaunchKernelGGL((brick_kernel<2, 0, 0>), grid, dim3(64), lds, stream, L); break;
     case 3: hipLaunchKernelGGL((brick_kernel<3, 0, 0>), grid, dim3(64), lds, stream, L); break;
-    case 4: hipLaunchKernelGGL((brick_kernel<4, 0, 0>), grid, dim3(64), lds, stream, L); break;
+    case 4:
+        // whole bricks, no diagnostic option: the form whose layer loop has only counted waits (brick_kernel's WHOLE)
+        if (L.n % 64 == 0 && L.n % kBrickRows == 0 && !L.atomic_acc && !L.pad2_) hipLaunchKernelGGL((brick_kernel<4, 0, 0, false, true>), grid, dim3(64), lds, stream, L);
+        else hipLaunchKernelGGL((brick_kernel<4, 0, 0>), grid, dim3(64), lds, stream, L);
+        break;
     default: return -1;
     }
     return hipGetLastError() == hipSuccess ? 0 : -2;
