@@ -344,6 +344,8 @@ int ftte_host_unregister(ftte_ctx *ctx, void *ptr);
  * "direction_slices" and "multi_rccl" (1: the last direction-split sweep was summed over RCCL), "rccl_loadable", "rccl_selftest" (runs the
  * direction sum's RCCL calls on a clique of one rank, the first device: 1 = the piece came back unchanged; negative = it could not
  * run), the rest from its first device.
+ * "device_objects": device buffers, pinned buffers, streams, events and captured graphs the library holds at the moment, over all
+ * contexts of the process (single- and multi-device contexts alike): what a destroyed context had made is no longer in it.
  * -1 for an unknown name. */
 long long ftte_counter(const ftte_ctx *ctx, const char *name);
 

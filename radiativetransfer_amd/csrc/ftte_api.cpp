@@ -51,7 +51,7 @@ int ftte_create(ftte_ctx **out, int ndev, const int *dev_ids)
         return fail(nullptr, FTTE_ERR_NO_DEVICE, std::string("ftte_create: kernels are built for gfx950 only, device is ") + prop.gcnArchName);
     ftte_ctx *c = new ftte_ctx;
     c->device = dev;
-    if (hipSetDevice(dev) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamDefault) != hipSuccess) {
+    if (hipSetDevice(dev) != hipSuccess || c->stream.create(hipStreamDefault) != hipSuccess) {
         delete c;
         return fail(nullptr, FTTE_ERR_NO_DEVICE, "ftte_create: cannot create a stream on the device");
     }
@@ -65,69 +65,7 @@ int ftte_destroy(ftte_ctx *c)
     if (c->multi) return multi_destroy(c);
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (int l = 0; l < 3; ++l) {
-        if (c->kappa[l]) (void)hipFree(c->kappa[l]);
-        if (c->kappa_tiled[l]) (void)hipFree(c->kappa_tiled[l]);
-        if (c->emis[l]) (void)hipFree(c->emis[l]);
-        for (int s = 0; s < kMaxAcc; ++s) if (c->acc[l][s]) (void)hipFree(c->acc[l][s]);
-    }
-    if (c->d_bdeps) (void)hipFree(c->d_bdeps);
-    if (c->d_bdone) (void)hipFree(c->d_bdone);
-    if (c->d_bqueue) (void)hipFree(c->d_bqueue);
-    if (c->d_bsync) (void)hipFree(c->d_bsync);
-    if (c->h_berror) (void)hipHostFree(c->h_berror);
-    if (c->d_blayers) (void)hipFree(c->d_blayers);
-    if (c->d_bgroups) (void)hipFree(c->d_bgroups);
-    if (c->d_mblocks) (void)hipFree(c->d_mblocks);
-    if (c->d_btasks) (void)hipFree(c->d_btasks);
-    if (c->d_faces) (void)hipFree(c->d_faces);
-    if (c->d_layers) (void)hipFree(c->d_layers);
-    if (c->d_items) (void)hipFree(c->d_items);
-    if (c->d_uvb) (void)hipFree(c->d_uvb);
-    free_forests(c);
-    free_hybrid(c);
-    if (c->d_leaf_of_base) (void)hipFree(c->d_leaf_of_base);
-    for (int l = 0; l < 3; ++l) if (c->base_kappa[l]) (void)hipFree(c->base_kappa[l]);
-    for (int l = 0; l < 3; ++l) if (c->base_emis[l]) (void)hipFree(c->base_emis[l]);
-    for (int l = 0; l < 3; ++l) {
-        if (c->fine_kappa[l]) (void)hipFree(c->fine_kappa[l]);
-        if (c->fine_emis[l]) (void)hipFree(c->fine_emis[l]);
-        for (int a = 0; a < kMaxAcc; ++a) if (c->fine_acc[l][a]) (void)hipFree(c->fine_acc[l][a]);
-    }
-    if (c->amr_Iout) (void)hipFree(c->amr_Iout);
-    if (c->amr_mean) (void)hipFree(c->amr_mean);
-    if (c->d_amr_dirs) (void)hipFree(c->d_amr_dirs);
-    if (c->d_amr_tables) (void)hipFree(c->d_amr_tables);
-    if (c->amr_kappa) (void)hipFree(c->amr_kappa);
-    if (c->amr_emis) (void)hipFree(c->amr_emis);
-    if (c->merge_stream) (void)hipStreamDestroy(c->merge_stream);
-    if (c->ev_layout_done) (void)hipEventDestroy(c->ev_layout_done);
-    if (c->ev_merge_done) (void)hipEventDestroy(c->ev_merge_done);
-    if (c->ev_layouts_ready) (void)hipEventDestroy(c->ev_layouts_ready);
-    if (c->ev_sweep_done) (void)hipEventDestroy(c->ev_sweep_done);
-    for (auto &q : c->lane_stream) (void)hipStreamDestroy(q);
-    for (auto &e : c->pipe_up) (void)hipEventDestroy(e);
-    for (auto &e : c->lane_done) (void)hipEventDestroy(e);
-    for (auto &e : c->ev_merge_point) (void)hipEventDestroy(e);
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    for (auto &e : c->ev_combine) if (e) (void)hipEventDestroy(e);
-    if (c->host_J_dev) (void)hipFree(c->host_J_dev);
-    for (int q = 0; q < 2; ++q) {
-        if (c->stage[q]) (void)hipHostFree(c->stage[q]);
-        if (c->stage_ev[q]) (void)hipEventDestroy(c->stage_ev[q]);
-    }
-    for (auto &r : c->registered) (void)hipHostUnregister((void *)r.base);
-    c->point.release();
-    c->drop_chem_grid();
-    if (c->chem_k) (void)hipFree(c->chem_k);
-    if (c->chem_counters) (void)hipFree(c->chem_counters);
-    if (c->chem_mass) (void)hipFree(c->chem_mass);
-    for (auto &t : c->timing) {
-        (void)hipEventDestroy(t.start); (void)hipEventDestroy(t.stop);
-        for (auto &e : t.first) (void)hipEventDestroy(e);
-        for (auto &e : t.last) (void)hipEventDestroy(e);
-    }
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    for (auto &r : c->registered) (void)hipHostUnregister((void *)r.base); // the caller's arrays: pinned here, not owned
     delete c;
     return FTTE_OK;
 }
@@ -166,24 +104,18 @@ int ftte_set_grid(ftte_ctx *c, int nx, int ny, int nz, int64_t ncell, const int3
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->stream);
         for (int l = 0; l < 3; ++l) {
-            if (c->kappa[l]) { (void)hipFree(c->kappa[l]); c->kappa[l] = nullptr; }
-            if (c->kappa_tiled[l]) { (void)hipFree(c->kappa_tiled[l]); c->kappa_tiled[l] = nullptr; }
-            if (c->emis[l]) { (void)hipFree(c->emis[l]); c->emis[l] = nullptr; }
-            for (int s = 0; s < kMaxAcc; ++s) if (c->acc[l][s]) { (void)hipFree(c->acc[l][s]); c->acc[l][s] = nullptr; }
+            c->kappa[l].reset(); c->kappa_tiled[l].reset(); c->emis[l].reset();
+            for (auto &a : c->acc[l]) a.reset();
         }
         c->emit_mode = 0;
-        if (c->amr_Iout) { (void)hipFree(c->amr_Iout); c->amr_Iout = nullptr; }
-        if (c->amr_mean) { (void)hipFree(c->amr_mean); c->amr_mean = nullptr; }
-        if (c->amr_kappa) { (void)hipFree(c->amr_kappa); c->amr_kappa = nullptr; }
-        if (c->amr_emis) { (void)hipFree(c->amr_emis); c->amr_emis = nullptr; }
-        c->kappa_cap = c->acc_cap = c->amr_scratch_cap = c->amr_kappa_cap = c->amr_emis_cap = 0;
+        c->amr_Iout.reset(); c->amr_mean.reset(); c->amr_kappa.reset(); c->amr_emis.reset();
         c->nnu = 0;
     }
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     free_forests(c);
     free_hybrid(c);
-    if (c->d_leaf_of_base) { (void)hipFree(c->d_leaf_of_base); c->d_leaf_of_base = nullptr; }
+    c->d_leaf_of_base.reset();
     c->point.drop_grid();
     c->drop_chem_grid();
     c->leaf_level.assign(level, level + ncell);
@@ -247,9 +179,9 @@ int ftte_set_species(ftte_ctx *c, int nnu, const double *HI, const double *HeI, 
     if ((rc = wait_sweep(c))) return rc;
     FTTE_HIP(c, hipStreamSynchronize(c->stream));
     if ((rc = ensure_kappa(c, nnu))) return rc;
-    double *tmp = nullptr;
+    DeviceBuffer<double> tmp;
     const size_t nc = (size_t)c->ncell;
-    FTTE_HIP(c, hipMalloc((void **)&tmp, sizeof(double) * (3 * nc + 3 * (size_t)nnu)));
+    FTTE_HIP(c, tmp.reserve(3 * nc + 3 * (size_t)nnu));
     hipError_t e = hipMemcpyAsync(tmp, HI, sizeof(double) * nc, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(tmp + nc, HeI, sizeof(double) * nc, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(tmp + 2 * nc, HeII, sizeof(double) * nc, hipMemcpyHostToDevice, c->stream);
@@ -257,7 +189,6 @@ int ftte_set_species(ftte_ctx *c, int nnu, const double *HI, const double *HeI, 
     int lrc = 0;
     if (e == hipSuccess) lrc = launch_opacity(tmp, tmp + nc, tmp + 2 * nc, tmp + 3 * nc, c->kappa[0], (long)nc, nnu, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(tmp);
     if (e != hipSuccess) return fail(c, FTTE_ERR_NO_DEVICE, std::string("ftte_set_species: ") + hipGetErrorString(e));
     if (lrc) return fail(c, FTTE_ERR_NO_DEVICE, "ftte_set_species: kernel launch failed");
     c->nnu = nnu;
@@ -276,7 +207,7 @@ static int set_emission(ftte_ctx *c, int mode, const double *values, bool on_dev
     FTTE_HIP(c, hipSetDevice(c->device));
     if ((rc = wait_sweep(c))) return rc;
     if (!on_device) FTTE_HIP(c, hipStreamSynchronize(c->stream));
-    if (!c->emis[0]) FTTE_HIP(c, hipMalloc((void **)&c->emis[0], sizeof(double) * c->kappa_cap));
+    FTTE_HIP(c, c->emis[0].reserve(c->kappa[0].capacity()));
     const size_t bytes = sizeof(double) * (size_t)c->nnu * c->ncell;
     FTTE_HIP(c, hipMemcpyAsync(c->emis[0], values, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
     FTTE_HIP(c, hipStreamSynchronize(c->stream)); // the sweep may run on another stream: the copy must have landed
@@ -422,7 +353,7 @@ int ftte_diffuse_sweep(ftte_ctx *c, int ndir, const double *phi, const double *t
     if (!J) return fail(c, FTTE_ERR_ARG, "ftte_diffuse_sweep: J is NULL");
     FTTE_HIP(c, hipSetDevice(c->device));
     const size_t elems = (size_t)c->nnu * c->ncell;
-    if ((rc = ensure(c, &c->host_J_dev, &c->host_J_cap, elems))) return rc; // kept from call to call
+    FTTE_HIP(c, c->host_J_dev.reserve(elems)); // kept from call to call
     if ((rc = ftte_diffuse_sweep_device(c, ndir, phi, theta, w, uvb, c->host_J_dev, nullptr))) return rc;
     if ((rc = download(c, J, c->host_J_dev, sizeof(double) * elems))) return rc;
     return wait_sweep(c); // the sweep has drained: report a dataflow sweep that gave up now rather than at the next call
@@ -453,7 +384,7 @@ int ftte_diffuse_iteration(ftte_ctx *c, int nnu, const double *kappa, int ndir, 
     c->kappa_ready[0] = c->kappa_ready[1] = c->kappa_ready[2] = c->kappa_ready[3] = false;
     ++c->n_kappa_sets;
     const size_t elems = (size_t)nnu * c->ncell;
-    if ((rc = ensure(c, &c->host_J_dev, &c->host_J_cap, elems))) return rc;
+    FTTE_HIP(c, c->host_J_dev.reserve(elems));
     const HostPipe pipe{kappa, J};
     if ((rc = brick_sweep(c, ndir, phi, theta, w, uvb, c->host_J_dev, c->stream, &pipe))) {
         c->kappa_ready[0] = c->kappa_ready[1] = c->kappa_ready[2] = false;
@@ -500,6 +431,7 @@ long long ftte_counter(const ftte_ctx *c, const char *name)
     if (!std::strcmp(name, "grid_builds")) return c->n_grid_builds;
     if (!std::strcmp(name, "plan_builds")) return c->n_plan_builds;
     if (!std::strcmp(name, "forest_builds")) return c->n_forest_builds;
+    if (!std::strcmp(name, "device_objects")) return g_device_objects.load();
     if (!std::strcmp(name, "hybrid_boxes")) return (c->hplan.valid && c->hplan.worthwhile) ? c->hplan.most_boxes : 0;
     if (!std::strcmp(name, "hybrid_passes")) return (c->hplan.valid && c->hplan.worthwhile) ? c->hplan.npass : 0;
     if (!std::strcmp(name, "fine_block")) return (c->hplan.valid && c->hplan.worthwhile && c->hplan.fine.active) ? c->hplan.fine.n : 0;
@@ -779,8 +711,8 @@ int ftte_set_rate_coefficients(ftte_ctx *c, int nratec, double logtem0, double l
         return fail(c, FTTE_ERR_ARG, "ftte_set_rate_coefficients: bad argument");
     FTTE_HIP(c, hipSetDevice(c->device));
     FTTE_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->chem_k && c->chem_nratec != nratec) { FTTE_HIP(c, hipFree(c->chem_k)); c->chem_k = nullptr; }
-    if (!c->chem_k) FTTE_HIP(c, hipMalloc((void **)&c->chem_k, sizeof(double) * 6 * (size_t)nratec));
+    if (c->chem_nratec != nratec) c->chem_k.reset();
+    FTTE_HIP(c, c->chem_k.reserve(6 * (size_t)nratec));
     const double *src[6] = {k1a, k2a, k3a, k4a, k5a, k6a};
     for (int r = 0; r < 6; ++r)
         FTTE_HIP(c, hipMemcpyAsync(c->chem_k + (size_t)r * nratec, src[r], sizeof(double) * nratec, hipMemcpyHostToDevice, c->stream));
@@ -809,7 +741,7 @@ int ftte_set_temperature(ftte_ctx *c, const double *tgas)
             });
         for (auto &th : pool) th.join();
     }
-    if (!c->chem_logtem) FTTE_HIP(c, hipMalloc((void **)&c->chem_logtem, sizeof(double) * (size_t)c->ncell));
+    FTTE_HIP(c, c->chem_logtem.reserve((size_t)c->ncell));
     FTTE_HIP(c, hipMemcpyAsync(c->chem_logtem, logtem.data(), sizeof(double) * (size_t)c->ncell, hipMemcpyHostToDevice, c->stream));
     FTTE_HIP(c, hipStreamSynchronize(c->stream));
     c->chem_temperature_set = true;
@@ -834,16 +766,16 @@ static int solve_rates(ftte_ctx *c, int run_uvb, const double *J, bool J_on_devi
     FTTE_HIP(c, hipSetDevice(c->device));
     const size_t nc = (size_t)c->ncell;
     if (!c->chem_level) {
-        FTTE_HIP(c, hipMalloc((void **)&c->chem_level, nc));
+        FTTE_HIP(c, c->chem_level.reserve(nc));
         FTTE_HIP(c, hipMemcpyAsync(c->chem_level, c->leaf_level.data(), nc, hipMemcpyHostToDevice, c->stream));
     }
-    if (!c->chem_out) FTTE_HIP(c, hipMalloc((void **)&c->chem_out, sizeof(double) * 3 * nc));
-    if (!c->chem_counters) FTTE_HIP(c, hipMalloc((void **)&c->chem_counters, sizeof(unsigned long long) * 4));
+    FTTE_HIP(c, c->chem_out.reserve(3 * nc));
+    FTTE_HIP(c, c->chem_counters.reserve(4));
     const double *J_dev = nullptr;
     if (run_uvb) {
         if (J_on_device) J_dev = J;
         else {
-            if (!c->chem_J) FTTE_HIP(c, hipMalloc((void **)&c->chem_J, sizeof(double) * 3 * nc));
+            FTTE_HIP(c, c->chem_J.reserve(3 * nc));
             FTTE_HIP(c, hipMemcpyAsync(c->chem_J, J, sizeof(double) * 3 * nc, hipMemcpyHostToDevice, c->stream));
             J_dev = c->chem_J;
         }
@@ -906,10 +838,10 @@ static int hydrogen_mass(ftte_ctx *c, const double *HI_dev, double *neutral, dou
     PointState &P = c->point;
     const size_t nc = (size_t)c->ncell;
     if (!c->chem_level) {
-        FTTE_HIP(c, hipMalloc((void **)&c->chem_level, nc));
+        FTTE_HIP(c, c->chem_level.reserve(nc));
         FTTE_HIP(c, hipMemcpyAsync(c->chem_level, c->leaf_level.data(), nc, hipMemcpyHostToDevice, c->stream));
     }
-    if (!c->chem_mass) FTTE_HIP(c, hipMalloc((void **)&c->chem_mass, sizeof(double) * kMassParts));
+    FTTE_HIP(c, c->chem_mass.reserve(kMassParts));
     if (launch_hydrogen_mass(c->chem_level, HI_dev, P.medium[3], (long)nc, c->n, c->box, c->chem_mass, c->stream))
         return fail(c, FTTE_ERR_NO_DEVICE, std::string(who) + ": kernel launch failed");
     double out[2];
@@ -936,11 +868,11 @@ int ftte_initial_ionization_equilibrium(ftte_ctx *c, const double *uniform, doub
     FTTE_HIP(c, hipSetDevice(c->device));
     const size_t nc = (size_t)c->ncell;
     if (!c->chem_level) {
-        FTTE_HIP(c, hipMalloc((void **)&c->chem_level, nc));
+        FTTE_HIP(c, c->chem_level.reserve(nc));
         FTTE_HIP(c, hipMemcpyAsync(c->chem_level, c->leaf_level.data(), nc, hipMemcpyHostToDevice, c->stream));
     }
-    if (!c->chem_out) FTTE_HIP(c, hipMalloc((void **)&c->chem_out, sizeof(double) * 3 * nc));
-    if (!c->chem_counters) FTTE_HIP(c, hipMalloc((void **)&c->chem_counters, sizeof(unsigned long long) * 4));
+    FTTE_HIP(c, c->chem_out.reserve(3 * nc));
+    FTTE_HIP(c, c->chem_counters.reserve(4));
     const unsigned long long init[4] = {~0ull, 0ull, 0ull, 0ull};
     FTTE_HIP(c, hipMemcpyAsync(c->chem_counters, init, sizeof init, hipMemcpyHostToDevice, c->stream));
 
@@ -1017,14 +949,13 @@ int ftte_compute_opacities(ftte_ctx *c, int nnu, const double *beta)
     if ((rc = wait_sweep(c))) return rc;
     FTTE_HIP(c, hipStreamSynchronize(c->stream));
     if ((rc = ensure_kappa(c, nnu))) return rc;
-    double *dbeta = nullptr;
-    FTTE_HIP(c, hipMalloc((void **)&dbeta, sizeof(double) * 3 * (size_t)nnu));
+    DeviceBuffer<double> dbeta;
+    FTTE_HIP(c, dbeta.reserve(3 * (size_t)nnu));
     hipError_t e = hipMemcpyAsync(dbeta, beta, sizeof(double) * 3 * nnu, hipMemcpyHostToDevice, c->stream);
     int lrc = 0;
     if (e == hipSuccess)
         lrc = launch_opacity(c->point.medium[0], c->point.medium[1], c->point.medium[2], dbeta, c->kappa[0], (long)c->ncell, nnu, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(dbeta);
     if (e != hipSuccess) return fail(c, FTTE_ERR_NO_DEVICE, std::string("ftte_compute_opacities: ") + hipGetErrorString(e));
     if (lrc) return fail(c, FTTE_ERR_NO_DEVICE, "ftte_compute_opacities: kernel launch failed");
     c->nnu = nnu;
@@ -1044,17 +975,16 @@ static int assign_uvb(ftte_ctx *c, int nnu, const double *uvb, double threshold,
         return fail(c, FTTE_ERR_STATE, std::string(who) + ": no medium with density (ftte_set_medium with rho)");
     FTTE_HIP(c, hipSetDevice(c->device));
     const size_t nc = (size_t)c->ncell;
-    double *duvb = nullptr, *dJ = J_on_device ? J : nullptr;
-    FTTE_HIP(c, hipMalloc((void **)&duvb, sizeof(double) * nnu));
+    DeviceBuffer<double> duvb, J_tmp;
+    FTTE_HIP(c, duvb.reserve((size_t)nnu));
     hipError_t e = hipSuccess;
-    if (!J_on_device) e = hipMalloc((void **)&dJ, sizeof(double) * nc * nnu);
+    if (!J_on_device) e = J_tmp.reserve(nc * nnu);
+    double *const dJ = J_on_device ? J : J_tmp.get();
     if (e == hipSuccess) e = hipMemcpyAsync(duvb, uvb, sizeof(double) * nnu, hipMemcpyHostToDevice, c->stream);
     int lrc = 0;
     if (e == hipSuccess) lrc = launch_thin_limit(P.medium[0], P.medium[1], P.medium[2], P.medium[3], duvb, threshold, dJ, (long)nc, nnu, c->stream);
     if (e == hipSuccess && !J_on_device) e = hipMemcpyAsync(J, dJ, sizeof(double) * nc * nnu, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(duvb);
-    if (!J_on_device && dJ) (void)hipFree(dJ);
     if (e != hipSuccess) return fail(c, FTTE_ERR_NO_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
     if (lrc) return fail(c, FTTE_ERR_NO_DEVICE, std::string(who) + ": kernel launch failed");
     return FTTE_OK;

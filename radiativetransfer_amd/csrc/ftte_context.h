@@ -2,6 +2,9 @@
 // entry points of the planners (ftte_plan.cpp), the sweeps (ftte_sweeps.cpp: segment forests, cell-fixed bricks), the hybrid sweep
 // of refined cell arrays (ftte_hybrid.cpp) and the host-array transfers (ftte_host_arrays.cpp).  ftte_api.cpp is the C ABI itself.
 //
+// Every device buffer, pinned buffer, stream, event and graph of the context is a member that owns it (ftte_device.h): a buffer's
+// capacity travels with its pointer, `delete c` releases everything, and a new buffer is added by declaring it.
+//
 // There is no CPU fallback behind any of this: every entry point that computes on the grid needs a HIP device and fails with
 // FTTE_ERR_NO_DEVICE otherwise.
 #pragma once
@@ -20,6 +23,7 @@
 
 #include "../../include/ftte.h"
 #include "ftte_amr.h"
+#include "ftte_device.h"
 #include "ftte_geometry.h"
 #include "ftte_internal.h"
 #include "ftte_kernels.h"
@@ -107,11 +111,11 @@ struct BrickPlan {
 };
 
 struct LaunchTiming {
-    hipEvent_t start = nullptr, stop = nullptr;
+    Event start, stop;
     int64_t updates = 0;
     // brick sweep with per-lane layouts and merges: the stage launches of lane k lie between first[k] and last[k] (recorded on the
     // lane's stream); the phase is from the earliest first to the latest last, both measured from `start`
-    std::vector<hipEvent_t> first, last;
+    std::vector<Event> first, last;
     int lanes = 0;
 };
 
@@ -126,7 +130,7 @@ namespace ftte { struct Multi; }
 struct ftte_ctx {
     ftte::Multi *multi = nullptr;   // ftte_create with ndev > 1: this context only routes to one single-device context per device (ftte_multi.cpp)
     int device = 0;
-    hipStream_t stream = nullptr;
+    Stream stream;                  // (declared in front of the other owners: it goes last)
     std::string err;
 
     bool grid_set = false;
@@ -135,35 +139,33 @@ struct ftte_ctx {
     double box = 0;
 
     int nnu = 0;
-    double *kappa[3] = {nullptr, nullptr, nullptr}; // layouts 0,1,2
+    DeviceBuffer<double> kappa[3]; // layouts 0,1,2; [1], [2] and the emis / kappa_tiled buffers are made at the capacity of [0]
     bool kappa_ready[4] = {false, false, false, false}; // [3]: the cell-major copy of the forest path
     // the opacities once more in brick order (BrickLaunch::tiled), per axis order; valid while kappa_tiled_from is the count of
     // opacity changes (n_kappa_sets) they were made at
-    double *kappa_tiled[3] = {nullptr, nullptr, nullptr};
+    DeviceBuffer<double> kappa_tiled[3];
     long long kappa_tiled_from[3] = {-1, -1, -1}, n_kappa_sets = 0;
     int kappa_tiled_chunk[3] = {0, 0, 0}; // layers per piece they were made with (tiled == 2), else 0
     int tiled_opt = 0; // option "tiled" (measured: no gain)
     int amr_kappa_form = 0;  // what that copy holds: 0 every leaf in cell-array order, 1 the leaves of the hybrid plan's list
-    size_t kappa_cap = 0; // elements per layout buffer
 
     // emissivity (mode 1: the reference's eta) or source function (mode 2), same three layouts as kappa
     int emit_mode = 0;
-    double *emis[3] = {nullptr, nullptr, nullptr};
+    DeviceBuffer<double> emis[3];
     bool emis_ready[4] = {false, false, false, false};
 
-    double *acc[3][kMaxAcc] = {};
-    size_t acc_cap = 0; // elements per accumulator
+    DeviceBuffer<double> acc[3][kMaxAcc]; // one size for all of them (accumulator_size)
 
     int rows = 8, slots = 8, waves = 4, stack = 1;
 
     // which organisation sweeps a uniform grid: 0 = the default = 2 = cell-fixed bricks (brick_kernel), 1 = ray-following tiles
     // (sweep_kernel)
     int engine = 0, chunk = 0, group = 0, brick_waves = 4, pair_waves = 4, last_brick_form = -1, last_brick_dataflow = -1, share = 2, team = -1, lanes = 2; // chunk, group: 0 = by the parallelism (build_brick_plan)
-    std::vector<hipStream_t> lane_stream;   // extra streams of the brick sweep (frequency groups are independent)
-    std::vector<hipEvent_t> pipe_up;        // ftte_diffuse_iteration: lane k's opacities have arrived
+    std::vector<Stream> lane_stream;        // extra streams of the brick sweep (frequency groups are independent)
+    std::vector<Event> pipe_up;             // ftte_diffuse_iteration: lane k's opacities have arrived
     bool stage_used[2] = {false, false};    // the pinned staging block has a transfer recorded on stage_ev
-    std::vector<hipEvent_t> lane_done;
-    hipEvent_t ev_fork = nullptr;
+    std::vector<Event> lane_done;
+    Event ev_fork;
     // option: 0 = a launch per stage; 1, 2 = the bricks of a sweep in ONE launch where the grid allows it, a workgroup per brick,
     // waiting for each other through flags (cross-XCD hand-overs: L2 write-back per brick, or write-through stores); 3 = one launch of
     // persistent workgroups that draw bricks from a queue per XCD (hand-overs stay behind one L2: plain stores)
@@ -171,26 +173,26 @@ struct ftte_ctx {
     int atomic_acc = 0;               // option "atomic_acc": later visitors of an accumulator add with fp64 atomics instead of read-add-store
     int ablate = 0;                   // diagnostic option "ablate": parts of the brick kernel's memory traffic left out (wrong J; timing only)
     int queue_mix = 0;                // persistent form: 0 = a frequency group per queue where they divide, else by load; 1 = by load; 2 = (group + accumulator) mod queues
-    int32_t *d_bdeps = nullptr; size_t d_bdeps_cap = 0;
-    uint32_t *d_bdone = nullptr; size_t d_bdone_cap = 0;
-    uint32_t *d_bsync = nullptr;      // [32 q] ticket of queue q (one counter, [0], without queues), [32 kBrickQueues] error
-    uint32_t *h_berror = nullptr;     // pinned: [0] the error flag of the last dataflow sweep, [1 + q] its tickets, copied back behind it
+    DeviceBuffer<int32_t> d_bdeps;
+    DeviceBuffer<uint32_t> d_bdone;
+    DeviceBuffer<uint32_t> d_bsync;   // [32 q] ticket of queue q (one counter, [0], without queues), [32 kBrickQueues] error
+    PinnedBuffer<uint32_t> h_berror;  // pinned: [0] the error flag of the last dataflow sweep, [1 + q] its tickets, copied back behind it
     uint32_t bqlen[kBrickQueues] = {}; // what those tickets must have reached (0: no persistent sweep pending)
-    uint32_t *d_bqueue = nullptr; size_t d_bqueue_cap = 0; bool bqueue_uploaded = false;
+    DeviceBuffer<uint32_t> d_bqueue; bool bqueue_uploaded = false;
     int xcc_count = -1;               // XCC ids this device reports (census, ftte_brick.hip); -1: not taken yet
     int8_t xcc_queue[16] = {};        // XCC id -> 0 .. xcc_count - 1, or -1
     uint32_t bepoch = 0;
     BrickPlan bplan;
     bool bplan_uploaded = false;
-    LayerRec *d_blayers = nullptr; size_t d_blayers_cap = 0;
-    BrickGroup *d_bgroups = nullptr; size_t d_bgroups_cap = 0;
-    BrickTask *d_btasks = nullptr; size_t d_btasks_cap = 0;
-    double *d_faces = nullptr; size_t d_faces_cap = 0;
+    DeviceBuffer<LayerRec> d_blayers;
+    DeviceBuffer<BrickGroup> d_bgroups;
+    DeviceBuffer<BrickTask> d_btasks;
+    DeviceBuffer<double> d_faces;
 
     Plan plan;
-    LayerRec *d_layers = nullptr; size_t d_layers_cap = 0;
-    WorkItem *d_items = nullptr;  size_t d_items_cap = 0;
-    double *d_uvb = nullptr;      size_t d_uvb_cap = 0;
+    DeviceBuffer<LayerRec> d_layers;
+    DeviceBuffer<WorkItem> d_items;
+    DeviceBuffer<double> d_uvb;
     std::vector<char> bgroups_sent;   // the bytes d_bgroups holds (brick_sweep), empty: unknown
     std::vector<double> uvb_sent;     // the values d_uvb holds (brick_sweep), empty: unknown
     bool plan_uploaded = false;
@@ -203,31 +205,30 @@ struct ftte_ctx {
     bool use_forest = false;  // refined grid (or option "forest" = 1 on a uniform one, for cross-checks)
     int force_forest = 0;
     struct ForestDev {
-        SegRec *rec = nullptr;
-        uint8_t *active = nullptr;
+        DeviceBuffer<SegRec> rec;
+        DeviceBuffer<uint8_t> active;
         std::vector<int64_t> depth_off;
         double w = 0;
     };
     std::vector<ForestDev> forests;
     std::vector<double> forest_key; // phi, theta, w of the cached forests (+ box)
-    AmrDirRec *d_amr_dirs = nullptr; size_t d_amr_dirs_cap = 0;      // per-direction records of the forest batches
-    int64_t *d_amr_tables = nullptr; size_t d_amr_tables_cap = 0;    // per batch and depth: count[], begin[]
-    double *amr_Iout = nullptr, *amr_mean = nullptr;
-    double *amr_kappa = nullptr, *amr_emis = nullptr; // [ncell][nnu] copies
-    size_t amr_kappa_cap = 0, amr_emis_cap = 0;
-    size_t amr_scratch_cap = 0; // elements per array
+    DeviceBuffer<AmrDirRec> d_amr_dirs;     // per-direction records of the forest batches
+    DeviceBuffer<int64_t> d_amr_tables;     // per batch and depth: count[], begin[]
+    DeviceBuffer<double> amr_Iout, amr_mean; // segment scratch, the same number of elements each (amr_scratch)
+    DeviceBuffer<double> amr_kappa, amr_emis; // [ncell][nnu] copies
+    size_t amr_scratch() const { return std::min(amr_Iout.capacity(), amr_mean.capacity()); }
 
     // partial merges run beside the sweeps of the next layout on their own (non-blocking) stream
-    hipStream_t merge_stream = nullptr;
-    hipEvent_t ev_layout_done = nullptr, ev_merge_done = nullptr, ev_layouts_ready = nullptr;
+    Stream merge_stream;
+    Event ev_layout_done, ev_merge_done, ev_layouts_ready;
     // brick sweep, option "merge_overlap" (1 = default): J merged block by block on merge_stream as the stages finish the blocks
     // (BrickPlan::merge_blocks), behind ev_merge_point[lane * points + m] of each lane; 0 = one merge after the last stage
     int merge_overlap = 1;
-    std::vector<hipEvent_t> ev_merge_point;
-    int32_t *d_mblocks = nullptr; size_t d_mblocks_cap = 0;
+    std::vector<Event> ev_merge_point;
+    DeviceBuffer<int32_t> d_mblocks;
     // end of the last sweep on whatever stream the caller gave it: the setters and the next sweep wait for it before they
     // overwrite what that sweep reads
-    hipEvent_t ev_sweep_done = nullptr;
+    Event ev_sweep_done;
     bool sweep_pending = false;
 
     // Hybrid sweep of a refined cell array: bricks outside a box around the refined cells, the segment forest inside it
@@ -238,13 +239,13 @@ struct ftte_ctx {
     int hybrid_lanes = 1;                 // option "box_lanes": along u the boxes of the hybrid sweep end on multiples of this many lanes
     int halves = 3;                       // option "pipelines": the hybrid sweep as this many independent pipelines on streams of their own (1..kMaxPipes)
     static constexpr int kMaxPipes = 4;
-    hipEvent_t ev_combine[kMaxPipes] = {nullptr, nullptr, nullptr, nullptr}; // hybrid sweep: pipeline k's forest means are in J
+    Event ev_combine[kMaxPipes]; // hybrid sweep: pipeline k's forest means are in J
     struct HybridPlan {
         bool valid = false, worthwhile = false;
         std::vector<double> key;          // box, chunk, group, share, then phi, theta, w
         BrickPlan bricks;                 // groups, tasks of the bricks outside the regions (phase 1, then phase 3)
         size_t phase1_stages = 0;         // stage lists per phase
-        hipGraphExec_t graph_exec = nullptr; // the launches of one sweep, captured (hybrid_sweep)
+        GraphExec graph_exec;             // the launches of one sweep, captured (hybrid_sweep)
         std::vector<uintptr_t> graph_sig;    // what they name: J, the buffers, the tables
         bool slots = false;               // several passes: launch lists by slot (earliest launch a brick's inputs allow), not by phase
         std::vector<std::vector<int>> pass_at; // [pipeline][pass] the list in front of which the pass's forests are launched
@@ -256,11 +257,11 @@ struct ftte_ctx {
         std::vector<std::vector<int>> half_dirs; // directions of each half, list order
         std::vector<size_t> stage_off;    // into bricks.tasks: [half][list]
         int64_t brick_updates = 0;        // cell.direction updates the bricks perform (per frequency group)
-        struct Dir { SegRec *rec = nullptr; uint8_t *active = nullptr; AmrExport *exports = nullptr; int64_t nexports = 0;
-                     AmrImport *imports = nullptr; int64_t nimports = 0; // into the face rings of a fine block's bricks
+        struct Dir { DeviceBuffer<SegRec> rec; DeviceBuffer<uint8_t> active; DeviceBuffer<AmrExport> exports; int64_t nexports = 0;
+                     DeviceBuffer<AmrImport> imports; int64_t nimports = 0; // into the face rings of a fine block's bricks
                      std::vector<int64_t> depth_off; std::vector<int32_t> pass_first; std::vector<int64_t> export_first; };
         std::vector<Dir> dirs;
-        int32_t *cells = nullptr; int64_t ncells = 0; // the leaves inside the box of at least one direction
+        DeviceBuffer<int32_t> cells; int64_t ncells = 0; // the leaves inside the box of at least one direction
         bool uploaded = false;
         // A fully refined block swept by bricks of its own on the fine level (option "fine_bricks"; one cluster that is a cube of
         // base cells refined exactly once, twice its side a multiple of 64): inside it the fine cells are a uniform grid
@@ -274,32 +275,27 @@ struct ftte_ctx {
             int nstages = 0;
             int64_t face_base = 0;              // where the fine face block starts inside a direction's face block (= bricks.face_elems)
             int64_t updates = 0;                // cell.direction updates the fine bricks perform (per frequency group)
-            int32_t *leaf_of_fine = nullptr;    // device: [n^3], fine cell in storage order -> leaf
-            LayerRec *layers = nullptr; BrickTask *tasks = nullptr; BrickGroup *groups = nullptr; // device
+            DeviceBuffer<int32_t> leaf_of_fine; // device: [n^3], fine cell in storage order -> leaf
+            DeviceBuffer<LayerRec> layers; DeviceBuffer<BrickTask> tasks; DeviceBuffer<BrickGroup> groups; // device
         } fine;
     } hplan;
     int forest_fuse = 4096;           // option "forest_fuse": levels of a forest with at most this many (segment, group) pairs in one launch (0: a launch per level)
     int fine_bricks = 1, fine_chunk = 0;  // options "fine_bricks", "fine_chunk" (0: the base bricks' chunk)
-    double *fine_kappa[3] = {nullptr, nullptr, nullptr};  // the fine block's opacities, dense, in the three layouts
-    size_t fine_kappa_cap = 0;
-    double *fine_emis[3] = {nullptr, nullptr, nullptr};   // its emissivity / source function
-    size_t fine_emis_cap = 0;
-    double *fine_acc[3][kMaxAcc] = {};    // its groups' J accumulators
-    size_t fine_acc_cap = 0;
-    int32_t *d_leaf_of_base = nullptr;
-    double *base_kappa[3] = {nullptr, nullptr, nullptr};
-    size_t base_kappa_cap = 0;
-    double *base_emis[3] = {nullptr, nullptr, nullptr}; // emissivity / source function of the base cells (hybrid sweep with emission)
-    size_t base_emis_cap = 0;
+    DeviceBuffer<double> fine_kappa[3];   // the fine block's opacities, dense, in the three layouts
+    DeviceBuffer<double> fine_emis[3];    // its emissivity / source function
+    DeviceBuffer<double> fine_acc[3][kMaxAcc]; // its groups' J accumulators
+    DeviceBuffer<int32_t> d_leaf_of_base;
+    DeviceBuffer<double> base_kappa[3];
+    DeviceBuffer<double> base_emis[3];    // emissivity / source function of the base cells (hybrid sweep with emission)
 
     PointState point; // point sources: rate tables, medium, tracer scratch
 
     // host-array boundary (ftte_set_opacity / ftte_diffuse_sweep): J lives in a device buffer the context keeps, and
     // pageable host arrays cross PCIe through two pinned staging blocks filled by a few host threads while the other
     // block is in flight; arrays the caller has registered (ftte_host_register) are copied by the DMA engine directly
-    double *host_J_dev = nullptr; size_t host_J_cap = 0;
-    void *stage[2] = {nullptr, nullptr};
-    hipEvent_t stage_ev[2] = {nullptr, nullptr};
+    DeviceBuffer<double> host_J_dev;
+    PinnedBuffer<char> stage[2];
+    Event stage_ev[2];
     struct HostRange { const char *base; size_t bytes; };
     std::vector<HostRange> registered;
     std::vector<HostRange> registered_elsewhere; // pinned by another context of the same process (the devices of one multi-device context)
@@ -309,23 +305,20 @@ struct ftte_ctx {
 
     // ionisation equilibrium (solveRateEquations)
     std::vector<int8_t> leaf_level;  // per leaf, as handed to ftte_set_grid
-    int8_t *chem_level = nullptr;
-    double *chem_k = nullptr;        // [6][nratec]
+    DeviceBuffer<int8_t> chem_level;
+    DeviceBuffer<double> chem_k;     // [6][nratec]
     int chem_nratec = 0;
     double chem_logtem0 = 0, chem_logtem9 = 0, chem_dlogtem = 0;
-    double *chem_logtem = nullptr;   // [ncell] log of the gas temperature
+    DeviceBuffer<double> chem_logtem; // [ncell] log of the gas temperature
     bool chem_temperature_set = false;
-    double *chem_out = nullptr, *chem_J = nullptr; // [3][ncell] each
-    unsigned long long *chem_counters = nullptr;   // first bad cell, bits of the largest change, bisection steps
+    DeviceBuffer<double> chem_out, chem_J; // [3][ncell] each
+    DeviceBuffer<unsigned long long> chem_counters; // first bad cell, bits of the largest change, bisection steps
     long long chem_steps = 0;
-    double *chem_mass = nullptr;     // computeMass: per-workgroup partial sums, then the two totals (kMassParts)
+    DeviceBuffer<double> chem_mass;  // computeMass: per-workgroup partial sums, then the two totals (kMassParts)
 
     void drop_chem_grid()
     {
-        if (chem_level) { (void)hipFree(chem_level); chem_level = nullptr; }
-        if (chem_logtem) { (void)hipFree(chem_logtem); chem_logtem = nullptr; }
-        if (chem_out) { (void)hipFree(chem_out); chem_out = nullptr; }
-        if (chem_J) { (void)hipFree(chem_J); chem_J = nullptr; }
+        chem_level.reset(); chem_logtem.reset(); chem_out.reset(); chem_J.reset();
         chem_temperature_set = false;
     }
 };
@@ -355,16 +348,6 @@ int fail(ftte_ctx *c, int code, const std::string &msg);
 
 int fold_status(int rc);
 
-template <typename T> int ensure(ftte_ctx *c, T **p, size_t *cap, size_t need)
-{
-    if (*cap >= need && *p) return FTTE_OK;
-    if (*p) FTTE_HIP(c, hipFree(*p));
-    *p = nullptr; *cap = 0;
-    FTTE_HIP(c, hipMalloc((void **)p, std::max<size_t>(need, 1) * sizeof(T)));
-    *cap = need;
-    return FTTE_OK;
-}
-
 // ---- ftte_plan.cpp
 // A cubic sub-grid planned like a grid of its own (the fine cells of a fully refined block): side, cell size, and where the layers'
 // patterns come from (`patterns` fills n of them for direction d, folded to phi, theta, izone; returns 0 or an ftte_status)
@@ -388,6 +371,9 @@ int check_ready(ftte_ctx *c, bool need_kappa);
 int wait_sweep(ftte_ctx *c);
 int mark_sweep(ftte_ctx *c, hipStream_t stream);
 void free_forests(ftte_ctx *c);
+// The accumulators of a set (ftte_ctx::acc, fine_acc) have one size.  Where that is less than per_acc elements every one of them is
+// released; returns the size to reserve for those a sweep uses.
+size_t accumulator_size(DeviceBuffer<double> (&acc)[3][kMaxAcc], size_t per_acc);
 
 // One direction of a forest pass as the host knows it
 struct ForestDirHost {

@@ -35,8 +35,8 @@ void parallel_copy(void *dst, const void *src, size_t bytes)
 int ensure_stage(ftte_ctx *c)
 {
     for (int q = 0; q < 2; ++q) {
-        if (!c->stage[q]) FTTE_HIP(c, hipHostMalloc(&c->stage[q], kStageBytes, hipHostMallocDefault));
-        if (!c->stage_ev[q]) FTTE_HIP(c, hipEventCreateWithFlags(&c->stage_ev[q], hipEventDisableTiming));
+        FTTE_HIP(c, c->stage[q].reserve(kStageBytes));
+        FTTE_HIP(c, c->stage_ev[q].create(hipEventDisableTiming));
     }
     return FTTE_OK;
 }

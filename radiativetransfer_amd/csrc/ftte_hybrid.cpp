@@ -14,26 +14,22 @@ namespace ftte {
 
 static void drop_graph(ftte_ctx::HybridPlan &H)
 {
-    if (H.graph_exec) (void)hipGraphExecDestroy(H.graph_exec);
-    H.graph_exec = nullptr;
+    H.graph_exec.reset();
     H.graph_sig.clear();
 }
 
 void free_hybrid(ftte_ctx *c)
 {
-    drop_graph(c->hplan);
-    for (auto &d : c->hplan.dirs) {
-        if (d.rec) (void)hipFree(d.rec);
-        if (d.active) (void)hipFree(d.active);
-        if (d.exports) (void)hipFree(d.exports);
-    }
-    if (c->hplan.cells) (void)hipFree(c->hplan.cells);
-    for (auto &D : c->hplan.dirs) if (D.imports) (void)hipFree(D.imports);
-    if (c->hplan.fine.leaf_of_fine) (void)hipFree(c->hplan.fine.leaf_of_fine);
-    if (c->hplan.fine.layers) (void)hipFree(c->hplan.fine.layers);
-    if (c->hplan.fine.tasks) (void)hipFree(c->hplan.fine.tasks);
-    if (c->hplan.fine.groups) (void)hipFree(c->hplan.fine.groups);
     c->hplan = ftte_ctx::HybridPlan();
+}
+
+// Three layouts of one size: where one of them is too small all three are released before the first is allocated anew
+static int reserve_layouts(ftte_ctx *c, DeviceBuffer<double> (&buf)[3], size_t need)
+{
+    if (std::min({buf[0].capacity(), buf[1].capacity(), buf[2].capacity()}) < need)
+        for (auto &b : buf) b.reset();
+    for (auto &b : buf) FTTE_HIP(c, b.reserve(need));
+    return FTTE_OK;
 }
 
 // Where the refined base cells are, in storage coordinates (1-based, inclusive): one bounding box per cluster.  Two refined cells
@@ -624,7 +620,7 @@ int build_hybrid_plan(ftte_ctx *c, int ndir, const double *phi, const double *th
     for (int64_t q = 0; q < ncell; ++q)
         if (in_any[(size_t)q]) { place[(size_t)q] = (int32_t)cells.size(); cells.push_back((int32_t)q); }
     H.ncells = (int64_t)cells.size();
-    FTTE_HIP(c, hipMalloc((void **)&H.cells, sizeof(int32_t) * std::max<size_t>(cells.size(), 1)));
+    FTTE_HIP(c, H.cells.reserve(cells.size()));
     if (!cells.empty()) FTTE_HIP(c, hipMemcpy(H.cells, cells.data(), sizeof(int32_t) * cells.size(), hipMemcpyHostToDevice));
     {
         auto renumber = [&](int32_t sg) { return sg < 0 ? sg : 3 * place[(size_t)(sg / 3)] + sg % 3; }; // negative: inflow / import marks
@@ -657,16 +653,16 @@ int build_hybrid_plan(ftte_ctx *c, int ndir, const double *phi, const double *th
     }
     for (int d = 0; d < ndir; ++d) {
         ftte_ctx::HybridPlan::Dir &D = H.dirs[(size_t)d];
-        FTTE_HIP(c, hipMalloc((void **)&D.rec, sizeof(SegRec) * rec[(size_t)d].size()));
-        FTTE_HIP(c, hipMalloc((void **)&D.active, std::max<size_t>(bytes[(size_t)d].size(), 1)));
-        FTTE_HIP(c, hipMalloc((void **)&D.exports, sizeof(AmrExport) * std::max<size_t>(exports[(size_t)d].size(), 1)));
+        FTTE_HIP(c, D.rec.reserve(rec[(size_t)d].size()));
+        FTTE_HIP(c, D.active.reserve(bytes[(size_t)d].size()));
+        FTTE_HIP(c, D.exports.reserve(exports[(size_t)d].size()));
         FTTE_HIP(c, hipMemcpy(D.rec, rec[(size_t)d].data(), sizeof(SegRec) * rec[(size_t)d].size(), hipMemcpyHostToDevice));
         if (!bytes[(size_t)d].empty()) FTTE_HIP(c, hipMemcpy(D.active, bytes[(size_t)d].data(), bytes[(size_t)d].size(), hipMemcpyHostToDevice));
         if (!exports[(size_t)d].empty())
             FTTE_HIP(c, hipMemcpy(D.exports, exports[(size_t)d].data(), sizeof(AmrExport) * exports[(size_t)d].size(), hipMemcpyHostToDevice));
         D.nimports = (int64_t)imports[(size_t)d].size();
         if (D.nimports) {
-            FTTE_HIP(c, hipMalloc((void **)&D.imports, sizeof(AmrImport) * imports[(size_t)d].size()));
+            FTTE_HIP(c, D.imports.reserve(imports[(size_t)d].size()));
             FTTE_HIP(c, hipMemcpy(D.imports, imports[(size_t)d].data(), sizeof(AmrImport) * imports[(size_t)d].size(), hipMemcpyHostToDevice));
         }
         std::vector<SegRec>().swap(rec[(size_t)d]);
@@ -684,13 +680,13 @@ int build_hybrid_plan(ftte_ctx *c, int ndir, const double *phi, const double *th
                     map[((size_t)a * nf + b) * nf + d] = c->tree.leaf[(size_t)(c->tree.child0[(size_t)node] + 4 * (a % 2) + 2 * (b % 2) + (d % 2))];
                 }
         const BrickPlan &Q = FN.plan;
-        FTTE_HIP(c, hipMalloc((void **)&FN.leaf_of_fine, sizeof(int32_t) * map.size()));
+        FTTE_HIP(c, FN.leaf_of_fine.reserve(map.size()));
         FTTE_HIP(c, hipMemcpy(FN.leaf_of_fine, map.data(), sizeof(int32_t) * map.size(), hipMemcpyHostToDevice));
-        FTTE_HIP(c, hipMalloc((void **)&FN.layers, sizeof(LayerRec) * Q.layers.size()));
+        FTTE_HIP(c, FN.layers.reserve(Q.layers.size()));
         FTTE_HIP(c, hipMemcpy(FN.layers, Q.layers.data(), sizeof(LayerRec) * Q.layers.size(), hipMemcpyHostToDevice));
-        FTTE_HIP(c, hipMalloc((void **)&FN.tasks, sizeof(BrickTask) * Q.tasks.size()));
+        FTTE_HIP(c, FN.tasks.reserve(Q.tasks.size()));
         FTTE_HIP(c, hipMemcpy(FN.tasks, Q.tasks.data(), sizeof(BrickTask) * Q.tasks.size(), hipMemcpyHostToDevice));
-        FTTE_HIP(c, hipMalloc((void **)&FN.groups, sizeof(BrickGroup) * Q.groups.size()));
+        FTTE_HIP(c, FN.groups.reserve(Q.groups.size()));
     }
     c->kappa_ready[3] = false; // the forests' copy of the opacities follows the list
     H.uploaded = false;
@@ -718,39 +714,25 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     if (!c->d_leaf_of_base) {
         std::vector<int32_t> map((size_t)nbase);
         for (int64_t b = 0; b < nbase; ++b) map[(size_t)b] = c->tree.leaf[(size_t)b];
-        FTTE_HIP(c, hipMalloc((void **)&c->d_leaf_of_base, sizeof(int32_t) * (size_t)nbase));
+        FTTE_HIP(c, c->d_leaf_of_base.reserve((size_t)nbase));
         FTTE_HIP(c, hipMemcpy(c->d_leaf_of_base, map.data(), sizeof(int32_t) * (size_t)nbase, hipMemcpyHostToDevice));
     }
     const size_t per_base = (size_t)nnu * (size_t)nbase;
-    if (c->base_kappa_cap < per_base) {
-        for (int l = 0; l < 3; ++l) if (c->base_kappa[l]) { FTTE_HIP(c, hipFree(c->base_kappa[l])); c->base_kappa[l] = nullptr; }
-        for (int l = 0; l < 3; ++l) FTTE_HIP(c, hipMalloc((void **)&c->base_kappa[l], sizeof(double) * per_base));
-        c->base_kappa_cap = per_base;
-    }
+    if ((rc = reserve_layouts(c, c->base_kappa, per_base))) return rc;
     const int emit = c->emit_mode;
-    if (emit && c->base_emis_cap < per_base) {
-        for (int l = 0; l < 3; ++l) if (c->base_emis[l]) { FTTE_HIP(c, hipFree(c->base_emis[l])); c->base_emis[l] = nullptr; }
-        for (int l = 0; l < 3; ++l) FTTE_HIP(c, hipMalloc((void **)&c->base_emis[l], sizeof(double) * per_base));
-        c->base_emis_cap = per_base;
-    }
-    if (c->acc_cap < (size_t)nnu * (size_t)ncell) {
-        for (int l = 0; l < 3; ++l)
-            for (int s = 0; s < kMaxAcc; ++s)
-                if (c->acc[l][s]) { FTTE_HIP(c, hipFree(c->acc[l][s])); c->acc[l][s] = nullptr; }
-        c->acc_cap = (size_t)nnu * (size_t)ncell;
-    }
+    if (emit && (rc = reserve_layouts(c, c->base_emis, per_base))) return rc;
+    const size_t acc_size = accumulator_size(c->acc, (size_t)nnu * (size_t)ncell);
     for (int l = 0; l < 3; ++l)
-        for (int s = 0; s < P.nacc[l]; ++s)
-            if (!c->acc[l][s]) FTTE_HIP(c, hipMalloc((void **)&c->acc[l][s], sizeof(double) * c->acc_cap));
+        for (int s = 0; s < P.nacc[l]; ++s) FTTE_HIP(c, c->acc[l][s].reserve(acc_size));
     ftte_ctx::HybridPlan::Fine &FN = H.fine;
     // a direction's face block: the base bricks' rings, then (a fine block swept by bricks) the fine bricks' own
     const int64_t face_elems = P.face_elems + (FN.active ? FN.plan.face_elems : 0);
     const size_t face_need = (size_t)ndir * nnu * (size_t)face_elems;
-    if ((rc = ensure(c, &c->d_faces, &c->d_faces_cap, face_need))) return rc;
+    FTTE_HIP(c, c->d_faces.reserve(face_need));
     if (!H.uploaded) {
-        if ((rc = ensure(c, &c->d_blayers, &c->d_blayers_cap, P.layers.size()))) return rc;
-        if ((rc = ensure(c, &c->d_btasks, &c->d_btasks_cap, P.tasks.size()))) return rc;
-        if ((rc = ensure(c, &c->d_bgroups, &c->d_bgroups_cap, P.groups.size()))) return rc;
+        FTTE_HIP(c, c->d_blayers.reserve(P.layers.size()));
+        FTTE_HIP(c, c->d_btasks.reserve(P.tasks.size()));
+        FTTE_HIP(c, c->d_bgroups.reserve(P.groups.size()));
         FTTE_HIP(c, hipMemcpy(c->d_blayers, P.layers.data(), sizeof(LayerRec) * P.layers.size(), hipMemcpyHostToDevice));
         if (!P.tasks.empty()) FTTE_HIP(c, hipMemcpy(c->d_btasks, P.tasks.data(), sizeof(BrickTask) * P.tasks.size(), hipMemcpyHostToDevice));
         H.uploaded = true;
@@ -780,24 +762,11 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
         // the fine block's own arrays -- opacities in the three layouts, an accumulator per group -- and its group records
         const BrickPlan &Q = FN.plan;
         const size_t per_fine = (size_t)nnu * (size_t)FN.n * FN.n * FN.n;
-        if (c->fine_kappa_cap < per_fine) {
-            for (int l = 0; l < 3; ++l) if (c->fine_kappa[l]) { FTTE_HIP(c, hipFree(c->fine_kappa[l])); c->fine_kappa[l] = nullptr; }
-            for (int l = 0; l < 3; ++l) FTTE_HIP(c, hipMalloc((void **)&c->fine_kappa[l], sizeof(double) * per_fine));
-            c->fine_kappa_cap = per_fine;
-        }
-        if (c->fine_acc_cap < per_fine) {
-            for (int l = 0; l < 3; ++l)
-                for (int a = 0; a < kMaxAcc; ++a) if (c->fine_acc[l][a]) { FTTE_HIP(c, hipFree(c->fine_acc[l][a])); c->fine_acc[l][a] = nullptr; }
-            c->fine_acc_cap = per_fine;
-        }
+        if ((rc = reserve_layouts(c, c->fine_kappa, per_fine))) return rc;
+        const size_t fine_acc_size = accumulator_size(c->fine_acc, per_fine);
         for (int l = 0; l < 3; ++l)
-            for (int a = 0; a < Q.nacc[l]; ++a)
-                if (!c->fine_acc[l][a]) FTTE_HIP(c, hipMalloc((void **)&c->fine_acc[l][a], sizeof(double) * c->fine_acc_cap));
-        if (emit && c->fine_emis_cap < per_fine) {
-            for (int l = 0; l < 3; ++l) if (c->fine_emis[l]) { FTTE_HIP(c, hipFree(c->fine_emis[l])); c->fine_emis[l] = nullptr; }
-            for (int l = 0; l < 3; ++l) FTTE_HIP(c, hipMalloc((void **)&c->fine_emis[l], sizeof(double) * per_fine));
-            c->fine_emis_cap = per_fine;
-        }
+            for (int a = 0; a < Q.nacc[l]; ++a) FTTE_HIP(c, c->fine_acc[l][a].reserve(fine_acc_size));
+        if (emit && (rc = reserve_layouts(c, c->fine_emis, per_fine))) return rc;
         std::vector<BrickGroup> G(Q.groups.size());
         std::memset(G.data(), 0, sizeof(BrickGroup) * G.size());
         for (size_t g = 0; g < Q.groups.size(); ++g) {
@@ -817,7 +786,7 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
         }
         FTTE_HIP(c, hipMemcpy(FN.groups, G.data(), sizeof(BrickGroup) * G.size(), hipMemcpyHostToDevice));
     }
-    if ((rc = ensure(c, &c->d_uvb, &c->d_uvb_cap, (size_t)nnu))) return rc;
+    FTTE_HIP(c, c->d_uvb.reserve((size_t)nnu));
     FTTE_HIP(c, hipMemcpy(c->d_uvb, uvb, sizeof(double) * nnu, hipMemcpyHostToDevice)); c->uvb_sent.clear();
 
     // forest scratch: as forest_sweep, for the leaves of the plan's list only
@@ -825,38 +794,35 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     // (numbered by the list, a direction's scratch is small: every direction at once, where the memory is there)
     const int most = c->forest_batch > 0 ? c->forest_batch : 1024;
     int batch = std::max(1, std::min(ndir, most));
-    if (c->amr_scratch_cap < per_dir * (size_t)batch) {
-        if (c->amr_Iout) { FTTE_HIP(c, hipFree(c->amr_Iout)); c->amr_Iout = nullptr; }
-        if (c->amr_mean) { FTTE_HIP(c, hipFree(c->amr_mean)); c->amr_mean = nullptr; }
-        c->amr_scratch_cap = 0;
+    if (c->amr_scratch() < per_dir * (size_t)batch) {
+        c->amr_Iout.reset(); c->amr_mean.reset();
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess)
             batch = (int)std::max<size_t>(1, std::min<size_t>((size_t)batch, (size_t)(0.6 * (double)free_b) / (2 * sizeof(double) * per_dir)));
-        FTTE_HIP(c, hipMalloc((void **)&c->amr_Iout, sizeof(double) * per_dir * (size_t)batch));
-        FTTE_HIP(c, hipMalloc((void **)&c->amr_mean, sizeof(double) * per_dir * (size_t)batch));
-        c->amr_scratch_cap = per_dir * (size_t)batch;
-    } else batch = (int)std::min<size_t>((size_t)most, c->amr_scratch_cap / per_dir);
+        FTTE_HIP(c, c->amr_Iout.reserve(per_dir * (size_t)batch));
+        FTTE_HIP(c, c->amr_mean.reserve(per_dir * (size_t)batch));
+    } else batch = (int)std::min<size_t>((size_t)most, c->amr_scratch() / per_dir);
     // Several passes keep every direction's scratch from pass to pass, and pipelines whose launch lists go by slot have each their
     // own place for a pass (pass_at[pipeline][pass]): with fewer directions resident than the sweep has, all pipelines' forests
     // would have to go in one run at ONE place, in front of bricks of the other pipelines that feed them or behind bricks that
     // read what they export.  Both are left to the forest path for the whole tree.
     if (batch < ndir && (H.npass > 1 || (H.slots && H.nhalves > 1) || FN.active)) return FTTE_OK; // (a fine block's forests come in two passes)
-    if ((rc = ensure(c, &c->amr_kappa, &c->amr_kappa_cap, (size_t)nnu * (size_t)std::max<int64_t>(H.ncells, 1)))) return rc;
+    FTTE_HIP(c, c->amr_kappa.reserve((size_t)nnu * (size_t)std::max<int64_t>(H.ncells, 1)));
     if (!c->kappa_ready[3] || c->amr_kappa_form != 1) {
         if (launch_cell_major(c->kappa[0], c->amr_kappa, ncell, nnu, stream, H.cells, (long)H.ncells)) return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
         c->kappa_ready[3] = true; c->amr_kappa_form = 1;
     }
     if (emit) { // the emissivity / source function of the boxes' leaves, cell-major like their opacities; new every iteration
-        if ((rc = ensure(c, &c->amr_emis, &c->amr_emis_cap, (size_t)nnu * (size_t)std::max<int64_t>(H.ncells, 1)))) return rc;
+        FTTE_HIP(c, c->amr_emis.reserve((size_t)nnu * (size_t)std::max<int64_t>(H.ncells, 1)));
         if (launch_cell_major(c->emis[0], c->amr_emis, ncell, nnu, stream, H.cells, (long)H.ncells)) return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
         c->emis_ready[3] = false; // (the forest path for the whole tree keeps every leaf there)
     }
 
     while (c->timing.size() < 1) {
         LaunchTiming t;
-        FTTE_HIP(c, hipEventCreate(&t.start));
-        FTTE_HIP(c, hipEventCreate(&t.stop));
-        c->timing.push_back(t);
+        FTTE_HIP(c, t.start.create());
+        FTTE_HIP(c, t.stop.create());
+        c->timing.push_back(std::move(t));
     }
     LaunchTiming &Tm = c->timing[0];
     Tm.updates = (int64_t)ndir * ncell * nnu; Tm.lanes = 0;
@@ -924,14 +890,14 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     hipStream_t qs[ftte_ctx::kMaxPipes] = {stream, stream, stream, stream};
     if (nh > 1) {
         while ((int)c->lane_stream.size() < nh - 1) {
-            hipStream_t q; hipEvent_t e;
-            FTTE_HIP(c, hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
-            FTTE_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            c->lane_stream.push_back(q); c->lane_done.push_back(e);
+            Stream q; Event e;
+            FTTE_HIP(c, q.create(hipStreamNonBlocking));
+            FTTE_HIP(c, e.create(hipEventDisableTiming));
+            c->lane_stream.push_back(std::move(q)); c->lane_done.push_back(std::move(e));
         }
-        if (!c->ev_fork) FTTE_HIP(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+        FTTE_HIP(c, c->ev_fork.create(hipEventDisableTiming));
         for (int r = 0; r < nh; ++r) {
-            if (!c->ev_combine[r]) FTTE_HIP(c, hipEventCreateWithFlags(&c->ev_combine[r], hipEventDisableTiming));
+            FTTE_HIP(c, c->ev_combine[r].create(hipEventDisableTiming));
             if (r) qs[r] = c->lane_stream[(size_t)r - 1];
         }
     }
@@ -964,14 +930,14 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     // (FTTE_HYBRID_TIMELINE: events at the phase boundaries of every pipeline, printed when the sweep is over -- a timeline without
     // a tracer, whose own cost per launch changes what overlaps what)
     static const bool timeline = std::getenv("FTTE_HYBRID_TIMELINE") != nullptr;
-    struct Mark { hipEvent_t e; int pipe; const char *what; };
+    struct Mark { Event e; int pipe; const char *what; };
     std::vector<Mark> marks;
     auto mark = [&](hipStream_t q, int pipe, const char *what) {
         if (!timeline) return;
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return;
+        Event e;
+        if (e.create() != hipSuccess) return;
         (void)hipEventRecord(e, q);
-        marks.push_back({e, pipe, what});
+        marks.push_back({std::move(e), pipe, what});
     };
     // ---- the launches of one sweep: the same sequence every iteration while plan and buffers stay what they are
     auto issue = [&]() -> int {
@@ -1019,7 +985,7 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
                 const int r = nh > 1 ? h : 0;
                 for (int pass = 0; pass < H.npass; ++pass) {
                     if ((size_t)H.pass_at[(size_t)h][(size_t)pass] != l || (nh == 1 && h > 0)) continue;
-                    hipEvent_t before = (nh > 1 && r > 0) ? c->ev_combine[r - 1] : nullptr, after = (nh > 1 && r + 1 < nh) ? c->ev_combine[r] : nullptr;
+                    hipEvent_t before = (nh > 1 && r > 0) ? c->ev_combine[r - 1].get() : nullptr, after = (nh > 1 && r + 1 < nh) ? c->ev_combine[r].get() : nullptr;
                     if (FN.active) { // the forest before the fine block's bricks, those, the forest behind them; the means below
                         mark(qs[r], r, "bricks before the box done");
                         if ((rc = launch_forest_pass(c, qs[r], runs[(size_t)r], 0, 0, A))) return rc;
@@ -1079,13 +1045,13 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     // once into a hipGraph -- the streams' forks and joins become dependencies of the graph -- and replays it while the plan, J and
     // every buffer and table the launches name stay the same.  Measured on ROCm 7.2 / MI355X the replay is SLOWER than issuing the
     // launches (configs[3]: 15.8 against 12.2 ms; 8 clusters in 5 passes: 23.9 against 15.1 ms), so it is off by default.
-    std::vector<uintptr_t> sig = {(uintptr_t)J_dev, (uintptr_t)stream, (uintptr_t)nnu, (uintptr_t)nh, (uintptr_t)c->kappa[0], (uintptr_t)c->amr_kappa,
-                                  (uintptr_t)c->d_faces, (uintptr_t)c->amr_Iout, (uintptr_t)c->amr_mean, (uintptr_t)c->d_bgroups, (uintptr_t)c->d_btasks,
-                                  (uintptr_t)c->d_amr_dirs, (uintptr_t)c->d_amr_tables, (uintptr_t)c->d_uvb, (uintptr_t)c->d_leaf_of_base, (uintptr_t)H.cells,
-                                  (uintptr_t)c->brick_waves, (uintptr_t)emit, (uintptr_t)c->emis[0], (uintptr_t)c->amr_emis, (uintptr_t)c->forest_fuse,
-                                  (uintptr_t)c->base_emis[0], (uintptr_t)c->base_emis[1], (uintptr_t)c->base_emis[2]};
-    for (int l = 0; l < 3; ++l) { sig.push_back((uintptr_t)c->base_kappa[l]); for (int s2 = 0; s2 < P.nacc[l]; ++s2) sig.push_back((uintptr_t)c->acc[l][s2]); }
-    if (FN.active) for (int l = 0; l < 3; ++l) { sig.push_back((uintptr_t)c->fine_kappa[l]); sig.push_back((uintptr_t)c->fine_emis[l]); for (int s2 = 0; s2 < FN.plan.nacc[l]; ++s2) sig.push_back((uintptr_t)c->fine_acc[l][s2]); }
+    std::vector<uintptr_t> sig = {(uintptr_t)J_dev, (uintptr_t)stream, (uintptr_t)nnu, (uintptr_t)nh, (uintptr_t)c->kappa[0].get(), (uintptr_t)c->amr_kappa.get(),
+                                  (uintptr_t)c->d_faces.get(), (uintptr_t)c->amr_Iout.get(), (uintptr_t)c->amr_mean.get(), (uintptr_t)c->d_bgroups.get(), (uintptr_t)c->d_btasks.get(),
+                                  (uintptr_t)c->d_amr_dirs.get(), (uintptr_t)c->d_amr_tables.get(), (uintptr_t)c->d_uvb.get(), (uintptr_t)c->d_leaf_of_base.get(), (uintptr_t)H.cells.get(),
+                                  (uintptr_t)c->brick_waves, (uintptr_t)emit, (uintptr_t)c->emis[0].get(), (uintptr_t)c->amr_emis.get(), (uintptr_t)c->forest_fuse,
+                                  (uintptr_t)c->base_emis[0].get(), (uintptr_t)c->base_emis[1].get(), (uintptr_t)c->base_emis[2].get()};
+    for (int l = 0; l < 3; ++l) { sig.push_back((uintptr_t)c->base_kappa[l].get()); for (int s2 = 0; s2 < P.nacc[l]; ++s2) sig.push_back((uintptr_t)c->acc[l][s2].get()); }
+    if (FN.active) for (int l = 0; l < 3; ++l) { sig.push_back((uintptr_t)c->fine_kappa[l].get()); sig.push_back((uintptr_t)c->fine_emis[l].get()); for (int s2 = 0; s2 < FN.plan.nacc[l]; ++s2) sig.push_back((uintptr_t)c->fine_acc[l][s2].get()); }
     FTTE_HIP(c, hipEventRecord(Tm.start, stream));
     bool replayed = false;
     if (c->use_graph && H.graph_exec && H.graph_sig == sig) {
@@ -1094,12 +1060,15 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     }
     if (!replayed && c->use_graph) {
         drop_graph(H);
-        hipGraph_t graph = nullptr;
         if (hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed) == hipSuccess) {
             const int irc = issue();
-            const hipError_t e = hipStreamEndCapture(stream, &graph);
-            if (irc == FTTE_OK && e == hipSuccess && graph && hipGraphInstantiate(&H.graph_exec, graph, nullptr, nullptr, 0) == hipSuccess &&
-                hipGraphLaunch(H.graph_exec, stream) == hipSuccess) {
+            hipGraph_t captured = nullptr;
+            hipGraphExec_t exec = nullptr;
+            const hipError_t e = hipStreamEndCapture(stream, &captured);
+            Graph graph;
+            graph.adopt(captured);
+            if (irc == FTTE_OK && e == hipSuccess && graph && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) H.graph_exec.adopt(exec);
+            if (H.graph_exec && hipGraphLaunch(H.graph_exec, stream) == hipSuccess) {
                 H.graph_sig = sig;
                 replayed = true;
             } else {
@@ -1107,7 +1076,6 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
                 drop_graph(H);
                 c->use_graph = 0; // this runtime or this sequence does not capture: launches one by one from now on
             }
-            if (graph) (void)hipGraphDestroy(graph);
         } else { (void)hipGetLastError(); c->use_graph = 0; }
     }
     if (!replayed && (rc = issue())) return rc;
@@ -1118,7 +1086,6 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
             float ms = 0.f;
             (void)hipEventElapsedTime(&ms, Tm.start, m.e);
             std::fprintf(stderr, "[ftte] hybrid timeline: %8.3f ms  pipeline %2d  %s\n", ms, m.pipe, m.what);
-            (void)hipEventDestroy(m.e);
         }
         float ms = 0.f;
         (void)hipEventElapsedTime(&ms, Tm.start, Tm.stop);

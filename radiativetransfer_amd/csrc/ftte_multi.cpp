@@ -67,9 +67,8 @@ struct Multi {
     std::vector<ftte_ctx *> sub;       // one single-device context per device, in the caller's order
     std::vector<int> dev;
     int nnu = 0, r_nu = 1, r_dir = 1;
-    std::vector<double *> J_part, J_red; // per device: its sweep's J [groups][ncell] (padded to r_dir pieces); its piece of the sum
-    std::vector<size_t> J_cap, red_cap;
-    std::vector<hipEvent_t> swept;     // per device: its sweep is enqueued up to here
+    std::vector<DeviceBuffer<double>> J_part, J_red; // per device: its sweep's J [groups][ncell] (padded to r_dir pieces); its piece of the sum
+    std::vector<Event> swept;          // per device: its sweep is enqueued up to here
     std::vector<void *> comm;          // per device: its communicator inside its group of r_dir devices, or empty
     int comm_r_dir = 0, comm_r_nu = 0;
     bool rccl = false;
@@ -125,9 +124,8 @@ int multi_create(ftte_ctx **out, int ndev, const int *dev_ids)
         M.dev.push_back(dev_ids[k]);
     }
     c->device = dev_ids[0];
-    M.J_part.assign((size_t)ndev, nullptr); M.J_red.assign((size_t)ndev, nullptr);
-    M.J_cap.assign((size_t)ndev, 0); M.red_cap.assign((size_t)ndev, 0);
-    M.swept.assign((size_t)ndev, nullptr);
+    M.J_part.resize((size_t)ndev); M.J_red.resize((size_t)ndev);
+    M.swept.resize((size_t)ndev);
     *out = c;
     return FTTE_OK;
 }
@@ -138,9 +136,7 @@ int multi_destroy(ftte_ctx *c)
     for (size_t k = 0; k < M.sub.size(); ++k) {
         (void)hipSetDevice(M.dev[k]);
         (void)hipDeviceSynchronize();
-        if (M.J_part[k]) (void)hipFree(M.J_part[k]);
-        if (M.J_red[k]) (void)hipFree(M.J_red[k]);
-        if (M.swept[k]) (void)hipEventDestroy(M.swept[k]);
+        M.J_part[k].reset(); M.J_red[k].reset(); M.swept[k].reset();
     }
     drop_comms(M);
     for (ftte_ctx *s : M.sub) (void)ftte_destroy(s);
@@ -259,20 +255,11 @@ int multi_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
         groups_of(M, k, &lo, &hi);
         bounds(ndir, k / M.r_nu, M.r_dir, &dlo, &dhi);
         const size_t total = (size_t)(hi - lo) * ncell, piece = (total + (size_t)M.r_dir - 1) / (size_t)M.r_dir;
-        if (M.J_cap[(size_t)k] < piece * (size_t)M.r_dir) {
-            if (M.J_part[(size_t)k]) FTTE_HIP(s, hipFree(M.J_part[(size_t)k]));
-            M.J_part[(size_t)k] = nullptr; M.J_cap[(size_t)k] = 0;
-            FTTE_HIP(s, hipMalloc((void **)&M.J_part[(size_t)k], sizeof(double) * piece * (size_t)M.r_dir));
-            FTTE_HIP(s, hipMemset(M.J_part[(size_t)k], 0, sizeof(double) * piece * (size_t)M.r_dir)); // (the padding of the last piece stays zero)
-            M.J_cap[(size_t)k] = piece * (size_t)M.r_dir;
-        }
-        if (M.r_dir > 1 && M.red_cap[(size_t)k] < piece) {
-            if (M.J_red[(size_t)k]) FTTE_HIP(s, hipFree(M.J_red[(size_t)k]));
-            M.J_red[(size_t)k] = nullptr; M.red_cap[(size_t)k] = 0;
-            FTTE_HIP(s, hipMalloc((void **)&M.J_red[(size_t)k], sizeof(double) * piece));
-            M.red_cap[(size_t)k] = piece;
-        }
-        if (!M.swept[(size_t)k]) FTTE_HIP(s, hipEventCreateWithFlags(&M.swept[(size_t)k], hipEventDisableTiming));
+        bool fresh = false;
+        FTTE_HIP(s, M.J_part[(size_t)k].reserve(piece * (size_t)M.r_dir, &fresh));
+        if (fresh) FTTE_HIP(s, hipMemset(M.J_part[(size_t)k], 0, sizeof(double) * piece * (size_t)M.r_dir)); // (the padding of the last piece stays zero)
+        if (M.r_dir > 1) FTTE_HIP(s, M.J_red[(size_t)k].reserve(piece));
+        FTTE_HIP(s, M.swept[(size_t)k].create(hipEventDisableTiming));
         const int src = ftte_diffuse_sweep_device(s, dhi - dlo, phi + dlo, theta + dlo, w + dlo, uvb + lo, M.J_part[(size_t)k], nullptr);
         if (src) return src;
         FTTE_HIP(s, hipEventRecord(M.swept[(size_t)k], s->stream));
@@ -362,11 +349,11 @@ static long long rccl_selftest(const Multi &M)
     const size_t n = 4096;
     std::vector<double> in(n), out(n, 0.0);
     for (size_t i = 0; i < n; ++i) in[i] = 1.0 / (double)(i + 3);
-    double *d_in = nullptr, *d_out = nullptr;
+    DeviceBuffer<double> d_in, d_out;
     void *comm = nullptr;
     long long verdict = -2;
     hipStream_t stream = M.sub[0]->stream;
-    if (hipMalloc((void **)&d_in, n * sizeof(double)) == hipSuccess && hipMalloc((void **)&d_out, n * sizeof(double)) == hipSuccess &&
+    if (d_in.reserve(n) == hipSuccess && d_out.reserve(n) == hipSuccess &&
         hipMemcpy(d_in, in.data(), n * sizeof(double), hipMemcpyHostToDevice) == hipSuccess &&
         hipMemset(d_out, 0, n * sizeof(double)) == hipSuccess) {
         int rc = g_rccl.CommInitAll(&comm, 1, &dev);
@@ -381,8 +368,6 @@ static long long rccl_selftest(const Multi &M)
             verdict = std::memcmp(in.data(), out.data(), n * sizeof(double)) == 0 ? 1 : 0;
     }
     if (comm) (void)g_rccl.CommDestroy(comm);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
     (void)hipGetLastError();
     return verdict;
 }

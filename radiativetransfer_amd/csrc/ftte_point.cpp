@@ -35,19 +35,6 @@ int hip_fail(std::string *err, const char *what, hipError_t e)
         if (e_ != hipSuccess) return hip_fail(err, #call, e_);                                                     \
     } while (0)
 
-template <class T> int ensure(T *&p, size_t count, std::string *err)
-{
-    if (p) return 0;
-    POINT_HIP(hipMalloc((void **)&p, sizeof(T) * count));
-    return 0;
-}
-
-template <class T> void drop(T *&p)
-{
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
 // hydrogenic photoionisation cross-section above threshold, stellarBetaTable.f90:40-44 and :52-56
 inline double hydrogenic(double sigma0, double threshold, double nu)
 {
@@ -59,28 +46,17 @@ inline double hydrogenic(double sigma0, double threshold, double nu)
 
 void PointState::drop_grid()
 {
-    drop(node);
+    node.reset();
     tree_ready = false;
-    for (auto &m : medium) drop(m);
-    drop(packed);
+    for (auto &m : medium) m.reset();
+    packed.reset();
     packed_ready = false;
     medium_cells = 0;
     medium_ready = false;
     rho_given = false;
-    drop(rates); drop(rate_planes);
+    rates.reset(); rate_planes.reset();
     rates_cells = 0;
     std::vector<int32_t>().swap(node_of_leaf);
-}
-
-void PointState::release()
-{
-    drop_grid();
-    drop(tables); drop(logtab); drop(bins); drop(pixdir);
-    drop(queue[0]); drop(queue[1]); drop(counters); drop(src_node); drop(src_ndot); drop(sample_in); drop(sample_out);
-    drop(escape); drop(sigma_ratio);
-    escape_capacity = 0; sigma_ready = false;
-    tables_ready = false;
-    queue_capacity = src_capacity = sample_capacity = 0;
 }
 
 double dust_cross_section(double lambda_um, const double *a_smc)
@@ -313,9 +289,9 @@ int point_stellar_beta_table(PointState &P, hipStream_t stream, const double *a_
         }
         if ((rc = point_set_output_sigma(P, stream, sigma, err))) return rc;
     }
-    if ((rc = ensure(P.tables, (size_t)6 * kTableSize, err))) return rc;
-    if ((rc = ensure(P.logtab, (size_t)6 * kTableSize, err))) return rc;
-    if ((rc = ensure(P.bins, (size_t)kFrequencies, err))) return rc;
+    POINT_HIP(P.tables.reserve((size_t)6 * kTableSize));
+    POINT_HIP(P.logtab.reserve((size_t)6 * kTableSize));
+    POINT_HIP(P.bins.reserve((size_t)kFrequencies));
     POINT_HIP(hipMemcpyAsync(P.bins, bins.data(), sizeof(FreqBin) * bins.size(), hipMemcpyHostToDevice, stream));
     if (launch_rate_table(P.bins, (int)bins.size(), P.tables, P.logtab, stream)) { *err = "rate table kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
     POINT_HIP(hipStreamSynchronize(stream)); // `bins` leaves scope
@@ -330,8 +306,7 @@ int point_set_output_sigma(PointState &P, hipStream_t stream, const double *sigm
     const double thr[4] = {W(6.30e-18), W(1.58e-18), W(7.42e-18), W(5.4116737e-22)};
     for (int q = 0; q < 4; ++q)
         for (int ie = 0; ie < kOutputEnergies; ++ie) ratio[q * kOutputEnergies + ie] = sigma[q * kOutputEnergies + ie] / thr[q];
-    int rc;
-    if ((rc = ensure(P.sigma_ratio, (size_t)4 * kOutputEnergies, err))) return rc;
+    POINT_HIP(P.sigma_ratio.reserve((size_t)4 * kOutputEnergies));
     POINT_HIP(hipMemcpyAsync(P.sigma_ratio, ratio, sizeof ratio, hipMemcpyHostToDevice, stream));
     POINT_HIP(hipStreamSynchronize(stream));
     P.sigma_ready = true;
@@ -341,9 +316,8 @@ int point_set_output_sigma(PointState &P, hipStream_t stream, const double *sigm
 int point_set_tables(PointState &P, hipStream_t stream, const double *tables, std::string *err)
 {
     P.sigma_ready = false; // the cross-sections belong to the population whose tables these replace: ftte_set_output_sigma
-    int rc;
-    if ((rc = ensure(P.tables, (size_t)6 * kTableSize, err))) return rc;
-    if ((rc = ensure(P.logtab, (size_t)6 * kTableSize, err))) return rc;
+    POINT_HIP(P.tables.reserve((size_t)6 * kTableSize));
+    POINT_HIP(P.logtab.reserve((size_t)6 * kTableSize));
     POINT_HIP(hipMemcpyAsync(P.tables, tables, sizeof(double) * 6 * kTableSize, hipMemcpyHostToDevice, stream));
     if (launch_log_table(P.tables, P.logtab, stream)) { *err = "table kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
     POINT_HIP(hipStreamSynchronize(stream));
@@ -362,13 +336,8 @@ int point_get_tables(PointState &P, hipStream_t stream, double *tables, std::str
 int point_lookup(PointState &P, hipStream_t stream, int dust, int nsample, const double *tau, double *rates, std::string *err)
 {
     if (!P.tables_ready) { *err = "no rate tables: call ftte_stellar_beta_table or ftte_set_rate_tables first"; return FTTE_ERR_STATE; }
-    if (nsample > P.sample_capacity) {
-        drop(P.sample_in); drop(P.sample_out);
-        P.sample_capacity = 0;
-        POINT_HIP(hipMalloc((void **)&P.sample_in, sizeof(double) * 4 * nsample));
-        POINT_HIP(hipMalloc((void **)&P.sample_out, sizeof(double) * 6 * nsample));
-        P.sample_capacity = nsample;
-    }
+    POINT_HIP(P.sample_in.reserve((size_t)4 * nsample));
+    POINT_HIP(P.sample_out.reserve((size_t)6 * nsample));
     POINT_HIP(hipMemcpyAsync(P.sample_in, tau, sizeof(double) * 4 * nsample, hipMemcpyHostToDevice, stream));
     if (launch_rate_lookup(P.logtab, dust, nsample, P.sample_in, P.sample_out, stream)) { *err = "look-up kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
     POINT_HIP(hipMemcpyAsync(rates, P.sample_out, sizeof(double) * 6 * nsample, hipMemcpyDeviceToHost, stream));
@@ -380,15 +349,14 @@ int point_set_medium(PointState &P, hipStream_t stream, int64_t ncell, const dou
                      std::string *err)
 {
     if (P.medium_cells != ncell) {
-        for (auto &m : P.medium) drop(m);
-        drop(P.packed);
+        for (auto &m : P.medium) m.reset();
+        P.packed.reset();
         P.medium_cells = 0;
         P.medium_ready = false;
     }
     P.packed_ready = false;
     for (int f = 0; f < 5; ++f) {
-        int rc;
-        if ((rc = ensure(P.medium[f], (size_t)ncell, err))) return rc;
+        POINT_HIP(P.medium[f].reserve((size_t)ncell));
         if (field[f])
             POINT_HIP(hipMemcpyAsync(P.medium[f], field[f], sizeof(double) * ncell, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
         else
@@ -404,9 +372,8 @@ int point_set_medium(PointState &P, hipStream_t stream, int64_t ncell, const dou
 
 int point_zero_rates(PointState &P, hipStream_t stream, int64_t ncell, std::string *err)
 {
-    if (P.rates_cells != ncell) { drop(P.rates); drop(P.rate_planes); P.rates_cells = 0; }
-    int rc;
-    if ((rc = ensure(P.rates, (size_t)kCellRec * ncell, err))) return rc;
+    if (P.rates_cells != ncell) { P.rates.reset(); P.rate_planes.reset(); P.rates_cells = 0; }
+    POINT_HIP(P.rates.reserve((size_t)kCellRec * ncell));
     P.rates_cells = ncell;
     POINT_HIP(hipMemsetAsync(P.rates, 0, sizeof(double) * kCellRec * ncell, stream));
     return 0;
@@ -414,8 +381,7 @@ int point_zero_rates(PointState &P, hipStream_t stream, int64_t ncell, std::stri
 
 int point_rate_planes(PointState &P, hipStream_t stream, double **planes, std::string *err)
 {
-    int rc;
-    if ((rc = ensure(P.rate_planes, (size_t)6 * P.rates_cells, err))) return rc;
+    POINT_HIP(P.rate_planes.reserve((size_t)6 * P.rates_cells));
     if (launch_repack_rates(P.rate_planes, P.rates, (long)P.rates_cells, false, stream)) { *err = "layout kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
     *planes = P.rate_planes;
     return 0;
@@ -425,7 +391,7 @@ int point_set_rates(PointState &P, hipStream_t stream, int64_t ncell, const doub
 {
     int rc;
     if ((rc = point_zero_rates(P, stream, ncell, err))) return rc;
-    if ((rc = ensure(P.rate_planes, (size_t)6 * ncell, err))) return rc;
+    POINT_HIP(P.rate_planes.reserve((size_t)6 * ncell));
     POINT_HIP(hipMemcpyAsync(P.rate_planes, planes_host, sizeof(double) * 6 * ncell, hipMemcpyHostToDevice, stream));
     if (launch_repack_rates(P.rate_planes, P.rates, (long)ncell, true, stream)) { *err = "layout kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
     POINT_HIP(hipStreamSynchronize(stream));
@@ -443,19 +409,20 @@ int point_trace(PointState &P, hipStream_t stream, const AmrTree &tree, double b
 
     const size_t nnode = tree.parent.size();
     if (!P.tree_ready) {
-        drop(P.node);
+        P.node.reset();
         if (tree.refined()) {
             std::vector<NodeRec> nodes(nnode);
             for (size_t v = 0; v < nnode; ++v) nodes[v] = NodeRec{tree.child0[v], tree.leaf[v], tree.parent[v], (int32_t)tree.level[v]};
-            if ((rc = ensure(P.node, nnode, err))) return rc;
+            POINT_HIP(P.node.reserve(nnode));
             POINT_HIP(hipMemcpyAsync(P.node, nodes.data(), sizeof(NodeRec) * nnode, hipMemcpyHostToDevice, stream));
             POINT_HIP(hipStreamSynchronize(stream));
         }
         P.tree_ready = true;
     }
     if (!P.packed_ready) {
-        if ((rc = ensure(P.packed, (size_t)kCellRec * tree.ncell, err))) return rc;
-        if (launch_pack_medium(P.medium, P.packed, (long)tree.ncell, stream)) { *err = "layout kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
+        POINT_HIP(P.packed.reserve((size_t)kCellRec * tree.ncell));
+        const double *const fields[5] = {P.medium[0], P.medium[1], P.medium[2], P.medium[3], P.medium[4]};
+        if (launch_pack_medium(fields, P.packed, (long)tree.ncell, stream)) { *err = "layout kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
         P.packed_ready = true;
     }
     if (!P.pixdir) {
@@ -474,30 +441,17 @@ int point_trace(PointState &P, hipStream_t stream, const AmrTree &tree, double b
                 dir[3 * at + 2] = std::sin(theta);
             }
         }
-        if ((rc = ensure(P.pixdir, dir.size(), err))) return rc;
+        POINT_HIP(P.pixdir.reserve(dir.size()));
         POINT_HIP(hipMemcpyAsync(P.pixdir, dir.data(), sizeof(double) * dir.size(), hipMemcpyHostToDevice, stream));
         POINT_HIP(hipStreamSynchronize(stream));
         rmax_table(P.rmax);
     }
-    if (!P.counters) {
-        if ((rc = ensure(P.counters, 8, err))) return rc;
-    }
+    POINT_HIP(P.counters.reserve(8));
     const int batch_max = nsrc < kSplitBatch ? nsrc : kSplitBatch;
     const int32_t need = batch_max * 3072; // at most 12 * 4^4 rays of one source split into level 6
-    if (need > P.queue_capacity) {
-        drop(P.queue[0]); drop(P.queue[1]);
-        P.queue_capacity = 0;
-        POINT_HIP(hipMalloc((void **)&P.queue[0], sizeof(SplitRec) * need));
-        POINT_HIP(hipMalloc((void **)&P.queue[1], sizeof(SplitRec) * need));
-        P.queue_capacity = need;
-    }
-    if (batch_max > P.src_capacity) {
-        drop(P.src_node); drop(P.src_ndot);
-        P.src_capacity = 0;
-        POINT_HIP(hipMalloc((void **)&P.src_node, sizeof(int32_t) * batch_max));
-        POINT_HIP(hipMalloc((void **)&P.src_ndot, sizeof(double) * batch_max));
-        P.src_capacity = batch_max;
-    }
+    for (auto &q : P.queue) POINT_HIP(q.reserve((size_t)need));
+    POINT_HIP(P.src_node.reserve((size_t)batch_max));
+    POINT_HIP(P.src_ndot.reserve((size_t)batch_max));
 
     // cell-array index -> tree node (kept until the grid changes; the identity on a uniform grid)
     if (tree.refined() && P.node_of_leaf.size() != (size_t)tree.ncell) {
@@ -511,12 +465,7 @@ int point_trace(PointState &P, hipStream_t stream, const AmrTree &tree, double b
         node_of[s] = tree.refined() ? P.node_of_leaf[(size_t)src_cell[s]] : (int32_t)src_cell[s];
     }
 
-    if ((size_t)nsrc * kEscapeRec > P.escape_capacity) {
-        drop(P.escape);
-        P.escape_capacity = 0;
-        POINT_HIP(hipMalloc((void **)&P.escape, sizeof(double) * (size_t)nsrc * kEscapeRec));
-        P.escape_capacity = (size_t)nsrc * kEscapeRec;
-    }
+    POINT_HIP(P.escape.reserve((size_t)nsrc * kEscapeRec));
     POINT_HIP(hipMemsetAsync(P.escape, 0, sizeof(double) * (size_t)nsrc * kEscapeRec, stream)); // :1267-1270
 
     TraceRec T;
@@ -537,7 +486,7 @@ int point_trace(PointState &P, hipStream_t stream, const AmrTree &tree, double b
     T.src_node = P.src_node; T.src_ndot = P.src_ndot;
     T.out_count = P.counters; T.highest_level = P.counters + 1; T.error = P.counters + 2;
     T.steps = reinterpret_cast<unsigned long long *>(P.counters + 4);
-    T.out_capacity = P.queue_capacity;
+    T.out_capacity = (int32_t)std::min(P.queue[0].capacity(), P.queue[1].capacity());
 
     int32_t host_counters[4] = {0, 0, 0, 0};
     int highest = 0;

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "ftte_amr.h"
+#include "ftte_device.h"
 #include "ftte_internal.h"
 
 namespace ftte {
@@ -19,46 +20,41 @@ constexpr int kSplitBatch = 1024;    // sources traced together; bounds the spli
 // Everything the point-source path keeps on the device.  Owned by the context.
 struct PointState {
     // the tree, uploaded on first use after ftte_set_grid (nothing is uploaded for a uniform grid)
-    NodeRec *node = nullptr;
+    DeviceBuffer<NodeRec> node;
     bool tree_ready = false;
     std::vector<int32_t> node_of_leaf; // cell-array index -> node
     // HI, HeI, HeII, rho, abun2 in cell-array order
-    double *medium[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    DeviceBuffer<double> medium[5];
     int64_t medium_cells = 0;
     int dust = 0;
     bool medium_ready = false;
-    double *packed = nullptr;   // [ncell][kCellRec] copy the tracer reads, rebuilt when the medium changes
+    DeviceBuffer<double> packed; // [ncell][kCellRec] copy the tracer reads, rebuilt when the medium changes
     bool packed_ready = false;
     bool rho_given = false;   // ftte_set_medium received a density (the equilibrium update needs it)
     // [6][11^4] rate tables and their logarithms
-    double *tables = nullptr, *logtab = nullptr;
+    DeviceBuffer<double> tables, logtab;
     bool tables_ready = false;
-    FreqBin *bins = nullptr;
-    double *pixdir = nullptr; // [kPixelCount][3]
+    DeviceBuffer<FreqBin> bins;
+    DeviceBuffer<double> pixdir; // [kPixelCount][3]
     double rmax[30];
     // [ncell][kCellRec] krate24, krate25, krate26, crate24, crate25, crate26, 0, 0: what the tracer adds into
-    double *rates = nullptr;
+    DeviceBuffer<double> rates;
     int64_t rates_cells = 0;
-    double *rate_planes = nullptr; // [6][ncell]: the layout of the interface, filled on request
+    DeviceBuffer<double> rate_planes; // [6][ncell]: the layout of the interface, filled on request
     // tracer scratch
-    SplitRec *queue[2] = {nullptr, nullptr};
-    int32_t queue_capacity = 0;
-    int32_t *counters = nullptr; // [0] queue length, [1] highest pixel level, [2] error, [4..5] 64-bit count of cell crossings
+    DeviceBuffer<SplitRec> queue[2];
+    DeviceBuffer<int32_t> counters; // [0] queue length, [1] highest pixel level, [2] error, [4..5] 64-bit count of cell crossings
     long long ray_steps = 0;     // of the last trace
-    int32_t *src_node = nullptr;
-    double *src_ndot = nullptr;
-    int32_t src_capacity = 0;
-    double *sample_in = nullptr, *sample_out = nullptr;
-    int32_t sample_capacity = 0;
+    DeviceBuffer<int32_t> src_node;
+    DeviceBuffer<double> src_ndot;
+    DeviceBuffer<double> sample_in, sample_out;
     // escape bookkeeping of the last trace (startNewLongRay, equiSources.f90:3198-3233, 3336-3345): per star ndotRemaining[7],
     // ndotBoundary[7], ndotDust, ndotSpectrum[300]
-    double *escape = nullptr;            // device, [stars of the call][kEscapeRec]
-    size_t escape_capacity = 0;
+    DeviceBuffer<double> escape;         // device, [stars of the call][kEscapeRec]
     std::vector<double> escape_host, escape_ndot; // the same on the host after the trace; the stars' photon rates
-    double *sigma_ratio = nullptr;       // device [4][300]: outputSigma* / threshold cross-section (stellarBetaTable.f90:119-152)
+    DeviceBuffer<double> sigma_ratio;    // device [4][300]: outputSigma* / threshold cross-section (stellarBetaTable.f90:119-152)
     bool sigma_ready = false;
 
-    void release();
     void drop_grid(); // after ftte_set_grid: tree, medium and rates belong to the old grid
 };
 

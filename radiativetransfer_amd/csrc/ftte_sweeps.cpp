@@ -9,15 +9,10 @@ namespace ftte {
 int ensure_kappa(ftte_ctx *c, int nnu)
 {
     const size_t need = (size_t)nnu * c->ncell;
-    if (c->kappa[0] && c->kappa_cap >= need) return FTTE_OK;
-    for (int l = 0; l < 3; ++l) {
-        if (c->kappa[l]) { FTTE_HIP(c, hipFree(c->kappa[l])); c->kappa[l] = nullptr; }
-        if (c->kappa_tiled[l]) { FTTE_HIP(c, hipFree(c->kappa_tiled[l])); c->kappa_tiled[l] = nullptr; }
-        if (c->emis[l]) { FTTE_HIP(c, hipFree(c->emis[l])); c->emis[l] = nullptr; }
-    }
+    if (c->kappa[0] && c->kappa[0].capacity() >= need) return FTTE_OK;
+    for (int l = 0; l < 3; ++l) { c->kappa[l].reset(); c->kappa_tiled[l].reset(); c->emis[l].reset(); }
     c->emit_mode = 0; // sized by the old number of groups: has to be set again
-    FTTE_HIP(c, hipMalloc((void **)&c->kappa[0], need * sizeof(double)));
-    c->kappa_cap = need;
+    FTTE_HIP(c, c->kappa[0].reserve(need));
     return FTTE_OK;
 }
 
@@ -71,13 +66,13 @@ int wait_sweep(ftte_ctx *c)
 int xcc_census(ftte_ctx *c)
 {
     if (c->xcc_count >= 0) return FTTE_OK;
-    unsigned *mask_dev = nullptr, mask = 0;
-    FTTE_HIP(c, hipMalloc((void **)&mask_dev, sizeof(unsigned)));
+    DeviceBuffer<unsigned> mask_dev;
+    unsigned mask = 0;
+    FTTE_HIP(c, mask_dev.reserve(1));
     FTTE_HIP(c, hipMemset(mask_dev, 0, sizeof(unsigned)));
-    if (launch_xcc_census(mask_dev, c->stream)) { (void)hipFree(mask_dev); return fail(c, FTTE_ERR_NO_DEVICE, "census kernel launch failed"); }
+    if (launch_xcc_census(mask_dev, c->stream)) { return fail(c, FTTE_ERR_NO_DEVICE, "census kernel launch failed"); }
     FTTE_HIP(c, hipStreamSynchronize(c->stream));
     FTTE_HIP(c, hipMemcpy(&mask, mask_dev, sizeof(unsigned), hipMemcpyDeviceToHost));
-    FTTE_HIP(c, hipFree(mask_dev));
     c->xcc_count = 0;
     for (int x = 0; x < 16; ++x) c->xcc_queue[x] = (mask >> x) & 1u ? (int8_t)c->xcc_count++ : (int8_t)-1;
     return FTTE_OK;
@@ -85,7 +80,7 @@ int xcc_census(ftte_ctx *c)
 
 int mark_sweep(ftte_ctx *c, hipStream_t stream)
 {
-    if (!c->ev_sweep_done) FTTE_HIP(c, hipEventCreateWithFlags(&c->ev_sweep_done, hipEventDisableTiming));
+    FTTE_HIP(c, c->ev_sweep_done.create(hipEventDisableTiming));
     FTTE_HIP(c, hipEventRecord(c->ev_sweep_done, stream));
     c->sweep_pending = true;
     return FTTE_OK;
@@ -93,12 +88,19 @@ int mark_sweep(ftte_ctx *c, hipStream_t stream)
 
 void free_forests(ftte_ctx *c)
 {
-    for (auto &f : c->forests) {
-        if (f.rec) (void)hipFree(f.rec);
-        if (f.active) (void)hipFree(f.active);
-    }
     c->forests.clear();
     c->forest_key.clear();
+}
+
+size_t accumulator_size(DeviceBuffer<double> (&acc)[3][kMaxAcc], size_t per_acc)
+{
+    size_t have = 0;
+    for (auto &layout : acc)
+        for (auto &a : layout) have = std::max(have, a.capacity());
+    if (have >= per_acc) return have;
+    for (auto &layout : acc)
+        for (auto &a : layout) a.reset();
+    return per_acc;
 }
 
 // Tables of several independent runs (`sets`: direction lists that may run side by side on different streams, set q using the
@@ -108,7 +110,6 @@ void free_forests(ftte_ctx *c)
 int prepare_forests(ftte_ctx *c, hipStream_t stream, const std::vector<std::vector<ForestDirHost>> &sets, const std::vector<int> &slot0,
                     int batch, size_t per_dir, std::vector<ForestRun> *runs)
 {
-    int rc;
     std::vector<AmrDirRec> recs;
     std::vector<int64_t> tables;
     runs->assign(sets.size(), ForestRun());
@@ -186,8 +187,8 @@ int prepare_forests(ftte_ctx *c, hipStream_t stream, const std::vector<std::vect
             R.batches.push_back(B);
         }
     }
-    if ((rc = ensure(c, &c->d_amr_dirs, &c->d_amr_dirs_cap, recs.size()))) return rc;
-    if ((rc = ensure(c, &c->d_amr_tables, &c->d_amr_tables_cap, tables.size()))) return rc;
+    FTTE_HIP(c, c->d_amr_dirs.reserve(recs.size()));
+    FTTE_HIP(c, c->d_amr_tables.reserve(tables.size()));
     if (!recs.empty()) FTTE_HIP(c, hipMemcpyAsync(c->d_amr_dirs, recs.data(), sizeof(AmrDirRec) * recs.size(), hipMemcpyHostToDevice, stream));
     if (!tables.empty()) FTTE_HIP(c, hipMemcpyAsync(c->d_amr_tables, tables.data(), sizeof(int64_t) * tables.size(), hipMemcpyHostToDevice, stream));
     FTTE_HIP(c, hipStreamSynchronize(stream)); // the host vectors leave scope; pageable copies are staged anyway
@@ -339,8 +340,8 @@ int forest_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
                 ftte_ctx::ForestDev &D = c->forests[d0 + t];
                 D.w = w[d0 + t];
                 D.depth_off = F[t].depth_off;
-                FTTE_HIP(c, hipMalloc((void **)&D.rec, sizeof(SegRec) * rec[t].size()));
-                FTTE_HIP(c, hipMalloc((void **)&D.active, (size_t)ncell));
+                FTTE_HIP(c, D.rec.reserve(rec[t].size()));
+                FTTE_HIP(c, D.active.reserve((size_t)ncell));
                 FTTE_HIP(c, hipMemcpy(D.rec, rec[t].data(), sizeof(SegRec) * rec[t].size(), hipMemcpyHostToDevice));
                 FTTE_HIP(c, hipMemcpy(D.active, active[t].data(), (size_t)ncell, hipMemcpyHostToDevice));
             }
@@ -354,43 +355,37 @@ int forest_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     const size_t per_dir = (size_t)nseg * nnu;
     const int most = c->forest_batch > 0 ? c->forest_batch : kAmrBatch;
     int batch = std::max(1, std::min(ndir, most));
-    if (c->amr_scratch_cap < per_dir * (size_t)batch) {
+    if (c->amr_scratch() < per_dir * (size_t)batch) {
         FTTE_HIP(c, hipStreamSynchronize(stream));
-        if (c->amr_Iout) { FTTE_HIP(c, hipFree(c->amr_Iout)); c->amr_Iout = nullptr; }
-        if (c->amr_mean) { FTTE_HIP(c, hipFree(c->amr_mean)); c->amr_mean = nullptr; }
-        c->amr_scratch_cap = 0;
+        c->amr_Iout.reset(); c->amr_mean.reset();
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
             const size_t fits = (size_t)(0.9 * (double)free_b) / (2 * sizeof(double) * per_dir);
             batch = (int)std::max<size_t>(1, std::min<size_t>((size_t)batch, fits));
         }
         for (;;) {
-            hipError_t e1 = hipMalloc((void **)&c->amr_Iout, sizeof(double) * per_dir * (size_t)batch);
-            hipError_t e2 = e1 == hipSuccess ? hipMalloc((void **)&c->amr_mean, sizeof(double) * per_dir * (size_t)batch) : e1;
-            if (e1 == hipSuccess && e2 == hipSuccess) break;
-            if (c->amr_Iout) { (void)hipFree(c->amr_Iout); c->amr_Iout = nullptr; }
-            c->amr_mean = nullptr;
+            if (c->amr_Iout.reserve(per_dir * (size_t)batch) == hipSuccess && c->amr_mean.reserve(per_dir * (size_t)batch) == hipSuccess) break;
+            c->amr_Iout.reset(); c->amr_mean.reset();
             (void)hipGetLastError();
             if (batch == 1) return fail(c, FTTE_ERR_MEMORY, "refined-grid sweep: not enough device memory for the segment scratch of one direction");
             batch = (batch + 1) / 2;
         }
-        c->amr_scratch_cap = per_dir * (size_t)batch;
-    } else batch = (int)std::min<size_t>((size_t)most, c->amr_scratch_cap / per_dir);
+    } else batch = (int)std::min<size_t>((size_t)most, c->amr_scratch() / per_dir);
     FTTE_HIP(c, hipStreamSynchronize(stream)); // d_uvb below may still be read by the previous sweep
-    if ((rc = ensure(c, &c->d_uvb, &c->d_uvb_cap, (size_t)nnu))) return rc;
+    FTTE_HIP(c, c->d_uvb.reserve((size_t)nnu));
     FTTE_HIP(c, hipMemcpy(c->d_uvb, uvb, sizeof(double) * nnu, hipMemcpyHostToDevice)); c->uvb_sent.clear();
 
     // the forest path gathers by cell: all groups of a cell side by side (beyond 96 groups the transposing kernel's
     // tile no longer fits the LDS of a workgroup; the strided layout is read as it is)
     const bool cell_major = nnu <= 96;
     if (cell_major) {
-    if ((rc = ensure(c, &c->amr_kappa, &c->amr_kappa_cap, (size_t)nnu * ncell))) return rc;
+    FTTE_HIP(c, c->amr_kappa.reserve((size_t)nnu * ncell));
     if (!c->kappa_ready[3] || c->amr_kappa_form != 0) {
         if (launch_cell_major(c->kappa[0], c->amr_kappa, ncell, nnu, stream)) return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
         c->kappa_ready[3] = true; c->amr_kappa_form = 0;
     }
     if (c->emit_mode) {
-        if ((rc = ensure(c, &c->amr_emis, &c->amr_emis_cap, (size_t)nnu * ncell))) return rc;
+        FTTE_HIP(c, c->amr_emis.reserve((size_t)nnu * ncell));
         if (!c->emis_ready[3]) {
             if (launch_cell_major(c->emis[0], c->amr_emis, ncell, nnu, stream)) return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
             c->emis_ready[3] = true;
@@ -401,9 +396,9 @@ int forest_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     const int nbatch = (ndir + batch - 1) / batch;
     while ((int)c->timing.size() < nbatch) {
         LaunchTiming t;
-        FTTE_HIP(c, hipEventCreate(&t.start));
-        FTTE_HIP(c, hipEventCreate(&t.stop));
-        c->timing.push_back(t);
+        FTTE_HIP(c, t.start.create());
+        FTTE_HIP(c, t.stop.create());
+        c->timing.push_back(std::move(t));
     }
     c->timing_used = 0;
     if (ndir == 0) FTTE_HIP(c, hipMemsetAsync(J_dev, 0, sizeof(double) * (size_t)nnu * ncell, stream));
@@ -446,20 +441,13 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
     FTTE_HIP(c, hipStreamSynchronize(stream));
     if (stream != c->stream) FTTE_HIP(c, hipStreamSynchronize(c->stream));
 
-    if (c->acc_cap < per_acc) {
-        for (int l = 0; l < 3; ++l)
-            for (int s = 0; s < kMaxAcc; ++s)
-                if (c->acc[l][s]) { FTTE_HIP(c, hipFree(c->acc[l][s])); c->acc[l][s] = nullptr; }
-        c->acc_cap = per_acc;
-    }
+    const size_t acc_size = accumulator_size(c->acc, per_acc);
     const size_t face_need = (size_t)ndir * nnu * (size_t)P.face_elems;
-    if ((rc = ensure(c, &c->d_faces, &c->d_faces_cap, face_need))) return rc;
-    if (!c->merge_stream) {
-        FTTE_HIP(c, hipStreamCreateWithFlags(&c->merge_stream, hipStreamNonBlocking));
-        FTTE_HIP(c, hipEventCreateWithFlags(&c->ev_layout_done, hipEventDisableTiming));
-        FTTE_HIP(c, hipEventCreateWithFlags(&c->ev_merge_done, hipEventDisableTiming));
-        FTTE_HIP(c, hipEventCreateWithFlags(&c->ev_layouts_ready, hipEventDisableTiming));
-    }
+    FTTE_HIP(c, c->d_faces.reserve(face_need));
+    FTTE_HIP(c, c->merge_stream.create(hipStreamNonBlocking));
+    FTTE_HIP(c, c->ev_layout_done.create(hipEventDisableTiming));
+    FTTE_HIP(c, c->ev_merge_done.create(hipEventDisableTiming));
+    FTTE_HIP(c, c->ev_layouts_ready.create(hipEventDisableTiming));
     // Host arrays (ftte_diffuse_iteration): lanes of frequency groups (below) do their own layouts before their first stage and their
     // own merge after their last.
     // (With device-resident opacities, layouts up front and one merge at the end are faster: 37.4-38.0 against 38.6 ms per
@@ -482,17 +470,17 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
     // accumulators and the opacity in the layouts the groups march through
     for (int l = 0; l < 3; ++l) {
         for (int s = 0; s < P.nacc[l]; ++s)
-            if (!c->acc[l][s]) FTTE_HIP(c, hipMalloc((void **)&c->acc[l][s], sizeof(double) * c->acc_cap));
+            FTTE_HIP(c, c->acc[l][s].reserve(acc_size));
         if (P.nacc[l] && tiled) {
             if (c->kappa_tiled_from[l] != c->n_kappa_sets || c->kappa_tiled_chunk[l] != tchunk) {
-                if (!c->kappa_tiled[l]) FTTE_HIP(c, hipMalloc((void **)&c->kappa_tiled[l], sizeof(double) * c->kappa_cap));
+                FTTE_HIP(c, c->kappa_tiled[l].reserve(c->kappa[0].capacity()));
                 if (launch_to_layout(l, c->kappa[0], c->kappa_tiled[l], n, nnu, (long)c->ncell, stream, true, tchunk))
                     return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
                 c->kappa_tiled_from[l] = c->n_kappa_sets;
                 c->kappa_tiled_chunk[l] = tchunk;
             }
         } else if (P.nacc[l] && frame(l) == l && !c->kappa_ready[l]) {
-            if (!c->kappa[l]) FTTE_HIP(c, hipMalloc((void **)&c->kappa[l], sizeof(double) * c->kappa_cap));
+            FTTE_HIP(c, c->kappa[l].reserve(c->kappa[0].capacity()));
             if (!lane_ends) {
                 if (launch_to_layout(l, c->kappa[0], c->kappa[l], n, nnu, (long)c->ncell, stream))
                     return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
@@ -500,7 +488,7 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
             } else lane_layout[l] = true;
         }
         if (P.nacc[l] && frame(l) == l && c->emit_mode && !c->emis_ready[l]) {
-            if (!c->emis[l]) FTTE_HIP(c, hipMalloc((void **)&c->emis[l], sizeof(double) * c->kappa_cap));
+            FTTE_HIP(c, c->emis[l].reserve(c->kappa[0].capacity()));
             if (launch_to_layout(l, c->emis[0], c->emis[l], n, nnu, (long)c->ncell, stream))
                 return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
             c->emis_ready[l] = true;
@@ -509,19 +497,19 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
 
     if (!c->bplan_uploaded) {
         c->bgroups_sent.clear();
-        if ((rc = ensure(c, &c->d_blayers, &c->d_blayers_cap, P.layers.size()))) return rc;
-        if ((rc = ensure(c, &c->d_btasks, &c->d_btasks_cap, P.tasks.size()))) return rc;
-        if ((rc = ensure(c, &c->d_bgroups, &c->d_bgroups_cap, P.groups.size()))) return rc;
+        FTTE_HIP(c, c->d_blayers.reserve(P.layers.size()));
+        FTTE_HIP(c, c->d_btasks.reserve(P.tasks.size()));
+        FTTE_HIP(c, c->d_bgroups.reserve(P.groups.size()));
         if (!P.layers.empty())
             FTTE_HIP(c, hipMemcpy(c->d_blayers, P.layers.data(), sizeof(LayerRec) * P.layers.size(), hipMemcpyHostToDevice));
         if (!P.tasks.empty())
             FTTE_HIP(c, hipMemcpy(c->d_btasks, P.tasks.data(), sizeof(BrickTask) * P.tasks.size(), hipMemcpyHostToDevice));
         if (P.dataflow && !P.deps.empty()) {
-            if ((rc = ensure(c, &c->d_bdeps, &c->d_bdeps_cap, P.deps.size()))) return rc;
+            FTTE_HIP(c, c->d_bdeps.reserve(P.deps.size()));
             FTTE_HIP(c, hipMemcpy(c->d_bdeps, P.deps.data(), sizeof(int32_t) * P.deps.size(), hipMemcpyHostToDevice));
         }
         if (!P.merge_blocks.empty()) {
-            if ((rc = ensure(c, &c->d_mblocks, &c->d_mblocks_cap, P.merge_blocks.size()))) return rc;
+            FTTE_HIP(c, c->d_mblocks.reserve(P.merge_blocks.size()));
             FTTE_HIP(c, hipMemcpy(c->d_mblocks, P.merge_blocks.data(), sizeof(int32_t) * P.merge_blocks.size(), hipMemcpyHostToDevice));
         }
         c->bplan_uploaded = true;
@@ -578,7 +566,7 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
             c->bgroups_sent.assign((const char *)G.data(), (const char *)G.data() + bytes);
         }
     }
-    if ((rc = ensure(c, &c->d_uvb, &c->d_uvb_cap, (size_t)nnu))) return rc;
+    FTTE_HIP(c, c->d_uvb.reserve((size_t)nnu));
     if (c->uvb_sent.size() != (size_t)nnu || std::memcmp(c->uvb_sent.data(), uvb, sizeof(double) * nnu) != 0) {
         FTTE_HIP(c, hipMemcpy(c->d_uvb, uvb, sizeof(double) * nnu, hipMemcpyHostToDevice));
         c->uvb_sent.assign(uvb, uvb + nnu);
@@ -593,25 +581,25 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
     const int nulanes = P.glanes > 1 ? 1 : std::max(1, std::min(c->lanes, nnu)); // streams over frequency groups ...
     const int nlanes = nulanes * P.glanes;                                        // ... or over the groups of directions
     while ((int)c->lane_stream.size() < nlanes - 1) {
-        hipStream_t q; hipEvent_t e;
-        FTTE_HIP(c, hipStreamCreateWithFlags(&q, hipStreamNonBlocking));
-        FTTE_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        c->lane_stream.push_back(q); c->lane_done.push_back(e);
+        Stream q; Event e;
+        FTTE_HIP(c, q.create(hipStreamNonBlocking));
+        FTTE_HIP(c, e.create(hipEventDisableTiming));
+        c->lane_stream.push_back(std::move(q)); c->lane_done.push_back(std::move(e));
     }
-    if (!c->ev_fork) FTTE_HIP(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+    FTTE_HIP(c, c->ev_fork.create(hipEventDisableTiming));
     // (the plan has merge blocks only for stages on one lane of groups; with host arrays every lane merges its own after its stages)
     const bool overlap = c->merge_overlap && !lane_ends && !P.dataflow && P.glanes == 1 && !P.groups.empty() && !P.merge_stage.empty();
     const size_t npoints = overlap ? P.merge_stage.size() : 0;
     while (c->ev_merge_point.size() < (size_t)nlanes * npoints) {
-        hipEvent_t e;
-        FTTE_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        c->ev_merge_point.push_back(e);
+        Event e;
+        FTTE_HIP(c, e.create(hipEventDisableTiming));
+        c->ev_merge_point.push_back(std::move(e));
     }
     while (c->timing.size() < 1) {
         LaunchTiming t;
-        FTTE_HIP(c, hipEventCreate(&t.start));
-        FTTE_HIP(c, hipEventCreate(&t.stop));
-        c->timing.push_back(t);
+        FTTE_HIP(c, t.start.create());
+        FTTE_HIP(c, t.stop.create());
+        c->timing.push_back(std::move(t));
     }
     c->timing_used = 0;
 
@@ -622,10 +610,10 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
         T.lanes = 0;
         if (lane_ends) {
             while ((int)T.first.size() < nlanes) {
-                hipEvent_t a, b;
-                FTTE_HIP(c, hipEventCreate(&a));
-                FTTE_HIP(c, hipEventCreate(&b));
-                T.first.push_back(a); T.last.push_back(b);
+                Event a, b;
+                FTTE_HIP(c, a.create());
+                FTTE_HIP(c, b.create());
+                T.first.push_back(std::move(a)); T.last.push_back(std::move(b));
             }
         }
         FTTE_HIP(c, hipEventRecord(T.start, stream));
@@ -633,20 +621,19 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
             // every brick of the sweep in one launch; flags of `epoch` mark the finished ones (the array is zeroed when it is
             // (re)allocated and when the epoch wraps, never in between)
             const size_t nflags = P.tasks.size() * (size_t)nnu;
-            if (c->d_bdone_cap < nflags || c->bepoch == 0xffffffffu) {
-                if ((rc = ensure(c, &c->d_bdone, &c->d_bdone_cap, nflags))) return rc;
-                FTTE_HIP(c, hipMemsetAsync(c->d_bdone, 0, sizeof(uint32_t) * c->d_bdone_cap, stream));
+            bool fresh = false;
+            FTTE_HIP(c, c->d_bdone.reserve(nflags, &fresh));
+            if (fresh || c->bepoch == 0xffffffffu) {
+                FTTE_HIP(c, hipMemsetAsync(c->d_bdone, 0, sizeof(uint32_t) * c->d_bdone.capacity(), stream));
                 c->bepoch = 0;
             }
             constexpr size_t kSyncWords = 32 * (kBrickQueues + 1);
-            if (!c->d_bsync) {
-                FTTE_HIP(c, hipMalloc((void **)&c->d_bsync, sizeof(uint32_t) * kSyncWords));
-                FTTE_HIP(c, hipHostMalloc((void **)&c->h_berror, sizeof(uint32_t) * kSyncWords, hipHostMallocDefault));
-                std::memset(c->h_berror, 0, sizeof(uint32_t) * kSyncWords);
-            }
+            FTTE_HIP(c, c->d_bsync.reserve(kSyncWords));
+            FTTE_HIP(c, c->h_berror.reserve(kSyncWords, &fresh));
+            if (fresh) std::memset(c->h_berror, 0, sizeof(uint32_t) * kSyncWords);
             FTTE_HIP(c, hipMemsetAsync(c->d_bsync, 0, sizeof(uint32_t) * kSyncWords, stream));
-            if (P.persistent && (c->d_bqueue_cap < P.queue.size() || !c->bqueue_uploaded)) {
-                if ((rc = ensure(c, &c->d_bqueue, &c->d_bqueue_cap, P.queue.size()))) return rc;
+            if (P.persistent && (c->d_bqueue.capacity() < P.queue.size() || !c->bqueue_uploaded)) {
+                FTTE_HIP(c, c->d_bqueue.reserve(P.queue.size()));
                 FTTE_HIP(c, hipMemcpy(c->d_bqueue, P.queue.data(), sizeof(uint32_t) * P.queue.size(), hipMemcpyHostToDevice));
                 c->bqueue_uploaded = true;
             }
@@ -696,9 +683,9 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
             if (pipe) {
                 // this lane's opacities: after the lane before (one transfer at a time has the link to itself), then its layouts
                 while (c->pipe_up.size() < (size_t)nlanes) {
-                    hipEvent_t e;
-                    FTTE_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                    c->pipe_up.push_back(e);
+                    Event e;
+                    FTTE_HIP(c, e.create(hipEventDisableTiming));
+                    c->pipe_up.push_back(std::move(e));
                 }
                 if (lane) FTTE_HIP(c, hipStreamWaitEvent(q, c->pipe_up[(size_t)lane - 1], 0));
                 if ((rc = upload_on(c, q, c->kappa[0] + slice0, pipe->kappa + slice0, slice_bytes))) return rc;
@@ -833,32 +820,25 @@ int tile_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, co
     if (stream != c->stream) FTTE_HIP(c, hipStreamSynchronize(c->stream));
 
     if (!c->plan_uploaded) {
-        if ((rc = ensure(c, &c->d_layers, &c->d_layers_cap, P.layers.size()))) return rc;
-        if ((rc = ensure(c, &c->d_items, &c->d_items_cap, P.items.size()))) return rc;
+        FTTE_HIP(c, c->d_layers.reserve(P.layers.size()));
+        FTTE_HIP(c, c->d_items.reserve(P.items.size()));
         if (!P.layers.empty())
             FTTE_HIP(c, hipMemcpy(c->d_layers, P.layers.data(), sizeof(LayerRec) * P.layers.size(), hipMemcpyHostToDevice));
         if (!P.items.empty())
             FTTE_HIP(c, hipMemcpy(c->d_items, P.items.data(), sizeof(WorkItem) * P.items.size(), hipMemcpyHostToDevice));
         c->plan_uploaded = true;
     }
-    if ((rc = ensure(c, &c->d_uvb, &c->d_uvb_cap, (size_t)nnu))) return rc;
+    FTTE_HIP(c, c->d_uvb.reserve((size_t)nnu));
     FTTE_HIP(c, hipMemcpy(c->d_uvb, uvb, sizeof(double) * nnu, hipMemcpyHostToDevice)); c->uvb_sent.clear();
 
     // accumulators sized for this nnu
-    if (c->acc_cap < per_acc) {
-        for (int l = 0; l < 3; ++l)
-            for (int s = 0; s < kMaxAcc; ++s)
-                if (c->acc[l][s]) { FTTE_HIP(c, hipFree(c->acc[l][s])); c->acc[l][s] = nullptr; }
-        c->acc_cap = per_acc;
-    }
+    const size_t acc_size = accumulator_size(c->acc, per_acc);
     // a second (non-blocking) stream: the transposed copies of the opacity are made there while the directions that march
     // along storage-i (layout 0, the array as it was handed over) are already being swept, and later the merges run there
-    if (!c->merge_stream) {
-        FTTE_HIP(c, hipStreamCreateWithFlags(&c->merge_stream, hipStreamNonBlocking));
-        FTTE_HIP(c, hipEventCreateWithFlags(&c->ev_layout_done, hipEventDisableTiming));
-        FTTE_HIP(c, hipEventCreateWithFlags(&c->ev_merge_done, hipEventDisableTiming));
-        FTTE_HIP(c, hipEventCreateWithFlags(&c->ev_layouts_ready, hipEventDisableTiming));
-    }
+    FTTE_HIP(c, c->merge_stream.create(hipStreamNonBlocking));
+    FTTE_HIP(c, c->ev_layout_done.create(hipEventDisableTiming));
+    FTTE_HIP(c, c->ev_merge_done.create(hipEventDisableTiming));
+    FTTE_HIP(c, c->ev_layouts_ready.create(hipEventDisableTiming));
     // everything queued on `stream` so far (and the previous sweep's merges) comes first
     FTTE_HIP(c, hipEventRecord(c->ev_layout_done, stream));
     FTTE_HIP(c, hipStreamWaitEvent(c->merge_stream, c->ev_layout_done, 0));
@@ -867,17 +847,17 @@ int tile_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, co
         for (int s = 0; s < kMaxSlots; ++s) {
             if (!P.used[l][s]) continue;
             any = true;
-            if (!c->acc[l][s]) FTTE_HIP(c, hipMalloc((void **)&c->acc[l][s], sizeof(double) * c->acc_cap));
+            FTTE_HIP(c, c->acc[l][s].reserve(acc_size));
         }
         // opacity in the layout this march axis needs
         if (any && !c->kappa_ready[l]) {
-            if (!c->kappa[l]) FTTE_HIP(c, hipMalloc((void **)&c->kappa[l], sizeof(double) * c->kappa_cap));
+            FTTE_HIP(c, c->kappa[l].reserve(c->kappa[0].capacity()));
             if (launch_to_layout(l, c->kappa[0], c->kappa[l], n, nnu, (long)c->ncell, c->merge_stream))
                 return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
             c->kappa_ready[l] = true;
         }
         if (any && c->emit_mode && !c->emis_ready[l]) {
-            if (!c->emis[l]) FTTE_HIP(c, hipMalloc((void **)&c->emis[l], sizeof(double) * c->kappa_cap));
+            FTTE_HIP(c, c->emis[l].reserve(c->kappa[0].capacity()));
             if (launch_to_layout(l, c->emis[0], c->emis[l], n, nnu, (long)c->ncell, c->merge_stream))
                 return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
             c->emis_ready[l] = true;
@@ -889,9 +869,9 @@ int tile_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, co
     // events for the launch records
     while (c->timing.size() < P.launches.size()) {
         LaunchTiming t;
-        FTTE_HIP(c, hipEventCreate(&t.start));
-        FTTE_HIP(c, hipEventCreate(&t.stop));
-        c->timing.push_back(t);
+        FTTE_HIP(c, t.start.create());
+        FTTE_HIP(c, t.stop.create());
+        c->timing.push_back(std::move(t));
     }
     c->timing_used = 0;
 
