@@ -103,12 +103,11 @@ int ftte_set_grid(ftte_ctx *c, int nx, int ny, int nz, int64_t ncell, const int3
         // a different grid: drop everything sized by the old one
         (void)hipSetDevice(c->device);
         (void)hipStreamSynchronize(c->stream);
-        for (int l = 0; l < 3; ++l) {
-            c->kappa[l].reset(); c->kappa_tiled[l].reset(); c->emis[l].reset();
-            for (auto &a : c->acc[l]) a.reset();
-        }
+        c->kappa.release(); c->emis.release();
+        for (auto &layout : c->acc)
+            for (auto &a : layout) a.reset();
         c->emit_mode = 0;
-        c->amr_Iout.reset(); c->amr_mean.reset(); c->amr_kappa.reset(); c->amr_emis.reset();
+        c->amr_Iout.reset(); c->amr_mean.reset();
         c->nnu = 0;
     }
     (void)hipSetDevice(c->device);
@@ -120,8 +119,7 @@ int ftte_set_grid(ftte_ctx *c, int nx, int ny, int nz, int64_t ncell, const int3
     c->drop_chem_grid();
     c->leaf_level.assign(level, level + ncell);
     c->n = nx; c->ncell = ncell; c->box = box_cm; c->grid_set = true;
-    c->kappa_ready[0] = c->kappa_ready[1] = c->kappa_ready[2] = c->kappa_ready[3] = false;
-    ++c->n_kappa_sets;
+    c->kappa.invalidate();
     c->plan.valid = false;
     c->bplan.valid = false;
     c->tree = std::move(tree);
@@ -139,10 +137,9 @@ int ftte_set_opacity(ftte_ctx *c, int nnu, const double *kappa)
     if ((rc = wait_sweep(c))) return rc;
     FTTE_HIP(c, hipStreamSynchronize(c->stream));
     if ((rc = ensure_kappa(c, nnu))) return rc;
-    if ((rc = upload(c, c->kappa[0], kappa, sizeof(double) * nnu * c->ncell))) return rc;
+    if ((rc = upload(c, c->kappa.source(), kappa, sizeof(double) * nnu * c->ncell))) return rc;
     c->nnu = nnu;
-    c->kappa_ready[0] = true; c->kappa_ready[1] = c->kappa_ready[2] = c->kappa_ready[3] = false;
-    ++c->n_kappa_sets;
+    c->kappa.set();
     return FTTE_OK;
 }
 
@@ -158,15 +155,16 @@ int ftte_set_opacity_device(ftte_ctx *c, int nnu, const double *kappa_dev)
     // the caller's array, layout 1 too where the last sweep used it (the tile engine; the brick engine marches layout 1 through
     // layout 0).  Else the copy alone; the sweep makes what it needs.
     const bool same = !c->use_forest && c->nnu == nnu && !c->tiled_opt;
-    const bool with2 = same && c->kappa[2] && c->kappa_ready[2], with1 = with2 && c->kappa[1] && c->kappa_ready[1];
+    const bool with2 = same && c->kappa.current(MediumField::kLayout2), with1 = with2 && c->kappa.current(MediumField::kLayout1);
     if (with2) {
-        if (launch_set_layouts(kappa_dev, c->kappa[0], with1 ? c->kappa[1] : nullptr, c->kappa[2], c->n, nnu, (long)c->ncell, c->stream))
+        if (launch_set_layouts(kappa_dev, c->kappa.source(), with1 ? c->kappa.in_layout(1) : nullptr, c->kappa.in_layout(2), c->n, nnu, (long)c->ncell, c->stream))
             return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
-    } else FTTE_HIP(c, hipMemcpyAsync(c->kappa[0], kappa_dev, sizeof(double) * nnu * c->ncell, hipMemcpyDeviceToDevice, c->stream));
+    } else FTTE_HIP(c, hipMemcpyAsync(c->kappa.source(), kappa_dev, sizeof(double) * nnu * c->ncell, hipMemcpyDeviceToDevice, c->stream));
     FTTE_HIP(c, hipStreamSynchronize(c->stream)); // the sweep may run on another stream: the copies must have landed
     c->nnu = nnu;
-    c->kappa_ready[0] = true; c->kappa_ready[1] = with1; c->kappa_ready[2] = with2; c->kappa_ready[3] = false;
-    ++c->n_kappa_sets;
+    c->kappa.set();
+    if (with2) c->kappa.made(MediumField::kLayout2); // written in the same pass
+    if (with1) c->kappa.made(MediumField::kLayout1);
     return FTTE_OK;
 }
 
@@ -187,13 +185,12 @@ int ftte_set_species(ftte_ctx *c, int nnu, const double *HI, const double *HeI, 
     if (e == hipSuccess) e = hipMemcpyAsync(tmp + 2 * nc, HeII, sizeof(double) * nc, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(tmp + 3 * nc, beta, sizeof(double) * 3 * nnu, hipMemcpyHostToDevice, c->stream);
     int lrc = 0;
-    if (e == hipSuccess) lrc = launch_opacity(tmp, tmp + nc, tmp + 2 * nc, tmp + 3 * nc, c->kappa[0], (long)nc, nnu, c->stream);
+    if (e == hipSuccess) lrc = launch_opacity(tmp, tmp + nc, tmp + 2 * nc, tmp + 3 * nc, c->kappa.source(), (long)nc, nnu, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return fail(c, FTTE_ERR_NO_DEVICE, std::string("ftte_set_species: ") + hipGetErrorString(e));
     if (lrc) return fail(c, FTTE_ERR_NO_DEVICE, "ftte_set_species: kernel launch failed");
     c->nnu = nnu;
-    c->kappa_ready[0] = true; c->kappa_ready[1] = c->kappa_ready[2] = c->kappa_ready[3] = false;
-    ++c->n_kappa_sets;
+    c->kappa.set();
     return FTTE_OK;
 }
 
@@ -207,12 +204,12 @@ static int set_emission(ftte_ctx *c, int mode, const double *values, bool on_dev
     FTTE_HIP(c, hipSetDevice(c->device));
     if ((rc = wait_sweep(c))) return rc;
     if (!on_device) FTTE_HIP(c, hipStreamSynchronize(c->stream));
-    FTTE_HIP(c, c->emis[0].reserve(c->kappa[0].capacity()));
+    FTTE_HIP(c, c->emis.reserve_source(c->kappa.capacity()));
     const size_t bytes = sizeof(double) * (size_t)c->nnu * c->ncell;
-    FTTE_HIP(c, hipMemcpyAsync(c->emis[0], values, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    FTTE_HIP(c, hipMemcpyAsync(c->emis.source(), values, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
     FTTE_HIP(c, hipStreamSynchronize(c->stream)); // the sweep may run on another stream: the copy must have landed
     c->emit_mode = mode;
-    c->emis_ready[0] = true; c->emis_ready[1] = c->emis_ready[2] = c->emis_ready[3] = false;
+    c->emis.set();
     (void)who;
     return FTTE_OK;
 }
@@ -381,14 +378,12 @@ int ftte_diffuse_iteration(ftte_ctx *c, int nnu, const double *kappa, int ndir, 
     FTTE_HIP(c, hipStreamSynchronize(c->stream));
     if ((rc = ensure_kappa(c, nnu))) return rc;
     c->nnu = nnu;
-    c->kappa_ready[0] = c->kappa_ready[1] = c->kappa_ready[2] = c->kappa_ready[3] = false;
-    ++c->n_kappa_sets;
+    c->kappa.invalidate(); // the lanes bring it: set() when the last one has been issued (brick_sweep)
     const size_t elems = (size_t)nnu * c->ncell;
     FTTE_HIP(c, c->host_J_dev.reserve(elems));
     const HostPipe pipe{kappa, J};
     if ((rc = brick_sweep(c, ndir, phi, theta, w, uvb, c->host_J_dev, c->stream, &pipe))) {
-        c->kappa_ready[0] = c->kappa_ready[1] = c->kappa_ready[2] = false;
-        ++c->n_kappa_sets;
+        c->kappa.invalidate();
         return rc;
     }
     return wait_sweep(c); // J is in the caller's array on return
@@ -954,13 +949,12 @@ int ftte_compute_opacities(ftte_ctx *c, int nnu, const double *beta)
     hipError_t e = hipMemcpyAsync(dbeta, beta, sizeof(double) * 3 * nnu, hipMemcpyHostToDevice, c->stream);
     int lrc = 0;
     if (e == hipSuccess)
-        lrc = launch_opacity(c->point.medium[0], c->point.medium[1], c->point.medium[2], dbeta, c->kappa[0], (long)c->ncell, nnu, c->stream);
+        lrc = launch_opacity(c->point.medium[0], c->point.medium[1], c->point.medium[2], dbeta, c->kappa.source(), (long)c->ncell, nnu, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return fail(c, FTTE_ERR_NO_DEVICE, std::string("ftte_compute_opacities: ") + hipGetErrorString(e));
     if (lrc) return fail(c, FTTE_ERR_NO_DEVICE, "ftte_compute_opacities: kernel launch failed");
     c->nnu = nnu;
-    c->kappa_ready[0] = true; c->kappa_ready[1] = c->kappa_ready[2] = c->kappa_ready[3] = false;
-    ++c->n_kappa_sets;
+    c->kappa.set();
     return FTTE_OK;
 }
 

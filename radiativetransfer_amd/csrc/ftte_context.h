@@ -27,6 +27,7 @@
 #include "ftte_geometry.h"
 #include "ftte_internal.h"
 #include "ftte_kernels.h"
+#include "ftte_medium.h"
 #include "ftte_point.h"
 
 
@@ -139,20 +140,12 @@ struct ftte_ctx {
     double box = 0;
 
     int nnu = 0;
-    DeviceBuffer<double> kappa[3]; // layouts 0,1,2; [1], [2] and the emis / kappa_tiled buffers are made at the capacity of [0]
-    bool kappa_ready[4] = {false, false, false, false}; // [3]: the cell-major copy of the forest path
-    // the opacities once more in brick order (BrickLaunch::tiled), per axis order; valid while kappa_tiled_from is the count of
-    // opacity changes (n_kappa_sets) they were made at
-    DeviceBuffer<double> kappa_tiled[3];
-    long long kappa_tiled_from[3] = {-1, -1, -1}, n_kappa_sets = 0;
-    int kappa_tiled_chunk[3] = {0, 0, 0}; // layers per piece they were made with (tiled == 2), else 0
+    MediumField kappa; // the opacities, and their copies in the other layouts, in brick order and cell-major (ftte_medium.h)
     int tiled_opt = 0; // option "tiled" (measured: no gain)
-    int amr_kappa_form = 0;  // what that copy holds: 0 every leaf in cell-array order, 1 the leaves of the hybrid plan's list
 
-    // emissivity (mode 1: the reference's eta) or source function (mode 2), same three layouts as kappa
+    // emissivity (mode 1: the reference's eta) or source function (mode 2): sized as the opacities, the same copies
     int emit_mode = 0;
-    DeviceBuffer<double> emis[3];
-    bool emis_ready[4] = {false, false, false, false};
+    MediumField emis;
 
     DeviceBuffer<double> acc[3][kMaxAcc]; // one size for all of them (accumulator_size)
 
@@ -215,7 +208,6 @@ struct ftte_ctx {
     DeviceBuffer<AmrDirRec> d_amr_dirs;     // per-direction records of the forest batches
     DeviceBuffer<int64_t> d_amr_tables;     // per batch and depth: count[], begin[]
     DeviceBuffer<double> amr_Iout, amr_mean; // segment scratch, the same number of elements each (amr_scratch)
-    DeviceBuffer<double> amr_kappa, amr_emis; // [ncell][nnu] copies
     size_t amr_scratch() const { return std::min(amr_Iout.capacity(), amr_mean.capacity()); }
 
     // partial merges run beside the sweeps of the next layout on their own (non-blocking) stream
@@ -262,6 +254,7 @@ struct ftte_ctx {
                      std::vector<int64_t> depth_off; std::vector<int32_t> pass_first; std::vector<int64_t> export_first; };
         std::vector<Dir> dirs;
         DeviceBuffer<int32_t> cells; int64_t ncells = 0; // the leaves inside the box of at least one direction
+        long long cells_id = 0;           // which list of this context that is (ftte_ctx::leaf_lists): what the medium's cell-major copies follow
         bool uploaded = false;
         // A fully refined block swept by bricks of its own on the fine level (option "fine_bricks"; one cluster that is a cube of
         // base cells refined exactly once, twice its side a multiple of 64): inside it the fine cells are a uniform grid
@@ -279,6 +272,7 @@ struct ftte_ctx {
             DeviceBuffer<LayerRec> layers; DeviceBuffer<BrickTask> tasks; DeviceBuffer<BrickGroup> groups; // device
         } fine;
     } hplan;
+    long long leaf_lists = 0;         // leaf lists built so far (HybridPlan::cells_id counts from 1)
     int forest_fuse = 4096;           // option "forest_fuse": levels of a forest with at most this many (segment, group) pairs in one launch (0: a launch per level)
     int fine_bricks = 1, fine_chunk = 0;  // options "fine_bricks", "fine_chunk" (0: the base bricks' chunk)
     DeviceBuffer<double> fine_kappa[3];   // the fine block's opacities, dense, in the three layouts
@@ -371,6 +365,13 @@ int check_ready(ftte_ctx *c, bool need_kappa);
 int wait_sweep(ftte_ctx *c);
 int mark_sweep(ftte_ctx *c, hipStream_t stream);
 void free_forests(ftte_ctx *c);
+int ensure_timing(ftte_ctx *c, size_t count); // at least `count` launch records with both events
+// The cell-major copy of a field current on `stream`: every leaf in cell-array order, or (list: HybridPlan::cells_id) the leaves `cells`
+int make_cell_major(ftte_ctx *c, MediumField &f, hipStream_t stream, const int32_t *cells = nullptr, int64_t ncells = 0, long long list = 0);
+// Group g of a brick plan as the kernel reads it: its arrays in the layout it marches through, its directions' layer tables from
+// `layers` and face blocks from `faces`, face_stride elements per direction
+void fill_brick_group(BrickGroup &G, const BrickPlan &P, size_t g, const double *kappa, const double *emis, double *J, const LayerRec *layers,
+                      double *faces, size_t face_stride);
 // The accumulators of a set (ftte_ctx::acc, fine_acc) have one size.  Where that is less than per_acc elements every one of them is
 // released; returns the size to reserve for those a sweep uses.
 size_t accumulator_size(DeviceBuffer<double> (&acc)[3][kMaxAcc], size_t per_acc);

@@ -32,6 +32,20 @@ static int reserve_layouts(ftte_ctx *c, DeviceBuffer<double> (&buf)[3], size_t n
     return FTTE_OK;
 }
 
+// The values of a dense cube of `side`^3 cells (the base cells, a fine block) out of a field in leaf order: gathered through
+// leaf_of into dst[0], then transposed into the layouts that have accumulators
+static int gather_layouts(ftte_ctx *c, const MediumField &f, const int32_t *leaf_of, DeviceBuffer<double> (&dst)[3], const int (&nacc)[3], int side,
+                          hipStream_t stream)
+{
+    const long cells = (long)side * side * side;
+    if (launch_base_cells(f.source(), leaf_of, dst[0], cells, (long)c->ncell, c->nnu, stream))
+        return fail(c, FTTE_ERR_NO_DEVICE, "base-cell kernel launch failed");
+    for (int l = 1; l < 3; ++l)
+        if (nacc[l] && launch_to_layout(l, dst[0], dst[l], side, c->nnu, cells, stream))
+            return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
+    return FTTE_OK;
+}
+
 // Where the refined base cells are, in storage coordinates (1-based, inclusive): one bounding box per cluster.  Two refined cells
 // belong to one cluster when they lie within two 8-cell blocks of each other; what the per-izone alignment below still brings
 // into contact is merged there.
@@ -620,6 +634,7 @@ int build_hybrid_plan(ftte_ctx *c, int ndir, const double *phi, const double *th
     for (int64_t q = 0; q < ncell; ++q)
         if (in_any[(size_t)q]) { place[(size_t)q] = (int32_t)cells.size(); cells.push_back((int32_t)q); }
     H.ncells = (int64_t)cells.size();
+    H.cells_id = ++c->leaf_lists; // (a new list: the cell-major copies of the medium made for another one are not current)
     FTTE_HIP(c, H.cells.reserve(cells.size()));
     if (!cells.empty()) FTTE_HIP(c, hipMemcpy(H.cells, cells.data(), sizeof(int32_t) * cells.size(), hipMemcpyHostToDevice));
     {
@@ -688,7 +703,6 @@ int build_hybrid_plan(ftte_ctx *c, int ndir, const double *phi, const double *th
         FTTE_HIP(c, hipMemcpy(FN.tasks, Q.tasks.data(), sizeof(BrickTask) * Q.tasks.size(), hipMemcpyHostToDevice));
         FTTE_HIP(c, FN.groups.reserve(Q.groups.size()));
     }
-    c->kappa_ready[3] = false; // the forests' copy of the opacities follows the list
     H.uploaded = false;
     return FTTE_OK;
 }
@@ -743,18 +757,8 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
         std::memset(G.data(), 0, sizeof(BrickGroup) * G.size());
         for (size_t g = 0; g < P.groups.size(); ++g) {
             const BrickPlan::Group &Hg = P.groups[g];
-            const DirPlan &D0 = P.dirs[Hg.dirs[0]];
-            G[g].kappa = c->base_kappa[Hg.layout];
-            G[g].emis = emit ? c->base_emis[Hg.layout] : nullptr;
-            G[g].J = c->acc[Hg.layout][Hg.acc];
-            G[g].org = D0.org; G[g].si = D0.si; G[g].sv = D0.sv; G[g].su = D0.su;
-            G[g].ndir = (int)Hg.dirs.size();
-            for (size_t q = 0; q < Hg.dirs.size(); ++q) {
-                const int d = Hg.dirs[q];
-                G[g].dir[q].layers = c->d_blayers + P.dirs[d].layer_off;
-                G[g].dir[q].faces = c->d_faces + (size_t)d * nnu * (size_t)face_elems;
-                G[g].dir[q].w = P.dirs[d].w;
-            }
+            fill_brick_group(G[g], P, g, c->base_kappa[Hg.layout], emit ? c->base_emis[Hg.layout].get() : nullptr, c->acc[Hg.layout][Hg.acc], c->d_blayers,
+                             c->d_faces, (size_t)nnu * (size_t)face_elems);
         }
         FTTE_HIP(c, hipMemcpy(c->d_bgroups, G.data(), sizeof(BrickGroup) * G.size(), hipMemcpyHostToDevice)); c->bgroups_sent.clear();
     }
@@ -771,18 +775,8 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
         std::memset(G.data(), 0, sizeof(BrickGroup) * G.size());
         for (size_t g = 0; g < Q.groups.size(); ++g) {
             const BrickPlan::Group &Hg = Q.groups[g];
-            const DirPlan &D0 = Q.dirs[Hg.dirs[0]];
-            G[g].kappa = c->fine_kappa[Hg.layout];
-            G[g].emis = emit ? c->fine_emis[Hg.layout] : nullptr;
-            G[g].J = c->fine_acc[Hg.layout][Hg.acc];
-            G[g].org = D0.org; G[g].si = D0.si; G[g].sv = D0.sv; G[g].su = D0.su;
-            G[g].ndir = (int)Hg.dirs.size();
-            for (size_t q = 0; q < Hg.dirs.size(); ++q) {
-                const int d = Hg.dirs[q];
-                G[g].dir[q].layers = FN.layers + Q.dirs[d].layer_off;
-                G[g].dir[q].faces = c->d_faces + (size_t)d * nnu * (size_t)face_elems + (size_t)FN.face_base; // behind the base bricks' rings
-                G[g].dir[q].w = Q.dirs[d].w;
-            }
+            fill_brick_group(G[g], Q, g, c->fine_kappa[Hg.layout], emit ? c->fine_emis[Hg.layout].get() : nullptr, c->fine_acc[Hg.layout][Hg.acc], FN.layers,
+                             c->d_faces + (size_t)FN.face_base, (size_t)nnu * (size_t)face_elems); // (its faces: behind the base bricks' rings)
         }
         FTTE_HIP(c, hipMemcpy(FN.groups, G.data(), sizeof(BrickGroup) * G.size(), hipMemcpyHostToDevice));
     }
@@ -807,23 +801,11 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     // would have to go in one run at ONE place, in front of bricks of the other pipelines that feed them or behind bricks that
     // read what they export.  Both are left to the forest path for the whole tree.
     if (batch < ndir && (H.npass > 1 || (H.slots && H.nhalves > 1) || FN.active)) return FTTE_OK; // (a fine block's forests come in two passes)
-    FTTE_HIP(c, c->amr_kappa.reserve((size_t)nnu * (size_t)std::max<int64_t>(H.ncells, 1)));
-    if (!c->kappa_ready[3] || c->amr_kappa_form != 1) {
-        if (launch_cell_major(c->kappa[0], c->amr_kappa, ncell, nnu, stream, H.cells, (long)H.ncells)) return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
-        c->kappa_ready[3] = true; c->amr_kappa_form = 1;
-    }
-    if (emit) { // the emissivity / source function of the boxes' leaves, cell-major like their opacities; new every iteration
-        FTTE_HIP(c, c->amr_emis.reserve((size_t)nnu * (size_t)std::max<int64_t>(H.ncells, 1)));
-        if (launch_cell_major(c->emis[0], c->amr_emis, ncell, nnu, stream, H.cells, (long)H.ncells)) return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
-        c->emis_ready[3] = false; // (the forest path for the whole tree keeps every leaf there)
-    }
+    // the opacities of the boxes' leaves, cell-major, and their emissivity / source function (new every source iteration)
+    if ((rc = make_cell_major(c, c->kappa, stream, H.cells, H.ncells, H.cells_id))) return rc;
+    if (emit && (rc = make_cell_major(c, c->emis, stream, H.cells, H.ncells, H.cells_id))) return rc;
 
-    while (c->timing.size() < 1) {
-        LaunchTiming t;
-        FTTE_HIP(c, t.start.create());
-        FTTE_HIP(c, t.stop.create());
-        c->timing.push_back(std::move(t));
-    }
+    if ((rc = ensure_timing(c, 1))) return rc;
     LaunchTiming &Tm = c->timing[0];
     Tm.updates = (int64_t)ndir * ncell * nnu; Tm.lanes = 0;
     c->timing_used = 0;
@@ -903,7 +885,7 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     }
     AmrLevelRec A;
     std::memset(&A, 0, sizeof A);
-    A.kappa = c->amr_kappa; A.emis = emit ? c->amr_emis : nullptr;
+    A.kappa = c->kappa.copy(MediumField::kCellMajor); A.emis = emit ? c->emis.copy(MediumField::kCellMajor) : nullptr;
     A.group_stride = 1; A.cell_stride = nnu;
     A.emit = emit;
     A.uvb = c->d_uvb;
@@ -941,34 +923,12 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     };
     // ---- the launches of one sweep: the same sequence every iteration while plan and buffers stay what they are
     auto issue = [&]() -> int {
-        // ---- opacity of the base cells in the three layouts; accumulators and J start from zero
-        if (launch_base_cells(c->kappa[0], c->d_leaf_of_base, c->base_kappa[0], (long)nbase, (long)ncell, nnu, stream))
-            return fail(c, FTTE_ERR_NO_DEVICE, "base-cell kernel launch failed");
-        for (int l = 1; l < 3; ++l)
-            if (P.nacc[l] && launch_to_layout(l, c->base_kappa[0], c->base_kappa[l], n, nnu, (long)nbase, stream))
-                return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
-        if (emit) { // and their emissivity / source function
-            if (launch_base_cells(c->emis[0], c->d_leaf_of_base, c->base_emis[0], (long)nbase, (long)ncell, nnu, stream))
-                return fail(c, FTTE_ERR_NO_DEVICE, "base-cell kernel launch failed");
-            for (int l = 1; l < 3; ++l)
-                if (P.nacc[l] && launch_to_layout(l, c->base_emis[0], c->base_emis[l], n, nnu, (long)nbase, stream))
-                    return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
-        }
-        if (FN.active) { // the fine block's opacities, dense in its own storage order, then in the layouts its groups march through
-            const long nfine = (long)FN.n * FN.n * FN.n;
-            if (launch_base_cells(c->kappa[0], FN.leaf_of_fine, c->fine_kappa[0], nfine, (long)ncell, nnu, stream))
-                return fail(c, FTTE_ERR_NO_DEVICE, "base-cell kernel launch failed");
-            for (int l = 1; l < 3; ++l)
-                if (FN.plan.nacc[l] && launch_to_layout(l, c->fine_kappa[0], c->fine_kappa[l], FN.n, nnu, nfine, stream))
-                    return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
-            if (emit) { // and its emissivity / source function
-                if (launch_base_cells(c->emis[0], FN.leaf_of_fine, c->fine_emis[0], nfine, (long)ncell, nnu, stream))
-                    return fail(c, FTTE_ERR_NO_DEVICE, "base-cell kernel launch failed");
-                for (int l = 1; l < 3; ++l)
-                    if (FN.plan.nacc[l] && launch_to_layout(l, c->fine_emis[0], c->fine_emis[l], FN.n, nnu, nfine, stream))
-                        return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
-            }
-        }
+        // ---- opacity and emissivity / source function of the base cells in the three layouts, then (a fine block) of its cells,
+        // dense in its own storage order; accumulators and J start from zero
+        if ((rc = gather_layouts(c, c->kappa, c->d_leaf_of_base, c->base_kappa, P.nacc, n, stream))) return rc;
+        if (emit && (rc = gather_layouts(c, c->emis, c->d_leaf_of_base, c->base_emis, P.nacc, n, stream))) return rc;
+        if (FN.active && (rc = gather_layouts(c, c->kappa, FN.leaf_of_fine, c->fine_kappa, FN.plan.nacc, FN.n, stream))) return rc;
+        if (FN.active && emit && (rc = gather_layouts(c, c->emis, FN.leaf_of_fine, c->fine_emis, FN.plan.nacc, FN.n, stream))) return rc;
         for (int l = 0; l < 3; ++l)
             for (int s = 0; s < P.nacc[l]; ++s) FTTE_HIP(c, hipMemsetAsync(c->acc[l][s], 0, sizeof(double) * per_base, stream));
         FTTE_HIP(c, hipMemsetAsync(J_dev, 0, sizeof(double) * (size_t)nnu * ncell, stream));
@@ -1045,10 +1005,10 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     // once into a hipGraph -- the streams' forks and joins become dependencies of the graph -- and replays it while the plan, J and
     // every buffer and table the launches name stay the same.  Measured on ROCm 7.2 / MI355X the replay is SLOWER than issuing the
     // launches (configs[3]: 15.8 against 12.2 ms; 8 clusters in 5 passes: 23.9 against 15.1 ms), so it is off by default.
-    std::vector<uintptr_t> sig = {(uintptr_t)J_dev, (uintptr_t)stream, (uintptr_t)nnu, (uintptr_t)nh, (uintptr_t)c->kappa[0].get(), (uintptr_t)c->amr_kappa.get(),
+    std::vector<uintptr_t> sig = {(uintptr_t)J_dev, (uintptr_t)stream, (uintptr_t)nnu, (uintptr_t)nh, (uintptr_t)c->kappa.source(), (uintptr_t)c->kappa.copy(MediumField::kCellMajor),
                                   (uintptr_t)c->d_faces.get(), (uintptr_t)c->amr_Iout.get(), (uintptr_t)c->amr_mean.get(), (uintptr_t)c->d_bgroups.get(), (uintptr_t)c->d_btasks.get(),
                                   (uintptr_t)c->d_amr_dirs.get(), (uintptr_t)c->d_amr_tables.get(), (uintptr_t)c->d_uvb.get(), (uintptr_t)c->d_leaf_of_base.get(), (uintptr_t)H.cells.get(),
-                                  (uintptr_t)c->brick_waves, (uintptr_t)emit, (uintptr_t)c->emis[0].get(), (uintptr_t)c->amr_emis.get(), (uintptr_t)c->forest_fuse,
+                                  (uintptr_t)c->brick_waves, (uintptr_t)emit, (uintptr_t)c->emis.source(), (uintptr_t)c->emis.copy(MediumField::kCellMajor), (uintptr_t)c->forest_fuse,
                                   (uintptr_t)c->base_emis[0].get(), (uintptr_t)c->base_emis[1].get(), (uintptr_t)c->base_emis[2].get()};
     for (int l = 0; l < 3; ++l) { sig.push_back((uintptr_t)c->base_kappa[l].get()); for (int s2 = 0; s2 < P.nacc[l]; ++s2) sig.push_back((uintptr_t)c->acc[l][s2].get()); }
     if (FN.active) for (int l = 0; l < 3; ++l) { sig.push_back((uintptr_t)c->fine_kappa[l].get()); sig.push_back((uintptr_t)c->fine_emis[l].get()); for (int s2 = 0; s2 < FN.plan.nacc[l]; ++s2) sig.push_back((uintptr_t)c->fine_acc[l][s2].get()); }

@@ -9,11 +9,61 @@ namespace ftte {
 int ensure_kappa(ftte_ctx *c, int nnu)
 {
     const size_t need = (size_t)nnu * c->ncell;
-    if (c->kappa[0] && c->kappa[0].capacity() >= need) return FTTE_OK;
-    for (int l = 0; l < 3; ++l) { c->kappa[l].reset(); c->kappa_tiled[l].reset(); c->emis[l].reset(); }
-    c->emit_mode = 0; // sized by the old number of groups: has to be set again
-    FTTE_HIP(c, c->kappa[0].reserve(need));
+    if (c->kappa.source() && c->kappa.capacity() >= need) return FTTE_OK;
+    c->emis.release(); c->emit_mode = 0; // sized by the old number of groups: has to be set again
+    FTTE_HIP(c, c->kappa.reserve_source(need));
     return FTTE_OK;
+}
+
+int ensure_timing(ftte_ctx *c, size_t count)
+{
+    while (c->timing.size() < count) {
+        LaunchTiming t;
+        FTTE_HIP(c, t.start.create());
+        FTTE_HIP(c, t.stop.create());
+        c->timing.push_back(std::move(t));
+    }
+    return FTTE_OK;
+}
+
+// Layout l of a field (or, bricks: its brick-order copy for axis order l, tchunk layers per piece) current on `stream`
+static int make_layout(ftte_ctx *c, MediumField &f, int l, hipStream_t stream, bool bricks = false, int tchunk = 0)
+{
+    if (l == 0 && !bricks) return FTTE_OK; // the source itself
+    const MediumField::Copy x = bricks ? MediumField::bricks(l) : MediumField::layout(l);
+    if (f.current(x, tchunk)) return FTTE_OK;
+    FTTE_HIP(c, f.reserve(x));
+    if (launch_to_layout(l, f.source(), f.copy(x), c->n, c->nnu, (long)c->ncell, stream, bricks, tchunk))
+        return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
+    f.made(x, tchunk);
+    return FTTE_OK;
+}
+
+int make_cell_major(ftte_ctx *c, MediumField &f, hipStream_t stream, const int32_t *cells, int64_t ncells, long long list)
+{
+    const size_t count = list ? (size_t)std::max<int64_t>(ncells, 1) : (size_t)c->ncell;
+    FTTE_HIP(c, f.reserve(MediumField::kCellMajor, (size_t)c->nnu * count));
+    if (f.current(MediumField::kCellMajor, list)) return FTTE_OK;
+    if (launch_cell_major(f.source(), f.copy(MediumField::kCellMajor), (long)c->ncell, c->nnu, stream, cells, (long)ncells))
+        return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
+    f.made(MediumField::kCellMajor, list);
+    return FTTE_OK;
+}
+
+void fill_brick_group(BrickGroup &G, const BrickPlan &P, size_t g, const double *kappa, const double *emis, double *J, const LayerRec *layers,
+                      double *faces, size_t face_stride)
+{
+    const BrickPlan::Group &H = P.groups[g];
+    const DirPlan &D0 = P.dirs[H.dirs[0]];
+    G.kappa = kappa; G.emis = emis; G.J = J;
+    G.org = D0.org; G.si = D0.si; G.sv = D0.sv; G.su = D0.su;
+    G.ndir = (int)H.dirs.size();
+    for (size_t q = 0; q < H.dirs.size(); ++q) {
+        const int d = H.dirs[q];
+        G.dir[q].layers = layers + P.dirs[d].layer_off;
+        G.dir[q].faces = faces + (size_t)d * face_stride;
+        G.dir[q].w = P.dirs[d].w;
+    }
 }
 
 int check_ready(ftte_ctx *c, bool need_kappa)
@@ -24,7 +74,7 @@ int check_ready(ftte_ctx *c, bool need_kappa)
                                              "everything else create a context per device");
     if (!c) return FTTE_ERR_ARG;
     if (!c->grid_set) return fail(c, FTTE_ERR_STATE, "ftte_set_grid has not been called");
-    if (need_kappa && (!c->nnu || !c->kappa[0])) return fail(c, FTTE_ERR_STATE, "no opacities: call ftte_set_opacity / ftte_set_species first");
+    if (need_kappa && (!c->nnu || !c->kappa.source())) return fail(c, FTTE_ERR_STATE, "no opacities: call ftte_set_opacity / ftte_set_species first");
     return FTTE_OK;
 }
 
@@ -378,28 +428,10 @@ int forest_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     // the forest path gathers by cell: all groups of a cell side by side (beyond 96 groups the transposing kernel's
     // tile no longer fits the LDS of a workgroup; the strided layout is read as it is)
     const bool cell_major = nnu <= 96;
-    if (cell_major) {
-    FTTE_HIP(c, c->amr_kappa.reserve((size_t)nnu * ncell));
-    if (!c->kappa_ready[3] || c->amr_kappa_form != 0) {
-        if (launch_cell_major(c->kappa[0], c->amr_kappa, ncell, nnu, stream)) return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
-        c->kappa_ready[3] = true; c->amr_kappa_form = 0;
-    }
-    if (c->emit_mode) {
-        FTTE_HIP(c, c->amr_emis.reserve((size_t)nnu * ncell));
-        if (!c->emis_ready[3]) {
-            if (launch_cell_major(c->emis[0], c->amr_emis, ncell, nnu, stream)) return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
-            c->emis_ready[3] = true;
-        }
-    }
-    }
+    if (cell_major && (rc = make_cell_major(c, c->kappa, stream))) return rc;
+    if (cell_major && c->emit_mode && (rc = make_cell_major(c, c->emis, stream))) return rc;
 
-    const int nbatch = (ndir + batch - 1) / batch;
-    while ((int)c->timing.size() < nbatch) {
-        LaunchTiming t;
-        FTTE_HIP(c, t.start.create());
-        FTTE_HIP(c, t.stop.create());
-        c->timing.push_back(std::move(t));
-    }
+    if ((rc = ensure_timing(c, (size_t)((ndir + batch - 1) / batch)))) return rc;
     c->timing_used = 0;
     if (ndir == 0) FTTE_HIP(c, hipMemsetAsync(J_dev, 0, sizeof(double) * (size_t)nnu * ncell, stream));
 
@@ -407,8 +439,8 @@ int forest_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     {
         AmrLevelRec A;
         std::memset(&A, 0, sizeof A);
-        A.kappa = cell_major ? c->amr_kappa : c->kappa[0];
-        A.emis = !c->emit_mode ? nullptr : cell_major ? c->amr_emis : c->emis[0];
+        A.kappa = cell_major ? c->kappa.copy(MediumField::kCellMajor) : c->kappa.source();
+        A.emis = !c->emit_mode ? nullptr : cell_major ? c->emis.copy(MediumField::kCellMajor) : c->emis.source();
         A.group_stride = cell_major ? 1 : ncell;
         A.cell_stride = cell_major ? nnu : 1;
         A.emit = c->emit_mode;
@@ -464,35 +496,21 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
                        (c->tiled_opt == 1 || n % P.chunk == 0);
     const int tchunk = tiled && c->tiled_opt == 2 ? P.chunk : 0; // 2: a whole brick in one piece
     // Layout 1 ([jc][ic][kc]) holds the rows of layout 0 ([ic][jc][kc]) in another order: its groups march along jc through the
-    // layout-0 frame itself (BrickGroup si = +-n, sv = +-n^2), read kappa[0] and leave their accumulators in layout-0 order.  Only
+    // layout-0 frame itself (BrickGroup si = +-n, sv = +-n^2), read the source array and leave their accumulators in layout-0 order.  Only
     // layout 2, whose march runs along the contiguous axis, needs a transposed copy.  (Brick order keeps its own copy per layout.)
     auto frame = [tiled](int l) { return l == 1 && !tiled ? 0 : l; };
     // accumulators and the opacity in the layouts the groups march through
     for (int l = 0; l < 3; ++l) {
         for (int s = 0; s < P.nacc[l]; ++s)
             FTTE_HIP(c, c->acc[l][s].reserve(acc_size));
-        if (P.nacc[l] && tiled) {
-            if (c->kappa_tiled_from[l] != c->n_kappa_sets || c->kappa_tiled_chunk[l] != tchunk) {
-                FTTE_HIP(c, c->kappa_tiled[l].reserve(c->kappa[0].capacity()));
-                if (launch_to_layout(l, c->kappa[0], c->kappa_tiled[l], n, nnu, (long)c->ncell, stream, true, tchunk))
-                    return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
-                c->kappa_tiled_from[l] = c->n_kappa_sets;
-                c->kappa_tiled_chunk[l] = tchunk;
-            }
-        } else if (P.nacc[l] && frame(l) == l && !c->kappa_ready[l]) {
-            FTTE_HIP(c, c->kappa[l].reserve(c->kappa[0].capacity()));
-            if (!lane_ends) {
-                if (launch_to_layout(l, c->kappa[0], c->kappa[l], n, nnu, (long)c->ncell, stream))
-                    return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
-                c->kappa_ready[l] = true;
-            } else lane_layout[l] = true;
+        if (!P.nacc[l] || frame(l) != l) continue;
+        if (!lane_ends) {
+            if ((rc = make_layout(c, c->kappa, l, stream, tiled, tchunk))) return rc;
+        } else if (l) { // (nothing is current: the lanes bring the source) every lane transposes its own groups, below
+            FTTE_HIP(c, c->kappa.reserve(MediumField::layout(l)));
+            lane_layout[l] = true;
         }
-        if (P.nacc[l] && frame(l) == l && c->emit_mode && !c->emis_ready[l]) {
-            FTTE_HIP(c, c->emis[l].reserve(c->kappa[0].capacity()));
-            if (launch_to_layout(l, c->emis[0], c->emis[l], n, nnu, (long)c->ncell, stream))
-                return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
-            c->emis_ready[l] = true;
-        }
+        if (c->emit_mode && (rc = make_layout(c, c->emis, l, stream))) return rc;
     }
 
     if (!c->bplan_uploaded) {
@@ -522,10 +540,9 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
         for (size_t g = 0; g < P.groups.size(); ++g) {
             const BrickPlan::Group &H = P.groups[g];
             const DirPlan &D0 = P.dirs[H.dirs[0]];
-            G[g].kappa = tiled ? c->kappa_tiled[H.layout] : c->kappa[frame(H.layout)];
-            G[g].emis = c->emit_mode ? c->emis[frame(H.layout)] : nullptr;
-            G[g].J = c->acc[H.layout][H.acc];
-            G[g].org = D0.org; G[g].si = D0.si; G[g].sv = D0.sv; G[g].su = D0.su;
+            fill_brick_group(G[g], P, g, tiled ? c->kappa.copy(MediumField::bricks(H.layout)) : c->kappa.in_layout(frame(H.layout)),
+                             c->emit_mode ? c->emis.in_layout(frame(H.layout)) : nullptr, c->acc[H.layout][H.acc], c->d_blayers, c->d_faces,
+                             (size_t)nnu * (size_t)P.face_elems);
             if (frame(H.layout) != H.layout) { // march (jc) stride n, rows (ic) n^2 apart; a mirrored axis enters from its far end
                 const int64_t nn = (int64_t)n * n;
                 G[g].si = D0.si > 0 ? n : -n;
@@ -550,13 +567,6 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
                     G[g].org = (D0.si > 0 ? -piece : (nti - 1) * ntv * ntu * brick + (int64_t)tchunk * piece) +
                                (D0.sv > 0 ? 0 : (ntv - 1) * ntu * brick + (kBrickRows - 1) * 64) + (D0.su > 0 ? 0 : (ntu - 1) * brick);
                 }
-            }
-            G[g].ndir = (int)H.dirs.size();
-            for (size_t q = 0; q < H.dirs.size(); ++q) {
-                const int d = H.dirs[q];
-                G[g].dir[q].layers = c->d_blayers + P.dirs[d].layer_off;
-                G[g].dir[q].faces = c->d_faces + (size_t)d * nnu * (size_t)P.face_elems;
-                G[g].dir[q].w = P.dirs[d].w;
             }
         }
         // (a blocking copy each: skipped when the device already holds exactly these bytes, which is every iteration after the first)
@@ -595,12 +605,7 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
         FTTE_HIP(c, e.create(hipEventDisableTiming));
         c->ev_merge_point.push_back(std::move(e));
     }
-    while (c->timing.size() < 1) {
-        LaunchTiming t;
-        FTTE_HIP(c, t.start.create());
-        FTTE_HIP(c, t.stop.create());
-        c->timing.push_back(std::move(t));
-    }
+    if ((rc = ensure_timing(c, 1))) return rc;
     c->timing_used = 0;
 
     static const ftte_consts kMath = FTTE_CONSTS_INIT;
@@ -688,12 +693,12 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
                     c->pipe_up.push_back(std::move(e));
                 }
                 if (lane) FTTE_HIP(c, hipStreamWaitEvent(q, c->pipe_up[(size_t)lane - 1], 0));
-                if ((rc = upload_on(c, q, c->kappa[0] + slice0, pipe->kappa + slice0, slice_bytes))) return rc;
+                if ((rc = upload_on(c, q, c->kappa.source() + slice0, pipe->kappa + slice0, slice_bytes))) return rc;
                 FTTE_HIP(c, hipEventRecord(c->pipe_up[(size_t)lane], q));
             }
             if (lane_ends) {
                 for (int l = 1; l < 3; ++l)
-                    if (lane_layout[l] && launch_to_layout(l, c->kappa[0] + slice0, c->kappa[l] + slice0, n, nu1 - nu0, (long)c->ncell, q))
+                    if (lane_layout[l] && launch_to_layout(l, c->kappa.source() + slice0, c->kappa.in_layout(l) + slice0, n, nu1 - nu0, (long)c->ncell, q))
                         return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
                 FTTE_HIP(c, hipEventRecord(T.first[(size_t)lane], q));
             }
@@ -756,11 +761,10 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
                 hipStream_t q = lane == 0 ? stream : c->lane_stream[(size_t)lane - 1];
                 if ((rc = download_on(c, q, pipe->J + slice0, J_dev + slice0, slice_bytes))) return rc;
             }
-            c->kappa_ready[0] = true; // every lane has brought its groups
-            ++c->n_kappa_sets;
+            c->kappa.set(); // every lane has brought its groups
         }
         if (lane_ends) {
-            for (int l = 1; l < 3; ++l) if (lane_layout[l]) c->kappa_ready[l] = true; // ... and transposed them
+            for (int l = 1; l < 3; ++l) if (lane_layout[l]) c->kappa.made(MediumField::layout(l)); // ... and transposed them
             T.lanes = nlanes;
         }
         FTTE_HIP(c, hipEventRecord(T.stop, stream));
@@ -850,29 +854,14 @@ int tile_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, co
             FTTE_HIP(c, c->acc[l][s].reserve(acc_size));
         }
         // opacity in the layout this march axis needs
-        if (any && !c->kappa_ready[l]) {
-            FTTE_HIP(c, c->kappa[l].reserve(c->kappa[0].capacity()));
-            if (launch_to_layout(l, c->kappa[0], c->kappa[l], n, nnu, (long)c->ncell, c->merge_stream))
-                return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
-            c->kappa_ready[l] = true;
-        }
-        if (any && c->emit_mode && !c->emis_ready[l]) {
-            FTTE_HIP(c, c->emis[l].reserve(c->kappa[0].capacity()));
-            if (launch_to_layout(l, c->emis[0], c->emis[l], n, nnu, (long)c->ncell, c->merge_stream))
-                return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
-            c->emis_ready[l] = true;
-        }
+        if (any && (rc = make_layout(c, c->kappa, l, c->merge_stream))) return rc;
+        if (any && c->emit_mode && (rc = make_layout(c, c->emis, l, c->merge_stream))) return rc;
     }
     FTTE_HIP(c, hipEventRecord(c->ev_layouts_ready, c->merge_stream));
     bool layouts_awaited = false;
 
     // events for the launch records
-    while (c->timing.size() < P.launches.size()) {
-        LaunchTiming t;
-        FTTE_HIP(c, t.start.create());
-        FTTE_HIP(c, t.stop.create());
-        c->timing.push_back(std::move(t));
-    }
+    if ((rc = ensure_timing(c, P.launches.size()))) return rc;
     c->timing_used = 0;
 
     bool merged_any = false;
@@ -884,9 +873,9 @@ int tile_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, co
             const DirPlan &D = P.dirs[LP.dirs[s]];
             DirRec &R = L.dir[s];
             R.layers = c->d_layers + D.layer_off;
-            R.kappa = c->kappa[LP.layout];
+            R.kappa = c->kappa.in_layout(LP.layout);
             R.J = c->acc[LP.layout][LP.acc_base + s];
-            R.emis = c->emit_mode ? c->emis[LP.layout] : nullptr;
+            R.emis = c->emit_mode ? c->emis.in_layout(LP.layout) : nullptr;
             R.org = D.org;
             R.si = D.si; R.sv = D.sv; R.su = D.su;
             R.u_lo = D.u_lo; R.v_lo = D.v_lo;
