@@ -79,6 +79,40 @@ module ftte_binding
        real(c_double), intent(out) :: J(*)      ! (ncell, nnu)
      end function ftte_diffuse_sweep
 
+     ! The diagonal of the Lambda operator of the sweep with a source function (the build's own definition, not in the reference):
+     ! diag(cell, nu) = J(cell) of a sweep with S = 1 in that cell alone and no inflow.  Stale after a new grid, new opacities or
+     ! another direction list.
+     integer(c_int) function ftte_lambda_diagonal(ctx, ndir, phi, theta, w, diag) bind(C, name='ftte_lambda_diagonal')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: ndir
+       real(c_double), intent(in) :: phi(*), theta(*), w(*)
+       real(c_double), intent(out) :: diag(*)   ! (ncell, nnu)
+     end function ftte_lambda_diagonal
+
+     integer(c_int) function ftte_lambda_diagonal_device(ctx, ndir, phi, theta, w, diag_dev, stream) &
+          bind(C, name='ftte_lambda_diagonal_device')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: ndir
+       real(c_double), intent(in) :: phi(*), theta(*), w(*)
+       type(c_ptr), value :: diag_dev           ! double* in device memory (ncell, nnu)
+       type(c_ptr), value :: stream             ! hipStream_t, or c_null_ptr: the context's own
+     end function ftte_lambda_diagonal_device
+
+     ! S <- S + ((1 - eps) J + eps B - S) / (1 - (1 - eps) diag) on device arrays (diag_dev = c_null_ptr: S <- (1 - eps) J + eps B);
+     ! change = (max |S_new - S_old|, max |S_new|)
+     integer(c_int) function ftte_source_update_device(ctx, nnu, epsilon, B_dev, b_per_cell, J_dev, diag_dev, S_dev, change, stream) &
+          bind(C, name='ftte_source_update_device')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: nnu, b_per_cell
+       real(c_double), value :: epsilon
+       type(c_ptr), value :: B_dev, J_dev, diag_dev, S_dev   ! device memory; B (nnu), or (ncell, nnu) with b_per_cell = 1
+       real(c_double), intent(out) :: change(2)
+       type(c_ptr), value :: stream
+     end function ftte_source_update_device
+
      ! ftte_set_opacity + ftte_diffuse_sweep in one call; on a uniform grid the groups cross PCIe and are swept in overlapping lanes
      integer(c_int) function ftte_diffuse_iteration(ctx, nnu, kappa, ndir, phi, theta, w, uvb, J) bind(C, name='ftte_diffuse_iteration')
        import :: c_ptr, c_int, c_double

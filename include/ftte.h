@@ -140,6 +140,33 @@ int ftte_diffuse_iteration(ftte_ctx *ctx, int nnu, const double *kappa, int ndir
 int ftte_diffuse_sweep_device(ftte_ctx *ctx, int ndir, const double *phi, const double *theta, const double *w,
                               const double *uvb, double *J_dev, void *stream);
 
+/* ---- accelerated source iteration -------------------------------------------------------------
+ * NOT in the reference (like the source function itself, its emission never being enabled): the build's own definition.
+ *
+ * The diagonal of the discrete Lambda operator of the sweep with a source function.  A cell's share of a ray segment is
+ * S + (Iin - S) g(tau), g = (1 - exp(-tau))/tau; the (up to three) segments of a cell belong to different rays and each takes its
+ * Iin from ANOTHER cell or from the inflow, so a cell's own S enters its own J through S (1 - g) alone:
+ *     diag[nu][cell] = sum over directions  w/nseg * sum over the cell's segments (1 - g(kappa_nu(cell) * dpath_seg))
+ * evaluated with the sweep's own arithmetic in the sweep's own order (segments xy, xz, yz, then the mean, directions in list
+ * order): it equals J[cell] of a sweep with S = 1 in that cell and 0 elsewhere and no inflow, bit for bit, on uniform grids and
+ * refined cell arrays alike, whatever ftte_set_option says.  0 <= diag < sum of w.  Arguments as ftte_diffuse_sweep takes them
+ * (phi, theta, w before folding); diag[nnu][ncell] host memory, cell-array order, overwritten.
+ * It goes stale with a new grid, new opacities or another direction list; nothing is cached: recomputing is the caller's
+ * decision.  Errors as the sweep's (FTTE_ERR_STATE without grid or opacities); FTTE_ERR_UNSUPPORTED on a multi-device context. */
+int ftte_lambda_diagonal(ftte_ctx *ctx, int ndir, const double *phi, const double *theta, const double *w, double *diag);
+/* Same with diag in device memory; asynchronous on `stream` (NULL: the context's own), like ftte_diffuse_sweep_device. */
+int ftte_lambda_diagonal_device(ftte_ctx *ctx, int ndir, const double *phi, const double *theta, const double *w,
+                                double *diag_dev, void *stream);
+/* One step of the source iteration S = (1 - eps) J + eps B, element-wise over [nnu][ncell] device arrays, in one pass:
+ *     S <- S + ((1 - eps) J + eps B - S) / (1 - (1 - eps) diag)      (in this order of operations, IEEE division)
+ * the approximate-operator (Jacobi) update whose fixed point is that of the plain iteration; diag_dev = NULL: the plain update
+ * S <- (1 - eps) J + eps B.  B_dev: [nnu] (b_per_cell = 0) or [nnu][ncell].  change[2] (host, may be NULL) receives
+ * max |S_new - S_old| and max |S_new|: a measure of progress, not of the error (a slowly converging iteration changes little).
+ * A denominator that is not positive (the weights sum to more than 1/(1 - eps)) is FTTE_ERR_ARG naming the first such element;
+ * S is then unchanged.  Ordered on `stream`; returns when the step has completed. */
+int ftte_source_update_device(ftte_ctx *ctx, int nnu, double epsilon, const double *B_dev, int b_per_cell, const double *J_dev,
+                              const double *diag_dev, double *S_dev, double *change, void *stream);
+
 /* ---- point sources ---------------------------------------------------------------------------
  * The `runStellarTransfer` block, equiSources.f90:1256-1370: for each star particle build the rate
  * tables of its population (stellarBetaTable), then send 12 HEALPix rays from the centre of its host

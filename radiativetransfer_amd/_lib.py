@@ -49,6 +49,9 @@ SIGNATURES = {
     "ftte_diffuse_sweep": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "ftte_diffuse_iteration": (C.c_int, [_vp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "ftte_diffuse_sweep_device": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _vp, _vp]),
+    "ftte_lambda_diagonal": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp]),
+    "ftte_lambda_diagonal_device": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _vp, _vp]),
+    "ftte_source_update_device": (C.c_int, [_vp, C.c_int, C.c_double, _vp, C.c_int, _vp, _vp, _vp, _dp, _vp]),
     "ftte_stellar_beta_table": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_double, C.c_int,
                                           C.c_double, _dp]),
     "ftte_set_rate_tables": (C.c_int, [_vp, _dp]),

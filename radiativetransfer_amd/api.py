@@ -207,6 +207,36 @@ class DiffuseTransfer:
         self._ok(self._lib.ftte_diffuse_sweep_device(self._ctx, len(phi), _dp(phi), _dp(theta), _dp(weight), _dp(uvb),
                                                      C.c_void_p(j_device_ptr), C.c_void_p(stream)))
 
+    # -- accelerated source iteration (the build's own: the reference has no enabled emission)
+    def lambda_diagonal(self, phi, theta, weight) -> np.ndarray:
+        """The diagonal of the Lambda operator of the sweep with a source function, [nnu][ncell] (host): J[c] of a sweep with
+        S = 1 in cell c alone and no inflow, for every c at once (include/ftte.h: ftte_lambda_diagonal).  Stale after a new grid,
+        new opacities or another direction list."""
+        phi, theta, weight = map(_f64, (phi, theta, weight))
+        if not (len(phi) == len(theta) == len(weight)):
+            raise ValueError("direction arrays must have equal length")
+        diag = np.empty((max(self.nnu, 1), max(self.ncell, 1)))
+        self._ok(self._lib.ftte_lambda_diagonal(self._ctx, len(phi), _dp(phi), _dp(theta), _dp(weight), _dp(diag)))
+        return diag
+
+    def lambda_diagonal_device(self, phi, theta, weight, diag_device_ptr: int, stream: int = 0):
+        """Same with the diagonal [nnu][ncell] in device memory; asynchronous on `stream` (0 = own)."""
+        phi, theta, weight = map(_f64, (phi, theta, weight))
+        if not (len(phi) == len(theta) == len(weight)):
+            raise ValueError("direction arrays must have equal length")
+        self._ok(self._lib.ftte_lambda_diagonal_device(self._ctx, len(phi), _dp(phi), _dp(theta), _dp(weight),
+                                                       C.c_void_p(diag_device_ptr), C.c_void_p(stream)))
+
+    def source_update_device(self, nnu: int, epsilon: float, b_device_ptr: int, b_per_cell: bool, j_device_ptr: int,
+                             diag_device_ptr: Optional[int], s_device_ptr: int, stream: int = 0) -> Tuple[float, float]:
+        """S <- S + ((1 - eps) J + eps B - S) / (1 - (1 - eps) diag) on device arrays [nnu][ncell] (diag None: the plain
+        S <- (1 - eps) J + eps B); returns (max |S_new - S_old|, max |S_new|).  B: [nnu], or [nnu][ncell] with b_per_cell."""
+        change = (C.c_double * 2)()
+        self._ok(self._lib.ftte_source_update_device(self._ctx, int(nnu), float(epsilon), C.c_void_p(b_device_ptr), int(bool(b_per_cell)),
+                                                     C.c_void_p(j_device_ptr), C.c_void_p(diag_device_ptr) if diag_device_ptr else None,
+                                                     C.c_void_p(s_device_ptr), change, C.c_void_p(stream)))
+        return change[0], change[1]
+
     def transport_into(self, phi, theta, weight, uvb, J: np.ndarray) -> np.ndarray:
         """Same as transport() into a caller-owned J[nnu][ncell] (e.g. one registered with host_register)."""
         phi, theta, weight, uvb = map(_f64, (phi, theta, weight, uvb))

@@ -27,6 +27,7 @@
 #include "ftte_geometry.h"
 #include "ftte_internal.h"
 #include "ftte_kernels.h"
+#include "ftte_lambda.h"
 #include "ftte_medium.h"
 #include "ftte_point.h"
 
@@ -309,6 +310,17 @@ struct ftte_ctx {
     DeviceBuffer<unsigned long long> chem_counters; // first bad cell, bits of the largest change, bisection steps
     long long chem_steps = 0;
     DeviceBuffer<double> chem_mass;  // computeMass: per-workgroup partial sums, then the two totals (kMassParts)
+
+    // accelerated source iteration (ftte_lambda_host.cpp): the segment-length tables of the last direction list, the leaves' places on
+    // their levels (made for the tree of grid build lambda_leaves_grid) with the sub-layers that hold a leaf, the update's statistics
+    DeviceBuffer<LambdaRec> d_lambda_table;
+    DeviceBuffer<LambdaDir> d_lambda_dirs;
+    DeviceBuffer<LambdaLeaf> d_lambda_leaves;
+    long long lambda_leaves_grid = -1;
+    std::vector<uint8_t> lambda_used;  // [3 axes][level after level][position]
+    DeviceBuffer<double> d_lambda_host; // ftte_lambda_diagonal: the diagonal on its way to the caller's host array
+    DeviceBuffer<unsigned long long> d_update_stats;
+    PinnedBuffer<unsigned long long> h_update_stats;
 
     void drop_chem_grid()
     {

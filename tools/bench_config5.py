@@ -6,7 +6,9 @@ plane-parallel opacity stratification; per-iteration rate and convergence.  One 
 
 one rank per GPU, frequency groups first, then directions (distributed.Shard2D): a rank keeps J and S of its groups, and with
 N = 8 = the groups nothing is exchanged between the sweeps.  --rehearse-on-one-gpu: the ranks share GPU 0 and the collectives run
-on host copies over gloo (what a one-GPU box can check of the branch)."""
+on host copies over gloo (what a one-GPU box can check of the branch).
+--accelerate=diagonal | diagonal+ng: SourceIteration's accelerated schemes (default: the plain Lambda iteration); the time of the
+Lambda* call is printed once, the measure per iteration is then max |dS| / max |S| of the operator update."""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,6 +23,7 @@ from radiativetransfer_amd.distributed import Shard2D
 
 rehearse = "--rehearse-on-one-gpu" in sys.argv
 dump = [a.split("=", 1)[1] for a in sys.argv if a.startswith("--dump=")]
+accelerate = ([a.split("=", 1)[1] for a in sys.argv if a.startswith("--accelerate=")] or [None])[-1]
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 n = int(args[0]) if len(args) > 0 else 256
 iters = int(args[1]) if len(args) > 1 else 50
@@ -49,12 +52,19 @@ phi, theta, w = sh.directions(phi, theta, w)
 kappa = torch.from_numpy(np.ascontiguousarray(kappa_host[lo:hi])).to(dev)
 eng = rt.DiffuseTransfer(device=local)
 for a in sys.argv[1:]:                                   # library options: --team=2 ...
-    if a.startswith("--") and "=" in a and not a.startswith("--dump="):
+    if a.startswith("--") and "=" in a and not a.startswith(("--dump=", "--accelerate=")):
         eng.set_option(a[2:].split("=")[0], int(a.split("=")[1]))
 eng.set_uniform_grid(n, 1.0)
 eng.set_opacity_device(hi - lo, kappa.data_ptr())
 it = SourceIteration(eng, hi - lo, n ** 3, phi, theta, w, (uvb * 0.0 + 1e-30)[lo:hi], eps, (1e-21 * s_nu ** 0.5)[lo:hi], device=dev,
-                     shard=sh, stage_on_host=rehearse)
+                     shard=sh, stage_on_host=rehearse, accelerate=accelerate)
+if accelerate:
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    it.refresh()
+    torch.cuda.synchronize()
+    if rank == 0:
+        print(f"Lambda* ({accelerate}): {it.lambda_ms:7.1f} ms on the device, {(time.perf_counter() - t0) * 1e3:7.1f} ms with tables and sums", flush=True)
+measure = "|dS|/|S|" if accelerate else "|dJ|/|J|"
 if rank == 0 and world > 1:
     print(f"{world} ranks: {sh.describe()[:sh.describe().index(':')]}; rank 0 sweeps groups {lo}..{hi - 1} in {len(phi)} directions", flush=True)
 upd = n ** 3 * nnu * ndir
@@ -69,7 +79,7 @@ for k in range(iters):
         dist.all_reduce(dt, op=dist.ReduceOp.MAX)       # an iteration lasts as long as its slowest rank
     dt = float(dt[0])
     if rank == 0 and (k < 3 or k % 10 == 9 or k == iters - 1):
-        print(f"iteration {k + 1:3d}: {dt * 1e3:7.1f} ms  {upd / dt:.3e} updates/s  |dJ|/|J| = {change:.3e}", flush=True)
+        print(f"iteration {k + 1:3d}: {dt * 1e3:7.1f} ms  {upd / dt:.3e} updates/s  {measure} = {change:.3e}", flush=True)
 J = it.J
 if dump:                                                 # (tests: this rank's groups after the last iteration)
     np.save(os.path.join(dump[0], f"J{rank}.npy"), J.cpu().numpy())
