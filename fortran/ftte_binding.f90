@@ -186,6 +186,35 @@ module ftte_binding
        real(c_double), intent(out) :: total_integral
      end function ftte_stellar_beta_table
 
+     ! population slots: npop table sets side by side for ftte_point_sources_populations; the four population arrays (npop)
+     integer(c_int) function ftte_stellar_beta_tables(ctx, a_smc, nwave, wavelength_cm, nspectrum, nmetal, &
+          specific_luminosity, npop, iSpectrum, coefSpectrum, iMetal, coefMetal, total_integral) &
+          bind(C, name='ftte_stellar_beta_tables')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       real(c_double), intent(in) :: a_smc(7,5)
+       integer(c_int), value :: nwave, nspectrum, nmetal, npop
+       real(c_double), intent(in) :: wavelength_cm(*)
+       real(c_double), intent(in) :: specific_luminosity(*)
+       integer(c_int), intent(in) :: iSpectrum(*), iMetal(*)
+       real(c_double), intent(in) :: coefSpectrum(*), coefMetal(*)
+       real(c_double), intent(out) :: total_integral(*)
+     end function ftte_stellar_beta_tables
+
+     integer(c_int) function ftte_set_population_tables(ctx, npop, tables) bind(C, name='ftte_set_population_tables')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: npop
+       real(c_double), intent(in) :: tables(*)   ! npop sets as for ftte_set_rate_tables, one after the other
+     end function ftte_set_population_tables
+
+     integer(c_int) function ftte_get_population_tables(ctx, slot, tables) bind(C, name='ftte_get_population_tables')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: slot             ! 0-based
+       real(c_double), intent(out) :: tables(*)
+     end function ftte_get_population_tables
+
      integer(c_int) function ftte_set_rate_tables(ctx, tables) bind(C, name='ftte_set_rate_tables')
        import :: c_ptr, c_int, c_double
        type(c_ptr), value :: ctx
@@ -238,7 +267,19 @@ module ftte_binding
        integer(c_int), intent(out) :: highest_pixel_level
      end function ftte_point_sources
 
-     ! escape bookkeeping of the last ftte_point_sources call (equiSources.f90:3198-3233, 1342-1348); arrays as Fortran
+     ! star s reads population slot src_slot(s) (0-based); highest_pixel_level(nsrc) is per star
+     integer(c_int) function ftte_point_sources_populations(ctx, nsrc, src_cell, src_ndot, src_slot, highest_pixel_level) &
+          bind(C, name='ftte_point_sources_populations')
+       import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: nsrc
+       integer(c_int64_t), intent(in) :: src_cell(*)
+       real(c_double), intent(in) :: src_ndot(*)
+       integer(c_int32_t), intent(in) :: src_slot(*)
+       integer(c_int), intent(out) :: highest_pixel_level(*)
+     end function ftte_point_sources_populations
+
+     ! escape bookkeeping of the last ftte_point_sources / ftte_point_sources_populations call (equiSources.f90:3198-3233, 1342-1348); arrays as Fortran
      ! (7,nsrc), (7,nsrc), (nsrc), (300,nsrc), (7,nsrc); pass c_null_ptr-associated dummies by using the _opt variant if unwanted
      integer(c_int) function ftte_point_escape(ctx, nsrc, remaining, boundary, dust, spectrum, fraction) bind(C, name='ftte_point_escape')
        import :: c_ptr, c_int, c_double

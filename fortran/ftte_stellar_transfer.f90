@@ -13,6 +13,13 @@
 ! module localDefinitions / definitions are set, and cosmicSpectrum has received every star's share; the caller zeroes
 ! cosmicSpectrum before (:1258) and divides by nStarsSpecificAge after (:1366), as the reference does around its loop.
 ! localDefinitions is a module of the reference's main file: compile this file after it (INTEGRATION.md).
+!
+! ftteStarBatch (default 1: the reference's sequence, one table build and one trace per star).  Set it larger and that many stars
+! are traced together: each star's (iMetal, coefMetal) as before, stars with identical pairs share a population slot, one
+! ftte_stellar_beta_tables and one ftte_point_sources_populations per batch; the per-star results follow in star order.
+! The environment variable FTTE_STAR_BATCH sets it without a recompilation.  It is read once, at the module's first call, and where
+! it holds a number >= 1 it wins over a value the host program assigned before that call; a value assigned after the first call
+! holds from the next call on.
 module ftte_stellar_transfer
 
   use, intrinsic :: iso_c_binding
@@ -22,6 +29,7 @@ module ftte_stellar_transfer
   use ftte_binding
   implicit none
 
+  integer, save, public :: ftteStarBatch = 1
   type(c_ptr), save, private :: ctx = c_null_ptr
   integer(c_int64_t), private :: cursor
 
@@ -38,8 +46,24 @@ contains
     real(c_double) :: escRemaining(nradius), escBoundary(nradius), escDust(1), escSpectrum(nenergy), escFraction(nradius)
     integer(c_int) :: highest
     integer :: i, j, k, iStar, iMetal
+    ! a batch of stars (ftteStarBatch > 1) and its populations
+    integer(c_int64_t), allocatable :: bHost(:)
+    real(c_double), allocatable :: bNdot(:), popCoefS(:), popCoefM(:), popTotal(:)
+    real(c_double), allocatable :: bRemaining(:,:), bBoundary(:,:), bDust(:), bSpectrum(:,:), bFraction(:,:)
+    integer(c_int32_t), allocatable :: bSlot(:)
+    integer(c_int), allocatable :: bHighest(:), popSpectrum(:), popMetal(:)
+    integer, allocatable :: bStar(:)
+    integer :: nb, npop, ip, ib, nbatch, envStatus, envValue
+    character(len=16) :: envText
 
-    if (.not. c_associated(ctx)) call ftteCheck(c_null_ptr, ftte_create(ctx, 1, c_null_ptr), 'ftte_create')
+    if (.not. c_associated(ctx)) then
+       call ftteCheck(c_null_ptr, ftte_create(ctx, 1, c_null_ptr), 'ftte_create')
+       call get_environment_variable('FTTE_STAR_BATCH', envText, status=envStatus)
+       if (envStatus .eq. 0) then
+          read(envText, *, iostat=envStatus) envValue
+          if (envStatus .eq. 0 .and. envValue .ge. 1) ftteStarBatch = envValue
+       endif
+    endif
 
     ncell = 0
     do i = 1, nx
@@ -64,6 +88,16 @@ contains
          'ftte_set_medium')
     call ftteCheck(ctx, ftte_set_zero_rates(ctx), 'ftte_set_zero_rates')
 
+    nbatch = max(1, min(ftteStarBatch, nStars))
+    if (nbatch .gt. 1) then
+       allocate(bHost(nbatch), bNdot(nbatch), bSlot(nbatch), bHighest(nbatch), bStar(nbatch))
+       allocate(popSpectrum(nbatch), popCoefS(nbatch), popMetal(nbatch), popCoefM(nbatch), popTotal(nbatch))
+       allocate(bRemaining(nradius,nbatch), bBoundary(nradius,nbatch), bDust(nbatch), bSpectrum(nenergy,nbatch), &
+            bFraction(nradius,nbatch))
+    endif
+    nb = 0
+    npop = 0
+
     do iStar = 1, nStars
        if (star(iStar)%weight .gt. 0) then
           allocate(pos(3*star(iStar)%level+3))
@@ -85,6 +119,29 @@ contains
           coefMetal = (tmp-metallicity(iMetal))/(metallicity(iMetal+1)-metallicity(iMetal))
           coefMetal = min(max(0.d0,coefMetal),1.d0)
 
+          if (nbatch .gt. 1) then
+             ! into the batch: the slot of this star's population, a new one unless an earlier star of the batch has the same pair
+             ip = 1
+             do while (ip .le. npop)
+                if (popMetal(ip) .eq. iMetal .and. popCoefM(ip) .eq. coefMetal) exit
+                ip = ip + 1
+             enddo
+             if (ip .gt. npop) then
+                npop = ip
+                popSpectrum(ip) = iSpectrum
+                popCoefS(ip) = coefSpectrum
+                popMetal(ip) = iMetal
+                popCoefM(ip) = coefMetal
+             endif
+             nb = nb + 1
+             bStar(nb) = iStar
+             bHost(nb) = host(1)
+             bNdot(nb) = float(star(iStar)%weight)
+             bSlot(nb) = ip - 1
+             if (nb .eq. nbatch) call traceBatch
+             cycle
+          endif
+
           call ftteCheck(ctx, ftte_stellar_beta_table(ctx, a_smc, nWavelengths, wavelength, nSpectra, nMetallicity, &
                specificLuminosity, iSpectrum, coefSpectrum, iMetal, coefMetal, totalIntegral), 'ftte_stellar_beta_table')
 
@@ -105,6 +162,7 @@ contains
 1015      format('src: ', i5, i3, es13.5, i3, 7f9.5, i8)
        endif
     enddo
+    if (nb .gt. 0) call traceBatch
 
     call ftteCheck(ctx, ftte_get_point_rates(ctx, rates), 'ftte_get_point_rates')
     cursor = 0
@@ -115,6 +173,33 @@ contains
           enddo
        enddo
     enddo
+
+  contains
+
+    ! the nb stars collected so far: their npop populations in one call, the stars in one call, then per star and in star order
+    ! what the loop above produces for a single star
+    subroutine traceBatch
+      call ftteCheck(ctx, ftte_stellar_beta_tables(ctx, a_smc, nWavelengths, wavelength, nSpectra, nMetallicity, &
+           specificLuminosity, npop, popSpectrum, popCoefS, popMetal, popCoefM, popTotal), 'ftte_stellar_beta_tables')
+      call ftteCheck(ctx, ftte_point_sources_populations(ctx, nb, bHost, bNdot, bSlot, bHighest), &
+           'ftte_point_sources_populations')
+      call ftteCheck(ctx, ftte_point_escape(ctx, nb, bRemaining, bBoundary, bDust, bSpectrum, bFraction), 'ftte_point_escape')
+      do ib = 1, nb
+         highestPixelLevel = bHighest(ib)
+         ndotRemaining = bRemaining(:,ib)
+         ndotBoundary = bBoundary(:,ib)
+         ndotDust = bDust(ib)
+         ndotSpectrum = bSpectrum(:,ib)
+         fraction = bFraction(:,ib)
+         cosmicSpectrum = cosmicSpectrum + float(star(bStar(ib))%weight) * ndotSpectrum/(bNdot(ib)-ndotBoundary(nradius))
+         write(*,1016) bStar(ib), star(bStar(ib))%level, med(bHost(ib)+1,1) * mh / (psi * med(bHost(ib)+1,4)), &
+              highestPixelLevel, fraction, star(bStar(ib))%weight
+1016     format('src: ', i5, i3, es13.5, i3, 7f9.5, i8)
+      enddo
+      nb = 0
+      npop = 0
+    end subroutine traceBatch
+
   end subroutine ftteRunStellarTransfer
 
   recursive subroutine countCells(c, total)

@@ -180,6 +180,12 @@ int ftte_source_update_device(ftte_ctx *ctx, int nnu, double epsilon, const doub
  *   ftte_set_grid; ftte_set_medium; ftte_set_zero_rates;
  *   per population: ftte_stellar_beta_table (or ftte_set_rate_tables); ftte_point_sources(stars of it);
  *   ftte_get_point_rates.
+ * or, where every star has a population of its own (the reference builds its tables per star from the host cell's
+ * metallicity, equiSources.f90:1282-1299), batched:
+ *   ftte_set_grid; ftte_set_medium; ftte_set_zero_rates;
+ *   ftte_stellar_beta_tables(all populations of the batch) (or ftte_set_population_tables);
+ *   ftte_point_sources_populations(stars, the slot each reads); ftte_point_escape;
+ *   ftte_get_point_rates.
  * Rates accumulate on the device between ftte_set_zero_rates and ftte_get_point_rates. */
 
 #define FTTE_TABLE_SIZE 14641 /* (ndepth+1)^4 = 11^4, definitionsModule.f90:72-77 */
@@ -195,6 +201,23 @@ int ftte_source_update_device(ftte_ctx *ctx, int nnu, double epsilon, const doub
 int ftte_stellar_beta_table(ftte_ctx *ctx, const double *a_smc, int nwave, const double *wavelength_cm, int nspectrum,
                             int nmetal, const double *specific_luminosity, int iSpectrum, double coefSpectrum, int iMetal,
                             double coefMetal, double *total_integral);
+/* Population slots: npop table sets held side by side, for ftte_point_sources_populations.  The slots are apart from "the
+ * current tables" of the calls above, which neither read nor change them.  A slot takes 2 x 6 x FTTE_TABLE_SIZE doubles of device
+ * memory (1.4 MB); what does not fit in the free memory is FTTE_ERR_MEMORY, with the byte count in the message, and leaves the
+ * slots held as they were.  ftte_counter(ctx, "population_slots") is the number held.
+ *
+ * ftte_stellar_beta_tables: stellarBetaTable for npop populations (iSpectrum, coefSpectrum, iMetal, coefMetal)[npop] into slots
+ * 0..npop-1, replacing any earlier slots.  Per population the host work and the device arithmetic of ftte_stellar_beta_table, so
+ * that a slot holds bit for bit what that call stores; frequency grid and cross-sections once, one launch for all tables.
+ * total_integral[npop] (may be NULL).  Sets the output cross-sections like ftte_stellar_beta_table. */
+int ftte_stellar_beta_tables(ftte_ctx *ctx, const double *a_smc, int nwave, const double *wavelength_cm, int nspectrum,
+                             int nmetal, const double *specific_luminosity, int npop, const int *iSpectrum,
+                             const double *coefSpectrum, const int *iMetal, const double *coefMetal, double *total_integral);
+/* tables[npop][6][FTTE_TABLE_SIZE] computed elsewhere into slots 0..npop-1, replacing any earlier slots (each set laid out as for
+ * ftte_set_rate_tables).  The output cross-sections stay what they were (ftte_set_output_sigma). */
+int ftte_set_population_tables(ftte_ctx *ctx, int npop, const double *tables);
+/* tables[6][FTTE_TABLE_SIZE] of one slot */
+int ftte_get_population_tables(ftte_ctx *ctx, int slot, double *tables);
 /* Tables computed elsewhere (e.g. by the reference itself): tables[6][FTTE_TABLE_SIZE], order
  * reactionRate1, 2, 3, energyRate1, 2, 3, each the Fortran array (0:ndepth,0:ndepth,0:ndepth,0:ndepth)
  * (tau1, tau2, tau3, tauDust) as it lies in memory. */
@@ -221,8 +244,15 @@ int ftte_locate_cell(ftte_ctx *ctx, int level, const int32_t *position, int64_t 
  * rates.  highest_pixel_level (may be NULL): the largest value of the reference's highestPixelLevel over
  * these stars.  Deposition uses fp64 atomics: the last bits of the sums depend on the run. */
 int ftte_point_sources(ftte_ctx *ctx, int nsrc, const int64_t *src_cell, const double *src_ndot, int *highest_pixel_level);
+/* ftte_point_sources with star s reading the tables of population slot src_slot[s] (0-based) instead of the current tables.  Adds
+ * into the same rates and feeds ftte_point_escape and ftte_point_ray_steps the same way.  highest_pixel_level[nsrc] (may be NULL)
+ * is per star: the reference resets highestPixelLevel for every star (equiSources.f90:1266) and prints it in its `src:` line.
+ * A slot outside those held is FTTE_ERR_ARG (the message names the first such star), no slots FTTE_ERR_STATE; otherwise the
+ * preconditions of ftte_point_sources.  On an error the rates are unchanged. */
+int ftte_point_sources_populations(ftte_ctx *ctx, int nsrc, const int64_t *src_cell, const double *src_ndot, const int32_t *src_slot,
+                                   int *highest_pixel_level);
 /* The escape bookkeeping startNewLongRay keeps per star (equiSources.f90:3198-3233, :3336-3345; reset per star at :1267-1270), for
- * the nsrc stars of the LAST ftte_point_sources call, in its order: remaining[nsrc][7] = ndotRemaining and boundary[nsrc][7] =
+ * the nsrc stars of the LAST ftte_point_sources / ftte_point_sources_populations call, in its order: remaining[nsrc][7] = ndotRemaining and boundary[nsrc][7] =
  * ndotBoundary at outputRadius = 0.1, 0.3, 1, 3, 10, 30, 100 kpc (equiSources.f90:10), dust[nsrc] = ndotDust, spectrum[nsrc][300] =
  * ndotSpectrum at the last radius (zero unless the output cross-sections are known: ftte_stellar_beta_table computes them,
  * ftte_set_output_sigma hands them over), fraction[nsrc][7] as the main program forms it for its `src:` line (:1342-1348:

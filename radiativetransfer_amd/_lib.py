@@ -54,6 +54,9 @@ SIGNATURES = {
     "ftte_source_update_device": (C.c_int, [_vp, C.c_int, C.c_double, _vp, C.c_int, _vp, _vp, _vp, _dp, _vp]),
     "ftte_stellar_beta_table": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, C.c_double, C.c_int,
                                           C.c_double, _dp]),
+    "ftte_stellar_beta_tables": (C.c_int, [_vp, _dp, C.c_int, _dp, C.c_int, C.c_int, _dp, C.c_int, _ip, _dp, _ip, _dp, _dp]),
+    "ftte_set_population_tables": (C.c_int, [_vp, C.c_int, _dp]),
+    "ftte_get_population_tables": (C.c_int, [_vp, C.c_int, _dp]),
     "ftte_set_rate_tables": (C.c_int, [_vp, _dp]),
     "ftte_get_rate_tables": (C.c_int, [_vp, _dp]),
     "ftte_get_rates_hydrogen_helium": (C.c_int, [_vp, C.c_int, C.c_int, _dp, _dp]),
@@ -62,6 +65,7 @@ SIGNATURES = {
     "ftte_set_zero_rates": (C.c_int, [_vp]),
     "ftte_locate_cell": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "ftte_point_sources": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int64), _dp, _ip]),
+    "ftte_point_sources_populations": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int32), _ip]),
     "ftte_point_escape": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "ftte_set_output_sigma": (C.c_int, [_vp, _dp]),
     "ftte_get_point_rates": (C.c_int, [_vp, _dp]),

@@ -370,6 +370,46 @@ class StellarTransfer(DiffuseTransfer):
             float(coef_metal), C.byref(total)))
         return total.value
 
+    def stellar_beta_tables(self, a_smc, wavelength_cm, specific_luminosity, i_spectrum, coef_spectrum, i_metal,
+                            coef_metal) -> np.ndarray:
+        """stellarBetaTable for the populations (i_spectrum, coef_spectrum, i_metal, coef_metal)[npop] into population slots
+        0..npop-1, replacing earlier slots; each slot holds what stellar_beta_table stores for its population.  Returns
+        totalIntegral[npop]; the tables stay on the device."""
+        a = np.asfortranarray(_f64(a_smc).reshape(7, 5))
+        wl = _f64(wavelength_cm)
+        sl = _f64(specific_luminosity)
+        if sl.ndim != 3 or sl.shape[2] != wl.size:
+            raise ValueError("specific_luminosity must have shape [nmetal][nspectrum][nwave]")
+        slf = np.asfortranarray(sl)
+        i_s = np.ascontiguousarray(i_spectrum, dtype=np.intc).reshape(-1)
+        i_m = np.ascontiguousarray(i_metal, dtype=np.intc).reshape(-1)
+        c_s, c_m = _f64(coef_spectrum).reshape(-1), _f64(coef_metal).reshape(-1)
+        if not (i_s.size == i_m.size == c_s.size == c_m.size):
+            raise ValueError("the four population arrays must have equal length")
+        totals = np.empty(i_s.size)
+        self._ok(self._lib.ftte_stellar_beta_tables(
+            self._ctx, a.ctypes.data_as(C.POINTER(C.c_double)), wl.size, _dp(wl), sl.shape[1], sl.shape[0],
+            slf.ctypes.data_as(C.POINTER(C.c_double)), i_s.size, i_s.ctypes.data_as(C.POINTER(C.c_int)), _dp(c_s),
+            i_m.ctypes.data_as(C.POINTER(C.c_int)), _dp(c_m), _dp(totals)))
+        return totals
+
+    def set_population_tables(self, tables):
+        """tables[npop][6][11][11][11][11] computed elsewhere into population slots 0..npop-1, replacing earlier slots."""
+        tables = _f64(tables)
+        size = int(np.prod(TABLE_SHAPE))
+        if tables.size == 0 or tables.size % size:
+            raise ValueError("tables must have shape [npop][6][11][11][11][11]")
+        self._ok(self._lib.ftte_set_population_tables(self._ctx, tables.size // size, _dp(tables)))
+
+    def population_tables(self, slot: int) -> np.ndarray:
+        """The tables of one population slot, [6][11][11][11][11]."""
+        out = np.empty(TABLE_SHAPE)
+        self._ok(self._lib.ftte_get_population_tables(self._ctx, int(slot), _dp(out)))
+        return out
+
+    def population_slots(self) -> int:
+        return self.counter("population_slots")
+
     def set_rate_tables(self, tables):
         tables = _f64(tables)
         if tables.size != int(np.prod(TABLE_SHAPE)):
@@ -424,6 +464,20 @@ class StellarTransfer(DiffuseTransfer):
         self._ok(self._lib.ftte_point_sources(self._ctx, cells.size, cells.ctypes.data_as(C.POINTER(C.c_int64)), _dp(ndot),
                                               C.byref(highest)))
         return highest.value
+
+    def point_sources_populations(self, cells, ndot, slots) -> np.ndarray:
+        """point_sources with star s reading the tables of population slot slots[s] instead of the current tables.  Returns
+        each star's own highestPixelLevel."""
+        cells = np.ascontiguousarray(cells, dtype=np.int64)
+        ndot = _f64(ndot)
+        slots = np.ascontiguousarray(slots, dtype=np.int32)
+        if cells.size != ndot.size or cells.size != slots.size:
+            raise ValueError("cells, ndot and slots must have equal length")
+        highest = np.zeros(cells.size, dtype=np.intc)
+        self._ok(self._lib.ftte_point_sources_populations(self._ctx, cells.size, cells.ctypes.data_as(C.POINTER(C.c_int64)), _dp(ndot),
+                                                          slots.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                          highest.ctypes.data_as(C.POINTER(C.c_int))))
+        return highest
 
     def escape(self, nsrc: int) -> dict:
         """Escape bookkeeping of the last point_sources call (equiSources.f90:3198-3233, 1342-1348): dict of remaining [nsrc][7],

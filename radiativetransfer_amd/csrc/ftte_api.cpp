@@ -427,6 +427,7 @@ long long ftte_counter(const ftte_ctx *c, const char *name)
     if (!std::strcmp(name, "plan_builds")) return c->n_plan_builds;
     if (!std::strcmp(name, "forest_builds")) return c->n_forest_builds;
     if (!std::strcmp(name, "device_objects")) return g_device_objects.load();
+    if (!std::strcmp(name, "population_slots")) return c->point.nslots;
     if (!std::strcmp(name, "hybrid_boxes")) return (c->hplan.valid && c->hplan.worthwhile) ? c->hplan.most_boxes : 0;
     if (!std::strcmp(name, "hybrid_passes")) return (c->hplan.valid && c->hplan.worthwhile) ? c->hplan.npass : 0;
     if (!std::strcmp(name, "fine_block")) return (c->hplan.valid && c->hplan.worthwhile && c->hplan.fine.active) ? c->hplan.fine.n : 0;
@@ -533,6 +534,41 @@ int ftte_stellar_beta_table(ftte_ctx *c, const double *a_smc, int nwave, const d
     return rc;
 }
 
+int ftte_stellar_beta_tables(ftte_ctx *c, const double *a_smc, int nwave, const double *wavelength_cm, int nspectrum, int nmetal,
+                             const double *specific_luminosity, int npop, const int *iSpectrum, const double *coefSpectrum,
+                             const int *iMetal, const double *coefMetal, double *total_integral)
+{
+    if (c && c->multi) return check_ready(c, false); // (refuses: a multi-device context routes the diffuse sweep only)
+    if (!c) return FTTE_ERR_ARG;
+    if (!a_smc || !wavelength_cm || !specific_luminosity || nwave < 2 || nspectrum < 2 || nmetal < 2 || npop < 1 || !iSpectrum ||
+        !coefSpectrum || !iMetal || !coefMetal)
+        return fail(c, FTTE_ERR_ARG, "ftte_stellar_beta_tables: bad argument");
+    for (int p = 0; p < npop; ++p)
+        if (iSpectrum[p] < 1 || iSpectrum[p] + 1 > nspectrum || iMetal[p] < 1 || iMetal[p] + 1 > nmetal)
+            return fail(c, FTTE_ERR_ARG, "ftte_stellar_beta_tables: iSpectrum / iMetal of population " + std::to_string(p) + " outside the library");
+    FTTE_HIP(c, hipSetDevice(c->device));
+    return point_stellar_beta_tables(c->point, c->stream, a_smc, nwave, wavelength_cm, nspectrum, nmetal, specific_luminosity, npop,
+                                     iSpectrum, coefSpectrum, iMetal, coefMetal, total_integral, &c->err);
+}
+
+int ftte_set_population_tables(ftte_ctx *c, int npop, const double *tables)
+{
+    if (c && c->multi) return check_ready(c, false); // (refuses: a multi-device context routes the diffuse sweep only)
+    if (!c) return FTTE_ERR_ARG;
+    if (npop < 1 || !tables) return fail(c, FTTE_ERR_ARG, "ftte_set_population_tables: bad argument");
+    FTTE_HIP(c, hipSetDevice(c->device));
+    return point_set_population_tables(c->point, c->stream, npop, tables, &c->err);
+}
+
+int ftte_get_population_tables(ftte_ctx *c, int slot, double *tables)
+{
+    if (c && c->multi) return check_ready(c, false); // (refuses: a multi-device context routes the diffuse sweep only)
+    if (!c) return FTTE_ERR_ARG;
+    if (!tables) return fail(c, FTTE_ERR_ARG, "ftte_get_population_tables: bad argument");
+    FTTE_HIP(c, hipSetDevice(c->device));
+    return point_get_population_tables(c->point, c->stream, slot, tables, &c->err);
+}
+
 int ftte_set_rate_tables(ftte_ctx *c, const double *tables)
 {
     if (c && c->multi) return check_ready(c, false); // (refuses: a multi-device context routes the diffuse sweep only)
@@ -627,7 +663,21 @@ int ftte_point_sources(ftte_ctx *c, int nsrc, const int64_t *src_cell, const dou
     if (highest_pixel_level) *highest_pixel_level = 0;
     if (!nsrc) return FTTE_OK;
     FTTE_HIP(c, hipSetDevice(c->device));
-    return point_trace(c->point, c->stream, c->tree, c->box, nsrc, src_cell, src_ndot, highest_pixel_level, &c->err);
+    return point_trace(c->point, c->stream, c->tree, c->box, nsrc, src_cell, src_ndot, nullptr, highest_pixel_level, nullptr, &c->err);
+}
+
+int ftte_point_sources_populations(ftte_ctx *c, int nsrc, const int64_t *src_cell, const double *src_ndot, const int32_t *src_slot,
+                                   int *highest_pixel_level)
+{
+    int rc = check_ready(c, false);
+    if (rc) return rc;
+    if (nsrc < 0 || (nsrc && (!src_cell || !src_ndot || !src_slot))) return fail(c, FTTE_ERR_ARG, "ftte_point_sources_populations: bad argument");
+    if (!c->point.nslots)
+        return fail(c, FTTE_ERR_STATE, "no population slots: call ftte_stellar_beta_tables or ftte_set_population_tables first");
+    if (highest_pixel_level) std::fill(highest_pixel_level, highest_pixel_level + nsrc, 0);
+    if (!nsrc) return FTTE_OK;
+    FTTE_HIP(c, hipSetDevice(c->device));
+    return point_trace(c->point, c->stream, c->tree, c->box, nsrc, src_cell, src_ndot, src_slot, nullptr, highest_pixel_level, &c->err);
 }
 
 int ftte_point_escape(ftte_ctx *c, int nsrc, double *remaining, double *boundary, double *dust, double *spectrum, double *fraction)

@@ -252,7 +252,9 @@ struct TraceRec {
     int64_t ncell;
     double box;
     const double *medium;  // [ncell][kCellRec]
-    const double *logtab;  // [3][11^4][2] natural logs of the rate tables, (number, heating) pairs
+    const double *logtab;  // [3][11^4][2] natural logs of the rate tables, (number, heating) pairs; with slot_of: slot 0's
+    const int32_t *slot_of; // [sources of this batch] population slot each star reads, or nullptr: all read `logtab`
+    int64_t slot_stride;   // doubles between the slots' log tables
     const double *pixdir;  // [kPixelCount][3] unit vectors of all pixels of levels 1..6
     double rmax[kMaxPixelLevel + 1];
     double *rates;         // [ncell][kCellRec]
@@ -265,7 +267,7 @@ struct TraceRec {
     SplitRec *out;         // rays of this level that split
     int32_t *out_count;
     int32_t out_capacity;
-    int32_t *highest_level;
+    int32_t *highest_level;    // [sources of this batch] highest pixel level each star's rays reached
     int32_t *error;
     unsigned long long *steps; // cell crossings, all rays (instrumentation)
     // escape bookkeeping

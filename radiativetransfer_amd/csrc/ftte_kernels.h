@@ -45,9 +45,10 @@ int launch_amr_levels(const AmrLevelRec &A, const int64_t *tables, int ndepth, h
 int launch_amr_combine(const AmrLevelRec &A, double *J, bool zero_first, hipStream_t stream);
 
 // point sources: table accumulation (P3), logs of user tables, one pixel level of the tracer (P1 + P2)
-int launch_rate_table(const FreqBin *bins, int nbins, double *tables, double *logtab, hipStream_t stream);
+// npop populations side by side: bins[npop][nbins] -> tables[npop][6][11^4], logtab[npop][3][11^4][2], one launch
+int launch_rate_table(const FreqBin *bins, int nbins, int npop, double *tables, double *logtab, hipStream_t stream);
 int launch_rate_lookup(const double *logtab, int dust, int nsample, const double *tau, double *out, hipStream_t stream);
-int launch_log_table(const double *tables, double *logtab, hipStream_t stream);
+int launch_log_table(const double *tables, int npop, double *logtab, hipStream_t stream);
 int launch_point_trace(const TraceRec &T, hipStream_t stream);
 int launch_pack_medium(const double *const field[5], double *packed, long ncell, hipStream_t stream);
 int launch_repack_rates(double *planes, double *packed, long ncell, bool to_packed, hipStream_t stream);

@@ -873,12 +873,21 @@ int launch_amr_combine(const AmrLevelRec &A, double *J, bool zero_first, hipStre
 //   logtab[reaction][idust][i3][i2][i1][2]
 __device__ __forceinline__ size_t logtab_index(int reaction0, int flat) { return ((size_t)reaction0 * kTableSize + flat) * 2; }
 
-// stellarBetaTable's accumulation over frequency bins, one thread per depth tuple (stellarBetaTable.f90:217-285)
+// stellarBetaTable's accumulation over frequency bins, one thread per depth tuple (stellarBetaTable.f90:217-285), for every
+// population of a batch: kTableBlocks workgroups per population, so a workgroup never straddles two and its population is
+// a function of blockIdx alone.  bins[population][nbins], tables[population][6][11^4], logtab[population][3][11^4][2].  The bin
+// index and the population are wave-uniform: the 64 bytes of a bin arrive through the scalar cache, once per wavefront.
+constexpr int kTableBlocks = (kTableSize + 255) / 256, kLogTableBlocks = (3 * kTableSize + 255) / 256;
+
 __global__ void __launch_bounds__(256) rate_table_kernel(const FreqBin *__restrict__ bins, int nbins, double *__restrict__ tables,
                                                          double *__restrict__ logtab)
 {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int pop = blockIdx.x / kTableBlocks;
+    const int t = (blockIdx.x - pop * kTableBlocks) * blockDim.x + threadIdx.x;
     if (t >= kTableSize) return;
+    bins += (size_t)pop * nbins;
+    tables += (size_t)pop * 6 * kTableSize;
+    logtab += (size_t)pop * 6 * kTableSize;
     const int i1 = t % 11, i2 = (t / 11) % 11, i3 = (t / 121) % 11, id = t / 1331;
     // float(idepth)/float(ndepth)*maxOpticalDepth: a single-precision quotient widened, :236-242
     const double d1 = (double)((float)i1 / 10.f) * 10.0, d2 = (double)((float)i2 / 10.f) * 10.0;
@@ -901,10 +910,14 @@ __global__ void __launch_bounds__(256) rate_table_kernel(const FreqBin *__restri
     }
 }
 
+// the logarithms of tables handed over, per population as above
 __global__ void __launch_bounds__(256) log_table_kernel(const double *__restrict__ tables, double *__restrict__ logtab)
 {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int pop = blockIdx.x / kLogTableBlocks;
+    const int t = (blockIdx.x - pop * kLogTableBlocks) * blockDim.x + threadIdx.x;
     if (t >= 3 * kTableSize) return;
+    tables += (size_t)pop * 6 * kTableSize;
+    logtab += (size_t)pop * 6 * kTableSize;
     const int r = t / kTableSize, flat = t - r * kTableSize;
     logtab[logtab_index(r, flat)] = log(tables[r * kTableSize + flat]);
     logtab[logtab_index(r, flat) + 1] = log(tables[(3 + r) * kTableSize + flat]);
@@ -1073,6 +1086,9 @@ __global__ void __launch_bounds__(64) point_trace_kernel(const TraceRec T)
         ndot = R.ndot / 4.0;
     }
     if (pt[0] < 0. || pt[0] > 1. || pt[1] < 0. || pt[1] > 1. || pt[2] < 0. || pt[2] > 1.) { atomicMax(T.error, 2); return; }
+    // the tables of this star's population.  `src` counts from the first star of the batch, like T.escape: T.slot_of and
+    // T.highest_level start there too
+    const double *logtab = T.slot_of ? T.logtab + (size_t)T.slot_of[src] * T.slot_stride : T.logtab;
 
     const double *dir = T.pixdir + 3 * (size_t)(level_off + pixel);
     const double prox = dir[0], proy = dir[1], proz = dir[2];
@@ -1153,20 +1169,20 @@ __global__ void __launch_bounds__(64) point_trace_kernel(const TraceRec T)
         double a, b, ea, eb;
         double *K = T.rates + c * kCellRec; // krate24, krate25, krate26, crate24, crate25, crate26
         if (tau1 != 0.0) {
-            lookup_rates(T.logtab, T.dust, 1, d1, d2, d3, dd, a, ea);
-            lookup_rates(T.logtab, T.dust, 1, d1 + tau1, d2, d3, dd, b, eb);
+            lookup_rates(logtab, T.dust, 1, d1, d2, d3, dd, a, ea);
+            lookup_rates(logtab, T.dust, 1, d1 + tau1, d2, d3, dd, b, eb);
             unsafeAtomicAdd(K + 0, ndot * (a - b));
             unsafeAtomicAdd(K + 3, ndot * (ea - eb));
         }
         if (tau2 != 0.0) {
-            lookup_rates(T.logtab, T.dust, 2, d1, d2, d3, dd, a, ea);
-            lookup_rates(T.logtab, T.dust, 2, d1, d2 + tau2, d3, dd, b, eb);
+            lookup_rates(logtab, T.dust, 2, d1, d2, d3, dd, a, ea);
+            lookup_rates(logtab, T.dust, 2, d1, d2 + tau2, d3, dd, b, eb);
             unsafeAtomicAdd(K + 2, ndot * (a - b));
             unsafeAtomicAdd(K + 5, ndot * (ea - eb));
         }
         if (tau3 != 0.0) {
-            lookup_rates(T.logtab, T.dust, 3, d1, d2, d3, dd, a, ea);
-            lookup_rates(T.logtab, T.dust, 3, d1, d2, d3 + tau3, dd, b, eb);
+            lookup_rates(logtab, T.dust, 3, d1, d2, d3, dd, a, ea);
+            lookup_rates(logtab, T.dust, 3, d1, d2, d3 + tau3, dd, b, eb);
             unsafeAtomicAdd(K + 1, ndot * (a - b));
             unsafeAtomicAdd(K + 4, ndot * (ea - eb));
         }
@@ -1185,7 +1201,7 @@ __global__ void __launch_bounds__(64) point_trace_kernel(const TraceRec T)
     if (!split) return;
 
     // ---- hand the ray over to its four daughters: absoluteCoordinates, :3011-3047
-    atomicMax(T.highest_level, L + 1);
+    atomicMax(T.highest_level + src, L + 1);
     double p[3] = {pt[0], pt[1], pt[2]};
     int c = cell;
     for (int lvl = node_level(T, c); lvl > 0; --lvl) {
@@ -1278,15 +1294,17 @@ int launch_repack_rates(double *planes, double *packed, long ncell, bool to_pack
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-int launch_rate_table(const FreqBin *bins, int nbins, double *tables, double *logtab, hipStream_t stream)
+int launch_rate_table(const FreqBin *bins, int nbins, int npop, double *tables, double *logtab, hipStream_t stream)
 {
-    hipLaunchKernelGGL(rate_table_kernel, dim3((kTableSize + 255) / 256), dim3(256), 0, stream, bins, nbins, tables, logtab);
+    if (npop <= 0) return 0;
+    hipLaunchKernelGGL(rate_table_kernel, dim3((unsigned)npop * kTableBlocks), dim3(256), 0, stream, bins, nbins, tables, logtab);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-int launch_log_table(const double *tables, double *logtab, hipStream_t stream)
+int launch_log_table(const double *tables, int npop, double *logtab, hipStream_t stream)
 {
-    hipLaunchKernelGGL(log_table_kernel, dim3((3 * kTableSize + 255) / 256), dim3(256), 0, stream, tables, logtab);
+    if (npop <= 0) return 0;
+    hipLaunchKernelGGL(log_table_kernel, dim3((unsigned)npop * kLogTableBlocks), dim3(256), 0, stream, tables, logtab);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

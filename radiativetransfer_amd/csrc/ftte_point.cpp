@@ -1,6 +1,7 @@
 // ftte_point.cpp -- host side of the point-source path.  See ftte_point.h.
 #include "ftte_point.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 
@@ -236,66 +237,165 @@ void rmax_table(double *rmax30)
     }
 }
 
-int point_stellar_beta_table(PointState &P, hipStream_t stream, const double *a_smc, int nwave, const double *wavelength,
-                             int nspectrum, int nmetal, const double *spec, int iSpectrum, double cS, int iMetal, double cM,
-                             double *total_integral, std::string *err)
+namespace {
+
+// the frequency grid and the cross-sections on it, stellarBetaTable.f90:27-66: the same for every population
+struct FrequencyGrid { double nu[kFrequencies], s24[kFrequencies], s25[kFrequencies], s26[kFrequencies], sd[kFrequencies]; };
+
+void frequency_grid(const double *a_smc, FrequencyGrid &G)
 {
-    // the frequency grid and the cross-sections on it, stellarBetaTable.f90:27-66
-    static thread_local double nu[kFrequencies], s24[kFrequencies], s25[kFrequencies], s26[kFrequencies], sd[kFrequencies];
     const double freqdel = W(0.02);
     for (int i = 0; i < kFrequencies; ++i) {
-        nu[i] = std::pow(10.0, (double)i * freqdel);
-        const double lambda = c_light() / (nu[i] * ev_to_hz()) * W(1.e8); // Angstrom
-        sd[i] = dust_cross_section(lambda / W(1.e4), a_smc) * W(1.e-22);
-        s24[i] = nu[i] > kHydrogen ? hydrogenic(W(6.3e-18), kHydrogen, nu[i]) : 0.0;
-        s25[i] = nu[i] > kHeII ? hydrogenic(W(1.58e-18), kHeII, nu[i]) : 0.0;
-        s26[i] = nu[i] > kHeI ? W(7.42e-18) * (W(1.66) * std::pow(nu[i] / kHeI, (double)(-2.05f)) -
-                                               W(0.66) * std::pow(nu[i] / kHeI, (double)(-3.05f)))
-                              : 0.0;
+        G.nu[i] = std::pow(10.0, (double)i * freqdel);
+        const double lambda = c_light() / (G.nu[i] * ev_to_hz()) * W(1.e8); // Angstrom
+        G.sd[i] = dust_cross_section(lambda / W(1.e4), a_smc) * W(1.e-22);
+        G.s24[i] = G.nu[i] > kHydrogen ? hydrogenic(W(6.3e-18), kHydrogen, G.nu[i]) : 0.0;
+        G.s25[i] = G.nu[i] > kHeII ? hydrogenic(W(1.58e-18), kHeII, G.nu[i]) : 0.0;
+        G.s26[i] = G.nu[i] > kHeI ? W(7.42e-18) * (W(1.66) * std::pow(G.nu[i] / kHeI, (double)(-2.05f)) -
+                                                   W(0.66) * std::pow(G.nu[i] / kHeI, (double)(-3.05f)))
+                                  : 0.0;
     }
-    // what every depth tuple needs from a frequency bin, :217-232 and :243-246
-    std::vector<FreqBin> bins(kFrequencies - 1);
+}
+
+// what every depth tuple needs from a frequency bin of one population, :217-232 and :243-246; returns totalIntegral
+double population_bins(const FrequencyGrid &G, const double *spec, int nmetal, int nspectrum, int nwave, const double *wavelength,
+                       int iSpectrum, double cS, int iMetal, double cM, FreqBin *bins)
+{
     double total = 0.0;
     const double thr[3] = {kHydrogen, kHeI, kHeII};
     for (int i = 1; i < kFrequencies; ++i) {
-        const double freq = nu[i], delta_nu = nu[i] - nu[i - 1];
+        const double freq = G.nu[i], delta_nu = G.nu[i] - G.nu[i - 1];
         const double lum = stellar_population(spec, nmetal, nspectrum, nwave, wavelength, iSpectrum, cS, iMetal, cM, freq);
         FreqBin &B = bins[i - 1];
         B.dtmp = lum / (freq * ev_to_erg()) * delta_nu * ev_to_hz();
         if (freq >= kHydrogen) total = total + B.dtmp;
-        B.r24 = s24[i] / W(6.3e-18);
-        B.r26 = s26[i] / W(7.42e-18);
-        B.r25 = s25[i] / W(1.58e-18);
-        B.rdust = sd[i] / W(5.4116737e-22);
+        B.r24 = G.s24[i] / W(6.3e-18);
+        B.r26 = G.s26[i] / W(7.42e-18);
+        B.r25 = G.s25[i] / W(1.58e-18);
+        B.rdust = G.sd[i] / W(5.4116737e-22);
         for (int r = 0; r < 3; ++r) B.excess[r] = freq >= thr[r] ? (freq - thr[r]) * ev_to_erg() : -1.0;
     }
+    return total;
+}
+
+// the output energies and the cross-sections on them, stellarBetaTable.f90:119-152 (nenergy = 300 between lowerEnergy and
+// upperEnergy, definitionsModule.f90:290-292)
+int output_sigma(PointState &P, hipStream_t stream, const double *a_smc, std::string *err)
+{
+    double sigma[4 * kOutputEnergies];
+    const double lower = kHydrogen, upper = W(10.) * kHydrogen; // lowerEnergy, upperEnergy
+    for (int ie = 1; ie <= kOutputEnergies; ++ie) {
+        // float(ienergy-1)/float(nenergy-1) is a single-precision quotient, :122
+        const double freq = lower * std::exp((double)((float)(ie - 1) / (float)(kOutputEnergies - 1)) * (std::log(upper) - std::log(lower)));
+        const double lambda = c_light() / (freq * ev_to_hz()) * W(1.e8);
+        sigma[3 * kOutputEnergies + ie - 1] = dust_cross_section(lambda / W(1.e4), a_smc) * W(1.e-22);
+        sigma[0 * kOutputEnergies + ie - 1] = freq > kHydrogen ? hydrogenic(W(6.3e-18), kHydrogen, freq) : freq == kHydrogen ? W(6.3e-18) : 0.0;
+        sigma[1 * kOutputEnergies + ie - 1] = freq > kHeII ? hydrogenic(W(1.58e-18), kHeII, freq) : 0.0;
+        sigma[2 * kOutputEnergies + ie - 1] = freq > kHeI ? W(7.42e-18) * (W(1.66) * std::pow(freq / kHeI, (double)(-2.05f)) -
+                                                                           W(0.66) * std::pow(freq / kHeI, (double)(-3.05f)))
+                                                          : 0.0;
+    }
+    return point_set_output_sigma(P, stream, sigma, err);
+}
+
+constexpr size_t kSlotDoubles = (size_t)6 * kTableSize; // one slot's tables, and as many logarithms
+
+// Room for npop slots.  What is missing is compared with the free device memory (plus what the buffers to be replaced give back)
+// before anything is released, so that this refusal leaves the slots held as they were.  From the moment a slot buffer is
+// replaced no slot is held, until the caller has filled the new ones: also where the allocation itself or a later step fails.
+int reserve_slots(PointState &P, int npop, bool with_bins, std::string *err)
+{
+    const size_t want = (size_t)npop * kSlotDoubles, want_bins = with_bins ? (size_t)npop * kFrequencies : 0;
+    size_t need = 0, back = 0;
+    if (P.slot_tables.capacity() < want) { need += want * sizeof(double); back += P.slot_tables.capacity() * sizeof(double); }
+    if (P.slot_logtab.capacity() < want) { need += want * sizeof(double); back += P.slot_logtab.capacity() * sizeof(double); }
+    if (P.bins.capacity() < want_bins) { need += want_bins * sizeof(FreqBin); back += P.bins.capacity() * sizeof(FreqBin); }
+    if (need) {
+        size_t free_bytes = 0, total_bytes = 0;
+        POINT_HIP(hipMemGetInfo(&free_bytes, &total_bytes));
+        if (need > free_bytes + back) {
+            *err = "population slots: " + std::to_string(npop) + " slots need " + std::to_string(need) + " bytes of device memory, " +
+                   std::to_string(free_bytes + back) + " are free";
+            return FTTE_ERR_MEMORY;
+        }
+    }
+    if (P.slot_tables.capacity() < want || P.slot_logtab.capacity() < want) P.nslots = 0;
+    if (P.slot_tables.reserve(want) != hipSuccess || P.slot_logtab.reserve(want) != hipSuccess || P.bins.reserve(want_bins) != hipSuccess) {
+        (void)hipGetLastError();
+        P.slot_tables.reset(); P.slot_logtab.reset();
+        P.nslots = 0;
+        *err = "population slots: " + std::to_string(need) + " bytes of device memory could not be allocated";
+        return FTTE_ERR_MEMORY;
+    }
+    return 0;
+}
+
+} // namespace
+
+int point_stellar_beta_table(PointState &P, hipStream_t stream, const double *a_smc, int nwave, const double *wavelength,
+                             int nspectrum, int nmetal, const double *spec, int iSpectrum, double cS, int iMetal, double cM,
+                             double *total_integral, std::string *err)
+{
+    static thread_local FrequencyGrid G;
+    frequency_grid(a_smc, G);
+    std::vector<FreqBin> bins(kFrequencies - 1);
+    const double total = population_bins(G, spec, nmetal, nspectrum, nwave, wavelength, iSpectrum, cS, iMetal, cM, bins.data());
     if (total_integral) *total_integral = total;
 
     int rc;
-    {   // the output energies and the cross-sections on them, stellarBetaTable.f90:119-152 (nenergy = 300 between lowerEnergy
-        // and upperEnergy, definitionsModule.f90:290-292)
-        double sigma[4 * kOutputEnergies];
-        const double lower = kHydrogen, upper = W(10.) * kHydrogen; // lowerEnergy, upperEnergy
-        for (int ie = 1; ie <= kOutputEnergies; ++ie) {
-            // float(ienergy-1)/float(nenergy-1) is a single-precision quotient, :122
-            const double freq = lower * std::exp((double)((float)(ie - 1) / (float)(kOutputEnergies - 1)) * (std::log(upper) - std::log(lower)));
-            const double lambda = c_light() / (freq * ev_to_hz()) * W(1.e8);
-            sigma[3 * kOutputEnergies + ie - 1] = dust_cross_section(lambda / W(1.e4), a_smc) * W(1.e-22);
-            sigma[0 * kOutputEnergies + ie - 1] = freq > kHydrogen ? hydrogenic(W(6.3e-18), kHydrogen, freq) : freq == kHydrogen ? W(6.3e-18) : 0.0;
-            sigma[1 * kOutputEnergies + ie - 1] = freq > kHeII ? hydrogenic(W(1.58e-18), kHeII, freq) : 0.0;
-            sigma[2 * kOutputEnergies + ie - 1] = freq > kHeI ? W(7.42e-18) * (W(1.66) * std::pow(freq / kHeI, (double)(-2.05f)) -
-                                                                               W(0.66) * std::pow(freq / kHeI, (double)(-3.05f)))
-                                                              : 0.0;
-        }
-        if ((rc = point_set_output_sigma(P, stream, sigma, err))) return rc;
-    }
-    POINT_HIP(P.tables.reserve((size_t)6 * kTableSize));
-    POINT_HIP(P.logtab.reserve((size_t)6 * kTableSize));
+    if ((rc = output_sigma(P, stream, a_smc, err))) return rc;
+    POINT_HIP(P.tables.reserve(kSlotDoubles));
+    POINT_HIP(P.logtab.reserve(kSlotDoubles));
     POINT_HIP(P.bins.reserve((size_t)kFrequencies));
     POINT_HIP(hipMemcpyAsync(P.bins, bins.data(), sizeof(FreqBin) * bins.size(), hipMemcpyHostToDevice, stream));
-    if (launch_rate_table(P.bins, (int)bins.size(), P.tables, P.logtab, stream)) { *err = "rate table kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
+    if (launch_rate_table(P.bins, (int)bins.size(), 1, P.tables, P.logtab, stream)) { *err = "rate table kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
     POINT_HIP(hipStreamSynchronize(stream)); // `bins` leaves scope
     P.tables_ready = true;
+    return 0;
+}
+
+int point_stellar_beta_tables(PointState &P, hipStream_t stream, const double *a_smc, int nwave, const double *wavelength,
+                              int nspectrum, int nmetal, const double *spec, int npop, const int *iSpectrum, const double *cS,
+                              const int *iMetal, const double *cM, double *total_integral, std::string *err)
+{
+    static thread_local FrequencyGrid G;
+    frequency_grid(a_smc, G);
+    const int nbins = kFrequencies - 1;
+    std::vector<FreqBin> bins((size_t)npop * nbins);
+    for (int p = 0; p < npop; ++p) {
+        const double total = population_bins(G, spec, nmetal, nspectrum, nwave, wavelength, iSpectrum[p], cS[p], iMetal[p], cM[p],
+                                             bins.data() + (size_t)p * nbins);
+        if (total_integral) total_integral[p] = total;
+    }
+    int rc;
+    if ((rc = reserve_slots(P, npop, true, err))) return rc;
+    if ((rc = output_sigma(P, stream, a_smc, err))) return rc;
+    P.nslots = 0;
+    POINT_HIP(hipMemcpyAsync(P.bins, bins.data(), sizeof(FreqBin) * bins.size(), hipMemcpyHostToDevice, stream));
+    if (launch_rate_table(P.bins, nbins, npop, P.slot_tables, P.slot_logtab, stream)) { *err = "rate table kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
+    POINT_HIP(hipStreamSynchronize(stream)); // `bins` leaves scope
+    P.nslots = npop;
+    return 0;
+}
+
+int point_set_population_tables(PointState &P, hipStream_t stream, int npop, const double *tables, std::string *err)
+{
+    int rc;
+    if ((rc = reserve_slots(P, npop, false, err))) return rc;
+    P.nslots = 0;
+    POINT_HIP(hipMemcpyAsync(P.slot_tables, tables, sizeof(double) * kSlotDoubles * npop, hipMemcpyHostToDevice, stream));
+    if (launch_log_table(P.slot_tables, npop, P.slot_logtab, stream)) { *err = "table kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
+    POINT_HIP(hipStreamSynchronize(stream));
+    P.nslots = npop;
+    return 0;
+}
+
+int point_get_population_tables(PointState &P, hipStream_t stream, int slot, double *tables, std::string *err)
+{
+    if (!P.nslots) { *err = "no population slots: call ftte_stellar_beta_tables or ftte_set_population_tables first"; return FTTE_ERR_STATE; }
+    if (slot < 0 || slot >= P.nslots) { *err = "ftte_get_population_tables: slot " + std::to_string(slot) + " outside 0.." + std::to_string(P.nslots - 1); return FTTE_ERR_ARG; }
+    POINT_HIP(hipMemcpyAsync(tables, P.slot_tables + (size_t)slot * kSlotDoubles, sizeof(double) * kSlotDoubles, hipMemcpyDeviceToHost, stream));
+    POINT_HIP(hipStreamSynchronize(stream));
     return 0;
 }
 
@@ -319,7 +419,7 @@ int point_set_tables(PointState &P, hipStream_t stream, const double *tables, st
     POINT_HIP(P.tables.reserve((size_t)6 * kTableSize));
     POINT_HIP(P.logtab.reserve((size_t)6 * kTableSize));
     POINT_HIP(hipMemcpyAsync(P.tables, tables, sizeof(double) * 6 * kTableSize, hipMemcpyHostToDevice, stream));
-    if (launch_log_table(P.tables, P.logtab, stream)) { *err = "table kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
+    if (launch_log_table(P.tables, 1, P.logtab, stream)) { *err = "table kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
     POINT_HIP(hipStreamSynchronize(stream));
     P.tables_ready = true;
     return 0;
@@ -399,9 +499,10 @@ int point_set_rates(PointState &P, hipStream_t stream, int64_t ncell, const doub
 }
 
 int point_trace(PointState &P, hipStream_t stream, const AmrTree &tree, double box, int nsrc, const int64_t *src_cell,
-                const double *src_ndot, int *highest_pixel_level, std::string *err)
+                const double *src_ndot, const int32_t *src_slot, int *highest_pixel_level, int *highest_per_star, std::string *err)
 {
-    if (!P.tables_ready) { *err = "no rate tables: call ftte_stellar_beta_table or ftte_set_rate_tables first"; return FTTE_ERR_STATE; }
+    if (!src_slot && !P.tables_ready) { *err = "no rate tables: call ftte_stellar_beta_table or ftte_set_rate_tables first"; return FTTE_ERR_STATE; }
+    if (src_slot && !P.nslots) { *err = "no population slots: call ftte_stellar_beta_tables or ftte_set_population_tables first"; return FTTE_ERR_STATE; }
     if (!P.medium_ready || P.medium_cells != tree.ncell) { *err = "no medium: call ftte_set_medium after ftte_set_grid"; return FTTE_ERR_STATE; }
     int rc;
     if (!P.rates || P.rates_cells != tree.ncell)
@@ -464,6 +565,19 @@ int point_trace(PointState &P, hipStream_t stream, const AmrTree &tree, double b
         if (src_cell[s] < 0 || src_cell[s] >= tree.ncell) { *err = "ftte_point_sources: source cell outside the cell array"; return FTTE_ERR_ARG; }
         node_of[s] = tree.refined() ? P.node_of_leaf[(size_t)src_cell[s]] : (int32_t)src_cell[s];
     }
+    if (src_slot) {
+        for (int s = 0; s < nsrc; ++s)
+            if (src_slot[s] < 0 || src_slot[s] >= P.nslots) {
+                *err = "ftte_point_sources_populations: star " + std::to_string(s) + " names slot " + std::to_string(src_slot[s]) +
+                       ", outside 0.." + std::to_string(P.nslots - 1);
+                return FTTE_ERR_ARG;
+            }
+        // all stars of the call at once; a batch reads from its first star on, as it does in the escape records
+        POINT_HIP(P.src_slot.reserve((size_t)nsrc));
+        POINT_HIP(hipMemcpyAsync(P.src_slot, src_slot, sizeof(int32_t) * nsrc, hipMemcpyHostToDevice, stream));
+    }
+    POINT_HIP(P.src_highest.reserve((size_t)nsrc));
+    POINT_HIP(hipMemsetAsync(P.src_highest, 0, sizeof(int32_t) * (size_t)nsrc, stream)); // :1266
 
     POINT_HIP(P.escape.reserve((size_t)nsrc * kEscapeRec));
     POINT_HIP(hipMemsetAsync(P.escape, 0, sizeof(double) * (size_t)nsrc * kEscapeRec, stream)); // :1267-1270
@@ -479,39 +593,40 @@ int point_trace(PointState &P, hipStream_t stream, const AmrTree &tree, double b
     T.node = tree.refined() ? P.node : nullptr;
     T.n = tree.n; T.dust = P.dust; T.ncell = tree.ncell; T.box = box;
     T.medium = P.packed;
-    T.logtab = P.logtab; T.pixdir = P.pixdir;
+    T.logtab = src_slot ? P.slot_logtab : P.logtab; T.pixdir = P.pixdir;
+    T.slot_stride = (int64_t)6 * kTableSize;
     T.rmax[0] = 0.0;
     for (int L = 1; L <= kMaxPixelLevel; ++L) T.rmax[L] = P.rmax[L - 1];
     T.rates = P.rates;
     T.src_node = P.src_node; T.src_ndot = P.src_ndot;
-    T.out_count = P.counters; T.highest_level = P.counters + 1; T.error = P.counters + 2;
+    T.out_count = P.counters; T.error = P.counters + 2;
     T.steps = reinterpret_cast<unsigned long long *>(P.counters + 4);
     T.out_capacity = (int32_t)std::min(P.queue[0].capacity(), P.queue[1].capacity());
 
     int32_t host_counters[4] = {0, 0, 0, 0};
-    int highest = 0;
     for (int s0 = 0; s0 < nsrc; s0 += batch_max) {
         const int ns = nsrc - s0 < batch_max ? nsrc - s0 : batch_max;
         POINT_HIP(hipMemcpyAsync(P.src_node, node_of.data() + s0, sizeof(int32_t) * ns, hipMemcpyHostToDevice, stream));
         POINT_HIP(hipMemcpyAsync(P.src_ndot, src_ndot + s0, sizeof(double) * ns, hipMemcpyHostToDevice, stream));
         int32_t nrec = 0;
+        // R.src counts from the batch's first star: everything indexed by it starts at s0
         T.escape = P.escape + (size_t)s0 * kEscapeRec;
+        T.slot_of = src_slot ? P.src_slot + s0 : nullptr;
+        T.highest_level = P.src_highest + s0;
         for (int L = 1; L <= kMaxPixelLevel; ++L) {
             T.pixel_level = L;
             T.nrays = L == 1 ? 12 * ns : 4 * nrec;
             if (T.nrays == 0) break;
             T.in = P.queue[L & 1];
             T.out = P.queue[(L + 1) & 1];
-            // queue length back to zero, highest level and error carried over
+            // queue length back to zero, the error carried over
             host_counters[0] = 0;
-            host_counters[1] = highest;
-            POINT_HIP(hipMemcpyAsync(P.counters, host_counters, sizeof(int32_t) * 2, hipMemcpyHostToDevice, stream));
+            POINT_HIP(hipMemcpyAsync(P.counters, host_counters, sizeof(int32_t), hipMemcpyHostToDevice, stream));
             if (L == 1 && s0 == 0) POINT_HIP(hipMemsetAsync(P.counters + 2, 0, sizeof(int32_t) * 6, stream));
             if (launch_point_trace(T, stream)) { *err = "tracer kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
             POINT_HIP(hipMemcpyAsync(host_counters, P.counters, sizeof(int32_t) * 4, hipMemcpyDeviceToHost, stream));
             POINT_HIP(hipStreamSynchronize(stream));
             nrec = host_counters[0];
-            highest = host_counters[1];
             if (host_counters[2]) {
                 static const char *what[] = {"", "continuation cell outside the base grid", "error in checkPoint (start)",
                                              "error in checkPoint", "ray did not terminate", "split queue overflow"};
@@ -526,9 +641,12 @@ int point_trace(PointState &P, hipStream_t stream, const AmrTree &tree, double b
     P.escape_host.resize((size_t)nsrc * kEscapeRec);
     P.escape_ndot.assign(src_ndot, src_ndot + nsrc);
     POINT_HIP(hipMemcpyAsync(P.escape_host.data(), P.escape, sizeof(double) * (size_t)nsrc * kEscapeRec, hipMemcpyDeviceToHost, stream));
+    std::vector<int32_t> highest(nsrc);
+    POINT_HIP(hipMemcpyAsync(highest.data(), P.src_highest, sizeof(int32_t) * (size_t)nsrc, hipMemcpyDeviceToHost, stream));
     POINT_HIP(hipStreamSynchronize(stream));
     P.ray_steps = (long long)steps;
-    if (highest_pixel_level) *highest_pixel_level = highest;
+    if (highest_pixel_level) *highest_pixel_level = *std::max_element(highest.begin(), highest.end());
+    if (highest_per_star) std::copy(highest.begin(), highest.end(), highest_per_star);
     return 0;
 }
 

@@ -34,7 +34,10 @@ struct PointState {
     // [6][11^4] rate tables and their logarithms
     DeviceBuffer<double> tables, logtab;
     bool tables_ready = false;
-    DeviceBuffer<FreqBin> bins;
+    // population slots: nslots table sets side by side, [nslots][6][11^4] each, for stars that name the slot they read
+    DeviceBuffer<double> slot_tables, slot_logtab;
+    int nslots = 0;
+    DeviceBuffer<FreqBin> bins; // [populations of the call][kFrequencies - 1]
     DeviceBuffer<double> pixdir; // [kPixelCount][3]
     double rmax[30];
     // [ncell][kCellRec] krate24, krate25, krate26, crate24, crate25, crate26, 0, 0: what the tracer adds into
@@ -43,9 +46,10 @@ struct PointState {
     DeviceBuffer<double> rate_planes; // [6][ncell]: the layout of the interface, filled on request
     // tracer scratch
     DeviceBuffer<SplitRec> queue[2];
-    DeviceBuffer<int32_t> counters; // [0] queue length, [1] highest pixel level, [2] error, [4..5] 64-bit count of cell crossings
+    DeviceBuffer<int32_t> counters; // [0] queue length, [2] error, [4..5] 64-bit count of cell crossings
     long long ray_steps = 0;     // of the last trace
     DeviceBuffer<int32_t> src_node;
+    DeviceBuffer<int32_t> src_slot, src_highest; // [stars of the call]: the slot each reads, the highest pixel level each reached
     DeviceBuffer<double> src_ndot;
     DeviceBuffer<double> sample_in, sample_out;
     // escape bookkeeping of the last trace (startNewLongRay, equiSources.f90:3198-3233, 3336-3345): per star ndotRemaining[7],
@@ -81,6 +85,13 @@ void rmax_table(double *rmax30);
 int point_stellar_beta_table(PointState &P, hipStream_t stream, const double *a_smc, int nwave, const double *wavelength,
                              int nspectrum, int nmetal, const double *spec, int iSpectrum, double coefSpectrum, int iMetal,
                              double coefMetal, double *total_integral, std::string *err);
+// npop populations into slots 0..npop-1 (earlier slots are replaced): the host work of point_stellar_beta_table per population,
+// grid and cross-sections once, one launch for all tables; total_integral[npop] may be null
+int point_stellar_beta_tables(PointState &P, hipStream_t stream, const double *a_smc, int nwave, const double *wavelength,
+                              int nspectrum, int nmetal, const double *spec, int npop, const int *iSpectrum, const double *coefSpectrum,
+                              const int *iMetal, const double *coefMetal, double *total_integral, std::string *err);
+int point_set_population_tables(PointState &P, hipStream_t stream, int npop, const double *tables, std::string *err);
+int point_get_population_tables(PointState &P, hipStream_t stream, int slot, double *tables, std::string *err);
 int point_set_tables(PointState &P, hipStream_t stream, const double *tables, std::string *err);
 int point_get_tables(PointState &P, hipStream_t stream, double *tables, std::string *err);
 int point_lookup(PointState &P, hipStream_t stream, int dust, int nsample, const double *tau, double *rates, std::string *err);
@@ -90,8 +101,10 @@ int point_zero_rates(PointState &P, hipStream_t stream, int64_t ncell, std::stri
 // rates in the interface's layout [6][ncell], in device memory (valid until the next trace)
 int point_rate_planes(PointState &P, hipStream_t stream, double **planes, std::string *err);
 int point_set_rates(PointState &P, hipStream_t stream, int64_t ncell, const double *planes_host, std::string *err);
+// src_slot[nsrc]: the population slot each star reads, or null: all read the current tables.  highest_pixel_level: the maximum
+// over the stars; highest_per_star[nsrc]: each star's own.  Either may be null.
 int point_trace(PointState &P, hipStream_t stream, const AmrTree &tree, double box, int nsrc, const int64_t *src_cell,
-                const double *src_ndot, int *highest_pixel_level, std::string *err);
+                const double *src_ndot, const int32_t *src_slot, int *highest_pixel_level, int *highest_per_star, std::string *err);
 // outputSigma24, 25, 26, Dust [4][300] (absolute cross-sections, as the reference's module arrays hold them)
 int point_set_output_sigma(PointState &P, hipStream_t stream, const double *sigma, std::string *err);
 
