@@ -1,6 +1,7 @@
 // ftte_api.cpp -- the C ABI of include/ftte.h: context life cycle, grid and field setters, options, the sweep entry points, point
-// sources, equilibrium, host helpers.  The work behind them: ftte_plan.cpp (planners), ftte_sweeps.cpp (launch sequences),
-// ftte_hybrid.cpp (refined cell arrays), ftte_host_arrays.cpp (PCIe), ftte_point.cpp, ftte_amr.cpp, ftte_ingest.cpp.
+// sources, host helpers; the entry points that read or write the species medium are in ftte_chem.cpp.  The work behind them:
+// ftte_plan.cpp (planners), ftte_sweeps.cpp (launch sequences), ftte_hybrid.cpp (refined cell arrays), ftte_host_arrays.cpp (PCIe),
+// ftte_point.cpp, ftte_amr.cpp, ftte_ingest.cpp.
 //
 // There is no CPU fallback: every entry point that computes on the grid needs a HIP device and fails with FTTE_ERR_NO_DEVICE
 // otherwise.
@@ -17,6 +18,12 @@ int fail(ftte_ctx *c, int code, const std::string &msg)
     if (c) c->err = msg;
     else g_create_error = msg;
     return code;
+}
+
+int check_single(ftte_ctx *c)
+{
+    if (c && c->multi) return check_ready(c, false); // (refuses: a multi-device context routes the diffuse sweep only)
+    return c ? FTTE_OK : FTTE_ERR_ARG;
 }
 
 int fold_status(int rc)
@@ -115,8 +122,9 @@ int ftte_set_grid(ftte_ctx *c, int nx, int ny, int nz, int64_t ncell, const int3
     free_forests(c);
     free_hybrid(c);
     c->d_leaf_of_base.reset();
+    c->gas.drop();
     c->point.drop_grid();
-    c->drop_chem_grid();
+    c->chem.drop_grid();
     c->leaf_level.assign(level, level + ncell);
     c->n = nx; c->ncell = ncell; c->box = box_cm; c->grid_set = true;
     c->kappa.invalidate();
@@ -427,7 +435,7 @@ long long ftte_counter(const ftte_ctx *c, const char *name)
     if (!std::strcmp(name, "plan_builds")) return c->n_plan_builds;
     if (!std::strcmp(name, "forest_builds")) return c->n_forest_builds;
     if (!std::strcmp(name, "device_objects")) return g_device_objects.load();
-    if (!std::strcmp(name, "population_slots")) return c->point.nslots;
+    if (!std::strcmp(name, "population_slots")) return c->point.slots.count;
     if (!std::strcmp(name, "hybrid_boxes")) return (c->hplan.valid && c->hplan.worthwhile) ? c->hplan.most_boxes : 0;
     if (!std::strcmp(name, "hybrid_passes")) return (c->hplan.valid && c->hplan.worthwhile) ? c->hplan.npass : 0;
     if (!std::strcmp(name, "fine_block")) return (c->hplan.valid && c->hplan.worthwhile && c->hplan.fine.active) ? c->hplan.fine.n : 0;
@@ -522,24 +530,23 @@ int ftte_stellar_beta_table(ftte_ctx *c, const double *a_smc, int nwave, const d
                             const double *specific_luminosity, int iSpectrum, double coefSpectrum, int iMetal, double coefMetal,
                             double *total_integral)
 {
-    if (c && c->multi) return check_ready(c, false); // (refuses: a multi-device context routes the diffuse sweep only)
-    if (!c) return FTTE_ERR_ARG;
+    int rc = check_single(c);
+    if (rc) return rc;
     if (!a_smc || !wavelength_cm || !specific_luminosity || nwave < 2 || nspectrum < 2 || nmetal < 2)
         return fail(c, FTTE_ERR_ARG, "ftte_stellar_beta_table: bad argument");
     if (iSpectrum < 1 || iSpectrum + 1 > nspectrum || iMetal < 1 || iMetal + 1 > nmetal)
         return fail(c, FTTE_ERR_ARG, "ftte_stellar_beta_table: iSpectrum / iMetal outside the library");
     FTTE_HIP(c, hipSetDevice(c->device));
-    const int rc = point_stellar_beta_table(c->point, c->stream, a_smc, nwave, wavelength_cm, nspectrum, nmetal, specific_luminosity,
-                                            iSpectrum, coefSpectrum, iMetal, coefMetal, total_integral, &c->err);
-    return rc;
+    return point_stellar_beta_table(c->point, c->stream, a_smc, nwave, wavelength_cm, nspectrum, nmetal, specific_luminosity, iSpectrum,
+                                    coefSpectrum, iMetal, coefMetal, total_integral, &c->err);
 }
 
 int ftte_stellar_beta_tables(ftte_ctx *c, const double *a_smc, int nwave, const double *wavelength_cm, int nspectrum, int nmetal,
                              const double *specific_luminosity, int npop, const int *iSpectrum, const double *coefSpectrum,
                              const int *iMetal, const double *coefMetal, double *total_integral)
 {
-    if (c && c->multi) return check_ready(c, false); // (refuses: a multi-device context routes the diffuse sweep only)
-    if (!c) return FTTE_ERR_ARG;
+    int rc = check_single(c);
+    if (rc) return rc;
     if (!a_smc || !wavelength_cm || !specific_luminosity || nwave < 2 || nspectrum < 2 || nmetal < 2 || npop < 1 || !iSpectrum ||
         !coefSpectrum || !iMetal || !coefMetal)
         return fail(c, FTTE_ERR_ARG, "ftte_stellar_beta_tables: bad argument");
@@ -553,8 +560,8 @@ int ftte_stellar_beta_tables(ftte_ctx *c, const double *a_smc, int nwave, const 
 
 int ftte_set_population_tables(ftte_ctx *c, int npop, const double *tables)
 {
-    if (c && c->multi) return check_ready(c, false); // (refuses: a multi-device context routes the diffuse sweep only)
-    if (!c) return FTTE_ERR_ARG;
+    int rc = check_single(c);
+    if (rc) return rc;
     if (npop < 1 || !tables) return fail(c, FTTE_ERR_ARG, "ftte_set_population_tables: bad argument");
     FTTE_HIP(c, hipSetDevice(c->device));
     return point_set_population_tables(c->point, c->stream, npop, tables, &c->err);
@@ -562,17 +569,21 @@ int ftte_set_population_tables(ftte_ctx *c, int npop, const double *tables)
 
 int ftte_get_population_tables(ftte_ctx *c, int slot, double *tables)
 {
-    if (c && c->multi) return check_ready(c, false); // (refuses: a multi-device context routes the diffuse sweep only)
-    if (!c) return FTTE_ERR_ARG;
+    int rc = check_single(c);
+    if (rc) return rc;
     if (!tables) return fail(c, FTTE_ERR_ARG, "ftte_get_population_tables: bad argument");
+    const TableSets &S = c->point.slots;
+    if (!S.count) return fail(c, FTTE_ERR_STATE, "no population slots: call ftte_stellar_beta_tables or ftte_set_population_tables first");
+    if (slot < 0 || slot >= S.count)
+        return fail(c, FTTE_ERR_ARG, "ftte_get_population_tables: slot " + std::to_string(slot) + " outside 0.." + std::to_string(S.count - 1));
     FTTE_HIP(c, hipSetDevice(c->device));
-    return point_get_population_tables(c->point, c->stream, slot, tables, &c->err);
+    return point_get_tables(S, c->stream, slot, tables, &c->err);
 }
 
 int ftte_set_rate_tables(ftte_ctx *c, const double *tables)
 {
-    if (c && c->multi) return check_ready(c, false); // (refuses: a multi-device context routes the diffuse sweep only)
-    if (!c) return FTTE_ERR_ARG;
+    int rc = check_single(c);
+    if (rc) return rc;
     if (!tables) return fail(c, FTTE_ERR_ARG, "ftte_set_rate_tables: bad argument");
     FTTE_HIP(c, hipSetDevice(c->device));
     return point_set_tables(c->point, c->stream, tables, &c->err);
@@ -580,17 +591,18 @@ int ftte_set_rate_tables(ftte_ctx *c, const double *tables)
 
 int ftte_get_rate_tables(ftte_ctx *c, double *tables)
 {
-    if (c && c->multi) return check_ready(c, false); // (refuses: a multi-device context routes the diffuse sweep only)
-    if (!c) return FTTE_ERR_ARG;
+    int rc = check_single(c);
+    if (rc) return rc;
     if (!tables) return fail(c, FTTE_ERR_ARG, "ftte_get_rate_tables: bad argument");
+    if (!c->point.current.count) return fail(c, FTTE_ERR_STATE, "no rate tables: call ftte_stellar_beta_table or ftte_set_rate_tables first");
     FTTE_HIP(c, hipSetDevice(c->device));
-    return point_get_tables(c->point, c->stream, tables, &c->err);
+    return point_get_tables(c->point.current, c->stream, 0, tables, &c->err);
 }
 
 int ftte_get_rates_hydrogen_helium(ftte_ctx *c, int dust_approximation, int nsample, const double *tau, double *rates)
 {
-    if (c && c->multi) return check_ready(c, false); // (refuses: a multi-device context routes the diffuse sweep only)
-    if (!c) return FTTE_ERR_ARG;
+    int rc = check_single(c);
+    if (rc) return rc;
     if (nsample < 0 || (nsample && (!tau || !rates)) || dust_approximation < 0 || dust_approximation > 2)
         return fail(c, FTTE_ERR_ARG, "ftte_get_rates_hydrogen_helium: bad argument");
     if (!nsample) return FTTE_OK;
@@ -601,14 +613,13 @@ int ftte_get_rates_hydrogen_helium(ftte_ctx *c, int dust_approximation, int nsam
 static int set_medium(ftte_ctx *c, const double *HI, const double *HeI, const double *HeII, const double *rho, const double *abun2,
                       int dust, bool on_device, const char *who)
 {
-    if (c && c->multi) return check_ready(c, false); // (refuses: a multi-device context routes the diffuse sweep only)
     int rc = check_ready(c, false);
     if (rc) return rc;
     if (!HI || !HeI || !HeII || dust < 0 || dust > 2) return fail(c, FTTE_ERR_ARG, std::string(who) + ": bad argument");
     if ((dust >= 1 && !abun2) || (dust == 2 && !rho)) return fail(c, FTTE_ERR_ARG, std::string(who) + ": this dust approximation needs abun2 (and rho)");
     FTTE_HIP(c, hipSetDevice(c->device));
     const double *const field[5] = {HI, HeI, HeII, rho, abun2};
-    return point_set_medium(c->point, c->stream, c->ncell, field, on_device, dust, &c->err);
+    return point_set_medium(c->gas, c->stream, c->ncell, field, on_device, dust, &c->err);
 }
 
 int ftte_set_medium(ftte_ctx *c, const double *HI, const double *HeI, const double *HeII, const double *rho, const double *abun2,
@@ -663,7 +674,7 @@ int ftte_point_sources(ftte_ctx *c, int nsrc, const int64_t *src_cell, const dou
     if (highest_pixel_level) *highest_pixel_level = 0;
     if (!nsrc) return FTTE_OK;
     FTTE_HIP(c, hipSetDevice(c->device));
-    return point_trace(c->point, c->stream, c->tree, c->box, nsrc, src_cell, src_ndot, nullptr, highest_pixel_level, nullptr, &c->err);
+    return point_trace(c->point, c->gas, c->stream, c->tree, c->box, nsrc, src_cell, src_ndot, nullptr, highest_pixel_level, nullptr, &c->err);
 }
 
 int ftte_point_sources_populations(ftte_ctx *c, int nsrc, const int64_t *src_cell, const double *src_ndot, const int32_t *src_slot,
@@ -672,18 +683,18 @@ int ftte_point_sources_populations(ftte_ctx *c, int nsrc, const int64_t *src_cel
     int rc = check_ready(c, false);
     if (rc) return rc;
     if (nsrc < 0 || (nsrc && (!src_cell || !src_ndot || !src_slot))) return fail(c, FTTE_ERR_ARG, "ftte_point_sources_populations: bad argument");
-    if (!c->point.nslots)
+    if (!c->point.slots.count)
         return fail(c, FTTE_ERR_STATE, "no population slots: call ftte_stellar_beta_tables or ftte_set_population_tables first");
     if (highest_pixel_level) std::fill(highest_pixel_level, highest_pixel_level + nsrc, 0);
     if (!nsrc) return FTTE_OK;
     FTTE_HIP(c, hipSetDevice(c->device));
-    return point_trace(c->point, c->stream, c->tree, c->box, nsrc, src_cell, src_ndot, src_slot, nullptr, highest_pixel_level, &c->err);
+    return point_trace(c->point, c->gas, c->stream, c->tree, c->box, nsrc, src_cell, src_ndot, src_slot, nullptr, highest_pixel_level, &c->err);
 }
 
 int ftte_point_escape(ftte_ctx *c, int nsrc, double *remaining, double *boundary, double *dust, double *spectrum, double *fraction)
 {
-    if (c && c->multi) return check_ready(c, false); // (refuses: a multi-device context routes the diffuse sweep only)
-    if (!c) return FTTE_ERR_ARG;
+    int rc = check_single(c);
+    if (rc) return rc;
     const PointState &P = c->point;
     if (nsrc < 0 || (size_t)nsrc * kEscapeRec != P.escape_host.size())
         return fail(c, FTTE_ERR_ARG, "ftte_point_escape: nsrc is not the number of stars of the last ftte_point_sources");
@@ -703,8 +714,8 @@ int ftte_point_escape(ftte_ctx *c, int nsrc, double *remaining, double *boundary
 
 int ftte_set_output_sigma(ftte_ctx *c, const double *sigma)
 {
-    if (c && c->multi) return check_ready(c, false); // (refuses: a multi-device context routes the diffuse sweep only)
-    if (!c) return FTTE_ERR_ARG;
+    int rc = check_single(c);
+    if (rc) return rc;
     if (!sigma) return fail(c, FTTE_ERR_ARG, "ftte_set_output_sigma: bad argument");
     FTTE_HIP(c, hipSetDevice(c->device));
     return point_set_output_sigma(c->point, c->stream, sigma, &c->err);
@@ -744,307 +755,6 @@ int ftte_point_rates_device(ftte_ctx *c, double **rates_dev)
     FTTE_HIP(c, hipStreamSynchronize(c->stream));
     return FTTE_OK;
 }
-
-// ---- ionisation equilibrium ---------------------------------------------------------------------------------------
-
-int ftte_set_rate_coefficients(ftte_ctx *c, int nratec, double logtem0, double logtem9, double dlogtem, const double *k1a,
-                               const double *k2a, const double *k3a, const double *k4a, const double *k5a, const double *k6a)
-{
-    if (c && c->multi) return check_ready(c, false); // (refuses: a multi-device context routes the diffuse sweep only)
-    if (!c) return FTTE_ERR_ARG;
-    if (nratec < 2 || !(dlogtem > 0.0) || !(logtem9 > logtem0) || !k1a || !k2a || !k3a || !k4a || !k5a || !k6a)
-        return fail(c, FTTE_ERR_ARG, "ftte_set_rate_coefficients: bad argument");
-    FTTE_HIP(c, hipSetDevice(c->device));
-    FTTE_HIP(c, hipStreamSynchronize(c->stream));
-    if (c->chem_nratec != nratec) c->chem_k.reset();
-    FTTE_HIP(c, c->chem_k.reserve(6 * (size_t)nratec));
-    const double *src[6] = {k1a, k2a, k3a, k4a, k5a, k6a};
-    for (int r = 0; r < 6; ++r)
-        FTTE_HIP(c, hipMemcpyAsync(c->chem_k + (size_t)r * nratec, src[r], sizeof(double) * nratec, hipMemcpyHostToDevice, c->stream));
-    FTTE_HIP(c, hipStreamSynchronize(c->stream));
-    c->chem_nratec = nratec;
-    c->chem_logtem0 = logtem0; c->chem_logtem9 = logtem9; c->chem_dlogtem = dlogtem;
-    return FTTE_OK;
-}
-
-int ftte_set_temperature(ftte_ctx *c, const double *tgas)
-{
-    int rc = check_ready(c, false);
-    if (rc) return rc;
-    if (!tgas) return fail(c, FTTE_ERR_ARG, "ftte_set_temperature: bad argument");
-    FTTE_HIP(c, hipSetDevice(c->device));
-    // the logarithm is taken here, on the host, so that the device update consists of IEEE-exact operations only
-    std::vector<double> logtem((size_t)c->ncell);
-    {
-        const int nthreads = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
-        const int64_t chunk = (c->ncell + nthreads - 1) / nthreads;
-        std::vector<std::thread> pool;
-        for (int t = 0; t < nthreads; ++t)
-            pool.emplace_back([&, t] {
-                const int64_t lo = t * chunk, hi = std::min<int64_t>(c->ncell, lo + chunk);
-                for (int64_t q = lo; q < hi; ++q) logtem[(size_t)q] = std::log(tgas[q]);
-            });
-        for (auto &th : pool) th.join();
-    }
-    FTTE_HIP(c, c->chem_logtem.reserve((size_t)c->ncell));
-    FTTE_HIP(c, hipMemcpyAsync(c->chem_logtem, logtem.data(), sizeof(double) * (size_t)c->ncell, hipMemcpyHostToDevice, c->stream));
-    FTTE_HIP(c, hipStreamSynchronize(c->stream));
-    c->chem_temperature_set = true;
-    return FTTE_OK;
-}
-
-static int solve_rates(ftte_ctx *c, int run_uvb, const double *J, bool J_on_device, const double *ksi, const double *uniform,
-                       double threshold, int use_point_rates, double *max_change, const char *who)
-{
-    if (c && c->multi) return check_ready(c, false); // (refuses: a multi-device context routes the diffuse sweep only)
-    int rc = check_ready(c, false);
-    if (rc) return rc;
-    PointState &P = c->point;
-    if (!c->chem_k) return fail(c, FTTE_ERR_STATE, std::string(who) + ": no rate coefficients (ftte_set_rate_coefficients)");
-    if (!c->chem_temperature_set) return fail(c, FTTE_ERR_STATE, std::string(who) + ": no temperature (ftte_set_temperature)");
-    if (!P.medium_ready || P.medium_cells != c->ncell || !P.rho_given)
-        return fail(c, FTTE_ERR_STATE, std::string(who) + ": no medium with density (ftte_set_medium with rho)");
-    if (run_uvb && (!J || !ksi)) return fail(c, FTTE_ERR_ARG, std::string(who) + ": the transfer-driven update needs J and ksi");
-    if (!run_uvb && !uniform) return fail(c, FTTE_ERR_ARG, std::string(who) + ": the uniform-background update needs the background rates");
-    if (use_point_rates && (!P.rates || P.rates_cells != c->ncell))
-        return fail(c, FTTE_ERR_STATE, std::string(who) + ": no point-source rates (ftte_set_zero_rates / ftte_point_sources)");
-    FTTE_HIP(c, hipSetDevice(c->device));
-    const size_t nc = (size_t)c->ncell;
-    if (!c->chem_level) {
-        FTTE_HIP(c, c->chem_level.reserve(nc));
-        FTTE_HIP(c, hipMemcpyAsync(c->chem_level, c->leaf_level.data(), nc, hipMemcpyHostToDevice, c->stream));
-    }
-    FTTE_HIP(c, c->chem_out.reserve(3 * nc));
-    FTTE_HIP(c, c->chem_counters.reserve(4));
-    const double *J_dev = nullptr;
-    if (run_uvb) {
-        if (J_on_device) J_dev = J;
-        else {
-            FTTE_HIP(c, c->chem_J.reserve(3 * nc));
-            FTTE_HIP(c, hipMemcpyAsync(c->chem_J, J, sizeof(double) * 3 * nc, hipMemcpyHostToDevice, c->stream));
-            J_dev = c->chem_J;
-        }
-    }
-    const unsigned long long init[4] = {~0ull, 0ull, 0ull, 0ull};
-    FTTE_HIP(c, hipMemcpyAsync(c->chem_counters, init, sizeof init, hipMemcpyHostToDevice, c->stream));
-
-    ChemRec R;
-    std::memset(&R, 0, sizeof R);
-    R.level = c->chem_level;
-    R.rho = P.medium[3]; R.logtem = c->chem_logtem;
-    R.HI = P.medium[0]; R.HeI = P.medium[1]; R.HeII = P.medium[2];
-    R.HI_out = c->chem_out; R.HeI_out = c->chem_out + nc; R.HeII_out = c->chem_out + 2 * nc;
-    R.krate = use_point_rates ? P.rates : nullptr;
-    R.J = J_dev;
-    R.k = c->chem_k;
-    R.ncell = c->ncell; R.n = c->n; R.nratec = c->chem_nratec; R.run_uvb = run_uvb ? 1 : 0;
-    R.box = c->box; R.logtem0 = c->chem_logtem0; R.logtem9 = c->chem_logtem9; R.dlogtem = c->chem_dlogtem;
-    if (ksi) std::memcpy(R.ksi, ksi, sizeof R.ksi);
-    if (uniform) std::memcpy(R.uniform, uniform, sizeof R.uniform);
-    R.threshold = threshold;
-    R.first_bad = c->chem_counters; R.max_change = c->chem_counters + 1; R.steps = c->chem_counters + 2;
-    if (launch_rate_equations(R, c->stream)) return fail(c, FTTE_ERR_NO_DEVICE, std::string(who) + ": kernel launch failed");
-    unsigned long long out[4];
-    FTTE_HIP(c, hipMemcpyAsync(out, c->chem_counters, sizeof out, hipMemcpyDeviceToHost, c->stream));
-    FTTE_HIP(c, hipStreamSynchronize(c->stream));
-    if (out[0] != ~0ull) {
-        // the reference prints the species of the cell and stops (equiSources.f90:3637-3654); the state is left as it was
-        return fail(c, FTTE_ERR_RATES, std::string(who) + ": species fraction outside [0, 1] in cell " + std::to_string(out[0]) +
-                                           " (0-based cell-array index)");
-    }
-    for (int f = 0; f < 3; ++f)
-        FTTE_HIP(c, hipMemcpyAsync(P.medium[f], c->chem_out + f * nc, sizeof(double) * nc, hipMemcpyDeviceToDevice, c->stream));
-    P.packed_ready = false; // the tracer's packed copy of the medium is stale now
-    FTTE_HIP(c, hipStreamSynchronize(c->stream));
-    double change;
-    std::memcpy(&change, &out[1], sizeof change);
-    if (max_change) *max_change = change;
-    c->chem_steps = (long long)out[2];
-    return FTTE_OK;
-}
-
-int ftte_solve_rate_equations(ftte_ctx *c, int run_uvb_transfer, const double *J, const double *ksi, const double *uniform,
-                              double self_shielding_threshold, int use_point_rates, double *max_change)
-{
-    return solve_rates(c, run_uvb_transfer, J, false, ksi, uniform, self_shielding_threshold, use_point_rates, max_change,
-                       "ftte_solve_rate_equations");
-}
-
-int ftte_solve_rate_equations_device(ftte_ctx *c, int run_uvb_transfer, const double *J_dev, const double *ksi, const double *uniform,
-                                     double self_shielding_threshold, int use_point_rates, double *max_change)
-{
-    return solve_rates(c, run_uvb_transfer, J_dev, true, ksi, uniform, self_shielding_threshold, use_point_rates, max_change,
-                       "ftte_solve_rate_equations_device");
-}
-
-// computeMass over the leaves of HI (the medium's or a candidate's): the two totals [msun], deterministic
-static int hydrogen_mass(ftte_ctx *c, const double *HI_dev, double *neutral, double *total, const char *who)
-{
-    PointState &P = c->point;
-    const size_t nc = (size_t)c->ncell;
-    if (!c->chem_level) {
-        FTTE_HIP(c, c->chem_level.reserve(nc));
-        FTTE_HIP(c, hipMemcpyAsync(c->chem_level, c->leaf_level.data(), nc, hipMemcpyHostToDevice, c->stream));
-    }
-    FTTE_HIP(c, c->chem_mass.reserve(kMassParts));
-    if (launch_hydrogen_mass(c->chem_level, HI_dev, P.medium[3], (long)nc, c->n, c->box, c->chem_mass, c->stream))
-        return fail(c, FTTE_ERR_NO_DEVICE, std::string(who) + ": kernel launch failed");
-    double out[2];
-    FTTE_HIP(c, hipMemcpyAsync(out, c->chem_mass + 2 * kMassBlocks, sizeof out, hipMemcpyDeviceToHost, c->stream));
-    FTTE_HIP(c, hipStreamSynchronize(c->stream));
-    *neutral = out[0];
-    *total = out[1];
-    return FTTE_OK;
-}
-
-int ftte_initial_ionization_equilibrium(ftte_ctx *c, const double *uniform, double threshold, int passes, double *neutral_fraction)
-{
-    const char *who = "ftte_initial_ionization_equilibrium";
-    if (c && c->multi) return check_ready(c, false); // (refuses: a multi-device context routes the diffuse sweep only)
-    int rc = check_ready(c, false);
-    if (rc) return rc;
-    PointState &P = c->point;
-    if (!c->chem_k) return fail(c, FTTE_ERR_STATE, std::string(who) + ": no rate coefficients (ftte_set_rate_coefficients)");
-    if (!c->chem_temperature_set) return fail(c, FTTE_ERR_STATE, std::string(who) + ": no temperature (ftte_set_temperature)");
-    if (!P.medium_ready || P.medium_cells != c->ncell || !P.rho_given)
-        return fail(c, FTTE_ERR_STATE, std::string(who) + ": no medium with density (ftte_set_medium with rho)");
-    if (!uniform) return fail(c, FTTE_ERR_ARG, std::string(who) + ": the uniform-background update needs the background rates");
-    if (passes < 1) return fail(c, FTTE_ERR_ARG, std::string(who) + ": passes must be at least 1");
-    FTTE_HIP(c, hipSetDevice(c->device));
-    const size_t nc = (size_t)c->ncell;
-    if (!c->chem_level) {
-        FTTE_HIP(c, c->chem_level.reserve(nc));
-        FTTE_HIP(c, hipMemcpyAsync(c->chem_level, c->leaf_level.data(), nc, hipMemcpyHostToDevice, c->stream));
-    }
-    FTTE_HIP(c, c->chem_out.reserve(3 * nc));
-    FTTE_HIP(c, c->chem_counters.reserve(4));
-    const unsigned long long init[4] = {~0ull, 0ull, 0ull, 0ull};
-    FTTE_HIP(c, hipMemcpyAsync(c->chem_counters, init, sizeof init, hipMemcpyHostToDevice, c->stream));
-
-    ChemRec R;
-    std::memset(&R, 0, sizeof R);
-    R.level = c->chem_level;
-    R.rho = P.medium[3]; R.logtem = c->chem_logtem;
-    R.HI = P.medium[0]; R.HeI = P.medium[1]; R.HeII = P.medium[2];
-    R.HI_out = c->chem_out; R.HeI_out = c->chem_out + nc; R.HeII_out = c->chem_out + 2 * nc;
-    R.k = c->chem_k;
-    R.ncell = c->ncell; R.n = c->n; R.nratec = c->chem_nratec; R.passes = passes;
-    R.box = c->box; R.logtem0 = c->chem_logtem0; R.logtem9 = c->chem_logtem9; R.dlogtem = c->chem_dlogtem;
-    std::memcpy(R.uniform, uniform, sizeof R.uniform);
-    R.threshold = threshold;
-    R.first_bad = c->chem_counters; R.max_change = c->chem_counters + 1; R.steps = c->chem_counters + 2;
-    if (launch_initial_equilibrium(R, c->stream)) return fail(c, FTTE_ERR_NO_DEVICE, std::string(who) + ": kernel launch failed");
-    unsigned long long out[4];
-    FTTE_HIP(c, hipMemcpyAsync(out, c->chem_counters, sizeof out, hipMemcpyDeviceToHost, c->stream));
-    FTTE_HIP(c, hipStreamSynchronize(c->stream));
-    if (out[0] != ~0ull) {
-        // the reference prints the species of the cell and stops (equiSources.f90:3809-3818, :3832-3843); the state is left as it was
-        return fail(c, FTTE_ERR_RATES, std::string(who) + ": species fraction outside [0, 1] or no convergence in cell " +
-                                           std::to_string(out[0]) + " (0-based cell-array index)");
-    }
-    for (int f = 0; f < 3; ++f)
-        FTTE_HIP(c, hipMemcpyAsync(P.medium[f], c->chem_out + f * nc, sizeof(double) * nc, hipMemcpyDeviceToDevice, c->stream));
-    P.packed_ready = false; // the tracer's packed copy of the medium is stale now
-    FTTE_HIP(c, hipStreamSynchronize(c->stream));
-    c->chem_steps = (long long)out[2];
-    if (neutral_fraction) {
-        // equiSources.f90:1020-1022
-        double neutral = 0., total = 0.;
-        if ((rc = hydrogen_mass(c, P.medium[0], &neutral, &total, who))) return rc;
-        *neutral_fraction = neutral / total;
-    }
-    return FTTE_OK;
-}
-
-int ftte_hydrogen_mass(ftte_ctx *c, double *neutral_msun, double *total_msun)
-{
-    const char *who = "ftte_hydrogen_mass";
-    if (c && c->multi) return check_ready(c, false); // (refuses: a multi-device context routes the diffuse sweep only)
-    int rc = check_ready(c, false);
-    if (rc) return rc;
-    if (!neutral_msun || !total_msun) return fail(c, FTTE_ERR_ARG, std::string(who) + ": bad argument");
-    PointState &P = c->point;
-    if (!P.medium_ready || P.medium_cells != c->ncell || !P.rho_given)
-        return fail(c, FTTE_ERR_STATE, std::string(who) + ": no medium with density (ftte_set_medium with rho)");
-    FTTE_HIP(c, hipSetDevice(c->device));
-    return hydrogen_mass(c, P.medium[0], neutral_msun, total_msun, who);
-}
-
-int ftte_get_medium(ftte_ctx *c, double *HI, double *HeI, double *HeII)
-{
-    int rc = check_ready(c, false);
-    if (rc) return rc;
-    if (!HI || !HeI || !HeII) return fail(c, FTTE_ERR_ARG, "ftte_get_medium: bad argument");
-    if (!c->point.medium_ready || c->point.medium_cells != c->ncell) return fail(c, FTTE_ERR_STATE, "no medium: call ftte_set_medium first");
-    FTTE_HIP(c, hipSetDevice(c->device));
-    double *dst[3] = {HI, HeI, HeII};
-    for (int f = 0; f < 3; ++f)
-        FTTE_HIP(c, hipMemcpyAsync(dst[f], c->point.medium[f], sizeof(double) * (size_t)c->ncell, hipMemcpyDeviceToHost, c->stream));
-    FTTE_HIP(c, hipStreamSynchronize(c->stream));
-    return FTTE_OK;
-}
-
-int ftte_compute_opacities(ftte_ctx *c, int nnu, const double *beta)
-{
-    int rc = check_ready(c, false);
-    if (rc) return rc;
-    if (nnu < 1 || !beta) return fail(c, FTTE_ERR_ARG, "ftte_compute_opacities: bad argument");
-    if (!c->point.medium_ready || c->point.medium_cells != c->ncell) return fail(c, FTTE_ERR_STATE, "no medium: call ftte_set_medium first");
-    FTTE_HIP(c, hipSetDevice(c->device));
-    if ((rc = wait_sweep(c))) return rc;
-    FTTE_HIP(c, hipStreamSynchronize(c->stream));
-    if ((rc = ensure_kappa(c, nnu))) return rc;
-    DeviceBuffer<double> dbeta;
-    FTTE_HIP(c, dbeta.reserve(3 * (size_t)nnu));
-    hipError_t e = hipMemcpyAsync(dbeta, beta, sizeof(double) * 3 * nnu, hipMemcpyHostToDevice, c->stream);
-    int lrc = 0;
-    if (e == hipSuccess)
-        lrc = launch_opacity(c->point.medium[0], c->point.medium[1], c->point.medium[2], dbeta, c->kappa.source(), (long)c->ncell, nnu, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(c, FTTE_ERR_NO_DEVICE, std::string("ftte_compute_opacities: ") + hipGetErrorString(e));
-    if (lrc) return fail(c, FTTE_ERR_NO_DEVICE, "ftte_compute_opacities: kernel launch failed");
-    c->nnu = nnu;
-    c->kappa.set();
-    return FTTE_OK;
-}
-
-static int assign_uvb(ftte_ctx *c, int nnu, const double *uvb, double threshold, double *J, bool J_on_device, const char *who)
-{
-    if (c && c->multi) return check_ready(c, false); // (refuses: a multi-device context routes the diffuse sweep only)
-    int rc = check_ready(c, false);
-    if (rc) return rc;
-    if (nnu < 1 || !uvb || !J) return fail(c, FTTE_ERR_ARG, std::string(who) + ": bad argument");
-    PointState &P = c->point;
-    if (!P.medium_ready || P.medium_cells != c->ncell || !P.rho_given)
-        return fail(c, FTTE_ERR_STATE, std::string(who) + ": no medium with density (ftte_set_medium with rho)");
-    FTTE_HIP(c, hipSetDevice(c->device));
-    const size_t nc = (size_t)c->ncell;
-    DeviceBuffer<double> duvb, J_tmp;
-    FTTE_HIP(c, duvb.reserve((size_t)nnu));
-    hipError_t e = hipSuccess;
-    if (!J_on_device) e = J_tmp.reserve(nc * nnu);
-    double *const dJ = J_on_device ? J : J_tmp.get();
-    if (e == hipSuccess) e = hipMemcpyAsync(duvb, uvb, sizeof(double) * nnu, hipMemcpyHostToDevice, c->stream);
-    int lrc = 0;
-    if (e == hipSuccess) lrc = launch_thin_limit(P.medium[0], P.medium[1], P.medium[2], P.medium[3], duvb, threshold, dJ, (long)nc, nnu, c->stream);
-    if (e == hipSuccess && !J_on_device) e = hipMemcpyAsync(J, dJ, sizeof(double) * nc * nnu, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(c, FTTE_ERR_NO_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
-    if (lrc) return fail(c, FTTE_ERR_NO_DEVICE, std::string(who) + ": kernel launch failed");
-    return FTTE_OK;
-}
-
-int ftte_assign_uvb_radiation(ftte_ctx *c, int nnu, const double *uvb, double self_shielding_threshold, double *J)
-{
-    return assign_uvb(c, nnu, uvb, self_shielding_threshold, J, false, "ftte_assign_uvb_radiation");
-}
-
-int ftte_assign_uvb_radiation_device(ftte_ctx *c, int nnu, const double *uvb, double self_shielding_threshold, double *J_dev)
-{
-    return assign_uvb(c, nnu, uvb, self_shielding_threshold, J_dev, true, "ftte_assign_uvb_radiation_device");
-}
-
-long long ftte_rate_equation_steps(const ftte_ctx *c) { return c ? c->chem_steps : 0; }
 
 long long ftte_point_ray_steps(const ftte_ctx *c) { return c ? c->point.ray_steps : 0; }
 

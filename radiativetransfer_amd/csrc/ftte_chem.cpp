@@ -1,0 +1,289 @@
+// ftte_chem.cpp -- the entry points of include/ftte.h that read or write the species medium (ftte_ctx::gas) outside the tracer: the
+// ionisation chemistry (rate coefficients, temperature, the equilibrium update, the start-up equilibrium, the hydrogen census), the
+// species' way out, the opacities and the thin-limit radiation made from them.  The chemistry's own state is ftte_ctx::chem.
+#include "ftte_context.h"
+
+using namespace ftte;
+
+namespace {
+
+// the leaves' levels on the device: uploaded on first use after ftte_set_grid
+int ensure_level(ftte_ctx *c)
+{
+    if (c->chem.level) return FTTE_OK;
+    FTTE_HIP(c, c->chem.level.reserve((size_t)c->ncell));
+    FTTE_HIP(c, hipMemcpyAsync(c->chem.level, c->leaf_level.data(), (size_t)c->ncell, hipMemcpyHostToDevice, c->stream));
+    return FTTE_OK;
+}
+
+// What an update of the species has of its own, beside its arguments
+struct ChemUpdate {
+    const char *who;   // the entry point, in front of every text
+    const char *stops; // where the reference prints the species of the cell and stops; the state is left as it was
+    int (*launch)(const ChemRec &, hipStream_t);
+};
+
+// One update of HI, HeI, HeII over all leaves: the preconditions, the outputs and counters, the record, the launch, and then
+// either the refusal or the new species in the gas.  own(R) checks the entry point's arguments and fills its fields of the record,
+// uploading what they name; it runs behind the preconditions and in front of everything else, so that a bad argument allocates nothing.
+template <typename Own> int chem_update(ftte_ctx *c, const ChemUpdate &U, Own own, double *max_change)
+{
+    int rc = check_ready(c, false);
+    if (rc) return rc;
+    ChemState &K = c->chem;
+    GasState &G = c->gas;
+    const std::string who = std::string(U.who) + ": ";
+    if (!K.k) return fail(c, FTTE_ERR_STATE, who + "no rate coefficients (ftte_set_rate_coefficients)");
+    if (!K.temperature_set) return fail(c, FTTE_ERR_STATE, who + "no temperature (ftte_set_temperature)");
+    if (!G.ready_with_density(c->ncell)) return fail(c, FTTE_ERR_STATE, who + "no medium with density (ftte_set_medium with rho)");
+    FTTE_HIP(c, hipSetDevice(c->device));
+    ChemRec R;
+    std::memset(&R, 0, sizeof R);
+    if ((rc = own(R))) return rc;
+    const size_t nc = (size_t)c->ncell;
+    if ((rc = ensure_level(c))) return rc;
+    FTTE_HIP(c, K.out.reserve(3 * nc));
+    FTTE_HIP(c, K.counters.reserve(4));
+    const unsigned long long init[4] = {~0ull, 0ull, 0ull, 0ull};
+    FTTE_HIP(c, hipMemcpyAsync(K.counters, init, sizeof init, hipMemcpyHostToDevice, c->stream));
+
+    R.level = K.level;
+    R.rho = G.field(GasState::kRho); R.logtem = K.logtem;
+    R.HI = G.field(GasState::kHI); R.HeI = G.field(GasState::kHeI); R.HeII = G.field(GasState::kHeII);
+    R.HI_out = K.out; R.HeI_out = K.out + nc; R.HeII_out = K.out + 2 * nc;
+    R.k = K.k;
+    R.ncell = c->ncell; R.n = c->n; R.nratec = K.nratec;
+    R.box = c->box; R.logtem0 = K.logtem0; R.logtem9 = K.logtem9; R.dlogtem = K.dlogtem;
+    R.first_bad = K.counters; R.max_change = K.counters + 1; R.steps = K.counters + 2;
+    if (U.launch(R, c->stream)) return fail(c, FTTE_ERR_NO_DEVICE, who + "kernel launch failed");
+    unsigned long long out[4];
+    FTTE_HIP(c, hipMemcpyAsync(out, K.counters, sizeof out, hipMemcpyDeviceToHost, c->stream));
+    FTTE_HIP(c, hipStreamSynchronize(c->stream));
+    if (out[0] != ~0ull) return fail(c, FTTE_ERR_RATES, who + U.stops + " in cell " + std::to_string(out[0]) + " (0-based cell-array index)");
+    for (int f = 0; f < 3; ++f)
+        FTTE_HIP(c, hipMemcpyAsync(G.field(f), K.out + f * nc, sizeof(double) * nc, hipMemcpyDeviceToDevice, c->stream));
+    G.species_changed();
+    FTTE_HIP(c, hipStreamSynchronize(c->stream));
+    if (max_change) std::memcpy(max_change, &out[1], sizeof *max_change);
+    K.steps = (long long)out[2];
+    return FTTE_OK;
+}
+
+// solveRateEquations (equiSources.f90:3459-3677; it stops at :3637-3654)
+int solve_rates(ftte_ctx *c, int run_uvb, const double *J, bool J_on_device, const double *ksi, const double *uniform, double threshold,
+                int use_point_rates, double *max_change, const char *who)
+{
+    const ChemUpdate U{who, "species fraction outside [0, 1]", launch_rate_equations};
+    return chem_update(c, U, [&](ChemRec &R) -> int {
+        const PointState &P = c->point;
+        if (run_uvb && (!J || !ksi)) return fail(c, FTTE_ERR_ARG, std::string(who) + ": the transfer-driven update needs J and ksi");
+        if (!run_uvb && !uniform) return fail(c, FTTE_ERR_ARG, std::string(who) + ": the uniform-background update needs the background rates");
+        if (use_point_rates && (!P.rates || P.rates_cells != c->ncell))
+            return fail(c, FTTE_ERR_STATE, std::string(who) + ": no point-source rates (ftte_set_zero_rates / ftte_point_sources)");
+        if (run_uvb && !J_on_device) {
+            const size_t nc = (size_t)c->ncell;
+            FTTE_HIP(c, c->chem.J.reserve(3 * nc));
+            FTTE_HIP(c, hipMemcpyAsync(c->chem.J, J, sizeof(double) * 3 * nc, hipMemcpyHostToDevice, c->stream));
+            J = c->chem.J;
+        }
+        R.J = run_uvb ? J : nullptr;
+        R.krate = use_point_rates ? P.rates.get() : nullptr;
+        R.run_uvb = run_uvb ? 1 : 0;
+        if (ksi) std::memcpy(R.ksi, ksi, sizeof R.ksi);
+        if (uniform) std::memcpy(R.uniform, uniform, sizeof R.uniform);
+        R.threshold = threshold;
+        return FTTE_OK;
+    }, max_change);
+}
+
+// computeMass over the leaves of HI (the medium's or a candidate's): the two totals [msun], deterministic
+int hydrogen_mass(ftte_ctx *c, const double *HI_dev, double *neutral, double *total, const char *who)
+{
+    int rc = ensure_level(c);
+    if (rc) return rc;
+    FTTE_HIP(c, c->chem.mass.reserve(kMassParts));
+    if (launch_hydrogen_mass(c->chem.level, HI_dev, c->gas.field(GasState::kRho), (long)c->ncell, c->n, c->box, c->chem.mass, c->stream))
+        return fail(c, FTTE_ERR_NO_DEVICE, std::string(who) + ": kernel launch failed");
+    double out[2];
+    FTTE_HIP(c, hipMemcpyAsync(out, c->chem.mass + 2 * kMassBlocks, sizeof out, hipMemcpyDeviceToHost, c->stream));
+    FTTE_HIP(c, hipStreamSynchronize(c->stream));
+    *neutral = out[0];
+    *total = out[1];
+    return FTTE_OK;
+}
+
+int assign_uvb(ftte_ctx *c, int nnu, const double *uvb, double threshold, double *J, bool J_on_device, const char *who)
+{
+    int rc = check_ready(c, false);
+    if (rc) return rc;
+    if (nnu < 1 || !uvb || !J) return fail(c, FTTE_ERR_ARG, std::string(who) + ": bad argument");
+    const GasState &G = c->gas;
+    if (!G.ready_with_density(c->ncell)) return fail(c, FTTE_ERR_STATE, std::string(who) + ": no medium with density (ftte_set_medium with rho)");
+    FTTE_HIP(c, hipSetDevice(c->device));
+    const size_t nc = (size_t)c->ncell;
+    DeviceBuffer<double> duvb, J_tmp;
+    FTTE_HIP(c, duvb.reserve((size_t)nnu));
+    hipError_t e = hipSuccess;
+    if (!J_on_device) e = J_tmp.reserve(nc * nnu);
+    double *const dJ = J_on_device ? J : J_tmp.get();
+    if (e == hipSuccess) e = hipMemcpyAsync(duvb, uvb, sizeof(double) * nnu, hipMemcpyHostToDevice, c->stream);
+    int lrc = 0;
+    if (e == hipSuccess)
+        lrc = launch_thin_limit(G.field(GasState::kHI), G.field(GasState::kHeI), G.field(GasState::kHeII), G.field(GasState::kRho), duvb, threshold, dJ,
+                                (long)nc, nnu, c->stream);
+    if (e == hipSuccess && !J_on_device) e = hipMemcpyAsync(J, dJ, sizeof(double) * nc * nnu, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return fail(c, FTTE_ERR_NO_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    if (lrc) return fail(c, FTTE_ERR_NO_DEVICE, std::string(who) + ": kernel launch failed");
+    return FTTE_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int ftte_set_rate_coefficients(ftte_ctx *c, int nratec, double logtem0, double logtem9, double dlogtem, const double *k1a,
+                               const double *k2a, const double *k3a, const double *k4a, const double *k5a, const double *k6a)
+{
+    int rc = check_single(c);
+    if (rc) return rc;
+    if (nratec < 2 || !(dlogtem > 0.0) || !(logtem9 > logtem0) || !k1a || !k2a || !k3a || !k4a || !k5a || !k6a)
+        return fail(c, FTTE_ERR_ARG, "ftte_set_rate_coefficients: bad argument");
+    ChemState &K = c->chem;
+    FTTE_HIP(c, hipSetDevice(c->device));
+    FTTE_HIP(c, hipStreamSynchronize(c->stream));
+    if (K.nratec != nratec) K.k.reset();
+    FTTE_HIP(c, K.k.reserve(6 * (size_t)nratec));
+    const double *src[6] = {k1a, k2a, k3a, k4a, k5a, k6a};
+    for (int r = 0; r < 6; ++r)
+        FTTE_HIP(c, hipMemcpyAsync(K.k + (size_t)r * nratec, src[r], sizeof(double) * nratec, hipMemcpyHostToDevice, c->stream));
+    FTTE_HIP(c, hipStreamSynchronize(c->stream));
+    K.nratec = nratec;
+    K.logtem0 = logtem0; K.logtem9 = logtem9; K.dlogtem = dlogtem;
+    return FTTE_OK;
+}
+
+int ftte_set_temperature(ftte_ctx *c, const double *tgas)
+{
+    int rc = check_ready(c, false);
+    if (rc) return rc;
+    if (!tgas) return fail(c, FTTE_ERR_ARG, "ftte_set_temperature: bad argument");
+    FTTE_HIP(c, hipSetDevice(c->device));
+    // the logarithm is taken here, on the host, so that the device update consists of IEEE-exact operations only
+    std::vector<double> logtem((size_t)c->ncell);
+    {
+        const int nthreads = (int)std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+        const int64_t chunk = (c->ncell + nthreads - 1) / nthreads;
+        std::vector<std::thread> pool;
+        for (int t = 0; t < nthreads; ++t)
+            pool.emplace_back([&, t] {
+                const int64_t lo = t * chunk, hi = std::min<int64_t>(c->ncell, lo + chunk);
+                for (int64_t q = lo; q < hi; ++q) logtem[(size_t)q] = std::log(tgas[q]);
+            });
+        for (auto &th : pool) th.join();
+    }
+    FTTE_HIP(c, c->chem.logtem.reserve((size_t)c->ncell));
+    FTTE_HIP(c, hipMemcpyAsync(c->chem.logtem, logtem.data(), sizeof(double) * (size_t)c->ncell, hipMemcpyHostToDevice, c->stream));
+    FTTE_HIP(c, hipStreamSynchronize(c->stream));
+    c->chem.temperature_set = true;
+    return FTTE_OK;
+}
+
+int ftte_solve_rate_equations(ftte_ctx *c, int run_uvb_transfer, const double *J, const double *ksi, const double *uniform,
+                              double self_shielding_threshold, int use_point_rates, double *max_change)
+{
+    return solve_rates(c, run_uvb_transfer, J, false, ksi, uniform, self_shielding_threshold, use_point_rates, max_change,
+                       "ftte_solve_rate_equations");
+}
+
+int ftte_solve_rate_equations_device(ftte_ctx *c, int run_uvb_transfer, const double *J_dev, const double *ksi, const double *uniform,
+                                     double self_shielding_threshold, int use_point_rates, double *max_change)
+{
+    return solve_rates(c, run_uvb_transfer, J_dev, true, ksi, uniform, self_shielding_threshold, use_point_rates, max_change,
+                       "ftte_solve_rate_equations_device");
+}
+
+// initialIonizationEquilibrium (it stops at equiSources.f90:3809-3818, :3832-3843)
+int ftte_initial_ionization_equilibrium(ftte_ctx *c, const double *uniform, double threshold, int passes, double *neutral_fraction)
+{
+    const char *who = "ftte_initial_ionization_equilibrium";
+    const ChemUpdate U{who, "species fraction outside [0, 1] or no convergence", launch_initial_equilibrium};
+    int rc = chem_update(c, U, [&](ChemRec &R) -> int {
+        if (!uniform) return fail(c, FTTE_ERR_ARG, std::string(who) + ": the uniform-background update needs the background rates");
+        if (passes < 1) return fail(c, FTTE_ERR_ARG, std::string(who) + ": passes must be at least 1");
+        R.passes = passes;
+        std::memcpy(R.uniform, uniform, sizeof R.uniform);
+        R.threshold = threshold;
+        return FTTE_OK;
+    }, nullptr);
+    if (rc || !neutral_fraction) return rc;
+    // equiSources.f90:1020-1022
+    double neutral = 0., total = 0.;
+    if ((rc = hydrogen_mass(c, c->gas.field(GasState::kHI), &neutral, &total, who))) return rc;
+    *neutral_fraction = neutral / total;
+    return FTTE_OK;
+}
+
+int ftte_hydrogen_mass(ftte_ctx *c, double *neutral_msun, double *total_msun)
+{
+    const char *who = "ftte_hydrogen_mass";
+    int rc = check_ready(c, false);
+    if (rc) return rc;
+    if (!neutral_msun || !total_msun) return fail(c, FTTE_ERR_ARG, std::string(who) + ": bad argument");
+    if (!c->gas.ready_with_density(c->ncell)) return fail(c, FTTE_ERR_STATE, std::string(who) + ": no medium with density (ftte_set_medium with rho)");
+    FTTE_HIP(c, hipSetDevice(c->device));
+    return hydrogen_mass(c, c->gas.field(GasState::kHI), neutral_msun, total_msun, who);
+}
+
+int ftte_get_medium(ftte_ctx *c, double *HI, double *HeI, double *HeII)
+{
+    int rc = check_ready(c, false);
+    if (rc) return rc;
+    if (!HI || !HeI || !HeII) return fail(c, FTTE_ERR_ARG, "ftte_get_medium: bad argument");
+    if (!c->gas.ready(c->ncell)) return fail(c, FTTE_ERR_STATE, "no medium: call ftte_set_medium first");
+    FTTE_HIP(c, hipSetDevice(c->device));
+    double *dst[3] = {HI, HeI, HeII};
+    for (int f = 0; f < 3; ++f)
+        FTTE_HIP(c, hipMemcpyAsync(dst[f], c->gas.field(f), sizeof(double) * (size_t)c->ncell, hipMemcpyDeviceToHost, c->stream));
+    FTTE_HIP(c, hipStreamSynchronize(c->stream));
+    return FTTE_OK;
+}
+
+int ftte_compute_opacities(ftte_ctx *c, int nnu, const double *beta)
+{
+    int rc = check_ready(c, false);
+    if (rc) return rc;
+    if (nnu < 1 || !beta) return fail(c, FTTE_ERR_ARG, "ftte_compute_opacities: bad argument");
+    const GasState &G = c->gas;
+    if (!G.ready(c->ncell)) return fail(c, FTTE_ERR_STATE, "no medium: call ftte_set_medium first");
+    FTTE_HIP(c, hipSetDevice(c->device));
+    if ((rc = wait_sweep(c))) return rc;
+    FTTE_HIP(c, hipStreamSynchronize(c->stream));
+    if ((rc = ensure_kappa(c, nnu))) return rc;
+    DeviceBuffer<double> dbeta;
+    FTTE_HIP(c, dbeta.reserve(3 * (size_t)nnu));
+    hipError_t e = hipMemcpyAsync(dbeta, beta, sizeof(double) * 3 * nnu, hipMemcpyHostToDevice, c->stream);
+    int lrc = 0;
+    if (e == hipSuccess)
+        lrc = launch_opacity(G.field(GasState::kHI), G.field(GasState::kHeI), G.field(GasState::kHeII), dbeta, c->kappa.source(), (long)c->ncell, nnu, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return fail(c, FTTE_ERR_NO_DEVICE, std::string("ftte_compute_opacities: ") + hipGetErrorString(e));
+    if (lrc) return fail(c, FTTE_ERR_NO_DEVICE, "ftte_compute_opacities: kernel launch failed");
+    c->nnu = nnu;
+    c->kappa.set();
+    return FTTE_OK;
+}
+
+int ftte_assign_uvb_radiation(ftte_ctx *c, int nnu, const double *uvb, double self_shielding_threshold, double *J)
+{
+    return assign_uvb(c, nnu, uvb, self_shielding_threshold, J, false, "ftte_assign_uvb_radiation");
+}
+
+int ftte_assign_uvb_radiation_device(ftte_ctx *c, int nnu, const double *uvb, double self_shielding_threshold, double *J_dev)
+{
+    return assign_uvb(c, nnu, uvb, self_shielding_threshold, J_dev, true, "ftte_assign_uvb_radiation_device");
+}
+
+long long ftte_rate_equation_steps(const ftte_ctx *c) { return c ? c->chem.steps : 0; }
+
+} // extern "C"

@@ -1,6 +1,7 @@
 // ftte_context.h -- what the translation units behind include/ftte.h share: the sweep plans, the context, and the internal
 // entry points of the planners (ftte_plan.cpp), the sweeps (ftte_sweeps.cpp: segment forests, cell-fixed bricks), the hybrid sweep
-// of refined cell arrays (ftte_hybrid.cpp) and the host-array transfers (ftte_host_arrays.cpp).  ftte_api.cpp is the C ABI itself.
+// of refined cell arrays (ftte_hybrid.cpp) and the host-array transfers (ftte_host_arrays.cpp).  ftte_api.cpp is the C ABI itself,
+// ftte_chem.cpp its part that reads or writes the species medium.
 //
 // Every device buffer, pinned buffer, stream, event and graph of the context is a member that owns it (ftte_device.h): a buffer's
 // capacity travels with its pointer, `delete c` releases everything, and a new buffer is added by declaring it.
@@ -24,6 +25,7 @@
 #include "../../include/ftte.h"
 #include "ftte_amr.h"
 #include "ftte_device.h"
+#include "ftte_gas.h"
 #include "ftte_geometry.h"
 #include "ftte_internal.h"
 #include "ftte_kernels.h"
@@ -283,7 +285,10 @@ struct ftte_ctx {
     DeviceBuffer<double> base_kappa[3];
     DeviceBuffer<double> base_emis[3];    // emissivity / source function of the base cells (hybrid sweep with emission)
 
-    PointState point; // point sources: rate tables, medium, tracer scratch
+    // The species medium (ftte_gas.h): ftte_set_medium fills it; the tracer, the chemistry, the census, ftte_compute_opacities and
+    // the thin limit read it; the chemistry's updates write its species and say so
+    GasState gas;
+    PointState point; // point sources: tree, rate tables, rates, tracer scratch
 
     // host-array boundary (ftte_set_opacity / ftte_diffuse_sweep): J lives in a device buffer the context keeps, and
     // pageable host arrays cross PCIe through two pinned staging blocks filled by a few host threads while the other
@@ -298,18 +303,8 @@ struct ftte_ctx {
     // instrumentation (ftte_counter): how often the expensive host-side builds ran
     long long n_grid_builds = 0, n_plan_builds = 0, n_forest_builds = 0;
 
-    // ionisation equilibrium (solveRateEquations)
     std::vector<int8_t> leaf_level;  // per leaf, as handed to ftte_set_grid
-    DeviceBuffer<int8_t> chem_level;
-    DeviceBuffer<double> chem_k;     // [6][nratec]
-    int chem_nratec = 0;
-    double chem_logtem0 = 0, chem_logtem9 = 0, chem_dlogtem = 0;
-    DeviceBuffer<double> chem_logtem; // [ncell] log of the gas temperature
-    bool chem_temperature_set = false;
-    DeviceBuffer<double> chem_out, chem_J; // [3][ncell] each
-    DeviceBuffer<unsigned long long> chem_counters; // first bad cell, bits of the largest change, bisection steps
-    long long chem_steps = 0;
-    DeviceBuffer<double> chem_mass;  // computeMass: per-workgroup partial sums, then the two totals (kMassParts)
+    ChemState chem;                  // ionisation equilibrium (ftte_chem.cpp)
 
     // accelerated source iteration (ftte_lambda_host.cpp): the segment-length tables of the last direction list, the leaves' places on
     // their levels (made for the tree of grid build lambda_leaves_grid) with the sub-layers that hold a leaf, the update's statistics
@@ -321,12 +316,6 @@ struct ftte_ctx {
     DeviceBuffer<double> d_lambda_host; // ftte_lambda_diagonal: the diagonal on its way to the caller's host array
     DeviceBuffer<unsigned long long> d_update_stats;
     PinnedBuffer<unsigned long long> h_update_stats;
-
-    void drop_chem_grid()
-    {
-        chem_level.reset(); chem_logtem.reset(); chem_out.reset(); chem_J.reset();
-        chem_temperature_set = false;
-    }
 };
 
 // Which form of the brick kernel sweeps: 0 one wavefront per brick, 2 a pair of wavefronts per brick.
@@ -353,6 +342,9 @@ int fail(ftte_ctx *c, int code, const std::string &msg);
     } while (0)
 
 int fold_status(int rc);
+// For the entry points that need no grid: 0, or what a missing or a multi-device context is refused with (check_ready does the
+// same as its first act)
+int check_single(ftte_ctx *c);
 
 // ---- ftte_plan.cpp
 // A cubic sub-grid planned like a grid of its own (the fine cells of a fully refined block): side, cell size, and where the layers'

@@ -1,0 +1,90 @@
+// ftte_gas.h -- GasState: the species medium the point-source tracer, the chemistry, the opacities and the thin limit share (HI,
+// HeI, HeII, rho, abun2 in cell-array order), with the packed copy the tracer reads.  The species have a version and the packed copy
+// remembers the version it was made from, as a MediumField's copies do (ftte_medium.h): whoever writes the species says
+// species_changed(), and the tracer asks packed_current().  Launches nothing and copies nothing: point_set_medium fills it.
+// ChemState: what the ionisation chemistry keeps beside the gas (ftte_chem.cpp).
+#pragma once
+
+#include <cstdint>
+
+#include "ftte_device.h"
+
+namespace ftte {
+
+class GasState {
+public:
+    enum { kHI, kHeI, kHeII, kRho, kAbun2, kFields };
+    double *field(int f) const { return field_[f]; }
+    int dust() const { return dust_; } // dustApproximation of the last fill
+    bool ready(int64_t ncell) const { return cells_ > 0 && cells_ == ncell; }
+    bool ready_with_density(int64_t ncell) const { return ready(ncell) && density_; } // (the chemistry and the census need rho)
+
+    // Room for a fill of ncell cells, which starts here: the packed copy is stale.  For another cell count everything is released
+    // first and the gas is not ready until filled(); for the same one the buffers, the packed copy's among them, stay.  On failure
+    // the gas is empty.
+    hipError_t reserve(int64_t ncell)
+    {
+        species_changed();
+        if (cells_ != ncell) drop();
+        for (auto &f : field_) {
+            const hipError_t e = f.reserve((size_t)ncell);
+            if (e != hipSuccess) { drop(); return e; }
+        }
+        return hipSuccess;
+    }
+    void filled(int64_t ncell, int dust, bool density)
+    {
+        cells_ = ncell; dust_ = dust; density_ = density;
+    }
+    void species_changed() { ++version_; } // the packed copy is stale
+    void drop()                            // another grid: nothing of the old one is kept
+    {
+        for (auto &f : field_) f.reset();
+        packed_.reset();
+        packed_from_ = kNever;
+        cells_ = 0;
+        density_ = false;
+    }
+
+    // the tracer's copy, [cells][cell_rec]: room (a new buffer holds nothing), then the launch, then packed_made()
+    double *packed() const { return packed_; }
+    hipError_t reserve_packed(int cell_rec)
+    {
+        bool fresh = false;
+        const hipError_t e = packed_.reserve((size_t)cell_rec * (size_t)cells_, &fresh);
+        if (fresh || e != hipSuccess) packed_from_ = kNever;
+        return e;
+    }
+    bool packed_current() const { return packed_ && packed_from_ == version_; }
+    void packed_made() { packed_from_ = version_; }
+
+private:
+    static constexpr long long kNever = -1;
+    DeviceBuffer<double> field_[kFields], packed_;
+    int64_t cells_ = 0; // of the last fill; 0: none
+    int dust_ = 0;
+    bool density_ = false; // that fill brought a density
+    long long version_ = 0, packed_from_ = kNever;
+};
+
+// ionisation equilibrium (solveRateEquations, initialIonizationEquilibrium, computeMass)
+struct ChemState {
+    DeviceBuffer<int8_t> level;   // per leaf, uploaded on first use after ftte_set_grid
+    DeviceBuffer<double> k;       // [6][nratec]
+    int nratec = 0;
+    double logtem0 = 0, logtem9 = 0, dlogtem = 0;
+    DeviceBuffer<double> logtem;  // [ncell] log of the gas temperature
+    bool temperature_set = false;
+    DeviceBuffer<double> out, J;  // [3][ncell] each
+    DeviceBuffer<unsigned long long> counters; // first bad cell, bits of the largest change, bisection steps
+    long long steps = 0;          // of the last update
+    DeviceBuffer<double> mass;    // computeMass: per-workgroup partial sums, then the two totals (kMassParts)
+
+    void drop_grid() // after ftte_set_grid: what is sized by the old grid; the rate coefficients stay
+    {
+        level.reset(); logtem.reset(); out.reset(); J.reset();
+        temperature_set = false;
+    }
+};
+
+} // namespace ftte

@@ -49,12 +49,6 @@ void PointState::drop_grid()
 {
     node.reset();
     tree_ready = false;
-    for (auto &m : medium) m.reset();
-    packed.reset();
-    packed_ready = false;
-    medium_cells = 0;
-    medium_ready = false;
-    rho_given = false;
     rates.reset(); rate_planes.reset();
     rates_cells = 0;
     std::vector<int32_t>().swap(node_of_leaf);
@@ -298,17 +292,15 @@ int output_sigma(PointState &P, hipStream_t stream, const double *a_smc, std::st
     return point_set_output_sigma(P, stream, sigma, err);
 }
 
-constexpr size_t kSlotDoubles = (size_t)6 * kTableSize; // one slot's tables, and as many logarithms
-
 // Room for npop slots.  What is missing is compared with the free device memory (plus what the buffers to be replaced give back)
 // before anything is released, so that this refusal leaves the slots held as they were.  From the moment a slot buffer is
 // replaced no slot is held, until the caller has filled the new ones: also where the allocation itself or a later step fails.
 int reserve_slots(PointState &P, int npop, bool with_bins, std::string *err)
 {
-    const size_t want = (size_t)npop * kSlotDoubles, want_bins = with_bins ? (size_t)npop * kFrequencies : 0;
+    const size_t want = (size_t)npop * kSetDoubles, want_bins = with_bins ? (size_t)npop * kFrequencies : 0;
     size_t need = 0, back = 0;
-    if (P.slot_tables.capacity() < want) { need += want * sizeof(double); back += P.slot_tables.capacity() * sizeof(double); }
-    if (P.slot_logtab.capacity() < want) { need += want * sizeof(double); back += P.slot_logtab.capacity() * sizeof(double); }
+    for (const DeviceBuffer<double> *b : {&P.slots.tables, &P.slots.logtab})
+        if (b->capacity() < want) { need += want * sizeof(double); back += b->capacity() * sizeof(double); }
     if (P.bins.capacity() < want_bins) { need += want_bins * sizeof(FreqBin); back += P.bins.capacity() * sizeof(FreqBin); }
     if (need) {
         size_t free_bytes = 0, total_bytes = 0;
@@ -319,14 +311,34 @@ int reserve_slots(PointState &P, int npop, bool with_bins, std::string *err)
             return FTTE_ERR_MEMORY;
         }
     }
-    if (P.slot_tables.capacity() < want || P.slot_logtab.capacity() < want) P.nslots = 0;
-    if (P.slot_tables.reserve(want) != hipSuccess || P.slot_logtab.reserve(want) != hipSuccess || P.bins.reserve(want_bins) != hipSuccess) {
+    if (P.slots.reserve(npop) != hipSuccess || P.bins.reserve(want_bins) != hipSuccess) {
         (void)hipGetLastError();
-        P.slot_tables.reset(); P.slot_logtab.reset();
-        P.nslots = 0;
+        P.slots = TableSets();
         *err = "population slots: " + std::to_string(need) + " bytes of device memory could not be allocated";
         return FTTE_ERR_MEMORY;
     }
+    return 0;
+}
+
+// The bins of n populations are on the host: n sets of S from them, one launch for all.  Returns when `bins` may go.
+int tables_from_bins(PointState &P, TableSets &S, hipStream_t stream, const std::vector<FreqBin> &bins, int n, std::string *err)
+{
+    S.count = 0;
+    POINT_HIP(hipMemcpyAsync(P.bins, bins.data(), sizeof(FreqBin) * bins.size(), hipMemcpyHostToDevice, stream));
+    if (launch_rate_table(P.bins, (int)bins.size() / n, n, S.tables, S.logtab, stream)) { *err = "rate table kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
+    POINT_HIP(hipStreamSynchronize(stream));
+    S.count = n;
+    return 0;
+}
+
+// n sets of S from the host, and their logarithms
+int tables_from_host(TableSets &S, hipStream_t stream, const double *tables, int n, std::string *err)
+{
+    S.count = 0;
+    POINT_HIP(hipMemcpyAsync(S.tables, tables, sizeof(double) * kSetDoubles * n, hipMemcpyHostToDevice, stream));
+    if (launch_log_table(S.tables, n, S.logtab, stream)) { *err = "table kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
+    POINT_HIP(hipStreamSynchronize(stream));
+    S.count = n;
     return 0;
 }
 
@@ -344,14 +356,9 @@ int point_stellar_beta_table(PointState &P, hipStream_t stream, const double *a_
 
     int rc;
     if ((rc = output_sigma(P, stream, a_smc, err))) return rc;
-    POINT_HIP(P.tables.reserve(kSlotDoubles));
-    POINT_HIP(P.logtab.reserve(kSlotDoubles));
+    POINT_HIP(P.current.reserve(1));
     POINT_HIP(P.bins.reserve((size_t)kFrequencies));
-    POINT_HIP(hipMemcpyAsync(P.bins, bins.data(), sizeof(FreqBin) * bins.size(), hipMemcpyHostToDevice, stream));
-    if (launch_rate_table(P.bins, (int)bins.size(), 1, P.tables, P.logtab, stream)) { *err = "rate table kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
-    POINT_HIP(hipStreamSynchronize(stream)); // `bins` leaves scope
-    P.tables_ready = true;
-    return 0;
+    return tables_from_bins(P, P.current, stream, bins, 1, err);
 }
 
 int point_stellar_beta_tables(PointState &P, hipStream_t stream, const double *a_smc, int nwave, const double *wavelength,
@@ -370,33 +377,14 @@ int point_stellar_beta_tables(PointState &P, hipStream_t stream, const double *a
     int rc;
     if ((rc = reserve_slots(P, npop, true, err))) return rc;
     if ((rc = output_sigma(P, stream, a_smc, err))) return rc;
-    P.nslots = 0;
-    POINT_HIP(hipMemcpyAsync(P.bins, bins.data(), sizeof(FreqBin) * bins.size(), hipMemcpyHostToDevice, stream));
-    if (launch_rate_table(P.bins, nbins, npop, P.slot_tables, P.slot_logtab, stream)) { *err = "rate table kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
-    POINT_HIP(hipStreamSynchronize(stream)); // `bins` leaves scope
-    P.nslots = npop;
-    return 0;
+    return tables_from_bins(P, P.slots, stream, bins, npop, err);
 }
 
 int point_set_population_tables(PointState &P, hipStream_t stream, int npop, const double *tables, std::string *err)
 {
     int rc;
     if ((rc = reserve_slots(P, npop, false, err))) return rc;
-    P.nslots = 0;
-    POINT_HIP(hipMemcpyAsync(P.slot_tables, tables, sizeof(double) * kSlotDoubles * npop, hipMemcpyHostToDevice, stream));
-    if (launch_log_table(P.slot_tables, npop, P.slot_logtab, stream)) { *err = "table kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
-    POINT_HIP(hipStreamSynchronize(stream));
-    P.nslots = npop;
-    return 0;
-}
-
-int point_get_population_tables(PointState &P, hipStream_t stream, int slot, double *tables, std::string *err)
-{
-    if (!P.nslots) { *err = "no population slots: call ftte_stellar_beta_tables or ftte_set_population_tables first"; return FTTE_ERR_STATE; }
-    if (slot < 0 || slot >= P.nslots) { *err = "ftte_get_population_tables: slot " + std::to_string(slot) + " outside 0.." + std::to_string(P.nslots - 1); return FTTE_ERR_ARG; }
-    POINT_HIP(hipMemcpyAsync(tables, P.slot_tables + (size_t)slot * kSlotDoubles, sizeof(double) * kSlotDoubles, hipMemcpyDeviceToHost, stream));
-    POINT_HIP(hipStreamSynchronize(stream));
-    return 0;
+    return tables_from_host(P.slots, stream, tables, npop, err);
 }
 
 int point_set_output_sigma(PointState &P, hipStream_t stream, const double *sigma, std::string *err)
@@ -416,57 +404,41 @@ int point_set_output_sigma(PointState &P, hipStream_t stream, const double *sigm
 int point_set_tables(PointState &P, hipStream_t stream, const double *tables, std::string *err)
 {
     P.sigma_ready = false; // the cross-sections belong to the population whose tables these replace: ftte_set_output_sigma
-    POINT_HIP(P.tables.reserve((size_t)6 * kTableSize));
-    POINT_HIP(P.logtab.reserve((size_t)6 * kTableSize));
-    POINT_HIP(hipMemcpyAsync(P.tables, tables, sizeof(double) * 6 * kTableSize, hipMemcpyHostToDevice, stream));
-    if (launch_log_table(P.tables, 1, P.logtab, stream)) { *err = "table kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
-    POINT_HIP(hipStreamSynchronize(stream));
-    P.tables_ready = true;
-    return 0;
+    POINT_HIP(P.current.reserve(1));
+    return tables_from_host(P.current, stream, tables, 1, err);
 }
 
-int point_get_tables(PointState &P, hipStream_t stream, double *tables, std::string *err)
+int point_get_tables(const TableSets &S, hipStream_t stream, int k, double *tables, std::string *err)
 {
-    if (!P.tables_ready) { *err = "no rate tables: call ftte_stellar_beta_table or ftte_set_rate_tables first"; return FTTE_ERR_STATE; }
-    POINT_HIP(hipMemcpyAsync(tables, P.tables, sizeof(double) * 6 * kTableSize, hipMemcpyDeviceToHost, stream));
+    POINT_HIP(hipMemcpyAsync(tables, S.tables + (size_t)k * kSetDoubles, sizeof(double) * kSetDoubles, hipMemcpyDeviceToHost, stream));
     POINT_HIP(hipStreamSynchronize(stream));
     return 0;
 }
 
 int point_lookup(PointState &P, hipStream_t stream, int dust, int nsample, const double *tau, double *rates, std::string *err)
 {
-    if (!P.tables_ready) { *err = "no rate tables: call ftte_stellar_beta_table or ftte_set_rate_tables first"; return FTTE_ERR_STATE; }
+    if (!P.current.count) { *err = "no rate tables: call ftte_stellar_beta_table or ftte_set_rate_tables first"; return FTTE_ERR_STATE; }
     POINT_HIP(P.sample_in.reserve((size_t)4 * nsample));
     POINT_HIP(P.sample_out.reserve((size_t)6 * nsample));
     POINT_HIP(hipMemcpyAsync(P.sample_in, tau, sizeof(double) * 4 * nsample, hipMemcpyHostToDevice, stream));
-    if (launch_rate_lookup(P.logtab, dust, nsample, P.sample_in, P.sample_out, stream)) { *err = "look-up kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
+    if (launch_rate_lookup(P.current.logtab, dust, nsample, P.sample_in, P.sample_out, stream)) { *err = "look-up kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
     POINT_HIP(hipMemcpyAsync(rates, P.sample_out, sizeof(double) * 6 * nsample, hipMemcpyDeviceToHost, stream));
     POINT_HIP(hipStreamSynchronize(stream));
     return 0;
 }
 
-int point_set_medium(PointState &P, hipStream_t stream, int64_t ncell, const double *const field[5], bool on_device, int dust,
+int point_set_medium(GasState &G, hipStream_t stream, int64_t ncell, const double *const field[5], bool on_device, int dust,
                      std::string *err)
 {
-    if (P.medium_cells != ncell) {
-        for (auto &m : P.medium) m.reset();
-        P.packed.reset();
-        P.medium_cells = 0;
-        P.medium_ready = false;
-    }
-    P.packed_ready = false;
-    for (int f = 0; f < 5; ++f) {
-        POINT_HIP(P.medium[f].reserve((size_t)ncell));
+    POINT_HIP(G.reserve(ncell));
+    for (int f = 0; f < GasState::kFields; ++f) {
         if (field[f])
-            POINT_HIP(hipMemcpyAsync(P.medium[f], field[f], sizeof(double) * ncell, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
+            POINT_HIP(hipMemcpyAsync(G.field(f), field[f], sizeof(double) * ncell, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, stream));
         else
-            POINT_HIP(hipMemsetAsync(P.medium[f], 0, sizeof(double) * ncell, stream)); // rho, abun2 are only read with dust
+            POINT_HIP(hipMemsetAsync(G.field(f), 0, sizeof(double) * ncell, stream)); // rho, abun2 are only read with dust
     }
     POINT_HIP(hipStreamSynchronize(stream));
-    P.medium_cells = ncell;
-    P.dust = dust;
-    P.medium_ready = true;
-    P.rho_given = field[3] != nullptr;
+    G.filled(ncell, dust, field[GasState::kRho] != nullptr);
     return 0;
 }
 
@@ -498,12 +470,12 @@ int point_set_rates(PointState &P, hipStream_t stream, int64_t ncell, const doub
     return 0;
 }
 
-int point_trace(PointState &P, hipStream_t stream, const AmrTree &tree, double box, int nsrc, const int64_t *src_cell,
+int point_trace(PointState &P, GasState &G, hipStream_t stream, const AmrTree &tree, double box, int nsrc, const int64_t *src_cell,
                 const double *src_ndot, const int32_t *src_slot, int *highest_pixel_level, int *highest_per_star, std::string *err)
 {
-    if (!src_slot && !P.tables_ready) { *err = "no rate tables: call ftte_stellar_beta_table or ftte_set_rate_tables first"; return FTTE_ERR_STATE; }
-    if (src_slot && !P.nslots) { *err = "no population slots: call ftte_stellar_beta_tables or ftte_set_population_tables first"; return FTTE_ERR_STATE; }
-    if (!P.medium_ready || P.medium_cells != tree.ncell) { *err = "no medium: call ftte_set_medium after ftte_set_grid"; return FTTE_ERR_STATE; }
+    if (!src_slot && !P.current.count) { *err = "no rate tables: call ftte_stellar_beta_table or ftte_set_rate_tables first"; return FTTE_ERR_STATE; }
+    if (src_slot && !P.slots.count) { *err = "no population slots: call ftte_stellar_beta_tables or ftte_set_population_tables first"; return FTTE_ERR_STATE; }
+    if (!G.ready(tree.ncell)) { *err = "no medium: call ftte_set_medium after ftte_set_grid"; return FTTE_ERR_STATE; }
     int rc;
     if (!P.rates || P.rates_cells != tree.ncell)
         if ((rc = point_zero_rates(P, stream, tree.ncell, err))) return rc;
@@ -520,11 +492,11 @@ int point_trace(PointState &P, hipStream_t stream, const AmrTree &tree, double b
         }
         P.tree_ready = true;
     }
-    if (!P.packed_ready) {
-        POINT_HIP(P.packed.reserve((size_t)kCellRec * tree.ncell));
-        const double *const fields[5] = {P.medium[0], P.medium[1], P.medium[2], P.medium[3], P.medium[4]};
-        if (launch_pack_medium(fields, P.packed, (long)tree.ncell, stream)) { *err = "layout kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
-        P.packed_ready = true;
+    POINT_HIP(G.reserve_packed(kCellRec));
+    if (!G.packed_current()) {
+        const double *const fields[5] = {G.field(0), G.field(1), G.field(2), G.field(3), G.field(4)};
+        if (launch_pack_medium(fields, G.packed(), (long)tree.ncell, stream)) { *err = "layout kernel failed to launch"; return FTTE_ERR_NO_DEVICE; }
+        G.packed_made();
     }
     if (!P.pixdir) {
         // unit vectors of every pixel of levels 1..6.  The reference evaluates cos(phi)*cos(theta), sin(phi)*cos(theta),
@@ -567,9 +539,9 @@ int point_trace(PointState &P, hipStream_t stream, const AmrTree &tree, double b
     }
     if (src_slot) {
         for (int s = 0; s < nsrc; ++s)
-            if (src_slot[s] < 0 || src_slot[s] >= P.nslots) {
+            if (src_slot[s] < 0 || src_slot[s] >= P.slots.count) {
                 *err = "ftte_point_sources_populations: star " + std::to_string(s) + " names slot " + std::to_string(src_slot[s]) +
-                       ", outside 0.." + std::to_string(P.nslots - 1);
+                       ", outside 0.." + std::to_string(P.slots.count - 1);
                 return FTTE_ERR_ARG;
             }
         // all stars of the call at once; a batch reads from its first star on, as it does in the escape records
@@ -591,9 +563,9 @@ int point_trace(PointState &P, hipStream_t stream, const AmrTree &tree, double b
         T.kpc = W(1.e3) * W(3.08568025e18); // definitionsModule.f90:21-22
     }
     T.node = tree.refined() ? P.node : nullptr;
-    T.n = tree.n; T.dust = P.dust; T.ncell = tree.ncell; T.box = box;
-    T.medium = P.packed;
-    T.logtab = src_slot ? P.slot_logtab : P.logtab; T.pixdir = P.pixdir;
+    T.n = tree.n; T.dust = G.dust(); T.ncell = tree.ncell; T.box = box;
+    T.medium = G.packed();
+    T.logtab = src_slot ? P.slots.logtab : P.current.logtab; T.pixdir = P.pixdir;
     T.slot_stride = (int64_t)6 * kTableSize;
     T.rmax[0] = 0.0;
     for (int L = 1; L <= kMaxPixelLevel; ++L) T.rmax[L] = P.rmax[L - 1];

@@ -2,7 +2,7 @@
 // tables (stellarBetaTable.f90), the table look-up (getRatesHydrogenHelium, equiSources.f90:4157-4311) and
 // the long-characteristics tracer with HEALPix ray splitting (startNewLongRay, equiSources.f90:3120-3385).
 #pragma once
-#include <hip/hip_runtime.h>
+#include <hip/hip_runtime_api.h>
 
 #include <cstdint>
 #include <string>
@@ -10,33 +10,41 @@
 
 #include "ftte_amr.h"
 #include "ftte_device.h"
+#include "ftte_gas.h"
 #include "ftte_internal.h"
 
 namespace ftte {
 
 constexpr int kFrequencies = 400;    // nfreq, stellarBetaTable.f90:14
 constexpr int kSplitBatch = 1024;    // sources traced together; bounds the split queues (3072 records each)
+constexpr size_t kSetDoubles = (size_t)6 * kTableSize; // one set of rate tables, and as many logarithms
 
-// Everything the point-source path keeps on the device.  Owned by the context.
+// `count` sets of rate tables side by side, [count][6][11^4], and their logarithms.  Used twice: the current tables (count 0 or 1)
+// and the population slots, for stars that name the slot they read.
+struct TableSets {
+    DeviceBuffer<double> tables, logtab;
+    int count = 0; // sets that hold what was put there last: 0 from the moment a buffer is replaced until the new ones are filled
+
+    // Room for n sets.  Buffers that have it stay, and the sets in them; on failure nothing is held.
+    hipError_t reserve(int n)
+    {
+        const size_t want = (size_t)n * kSetDoubles;
+        if (tables.capacity() < want || logtab.capacity() < want) count = 0;
+        hipError_t e = tables.reserve(want);
+        if (e == hipSuccess) e = logtab.reserve(want);
+        if (e != hipSuccess) { tables.reset(); logtab.reset(); count = 0; }
+        return e;
+    }
+};
+
+// What the point-source path keeps on the device: the tree, the rate tables, the rates it adds into, the tracer's scratch.  Owned
+// by the context.  The medium it traces through is the context's GasState (ftte_gas.h).
 struct PointState {
     // the tree, uploaded on first use after ftte_set_grid (nothing is uploaded for a uniform grid)
     DeviceBuffer<NodeRec> node;
     bool tree_ready = false;
     std::vector<int32_t> node_of_leaf; // cell-array index -> node
-    // HI, HeI, HeII, rho, abun2 in cell-array order
-    DeviceBuffer<double> medium[5];
-    int64_t medium_cells = 0;
-    int dust = 0;
-    bool medium_ready = false;
-    DeviceBuffer<double> packed; // [ncell][kCellRec] copy the tracer reads, rebuilt when the medium changes
-    bool packed_ready = false;
-    bool rho_given = false;   // ftte_set_medium received a density (the equilibrium update needs it)
-    // [6][11^4] rate tables and their logarithms
-    DeviceBuffer<double> tables, logtab;
-    bool tables_ready = false;
-    // population slots: nslots table sets side by side, [nslots][6][11^4] each, for stars that name the slot they read
-    DeviceBuffer<double> slot_tables, slot_logtab;
-    int nslots = 0;
+    TableSets current, slots; // the tables every star of ftte_point_sources reads; the population slots
     DeviceBuffer<FreqBin> bins; // [populations of the call][kFrequencies - 1]
     DeviceBuffer<double> pixdir; // [kPixelCount][3]
     double rmax[30];
@@ -59,7 +67,7 @@ struct PointState {
     DeviceBuffer<double> sigma_ratio;    // device [4][300]: outputSigma* / threshold cross-section (stellarBetaTable.f90:119-152)
     bool sigma_ready = false;
 
-    void drop_grid(); // after ftte_set_grid: tree, medium and rates belong to the old grid
+    void drop_grid(); // after ftte_set_grid: tree and rates belong to the old grid
 };
 
 // dustCrossSection, dustModule.f90:30-73 (SMC branch); a_smc is the Fortran array a_smc(7,5), lambda in micron
@@ -91,19 +99,20 @@ int point_stellar_beta_tables(PointState &P, hipStream_t stream, const double *a
                               int nspectrum, int nmetal, const double *spec, int npop, const int *iSpectrum, const double *coefSpectrum,
                               const int *iMetal, const double *coefMetal, double *total_integral, std::string *err);
 int point_set_population_tables(PointState &P, hipStream_t stream, int npop, const double *tables, std::string *err);
-int point_get_population_tables(PointState &P, hipStream_t stream, int slot, double *tables, std::string *err);
 int point_set_tables(PointState &P, hipStream_t stream, const double *tables, std::string *err);
-int point_get_tables(PointState &P, hipStream_t stream, double *tables, std::string *err);
+// set k of S (the caller has checked that there is one) to the host
+int point_get_tables(const TableSets &S, hipStream_t stream, int k, double *tables, std::string *err);
 int point_lookup(PointState &P, hipStream_t stream, int dust, int nsample, const double *tau, double *rates, std::string *err);
-int point_set_medium(PointState &P, hipStream_t stream, int64_t ncell, const double *const field[5], bool on_device, int dust,
+// fills the gas: field[5] = HI, HeI, HeII, rho, abun2 on the host or the device; rho and abun2 may be null (zeros)
+int point_set_medium(GasState &G, hipStream_t stream, int64_t ncell, const double *const field[5], bool on_device, int dust,
                      std::string *err);
 int point_zero_rates(PointState &P, hipStream_t stream, int64_t ncell, std::string *err);
 // rates in the interface's layout [6][ncell], in device memory (valid until the next trace)
 int point_rate_planes(PointState &P, hipStream_t stream, double **planes, std::string *err);
 int point_set_rates(PointState &P, hipStream_t stream, int64_t ncell, const double *planes_host, std::string *err);
 // src_slot[nsrc]: the population slot each star reads, or null: all read the current tables.  highest_pixel_level: the maximum
-// over the stars; highest_per_star[nsrc]: each star's own.  Either may be null.
-int point_trace(PointState &P, hipStream_t stream, const AmrTree &tree, double box, int nsrc, const int64_t *src_cell,
+// over the stars; highest_per_star[nsrc]: each star's own.  Either may be null.  Makes the gas's packed copy where it is not current.
+int point_trace(PointState &P, GasState &G, hipStream_t stream, const AmrTree &tree, double box, int nsrc, const int64_t *src_cell,
                 const double *src_ndot, const int32_t *src_slot, int *highest_pixel_level, int *highest_per_star, std::string *err);
 // outputSigma24, 25, 26, Dust [4][300] (absolute cross-sections, as the reference's module arrays hold them)
 int point_set_output_sigma(PointState &P, hipStream_t stream, const double *sigma, std::string *err);
