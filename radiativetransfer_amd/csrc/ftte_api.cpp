@@ -441,6 +441,7 @@ long long ftte_counter(const ftte_ctx *c, const char *name)
     if (!std::strcmp(name, "fine_block")) return (c->hplan.valid && c->hplan.worthwhile && c->hplan.fine.active) ? c->hplan.fine.n : 0;
     if (!std::strcmp(name, "brick_form")) return c->last_brick_form;
     if (!std::strcmp(name, "brick_dataflow")) return c->last_brick_dataflow;
+    if (!std::strcmp(name, "brick_whole")) return c->last_brick_whole; // 1: the last sweep's stage launches took the whole-brick form
     if (!std::strcmp(name, "brick_chunk")) return c->bplan.valid ? c->bplan.chunk : 0;
     if (!std::strcmp(name, "brick_queue_mix")) return (c->bplan.valid && c->bplan.persistent) ? c->bplan.qmix : -1;
     if (!std::strcmp(name, "brick_groups")) return c->bplan.valid ? (long long)c->bplan.groups.size() : 0;

@@ -126,19 +126,47 @@ __device__ __forceinline__ void brick_step(const ftte_consts &K, double lead, do
             }
         }
     }
-    // VUVB: vuvb is where the inflow lies in memory (brick_kernel<..., WHOLE>).  A brick at the domain's lower v-face then loads its
-    // inflow from there: one load on either path, whose wait the compiler can count, instead of a load on one path and a register on
-    // the other
-    if (HAS_V && VUVB) carry = *(gcdouble *)(vin ? vin + 8 * lane : vuvb);
+    // VUVB: vuvb is where the inflow lies in memory (brick_kernel<..., WHOLE>: no `through`, no `same_launch`, no lane range).  A brick at
+    // the domain's lower v-face then loads its inflow from there: one load on either path, whose wait the compiler can count, instead
+    // of a load on one path and a register on the other.
+    // And row 0 comes last: what row r takes from below is row r - 1's ray after that row's OWN pieces, never after its work on the
+    // ray it received, so row 0's pieces on the ray from the brick below feed nothing in this step.  Row 0 runs its own pieces, rows
+    // 1 .. RW - 1 run as ever, row 0's pieces on `face` come last: the load has the whole step to arrive, and the one wait for it
+    // stands at the end of the step.  Every segment, every cell's sum and every Jacc[r] += keeps its operands and their order.
+    constexpr bool FACE_LAST = HAS_V && VUVB;
+    double face = uvb, own0 = 0.0, own1 = 0.0; // row 0: the ray from the brick below, the means of its own pieces
+    if (FACE_LAST) face = *(gcdouble *)(vin ? vin + 8 * lane : vuvb);
     else if (HAS_V && vin) carry = same_launch ? fresh(vin + 8 * lane) : *(gcdouble *)(vin + 8 * lane);
     if (HAS_V && carry_in) carry = carry_in[lane]; // pair kernel: the wavefront below left it in LDS
     const bool hands_u = HAS_U && uout != nullptr && lane == hand_lane;
+    // The hand-over to the right is one lane's store.  Behind a branch the compiler cannot tell whether it was issued, and the wait
+    // for `face`, which is older, becomes vmcnt(0).  As a buffer store every lane issues it: the ring slot is the buffer (no bytes
+    // where nobody is to the right), the lanes that hand nothing over point past its end, and the hardware drops their part.
+    constexpr bool U_COUNTED = FACE_LAST && HAS_U;
+    unsigned upast = 0; // (one register; the row is the instruction's own offset)
+    if constexpr (U_COUNTED) upast = here(lane == hand_lane ? 0u : 0x40000000u);
+    auto hand_u = [&](int r, double x) __attribute__((always_inline)) {
+        typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+        __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, x), __builtin_amdgcn_make_buffer_rsrc((void *)uout, (short)0, uout ? 8 * RW : 0, 0x00020000),
+                                              upast + 8u * r, 0, 0);
+    };
 
 #pragma unroll
     for (int r = 0; r < RW; ++r) {
         double I = cur[r];
         const double m0 = brick_segment<EMIT>(K, lead, I, kap[r], xs[EMIT ? r : 0], d0); // xy piece, in the ray's own cell
         double acc = m0;
+        if (FACE_LAST && r == 0) { // its own pieces, and what row 1 takes from it; the rest after the top row
+            own0 = m0;
+            if (SHAPE == RC_THREE_U) {
+                hand_u(0, I);
+                I = shift_up_inject(I, ui[0]);
+                own1 = brick_segment<EMIT>(K, lead, I, kap[0], xs[0], d1);
+            }
+            carry = I;
+            __builtin_amdgcn_sched_barrier(0);
+            continue;
+        }
         if (SHAPE == RC_ONE) {
             cur[r] = I;
             Jacc[r] += ftte_cell_mean(acc, 1, w);
@@ -156,7 +184,8 @@ __device__ __forceinline__ void brick_step(const ftte_consts &K, double lead, do
             cur[r] = b;
             Jacc[r] += ftte_cell_mean(acc, 2, w);
         } else if (SHAPE == RC_THREE_U) { // 2nd piece one column on, 3rd one row on
-            if (hands_u) { if (through) __hip_atomic_store((double *)(uout + 8 * r), I, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else *(gdouble *)(uout + 8 * r) = I; }
+            if (U_COUNTED) hand_u(r, I);
+            else if (hands_u) { if (through) __hip_atomic_store((double *)(uout + 8 * r), I, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else *(gdouble *)(uout + 8 * r) = I; }
             I = shift_up_inject(I, ui[r]);
             if (take_lane) I = lane == take_lane ? ui[r] : I;
             const double m1 = brick_segment<EMIT>(K, lead, I, kap[r], xs[EMIT ? r : 0], d1);
@@ -178,7 +207,8 @@ __device__ __forceinline__ void brick_step(const ftte_consts &K, double lead, do
             double b = carry;
             carry = I;
             const double m1 = brick_segment<EMIT>(K, lead, b, kap[r], xs[EMIT ? r : 0], d1);
-            if (hands_u) { if (through) __hip_atomic_store((double *)(uout + 8 * r), b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else *(gdouble *)(uout + 8 * r) = b; }
+            if (U_COUNTED) hand_u(r, b);
+            else if (hands_u) { if (through) __hip_atomic_store((double *)(uout + 8 * r), b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); else *(gdouble *)(uout + 8 * r) = b; }
             b = shift_up_inject(b, ui[r]);
             if (take_lane) b = lane == take_lane ? ui[r] : b;
             const double m2 = brick_segment<EMIT>(K, lead, b, kap[r], xs[EMIT ? r : 0], d2);
@@ -195,6 +225,35 @@ __device__ __forceinline__ void brick_step(const ftte_consts &K, double lead, do
         }
         asm volatile("" : "+v"(Jacc[r]));
         __builtin_amdgcn_sched_barrier(0); // rows in program order: interleaved they multiply the live registers
+    }
+    if (FACE_LAST) { // row 0's pieces on the ray from below; the empty asm is where the step waits for it, once
+        asm volatile("" : "+v"(face));
+        double acc = own0;
+        if (SHAPE == RC_TWO_V) {
+            acc += brick_segment<EMIT>(K, lead, face, kap[0], xs[0], d1);
+        } else {
+            double m1 = own1, m2;
+            if (SHAPE == RC_THREE_U) {
+                m2 = brick_segment<EMIT>(K, lead, face, kap[0], xs[0], d2);
+            } else {
+                m1 = brick_segment<EMIT>(K, lead, face, kap[0], xs[0], d1);
+                hand_u(0, face);
+                face = shift_up_inject(face, ui[0]);
+                m2 = brick_segment<EMIT>(K, lead, face, kap[0], xs[0], d2);
+            }
+            if (third_first) {
+                acc += m2;
+                acc += m1;
+                asm volatile("" : "+v"(acc));
+            } else {
+                acc += m1;
+                acc += m2;
+            }
+        }
+        cur[0] = face;
+        Jacc[0] += ftte_cell_mean(acc, SHAPE == RC_TWO_V ? 2 : 3, w);
+        asm volatile("" : "+v"(Jacc[0]));
+        __builtin_amdgcn_sched_barrier(0);
     }
     if (HAS_V && carry_out) carry_out[lane] = carry; // pair kernel: for the wavefront above
     if (HAS_V && vout && active) { // the top row's ray goes on in the brick above
@@ -796,6 +855,12 @@ int launch_brick_pair(const BrickLaunch &L, int max_dirs, int waves, hipStream_t
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
+// whole bricks, no emission, no dataflow, no diagnostic option: the form whose layer loop has only counted waits (brick_kernel's WHOLE)
+bool brick_whole_form(const BrickLaunch &L, int waves, bool masked)
+{
+    return !masked && !L.emit && !L.ticket && !L.queue && waves == 4 && L.n % 64 == 0 && L.n % kBrickRows == 0 && !L.atomic_acc && !L.pad2_;
+}
+
 int launch_brick(const BrickLaunch &L, int max_dirs, int waves, hipStream_t stream, bool masked, int persistent)
 {
     if (L.ntasks <= 0) return 0;
@@ -828,8 +893,7 @@ int launch_brick(const BrickLaunch &L, int max_dirs, int waves, hipStream_t stre
     case 2: hipLaunchKernelGGL((brick_kernel<2, 0, 0>), grid, dim3(64), lds, stream, L); break;
     case 3: hipLaunchKernelGGL((brick_kernel<3, 0, 0>), grid, dim3(64), lds, stream, L); break;
     case 4:
-        // whole bricks, no diagnostic option: the form whose layer loop has only counted waits (brick_kernel's WHOLE)
-        if (L.n % 64 == 0 && L.n % kBrickRows == 0 && !L.atomic_acc && !L.pad2_) hipLaunchKernelGGL((brick_kernel<4, 0, 0, false, true>), grid, dim3(64), lds, stream, L);
+        if (brick_whole_form(L, waves, masked)) hipLaunchKernelGGL((brick_kernel<4, 0, 0, false, true>), grid, dim3(64), lds, stream, L);
         else hipLaunchKernelGGL((brick_kernel<4, 0, 0>), grid, dim3(64), lds, stream, L);
         break;
     default: return -1;

@@ -14,6 +14,7 @@ int launch_sweep(const LaunchRec &L, int rows, int waves, int stack, int nnu, hi
 // one stage of the cell-fixed brick sweep; max_dirs: directions of the launch's largest group (sizes the LDS); waves 2..4
 // persistent > 0 (BrickLaunch::queue set): the whole sweep in one launch of that many workgroups, a task queue per XCD
 int launch_brick(const BrickLaunch &L, int max_dirs, int waves, hipStream_t stream, bool masked = false, int persistent = 0);
+bool brick_whole_form(const BrickLaunch &L, int waves, bool masked = false); // does launch_brick take brick_kernel's WHOLE form for this launch?
 int launch_xcc_census(unsigned *mask_dev, hipStream_t stream); // bit x of *mask_dev set: some workgroup ran on the XCD whose HW_REG_XCC_ID is x
 int launch_brick_pair(const BrickLaunch &L, int max_dirs, int waves, hipStream_t stream); // two wavefronts per brick, four rows each
 // cell-array order -> layout 1 ([jc][ic][kc]) or 2 ([kc][ic][jc]); nnu groups, group_stride apart

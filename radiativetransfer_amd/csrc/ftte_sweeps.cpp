@@ -672,6 +672,7 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
             }
             c->last_brick_form = 0;
             c->last_brick_dataflow = P.persistent ? 3 : c->dataflow == 2 ? 2 : 1;
+            c->last_brick_whole = 0;
             const int lrc = launch_brick(L, P.max_dirs, c->brick_waves, stream, false, persistent);
             if (lrc) return fail(c, lrc == -1 ? FTTE_ERR_ARG : FTTE_ERR_NO_DEVICE, "brick kernel launch failed");
             FTTE_HIP(c, hipMemcpyAsync(c->h_berror, c->d_bsync, sizeof(uint32_t) * kSyncWords, hipMemcpyDeviceToHost, stream));
@@ -733,6 +734,7 @@ int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, c
                 const int form = brick_form(c, nnu);
                 c->last_brick_form = form;
                 c->last_brick_dataflow = 0;
+                c->last_brick_whole = form != 2 && brick_whole_form(L, c->brick_waves);
                 const int lrc = form == 2 ? launch_brick_pair(L, P.max_dirs, c->pair_waves, q) : launch_brick(L, P.max_dirs, c->brick_waves, q);
                 if (lrc) return fail(c, lrc == -1 ? FTTE_ERR_ARG : FTTE_ERR_NO_DEVICE, "brick kernel launch failed");
                 if ((rc = merge_point())) return rc;
