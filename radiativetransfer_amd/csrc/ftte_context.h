@@ -4,7 +4,9 @@
 // ftte_chem.cpp its part that reads or writes the species medium.
 //
 // Every device buffer, pinned buffer, stream, event and graph of the context is a member that owns it (ftte_device.h): a buffer's
-// capacity travels with its pointer, `delete c` releases everything, and a new buffer is added by declaring it.
+// capacity travels with its pointer, `delete c` releases everything, and a new buffer is added by declaring it.  What a buffer
+// holds has an owner as well: the medium's fields (ftte_medium.h), the gas (ftte_gas.h), and for the brick sweeps the tables of a
+// plan, the buffers that remember what they were sent and the state of the one-launch forms (ftte_bricks.h).
 //
 // There is no CPU fallback behind any of this: every entry point that computes on the grid needs a HIP device and fails with
 // FTTE_ERR_NO_DEVICE otherwise.
@@ -24,10 +26,9 @@
 
 #include "../../include/ftte.h"
 #include "ftte_amr.h"
-#include "ftte_device.h"
+#include "ftte_bricks.h"
 #include "ftte_gas.h"
 #include "ftte_geometry.h"
-#include "ftte_internal.h"
 #include "ftte_kernels.h"
 #include "ftte_lambda.h"
 #include "ftte_medium.h"
@@ -38,18 +39,6 @@ namespace ftte {
 
 
 extern std::string g_create_error; // what ftte_last_error(NULL) returns
-
-// one planned direction
-struct DirPlan {
-    int izone = 0, layout = 0;
-    double phi = 0, theta = 0, w = 0;
-    int64_t org = 0;
-    int si = 0, sv = 0, su = 0;
-    int u_lo = 1, v_lo = 1, ntu = 0, ntv = 0;
-    int du_mid = 0, dv_mid = 0; // drift at the middle layer: where a tile's rays are halfway through the grid
-    size_t layer_off = 0; // into the layer table
-    int slot = 0;
-};
 
 struct LaunchPlan {
     int layout = 0;
@@ -73,45 +62,6 @@ struct Plan {
     std::vector<WorkItem> items;
     std::vector<LaunchPlan> launches;
     bool used[3][kMaxSlots] = {};
-};
-
-// The brick organisation of the same sweep (ftte_brick.hip): directions grouped by izone, bricks ordered into stages
-struct BrickPlan {
-    bool valid = false;
-    // key
-    int n = 0, chunk = 0, gmax = 0, share = 0, want_glanes = 0, want_dataflow = 0;
-    double box = 0;
-    std::vector<double> phi, theta, w;
-    // content
-    std::vector<DirPlan> dirs;
-    std::vector<LayerRec> layers;
-    struct Group { int izone = 0, layout = 0, acc = 0, offset = 0, lane = 0; std::vector<int> dirs; };
-    std::vector<Group> groups;
-    std::vector<BrickTask> tasks;      // stage after stage
-    bool dataflow = false;             // one launch, bricks wait for each other through flags (needs whole bricks: n % 64 == 0)
-    std::vector<int32_t> deps;         // [tasks][kBrickDeps]
-    // persistent form (option "dataflow" = 3): one queue of (task, frequency slot) pairs per XCD, whole dependency chains each
-    bool persistent = false;
-    int qnnu = 0, nq = 0, qmix = 0;    // frequency groups and XCDs the queues were cut for, option "queue_mix"
-    std::vector<uint32_t> queue;       // work ids task * nnu + slot, queue after queue
-    uint32_t qoff[kBrickQueues] = {}, qlen[kBrickQueues] = {};
-    int64_t qload[kBrickQueues] = {};  // cell.direction.frequency updates per queue (balance: instrumentation)
-    int ut = kBrickRows, uw = 0;       // u-face ring: doubles per brick and layer, per layer
-    int64_t uqface_off = 0;            // BrickLaunch::uqface_off
-    int nslot = 2;                     // face slots along the march (BrickLaunch::nslot)
-    int glanes = 1, nstages = 0;       // the groups are dealt to `glanes` streams (the groups of one accumulator stay together)
-    std::vector<size_t> stage_off;     // [glanes][nstages + 1] into tasks
-    int64_t updates = 0;               // cell.direction updates of a sweep (per frequency group)
-    int ntu = 0, ntv = 0, nti = 0, up = 0, vp = 0, max_dirs = 0;
-    int64_t face_elems = 0, vface_off = 0, iface_off = 0;
-    int nacc[3] = {0, 0, 0};
-    // Merge blocks (option "merge_overlap", stages on one lane of groups): kMergeBlock^3 cells aligned with merge_kernel's tiles.
-    // Merge point m runs after stage merge_stage[m] and sums the blocks merge_blocks[merge_off[m] .. merge_off[m + 1]) (block id
-    // (bi * nmb + bj) * nmb + bk, bi along ic): those whose last writer is in a stage after merge_stage[m - 1] and not after merge_stage[m].
-    int nmb = 0;
-    std::vector<int32_t> merge_blocks;
-    std::vector<int> merge_stage;
-    std::vector<size_t> merge_off;
 };
 
 struct LaunchTiming {
@@ -169,28 +119,18 @@ struct ftte_ctx {
     int atomic_acc = 0;               // option "atomic_acc": later visitors of an accumulator add with fp64 atomics instead of read-add-store
     int ablate = 0;                   // diagnostic option "ablate": parts of the brick kernel's memory traffic left out (wrong J; timing only)
     int queue_mix = 0;                // persistent form: 0 = a frequency group per queue where they divide, else by load; 1 = by load; 2 = (group + accumulator) mod queues
-    DeviceBuffer<int32_t> d_bdeps;
-    DeviceBuffer<uint32_t> d_bdone;
-    DeviceBuffer<uint32_t> d_bsync;   // [32 q] ticket of queue q (one counter, [0], without queues), [32 kBrickQueues] error
-    PinnedBuffer<uint32_t> h_berror;  // pinned: [0] the error flag of the last dataflow sweep, [1 + q] its tickets, copied back behind it
-    uint32_t bqlen[kBrickQueues] = {}; // what those tickets must have reached (0: no persistent sweep pending)
-    DeviceBuffer<uint32_t> d_bqueue; bool bqueue_uploaded = false;
+    BrickDataflow bflow;              // flags, tickets and error word of the one-launch forms: brick_sweep prepares, wait_sweep checks
     int xcc_count = -1;               // XCC ids this device reports (census, ftte_brick.hip); -1: not taken yet
     int8_t xcc_queue[16] = {};        // XCC id -> 0 .. xcc_count - 1, or -1
-    uint32_t bepoch = 0;
+    long long brick_plans = 0;        // brick plans built so far (BrickPlan::id counts from 1)
     BrickPlan bplan;
-    bool bplan_uploaded = false;
-    DeviceBuffer<LayerRec> d_blayers;
-    DeviceBuffer<BrickGroup> d_bgroups;
-    DeviceBuffer<BrickTask> d_btasks;
+    BrickTables btables;              // the device side of bplan, or of the hybrid sweep's base plan (hplan.bricks): whichever swept last
     DeviceBuffer<double> d_faces;
 
     Plan plan;
     DeviceBuffer<LayerRec> d_layers;
     DeviceBuffer<WorkItem> d_items;
-    DeviceBuffer<double> d_uvb;
-    std::vector<char> bgroups_sent;   // the bytes d_bgroups holds (brick_sweep), empty: unknown
-    std::vector<double> uvb_sent;     // the values d_uvb holds (brick_sweep), empty: unknown
+    Sent<double> d_uvb;               // the background of the last sweep, whichever path it took
     bool plan_uploaded = false;
 
     std::vector<LaunchTiming> timing;
@@ -220,7 +160,6 @@ struct ftte_ctx {
     // (BrickPlan::merge_blocks), behind ev_merge_point[lane * points + m] of each lane; 0 = one merge after the last stage
     int merge_overlap = 1;
     std::vector<Event> ev_merge_point;
-    DeviceBuffer<int32_t> d_mblocks;
     // end of the last sweep on whatever stream the caller gave it: the setters and the next sweep wait for it before they
     // overwrite what that sweep reads
     Event ev_sweep_done;
@@ -258,7 +197,6 @@ struct ftte_ctx {
         std::vector<Dir> dirs;
         DeviceBuffer<int32_t> cells; int64_t ncells = 0; // the leaves inside the box of at least one direction
         long long cells_id = 0;           // which list of this context that is (ftte_ctx::leaf_lists): what the medium's cell-major copies follow
-        bool uploaded = false;
         // A fully refined block swept by bricks of its own on the fine level (option "fine_bricks"; one cluster that is a cube of
         // base cells refined exactly once, twice its side a multiple of 64): inside it the fine cells are a uniform grid
         // with a pattern per sub-layer, and the forest keeps only what lies around it (ftte_amr.h: ForestRegion::has_fine)
@@ -272,7 +210,7 @@ struct ftte_ctx {
             int64_t face_base = 0;              // where the fine face block starts inside a direction's face block (= bricks.face_elems)
             int64_t updates = 0;                // cell.direction updates the fine bricks perform (per frequency group)
             DeviceBuffer<int32_t> leaf_of_fine; // device: [n^3], fine cell in storage order -> leaf
-            DeviceBuffer<LayerRec> layers; DeviceBuffer<BrickTask> tasks; DeviceBuffer<BrickGroup> groups; // device
+            BrickTables tables;                 // device: the side of `plan` (uploaded when the plan is built)
         } fine;
     } hplan;
     long long leaf_lists = 0;         // leaf lists built so far (HybridPlan::cells_id counts from 1)

@@ -635,8 +635,7 @@ int build_hybrid_plan(ftte_ctx *c, int ndir, const double *phi, const double *th
         if (in_any[(size_t)q]) { place[(size_t)q] = (int32_t)cells.size(); cells.push_back((int32_t)q); }
     H.ncells = (int64_t)cells.size();
     H.cells_id = ++c->leaf_lists; // (a new list: the cell-major copies of the medium made for another one are not current)
-    FTTE_HIP(c, H.cells.reserve(cells.size()));
-    if (!cells.empty()) FTTE_HIP(c, hipMemcpy(H.cells, cells.data(), sizeof(int32_t) * cells.size(), hipMemcpyHostToDevice));
+    FTTE_HIP(c, to_device(H.cells, cells));
     {
         auto renumber = [&](int32_t sg) { return sg < 0 ? sg : 3 * place[(size_t)(sg / 3)] + sg % 3; }; // negative: inflow / import marks
         std::vector<int> bad((size_t)ndir, 0);
@@ -668,18 +667,11 @@ int build_hybrid_plan(ftte_ctx *c, int ndir, const double *phi, const double *th
     }
     for (int d = 0; d < ndir; ++d) {
         ftte_ctx::HybridPlan::Dir &D = H.dirs[(size_t)d];
-        FTTE_HIP(c, D.rec.reserve(rec[(size_t)d].size()));
-        FTTE_HIP(c, D.active.reserve(bytes[(size_t)d].size()));
-        FTTE_HIP(c, D.exports.reserve(exports[(size_t)d].size()));
-        FTTE_HIP(c, hipMemcpy(D.rec, rec[(size_t)d].data(), sizeof(SegRec) * rec[(size_t)d].size(), hipMemcpyHostToDevice));
-        if (!bytes[(size_t)d].empty()) FTTE_HIP(c, hipMemcpy(D.active, bytes[(size_t)d].data(), bytes[(size_t)d].size(), hipMemcpyHostToDevice));
-        if (!exports[(size_t)d].empty())
-            FTTE_HIP(c, hipMemcpy(D.exports, exports[(size_t)d].data(), sizeof(AmrExport) * exports[(size_t)d].size(), hipMemcpyHostToDevice));
+        FTTE_HIP(c, to_device(D.rec, rec[(size_t)d]));
+        FTTE_HIP(c, to_device(D.active, bytes[(size_t)d]));
+        FTTE_HIP(c, to_device(D.exports, exports[(size_t)d]));
         D.nimports = (int64_t)imports[(size_t)d].size();
-        if (D.nimports) {
-            FTTE_HIP(c, D.imports.reserve(imports[(size_t)d].size()));
-            FTTE_HIP(c, hipMemcpy(D.imports, imports[(size_t)d].data(), sizeof(AmrImport) * imports[(size_t)d].size(), hipMemcpyHostToDevice));
-        }
+        if (D.nimports) FTTE_HIP(c, to_device(D.imports, imports[(size_t)d]));
         std::vector<SegRec>().swap(rec[(size_t)d]);
         std::vector<uint8_t>().swap(bytes[(size_t)d]);
     }
@@ -694,16 +686,9 @@ int build_hybrid_plan(ftte_ctx *c, int ndir, const double *phi, const double *th
                     const int32_t node = (int32_t)(((int64_t)(FN.lo[0] - 1 + a / 2) * n + (FN.lo[1] - 1 + b / 2)) * n + (FN.lo[2] - 1 + d / 2));
                     map[((size_t)a * nf + b) * nf + d] = c->tree.leaf[(size_t)(c->tree.child0[(size_t)node] + 4 * (a % 2) + 2 * (b % 2) + (d % 2))];
                 }
-        const BrickPlan &Q = FN.plan;
-        FTTE_HIP(c, FN.leaf_of_fine.reserve(map.size()));
-        FTTE_HIP(c, hipMemcpy(FN.leaf_of_fine, map.data(), sizeof(int32_t) * map.size(), hipMemcpyHostToDevice));
-        FTTE_HIP(c, FN.layers.reserve(Q.layers.size()));
-        FTTE_HIP(c, hipMemcpy(FN.layers, Q.layers.data(), sizeof(LayerRec) * Q.layers.size(), hipMemcpyHostToDevice));
-        FTTE_HIP(c, FN.tasks.reserve(Q.tasks.size()));
-        FTTE_HIP(c, hipMemcpy(FN.tasks, Q.tasks.data(), sizeof(BrickTask) * Q.tasks.size(), hipMemcpyHostToDevice));
-        FTTE_HIP(c, FN.groups.reserve(Q.groups.size()));
+        FTTE_HIP(c, to_device(FN.leaf_of_fine, map));
+        FTTE_HIP(c, FN.tables.upload(FN.plan));
     }
-    H.uploaded = false;
     return FTTE_OK;
 }
 
@@ -728,8 +713,7 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     if (!c->d_leaf_of_base) {
         std::vector<int32_t> map((size_t)nbase);
         for (int64_t b = 0; b < nbase; ++b) map[(size_t)b] = c->tree.leaf[(size_t)b];
-        FTTE_HIP(c, c->d_leaf_of_base.reserve((size_t)nbase));
-        FTTE_HIP(c, hipMemcpy(c->d_leaf_of_base, map.data(), sizeof(int32_t) * (size_t)nbase, hipMemcpyHostToDevice));
+        FTTE_HIP(c, to_device(c->d_leaf_of_base, map));
     }
     const size_t per_base = (size_t)nnu * (size_t)nbase;
     if ((rc = reserve_layouts(c, c->base_kappa, per_base))) return rc;
@@ -743,25 +727,18 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     const int64_t face_elems = P.face_elems + (FN.active ? FN.plan.face_elems : 0);
     const size_t face_need = (size_t)ndir * nnu * (size_t)face_elems;
     FTTE_HIP(c, c->d_faces.reserve(face_need));
-    if (!H.uploaded) {
-        FTTE_HIP(c, c->d_blayers.reserve(P.layers.size()));
-        FTTE_HIP(c, c->d_btasks.reserve(P.tasks.size()));
-        FTTE_HIP(c, c->d_bgroups.reserve(P.groups.size()));
-        FTTE_HIP(c, hipMemcpy(c->d_blayers, P.layers.data(), sizeof(LayerRec) * P.layers.size(), hipMemcpyHostToDevice));
-        if (!P.tasks.empty()) FTTE_HIP(c, hipMemcpy(c->d_btasks, P.tasks.data(), sizeof(BrickTask) * P.tasks.size(), hipMemcpyHostToDevice));
-        H.uploaded = true;
-        c->bplan_uploaded = false; c->bplan.valid = false; // the uniform-grid plan shared these buffers
-    }
-    {
-        std::vector<BrickGroup> G(P.groups.size());
+    FTTE_HIP(c, c->btables.upload(P)); // (the tables the uniform grid's plan uses: whichever of the two swept last holds them)
+    // the group records of a plan: its arrays in the three layouts, its accumulators, its part of every direction's face block
+    auto send_groups = [&](const BrickPlan &Q, BrickTables &T, DeviceBuffer<double> (&kappa)[3], DeviceBuffer<double> (&emis)[3], DeviceBuffer<double> (&acc)[3][kMaxAcc], double *faces) {
+        std::vector<BrickGroup> G(Q.groups.size());
         std::memset(G.data(), 0, sizeof(BrickGroup) * G.size());
-        for (size_t g = 0; g < P.groups.size(); ++g) {
-            const BrickPlan::Group &Hg = P.groups[g];
-            fill_brick_group(G[g], P, g, c->base_kappa[Hg.layout], emit ? c->base_emis[Hg.layout].get() : nullptr, c->acc[Hg.layout][Hg.acc], c->d_blayers,
-                             c->d_faces, (size_t)nnu * (size_t)face_elems);
+        for (size_t g = 0; g < Q.groups.size(); ++g) {
+            const BrickPlan::Group &Hg = Q.groups[g];
+            fill_brick_group(G[g], Q, g, kappa[Hg.layout], emit ? emis[Hg.layout].get() : nullptr, acc[Hg.layout][Hg.acc], T.layers, faces, (size_t)nnu * (size_t)face_elems);
         }
-        FTTE_HIP(c, hipMemcpy(c->d_bgroups, G.data(), sizeof(BrickGroup) * G.size(), hipMemcpyHostToDevice)); c->bgroups_sent.clear();
-    }
+        return T.groups.send(G.data(), G.size());
+    };
+    FTTE_HIP(c, send_groups(P, c->btables, c->base_kappa, c->base_emis, c->acc, c->d_faces));
     if (FN.active) {
         // the fine block's own arrays -- opacities in the three layouts, an accumulator per group -- and its group records
         const BrickPlan &Q = FN.plan;
@@ -771,17 +748,9 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
         for (int l = 0; l < 3; ++l)
             for (int a = 0; a < Q.nacc[l]; ++a) FTTE_HIP(c, c->fine_acc[l][a].reserve(fine_acc_size));
         if (emit && (rc = reserve_layouts(c, c->fine_emis, per_fine))) return rc;
-        std::vector<BrickGroup> G(Q.groups.size());
-        std::memset(G.data(), 0, sizeof(BrickGroup) * G.size());
-        for (size_t g = 0; g < Q.groups.size(); ++g) {
-            const BrickPlan::Group &Hg = Q.groups[g];
-            fill_brick_group(G[g], Q, g, c->fine_kappa[Hg.layout], emit ? c->fine_emis[Hg.layout].get() : nullptr, c->fine_acc[Hg.layout][Hg.acc], FN.layers,
-                             c->d_faces + (size_t)FN.face_base, (size_t)nnu * (size_t)face_elems); // (its faces: behind the base bricks' rings)
-        }
-        FTTE_HIP(c, hipMemcpy(FN.groups, G.data(), sizeof(BrickGroup) * G.size(), hipMemcpyHostToDevice));
+        FTTE_HIP(c, send_groups(Q, FN.tables, c->fine_kappa, c->fine_emis, c->fine_acc, c->d_faces + (size_t)FN.face_base)); // (its faces: behind the base bricks' rings)
     }
-    FTTE_HIP(c, c->d_uvb.reserve((size_t)nnu));
-    FTTE_HIP(c, hipMemcpy(c->d_uvb, uvb, sizeof(double) * nnu, hipMemcpyHostToDevice)); c->uvb_sent.clear();
+    FTTE_HIP(c, c->d_uvb.send(uvb, (size_t)nnu));
 
     // forest scratch: as forest_sweep, for the leaves of the plan's list only
     const size_t per_dir = (size_t)3 * (size_t)std::max<int64_t>(H.ncells, 1) * nnu;
@@ -809,25 +778,13 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     LaunchTiming &Tm = c->timing[0];
     Tm.updates = (int64_t)ndir * ncell * nnu; Tm.lanes = 0;
     c->timing_used = 0;
-    static const ftte_consts kMath = FTTE_CONSTS_INIT;
     const size_t masked_lists = (size_t)H.nhalves * H.nlist;
     auto brick_stages = [&](int half, size_t from, size_t to, hipStream_t q) -> int {
       for (size_t l = from; l < to; ++l)
         for (int masked = 0; masked < 2; ++masked) { // the stage's whole bricks, then those a box cuts through
             const size_t *off = &H.stage_off[(masked ? masked_lists : 0) + (size_t)half * H.nlist];
             if (off[l + 1] == off[l]) continue;
-            BrickLaunch L;
-            std::memset(&L, 0, sizeof L);
-            L.groups = c->d_bgroups;
-            L.tasks = c->d_btasks + off[l];
-            L.uvb = c->d_uvb;
-            L.group_stride = nbase;
-            L.face_stride = face_elems;
-            L.vface_off = P.vface_off; L.iface_off = P.iface_off; L.uqface_off = P.uqface_off;
-            L.n = n; L.ntasks = (int)(off[l + 1] - off[l]); L.nnu = nnu; L.nu0 = 0; L.chunk = P.chunk;
-            L.up = P.up; L.vp = P.vp; L.uw = P.uw; L.ut = P.ut; L.nslot = P.nslot;
-            L.emit = emit;
-            L.math = kMath;
+            const BrickLaunch L = brick_launch(P, c->btables, off[l], off[l + 1], 0, nnu, nbase, face_elems, c->d_uvb, emit);
             const int lrc = launch_brick(L, P.max_dirs, c->brick_waves, q, masked != 0);
             if (lrc) return fail(c, lrc == -1 ? FTTE_ERR_ARG : FTTE_ERR_NO_DEVICE, "brick kernel launch failed");
         }
@@ -846,19 +803,8 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
         for (int st = 0; st < FN.nstages; ++st) {
             const size_t l = (size_t)half * (size_t)FN.nstages + (size_t)st;
             if (FN.stage_off[l + 1] == FN.stage_off[l]) continue;
-            BrickLaunch L;
-            std::memset(&L, 0, sizeof L);
-            L.groups = FN.groups;
-            L.tasks = FN.tasks + FN.stage_off[l];
-            L.uvb = c->d_uvb;
-            L.group_stride = (int64_t)FN.n * FN.n * FN.n;
-            L.face_stride = face_elems;
-            L.vface_off = Q.vface_off; L.iface_off = Q.iface_off; L.uqface_off = Q.uqface_off;
-            L.n = FN.n; L.ntasks = (int)(FN.stage_off[l + 1] - FN.stage_off[l]); L.nnu = nnu; L.nu0 = 0; L.chunk = Q.chunk;
-            L.up = Q.up; L.vp = Q.vp; L.uw = Q.uw; L.ut = Q.ut; L.nslot = Q.nslot;
+            BrickLaunch L = brick_launch(Q, FN.tables, FN.stage_off[l], FN.stage_off[l + 1], 0, nnu, (int64_t)FN.n * FN.n * FN.n, face_elems, c->d_uvb, emit);
             L.sub = 1;
-            L.emit = emit;
-            L.math = kMath;
             const int lrc = launch_brick(L, Q.max_dirs, c->brick_waves, q, false);
             if (lrc) return fail(c, lrc == -1 ? FTTE_ERR_ARG : FTTE_ERR_NO_DEVICE, "brick kernel launch failed");
         }
@@ -871,12 +817,7 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     const int nh = (H.nhalves > 1 && batch >= ndir) ? H.nhalves : 1; // scratch for every direction at once, or one pipeline
     hipStream_t qs[ftte_ctx::kMaxPipes] = {stream, stream, stream, stream};
     if (nh > 1) {
-        while ((int)c->lane_stream.size() < nh - 1) {
-            Stream q; Event e;
-            FTTE_HIP(c, q.create(hipStreamNonBlocking));
-            FTTE_HIP(c, e.create(hipEventDisableTiming));
-            c->lane_stream.push_back(std::move(q)); c->lane_done.push_back(std::move(e));
-        }
+        FTTE_HIP(c, ensure_lanes(c->lane_stream, c->lane_done, (size_t)nh - 1));
         FTTE_HIP(c, c->ev_fork.create(hipEventDisableTiming));
         for (int r = 0; r < nh; ++r) {
             FTTE_HIP(c, c->ev_combine[r].create(hipEventDisableTiming));
@@ -983,19 +924,13 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
 
         // ---- J of the unrefined base cells += what the bricks stored (layout after layout, accumulator after accumulator)
         {
-            const double *accs[3 * kMaxAcc];
-            int layouts[3 * kMaxAcc], count = 0;
-            for (int l = 0; l < 3; ++l)
-                for (int s = 0; s < P.nacc[l]; ++s) { accs[count] = c->acc[l][s]; layouts[count++] = l; }
-            if (count && launch_merge(accs, layouts, count, J_dev, n, nnu, (long)nbase, true, stream, c->d_leaf_of_base, (long)ncell))
+            const AccList B = acc_list(c->acc, P.nacc, kOwnFrame);
+            if (B.count && launch_merge(B.acc, B.layout, B.count, J_dev, n, nnu, (long)nbase, true, stream, c->d_leaf_of_base, (long)ncell))
                 return fail(c, FTTE_ERR_NO_DEVICE, "merge kernel launch failed");
         }
         if (FN.active) { // ... and J of the fine block's cells += what its bricks stored
-            const double *accs[3 * kMaxAcc];
-            int layouts[3 * kMaxAcc], count = 0;
-            for (int l = 0; l < 3; ++l)
-                for (int s = 0; s < FN.plan.nacc[l]; ++s) { accs[count] = c->fine_acc[l][s]; layouts[count++] = l; }
-            if (count && launch_merge(accs, layouts, count, J_dev, FN.n, nnu, (long)FN.n * FN.n * FN.n, true, stream, FN.leaf_of_fine, (long)ncell))
+            const AccList B = acc_list(c->fine_acc, FN.plan.nacc, kOwnFrame);
+            if (B.count && launch_merge(B.acc, B.layout, B.count, J_dev, FN.n, nnu, (long)FN.n * FN.n * FN.n, true, stream, FN.leaf_of_fine, (long)ncell))
                 return fail(c, FTTE_ERR_NO_DEVICE, "merge kernel launch failed");
         }
         return FTTE_OK;
@@ -1006,7 +941,7 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     // every buffer and table the launches name stay the same.  Measured on ROCm 7.2 / MI355X the replay is SLOWER than issuing the
     // launches (configs[3]: 15.8 against 12.2 ms; 8 clusters in 5 passes: 23.9 against 15.1 ms), so it is off by default.
     std::vector<uintptr_t> sig = {(uintptr_t)J_dev, (uintptr_t)stream, (uintptr_t)nnu, (uintptr_t)nh, (uintptr_t)c->kappa.source(), (uintptr_t)c->kappa.copy(MediumField::kCellMajor),
-                                  (uintptr_t)c->d_faces.get(), (uintptr_t)c->amr_Iout.get(), (uintptr_t)c->amr_mean.get(), (uintptr_t)c->d_bgroups.get(), (uintptr_t)c->d_btasks.get(),
+                                  (uintptr_t)c->d_faces.get(), (uintptr_t)c->amr_Iout.get(), (uintptr_t)c->amr_mean.get(), (uintptr_t)c->btables.groups.get(), (uintptr_t)c->btables.tasks.get(),
                                   (uintptr_t)c->d_amr_dirs.get(), (uintptr_t)c->d_amr_tables.get(), (uintptr_t)c->d_uvb.get(), (uintptr_t)c->d_leaf_of_base.get(), (uintptr_t)H.cells.get(),
                                   (uintptr_t)c->brick_waves, (uintptr_t)emit, (uintptr_t)c->emis.source(), (uintptr_t)c->emis.copy(MediumField::kCellMajor), (uintptr_t)c->forest_fuse,
                                   (uintptr_t)c->base_emis[0].get(), (uintptr_t)c->base_emis[1].get(), (uintptr_t)c->base_emis[2].get()};

@@ -211,6 +211,7 @@ int plan_brick_groups(ftte_ctx *c, BrickPlan &P, int ndir, const double *phi, co
     const int n = sub ? sub->n : c->n;
     ++c->n_plan_builds;
     P = BrickPlan();
+    P.id = ++c->brick_plans; // (a new plan: no BrickTables holds it)
     P.n = n; P.chunk = chunk; P.gmax = gmax; P.share = c->share; P.want_dataflow = want_dataflow; P.box = c->box;
     P.phi.assign(phi, phi + ndir); P.theta.assign(theta, theta + ndir); P.w.assign(w, w + ndir);
     P.dirs.resize(ndir);
@@ -338,7 +339,6 @@ int build_brick_plan(ftte_ctx *c, int ndir, const double *phi, const double *the
 
     if ((rc = plan_brick_groups(c, P, ndir, phi, theta, w, chunk, gmax, want_dataflow, false))) return rc;
     P.want_glanes = want_glanes;
-    c->bplan_uploaded = false;
 
     // streams: the groups of one accumulator stay on one stream (their launches are ordered against each other)
     P.glanes = std::max(1, std::min(want_glanes, P.nacc[0] + P.nacc[1] + P.nacc[2]));

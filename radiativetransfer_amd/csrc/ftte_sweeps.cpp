@@ -1,7 +1,5 @@
 // ftte_sweeps.cpp -- the launch sequences of the diffuse sweep: per-direction segment forests on refined cell arrays
 // (forest_sweep and its pieces, also used by the hybrid sweep) and cell-fixed bricks on uniform grids (brick_sweep).
-#include <cstdlib>
-
 #include "ftte_context.h"
 
 namespace ftte {
@@ -81,33 +79,10 @@ int check_ready(ftte_ctx *c, bool need_kappa)
 // the previous sweep may have been issued on a stream of the caller's: wait for its end before its inputs are rewritten
 int wait_sweep(ftte_ctx *c)
 {
-    if (c->sweep_pending) {
-        FTTE_HIP(c, hipEventSynchronize(c->ev_sweep_done));
-        c->sweep_pending = false;
-        if (c->h_berror && c->h_berror[32 * kBrickQueues]) {
-            c->h_berror[32 * kBrickQueues] = 0;
-            std::memset(c->bqlen, 0, sizeof c->bqlen);
-            return fail(c, FTTE_ERR_STALLED, "the previous sweep gave up: a brick waited for the bricks it depends on while nothing moved (its J is not valid)");
-        }
-        if (c->h_berror && c->bqlen[0] && std::getenv("FTTE_QUEUE_STATS")) { // instrumentation of the persistent form, per queue
-            unsigned long long began = 0;
-            std::memcpy(&began, c->h_berror + 32 * kBrickQueues + 2, 8);
-            began = ~began;
-            for (int q = 0; q < kBrickQueues; ++q) {
-                unsigned long long fin = 0, waited = 0;
-                std::memcpy(&fin, c->h_berror + 32 * q + 2, 8);
-                std::memcpy(&waited, c->h_berror + 32 * q + 4, 8);
-                std::fprintf(stderr, "[ftte] queue %d: %u tasks, %u workgroups, drained after %.3f ms, %.1f polls per task, load %lld updates\n", q, c->bqlen[q],
-                             c->h_berror[32 * q + 6], (double)(fin - began) * 1e-5, c->bqlen[q] ? (double)waited / c->bqlen[q] : 0.0, (long long)c->bplan.qload[q]);
-            }
-        }
-        for (int q = 0; q < kBrickQueues; ++q) {
-            const uint32_t want = c->bqlen[q];
-            c->bqlen[q] = 0;
-            if (want && c->h_berror && c->h_berror[32 * q] < want)
-                return fail(c, FTTE_ERR_STALLED, "the previous sweep left a task queue undrained: no workgroup ran on that queue's XCD (its J is not valid)");
-        }
-    }
+    if (!c->sweep_pending) return FTTE_OK;
+    FTTE_HIP(c, hipEventSynchronize(c->ev_sweep_done));
+    c->sweep_pending = false;
+    if (const char *why = c->bflow.check_after_sweep(c->bplan.qload)) return fail(c, FTTE_ERR_STALLED, why);
     return FTTE_OK;
 }
 
@@ -390,10 +365,8 @@ int forest_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
                 ftte_ctx::ForestDev &D = c->forests[d0 + t];
                 D.w = w[d0 + t];
                 D.depth_off = F[t].depth_off;
-                FTTE_HIP(c, D.rec.reserve(rec[t].size()));
-                FTTE_HIP(c, D.active.reserve((size_t)ncell));
-                FTTE_HIP(c, hipMemcpy(D.rec, rec[t].data(), sizeof(SegRec) * rec[t].size(), hipMemcpyHostToDevice));
-                FTTE_HIP(c, hipMemcpy(D.active, active[t].data(), (size_t)ncell, hipMemcpyHostToDevice));
+                FTTE_HIP(c, to_device(D.rec, rec[t]));
+                FTTE_HIP(c, to_device(D.active, active[t]));
             }
         }
         c->forest_key = key;
@@ -422,8 +395,7 @@ int forest_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
         }
     } else batch = (int)std::min<size_t>((size_t)most, c->amr_scratch() / per_dir);
     FTTE_HIP(c, hipStreamSynchronize(stream)); // d_uvb below may still be read by the previous sweep
-    FTTE_HIP(c, c->d_uvb.reserve((size_t)nnu));
-    FTTE_HIP(c, hipMemcpy(c->d_uvb, uvb, sizeof(double) * nnu, hipMemcpyHostToDevice)); c->uvb_sent.clear();
+    FTTE_HIP(c, c->d_uvb.send(uvb, (size_t)nnu));
 
     // the forest path gathers by cell: all groups of a cell side by side (beyond 96 groups the transposing kernel's
     // tile no longer fits the LDS of a workgroup; the strided layout is read as it is)
@@ -435,7 +407,6 @@ int forest_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     c->timing_used = 0;
     if (ndir == 0) FTTE_HIP(c, hipMemsetAsync(J_dev, 0, sizeof(double) * (size_t)nnu * ncell, stream));
 
-    static const ftte_consts kMath = FTTE_CONSTS_INIT;
     {
         AmrLevelRec A;
         std::memset(&A, 0, sizeof A);
@@ -459,350 +430,269 @@ int forest_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
 }
 
 
-int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, const double *w, const double *uvb, double *J_dev,
-                hipStream_t stream, const HostPipe *pipe)
+namespace {
+
+// The brick sweep of a uniform grid, step by step, and what its steps share
+struct BrickSweep {
+    ftte_ctx *c; const BrickPlan &P; double *J_dev; hipStream_t stream; const HostPipe *pipe; // (what brick_sweep was called with)
+    const int n = c->n, nnu = c->nnu;
+    // Host arrays (ftte_diffuse_iteration): lanes of frequency groups do their own layouts before their first stage and their own
+    // merge after their last.  (With device-resident opacities, layouts up front and one merge at the end are faster: 37.4-38.0
+    // against 38.6 ms per 256^3 x 8 x 96 step.  With host arrays in flight the lanes are staggered by the transfers and their ends
+    // fall into each other's sweeps anyway.)
+    bool lane_ends = false, lane_layout[3] = {false, false, false};
+    // Brick order for the opacities and the accumulators (BrickLaunch::tiled, option "tiled": no gain).  For
+    // grids made of whole bricks, device-resident opacities, the forms of the kernel that know it; a copy more per axis order.
+    bool tiled = false; int tchunk = 0; // tchunk (option 2): a whole brick in one piece
+    // Layout 1 ([jc][ic][kc]) holds the rows of layout 0 ([ic][jc][kc]) in another order: its groups march along jc through the
+    // layout-0 frame itself (BrickGroup si = +-n, sv = +-n^2), read the source array and leave their accumulators in layout-0 order.  Only
+    // layout 2, whose march runs along the contiguous axis, needs a transposed copy.  (Brick order keeps its own copy per layout.)
+    int frame[3] = {0, 0, 2};
+    // The stage sequence is issued once per "lane" (a subset of the frequency groups, which never touch each other's data, or of the
+    // groups of directions) on streams of their own: the tail of one lane's stage overlaps the next stage of another.  Lane 0 is the caller's stream.
+    int nulanes = 1, nlanes = 1;
+    bool overlap = false; // J merged block by block behind the stages (option "merge_overlap")
+    size_t npoints = 0;
+    hipStream_t queue(int lane) const { return lane == 0 ? stream : c->lane_stream[(size_t)lane - 1].get(); }
+    LaneSlice slice(int lane) const { return lane_slice(nnu, P.glanes > 1 ? 0 : lane, nulanes, c->ncell); }
+    BrickLaunch launch(size_t task0, size_t task1, int nu0, int nu1) const
+    {
+        BrickLaunch L = brick_launch(P, c->btables, task0, task1, nu0, nu1, c->ncell, P.face_elems, c->d_uvb, c->emit_mode);
+        L.tiled = tiled ? 1 : 0; L.pad2_ = c->ablate; L.atomic_acc = c->atomic_acc;
+        return L;
+    }
+    int prepare(int ndir, const double *uvb), one_launch(), lane_stages(int lane, LaunchTiming &T), merge();
+};
+
+// Brick order: cell (brick tu, tv; row r; lane; layer i) of a group at org + i * si + tu * bu + tv * bv + r * sv + lane (63 - lane
+// mirrored); tchunk: layer i = tchunk * ti + il + 1 at org + i * si + ti * bi, si = +-piece inside the brick
+void tiled_strides(BrickGroup &G, const DirPlan &D0, int n, int tchunk)
+{
+    const int64_t ntu = n / 64, ntv = n / kBrickRows, piece = 64 * kBrickRows;
+    G.sv = D0.sv > 0 ? 64 : -64;
+    G.bu = (int32_t)(D0.su > 0 ? piece : -piece);
+    G.bv = (int32_t)(D0.sv > 0 ? ntu * piece : -ntu * piece);
+    G.org = (int64_t)(D0.si > 0 ? -1 : n) * n * n + (D0.sv > 0 ? 0 : (ntv - 1) * ntu * piece + (kBrickRows - 1) * 64) + (D0.su > 0 ? 0 : (ntu - 1) * piece);
+    if (!tchunk) return;
+    const int64_t nti = n / tchunk, brick = piece * tchunk;
+    G.si = (int32_t)(D0.si > 0 ? piece : -piece);
+    G.bu = (int32_t)(D0.su > 0 ? brick : -brick);
+    G.bv = (int32_t)(D0.sv > 0 ? ntu * brick : -ntu * brick);
+    const int64_t step_i = D0.si > 0 ? ntv * ntu * brick : -ntv * ntu * brick;
+    G.bi = step_i - (int64_t)tchunk * G.si;
+    // i = 1 (ti = 0, il = 0): the first layer of brick 0 (si > 0) or the last layer of the last brick (si < 0)
+    G.org = (D0.si > 0 ? -piece : (nti - 1) * ntv * ntu * brick + (int64_t)tchunk * piece) + (D0.sv > 0 ? 0 : (ntv - 1) * ntu * brick + (kBrickRows - 1) * 64) +
+            (D0.su > 0 ? 0 : (ntu - 1) * brick);
+}
+
+// Preparation: accumulators and the medium in the layouts the groups march through, the plan's tables, the group records, the
+// background, the lanes' streams and events
+int BrickSweep::prepare(int ndir, const double *uvb)
 {
     int rc;
-    if ((rc = build_brick_plan(c, ndir, phi, theta, w))) return rc;
-    BrickPlan &P = c->bplan;
-    const int n = c->n, nnu = c->nnu;
-    const size_t per_acc = (size_t)nnu * c->ncell;
-
-    // everything below overwrites device tables the previous sweep may still be reading
-    if ((rc = wait_sweep(c))) return rc;
-    FTTE_HIP(c, hipStreamSynchronize(stream));
-    if (stream != c->stream) FTTE_HIP(c, hipStreamSynchronize(c->stream));
-
-    const size_t acc_size = accumulator_size(c->acc, per_acc);
-    const size_t face_need = (size_t)ndir * nnu * (size_t)P.face_elems;
-    FTTE_HIP(c, c->d_faces.reserve(face_need));
+    const size_t acc_size = accumulator_size(c->acc, (size_t)nnu * c->ncell);
+    FTTE_HIP(c, c->d_faces.reserve((size_t)ndir * nnu * (size_t)P.face_elems));
     FTTE_HIP(c, c->merge_stream.create(hipStreamNonBlocking));
     FTTE_HIP(c, c->ev_layout_done.create(hipEventDisableTiming));
     FTTE_HIP(c, c->ev_merge_done.create(hipEventDisableTiming));
     FTTE_HIP(c, c->ev_layouts_ready.create(hipEventDisableTiming));
-    // Host arrays (ftte_diffuse_iteration): lanes of frequency groups (below) do their own layouts before their first stage and their
-    // own merge after their last.
-    // (With device-resident opacities, layouts up front and one merge at the end are faster: 37.4-38.0 against 38.6 ms per
-    // 256^3 x 8 x 96 step.  With host arrays in flight the lanes are staggered by the transfers and their ends fall into each
-    // other's sweeps anyway.)
-    const bool lane_ends = pipe != nullptr;
-    bool lane_layout[3] = {false, false, false};
-    // Brick order for the opacities and the accumulators (BrickLaunch::tiled, option "tiled"): a brick's layer is then one piece of
-    // 4 KB instead of eight rows of 512 B a row of the frame apart.  A kernel that does nothing but these loads and stores gets a
-    // third more out of the memory system that way (tools/membench.hip); the sweep gets nothing (31.66 against 31.67 ms), so the
-    // option is off by default.  For grids made of whole bricks, device-resident opacities, the forms of the kernel that know it;
-    // costs one more copy of the opacities per axis order.
-    const bool tiled = c->tiled_opt && !pipe && !c->emit_mode && n % 64 == 0 && n % kBrickRows == 0 &&
-                       (c->tiled_opt == 1 || n % P.chunk == 0);
-    const int tchunk = tiled && c->tiled_opt == 2 ? P.chunk : 0; // 2: a whole brick in one piece
-    // Layout 1 ([jc][ic][kc]) holds the rows of layout 0 ([ic][jc][kc]) in another order: its groups march along jc through the
-    // layout-0 frame itself (BrickGroup si = +-n, sv = +-n^2), read the source array and leave their accumulators in layout-0 order.  Only
-    // layout 2, whose march runs along the contiguous axis, needs a transposed copy.  (Brick order keeps its own copy per layout.)
-    auto frame = [tiled](int l) { return l == 1 && !tiled ? 0 : l; };
-    // accumulators and the opacity in the layouts the groups march through
+    lane_ends = pipe != nullptr;
+    tiled = c->tiled_opt && !pipe && !c->emit_mode && n % 64 == 0 && n % kBrickRows == 0 && (c->tiled_opt == 1 || n % P.chunk == 0);
+    tchunk = tiled && c->tiled_opt == 2 ? P.chunk : 0;
+    frame[1] = tiled ? 1 : 0;
     for (int l = 0; l < 3; ++l) {
         for (int s = 0; s < P.nacc[l]; ++s)
             FTTE_HIP(c, c->acc[l][s].reserve(acc_size));
-        if (!P.nacc[l] || frame(l) != l) continue;
+        if (!P.nacc[l] || frame[l] != l) continue;
         if (!lane_ends) {
             if ((rc = make_layout(c, c->kappa, l, stream, tiled, tchunk))) return rc;
-        } else if (l) { // (nothing is current: the lanes bring the source) every lane transposes its own groups, below
+        } else if (l) { // (nothing is current: the lanes bring the source) every lane transposes its own groups (lane_stages)
             FTTE_HIP(c, c->kappa.reserve(MediumField::layout(l)));
             lane_layout[l] = true;
         }
         if (c->emit_mode && (rc = make_layout(c, c->emis, l, stream))) return rc;
     }
-
-    if (!c->bplan_uploaded) {
-        c->bgroups_sent.clear();
-        FTTE_HIP(c, c->d_blayers.reserve(P.layers.size()));
-        FTTE_HIP(c, c->d_btasks.reserve(P.tasks.size()));
-        FTTE_HIP(c, c->d_bgroups.reserve(P.groups.size()));
-        if (!P.layers.empty())
-            FTTE_HIP(c, hipMemcpy(c->d_blayers, P.layers.data(), sizeof(LayerRec) * P.layers.size(), hipMemcpyHostToDevice));
-        if (!P.tasks.empty())
-            FTTE_HIP(c, hipMemcpy(c->d_btasks, P.tasks.data(), sizeof(BrickTask) * P.tasks.size(), hipMemcpyHostToDevice));
-        if (P.dataflow && !P.deps.empty()) {
-            FTTE_HIP(c, c->d_bdeps.reserve(P.deps.size()));
-            FTTE_HIP(c, hipMemcpy(c->d_bdeps, P.deps.data(), sizeof(int32_t) * P.deps.size(), hipMemcpyHostToDevice));
-        }
-        if (!P.merge_blocks.empty()) {
-            FTTE_HIP(c, c->d_mblocks.reserve(P.merge_blocks.size()));
-            FTTE_HIP(c, hipMemcpy(c->d_mblocks, P.merge_blocks.data(), sizeof(int32_t) * P.merge_blocks.size(), hipMemcpyHostToDevice));
-        }
-        c->bplan_uploaded = true;
-        c->bqueue_uploaded = false;
-    }
+    FTTE_HIP(c, c->btables.upload(P));
     // the group records carry pointers that depend on nnu (face blocks) and on the buffers: rebuilt per sweep (a few KB)
-    {
-        std::vector<BrickGroup> G(P.groups.size());
-        std::memset(G.data(), 0, sizeof(BrickGroup) * G.size());
-        for (size_t g = 0; g < P.groups.size(); ++g) {
-            const BrickPlan::Group &H = P.groups[g];
-            const DirPlan &D0 = P.dirs[H.dirs[0]];
-            fill_brick_group(G[g], P, g, tiled ? c->kappa.copy(MediumField::bricks(H.layout)) : c->kappa.in_layout(frame(H.layout)),
-                             c->emit_mode ? c->emis.in_layout(frame(H.layout)) : nullptr, c->acc[H.layout][H.acc], c->d_blayers, c->d_faces,
-                             (size_t)nnu * (size_t)P.face_elems);
-            if (frame(H.layout) != H.layout) { // march (jc) stride n, rows (ic) n^2 apart; a mirrored axis enters from its far end
-                const int64_t nn = (int64_t)n * n;
-                G[g].si = D0.si > 0 ? n : -n;
-                G[g].sv = (int32_t)(D0.sv > 0 ? nn : -nn);
-                G[g].org = -1 + (D0.sv > 0 ? -nn : n * nn) + (D0.si > 0 ? -(int64_t)n : nn);
-            }
-            if (tiled) { // cell (brick tu, tv; row r; lane; layer i) at org + i * si + tu * bu + tv * bv + r * sv + lane (63 - lane mirrored)
-                const int64_t ntu = n / 64, ntv = n / kBrickRows, piece = 64 * kBrickRows;
-                G[g].sv = D0.sv > 0 ? 64 : -64;
-                G[g].bu = (int32_t)(D0.su > 0 ? piece : -piece);
-                G[g].bv = (int32_t)(D0.sv > 0 ? ntu * piece : -ntu * piece);
-                G[g].org = (int64_t)(D0.si > 0 ? -1 : n) * n * n + (D0.sv > 0 ? 0 : (ntv - 1) * ntu * piece + (kBrickRows - 1) * 64) +
-                           (D0.su > 0 ? 0 : (ntu - 1) * piece);
-                if (tchunk) { // layer i = chunk * ti + il + 1 at org + i * si + ti * bi: si = +-piece inside the brick
-                    const int64_t nti = n / tchunk, brick = piece * tchunk;
-                    G[g].si = (int32_t)(D0.si > 0 ? piece : -piece);
-                    G[g].bu = (int32_t)(D0.su > 0 ? brick : -brick);
-                    G[g].bv = (int32_t)(D0.sv > 0 ? ntu * brick : -ntu * brick);
-                    const int64_t step_i = D0.si > 0 ? ntv * ntu * brick : -ntv * ntu * brick;
-                    G[g].bi = step_i - (int64_t)tchunk * G[g].si;
-                    // i = 1 (ti = 0, il = 0): the first layer of brick 0 (si > 0) or the last layer of the last brick (si < 0)
-                    G[g].org = (D0.si > 0 ? -piece : (nti - 1) * ntv * ntu * brick + (int64_t)tchunk * piece) +
-                               (D0.sv > 0 ? 0 : (ntv - 1) * ntu * brick + (kBrickRows - 1) * 64) + (D0.su > 0 ? 0 : (ntu - 1) * brick);
-                }
-            }
+    std::vector<BrickGroup> G(P.groups.size());
+    std::memset(G.data(), 0, sizeof(BrickGroup) * G.size());
+    for (size_t g = 0; g < P.groups.size(); ++g) {
+        const BrickPlan::Group &H = P.groups[g];
+        const DirPlan &D0 = P.dirs[H.dirs[0]];
+        const int f = frame[H.layout];
+        fill_brick_group(G[g], P, g, tiled ? c->kappa.copy(MediumField::bricks(H.layout)) : c->kappa.in_layout(f), c->emit_mode ? c->emis.in_layout(f) : nullptr,
+                         c->acc[H.layout][H.acc], c->btables.layers, c->d_faces, (size_t)nnu * (size_t)P.face_elems);
+        if (f != H.layout) { // march (jc) stride n, rows (ic) n^2 apart; a mirrored axis enters from its far end
+            const int64_t nn = (int64_t)n * n;
+            G[g].si = D0.si > 0 ? n : -n;
+            G[g].sv = (int32_t)(D0.sv > 0 ? nn : -nn);
+            G[g].org = -1 + (D0.sv > 0 ? -nn : n * nn) + (D0.si > 0 ? -(int64_t)n : nn);
         }
-        // (a blocking copy each: skipped when the device already holds exactly these bytes, which is every iteration after the first)
-        const size_t bytes = sizeof(BrickGroup) * G.size();
-        if (bytes && (c->bgroups_sent.size() != bytes || std::memcmp(c->bgroups_sent.data(), G.data(), bytes) != 0)) {
-            FTTE_HIP(c, hipMemcpy(c->d_bgroups, G.data(), bytes, hipMemcpyHostToDevice));
-            c->bgroups_sent.assign((const char *)G.data(), (const char *)G.data() + bytes);
-        }
+        if (tiled) tiled_strides(G[g], D0, n, tchunk);
     }
-    FTTE_HIP(c, c->d_uvb.reserve((size_t)nnu));
-    if (c->uvb_sent.size() != (size_t)nnu || std::memcmp(c->uvb_sent.data(), uvb, sizeof(double) * nnu) != 0) {
-        FTTE_HIP(c, hipMemcpy(c->d_uvb, uvb, sizeof(double) * nnu, hipMemcpyHostToDevice));
-        c->uvb_sent.assign(uvb, uvb + nnu);
-    }
+    FTTE_HIP(c, c->btables.groups.send(G.data(), G.size()));
+    FTTE_HIP(c, c->d_uvb.send(uvb, (size_t)nnu));
 
-    // The frequency groups never touch each other's data (own slices of the accumulators and of the face rings), and a
-    // stage is a launch that drains before the next one starts: the stage sequence is therefore issued once per "lane"
-    // (a subset of the frequency groups) on streams of their own, so that the tail of one lane's stage overlaps the next
-    // stage of another.  Lane 0 is the caller's stream.  One pair of events brackets the whole phase: with kernels of
-    // several streams in flight together the time of a single launch says little.
-    const size_t nstages = (size_t)P.nstages, per_lane = nstages + 1;
-    const int nulanes = P.glanes > 1 ? 1 : std::max(1, std::min(c->lanes, nnu)); // streams over frequency groups ...
-    const int nlanes = nulanes * P.glanes;                                        // ... or over the groups of directions
-    while ((int)c->lane_stream.size() < nlanes - 1) {
-        Stream q; Event e;
-        FTTE_HIP(c, q.create(hipStreamNonBlocking));
-        FTTE_HIP(c, e.create(hipEventDisableTiming));
-        c->lane_stream.push_back(std::move(q)); c->lane_done.push_back(std::move(e));
-    }
+    nulanes = P.glanes > 1 ? 1 : std::max(1, std::min(c->lanes, nnu)); // streams over frequency groups ...
+    nlanes = nulanes * P.glanes;                                        // ... or over the groups of directions
+    FTTE_HIP(c, ensure_lanes(c->lane_stream, c->lane_done, (size_t)nlanes - 1));
     FTTE_HIP(c, c->ev_fork.create(hipEventDisableTiming));
     // (the plan has merge blocks only for stages on one lane of groups; with host arrays every lane merges its own after its stages)
-    const bool overlap = c->merge_overlap && !lane_ends && !P.dataflow && P.glanes == 1 && !P.groups.empty() && !P.merge_stage.empty();
-    const size_t npoints = overlap ? P.merge_stage.size() : 0;
-    while (c->ev_merge_point.size() < (size_t)nlanes * npoints) {
-        Event e;
-        FTTE_HIP(c, e.create(hipEventDisableTiming));
-        c->ev_merge_point.push_back(std::move(e));
-    }
+    overlap = c->merge_overlap && !lane_ends && !P.dataflow && P.glanes == 1 && !P.groups.empty() && !P.merge_stage.empty();
+    npoints = overlap ? P.merge_stage.size() : 0;
+    FTTE_HIP(c, ensure_events(c->ev_merge_point, (size_t)nlanes * npoints, hipEventDisableTiming));
     if ((rc = ensure_timing(c, 1))) return rc;
     c->timing_used = 0;
+    return FTTE_OK;
+}
 
-    static const ftte_consts kMath = FTTE_CONSTS_INIT;
-    if (!P.groups.empty()) {
-        LaunchTiming &T = c->timing[0];
-        T.updates = P.updates * nnu;
-        T.lanes = 0;
-        if (lane_ends) {
-            while ((int)T.first.size() < nlanes) {
-                Event a, b;
-                FTTE_HIP(c, a.create());
-                FTTE_HIP(c, b.create());
-                T.first.push_back(std::move(a)); T.last.push_back(std::move(b));
-            }
-        }
-        FTTE_HIP(c, hipEventRecord(T.start, stream));
-        if (P.dataflow) {
-            // every brick of the sweep in one launch; flags of `epoch` mark the finished ones (the array is zeroed when it is
-            // (re)allocated and when the epoch wraps, never in between)
-            const size_t nflags = P.tasks.size() * (size_t)nnu;
-            bool fresh = false;
-            FTTE_HIP(c, c->d_bdone.reserve(nflags, &fresh));
-            if (fresh || c->bepoch == 0xffffffffu) {
-                FTTE_HIP(c, hipMemsetAsync(c->d_bdone, 0, sizeof(uint32_t) * c->d_bdone.capacity(), stream));
-                c->bepoch = 0;
-            }
-            constexpr size_t kSyncWords = 32 * (kBrickQueues + 1);
-            FTTE_HIP(c, c->d_bsync.reserve(kSyncWords));
-            FTTE_HIP(c, c->h_berror.reserve(kSyncWords, &fresh));
-            if (fresh) std::memset(c->h_berror, 0, sizeof(uint32_t) * kSyncWords);
-            FTTE_HIP(c, hipMemsetAsync(c->d_bsync, 0, sizeof(uint32_t) * kSyncWords, stream));
-            if (P.persistent && (c->d_bqueue.capacity() < P.queue.size() || !c->bqueue_uploaded)) {
-                FTTE_HIP(c, c->d_bqueue.reserve(P.queue.size()));
-                FTTE_HIP(c, hipMemcpy(c->d_bqueue, P.queue.data(), sizeof(uint32_t) * P.queue.size(), hipMemcpyHostToDevice));
-                c->bqueue_uploaded = true;
-            }
-            BrickLaunch L;
-            std::memset(&L, 0, sizeof L);
-            L.groups = c->d_bgroups;
-            L.tasks = c->d_btasks;
-            L.uvb = c->d_uvb;
-            L.group_stride = c->ncell;
-            L.face_stride = P.face_elems;
-            L.vface_off = P.vface_off; L.iface_off = P.iface_off;
-            L.n = n; L.ntasks = (int)P.tasks.size(); L.nnu = nnu; L.nu0 = 0; L.chunk = P.chunk;
-            L.up = P.up; L.vp = P.vp; L.uw = P.uw; L.ut = P.ut; L.nslot = P.nslot;
-            L.emit = c->emit_mode;
-            L.ticket = c->d_bsync; L.error = c->d_bsync + 32 * kBrickQueues; L.done = c->d_bdone; L.deps = c->d_bdeps; L.epoch = ++c->bepoch; L.pad_ = c->dataflow == 2 ? 1 : 0;
-            L.math = kMath;
-            L.tiled = tiled ? 1 : 0;
-            L.pad2_ = c->ablate;
-            L.atomic_acc = c->atomic_acc;
-            int persistent = 0;
-            if (P.persistent) {
-                L.queue = c->d_bqueue;
-                std::memcpy(L.qoff, P.qoff, sizeof L.qoff);
-                std::memcpy(L.qlen, P.qlen, sizeof L.qlen);
-                std::memcpy(L.xcc_queue, c->xcc_queue, sizeof L.xcc_queue);
-                // as many workgroups as the GPU holds (four waves per SIMD; fewer fit when LDS is padded: the rest start late and
-                // find the queues empty)
-                hipDeviceProp_t prop;
-                FTTE_HIP(c, hipGetDeviceProperties(&prop, c->device));
-                persistent = (int)std::min<size_t>((size_t)prop.multiProcessorCount * 16, P.queue.size());
-            }
-            c->last_brick_form = 0;
-            c->last_brick_dataflow = P.persistent ? 3 : c->dataflow == 2 ? 2 : 1;
-            c->last_brick_whole = 0;
-            const int lrc = launch_brick(L, P.max_dirs, c->brick_waves, stream, false, persistent);
-            if (lrc) return fail(c, lrc == -1 ? FTTE_ERR_ARG : FTTE_ERR_NO_DEVICE, "brick kernel launch failed");
-            FTTE_HIP(c, hipMemcpyAsync(c->h_berror, c->d_bsync, sizeof(uint32_t) * kSyncWords, hipMemcpyDeviceToHost, stream));
-            if (P.persistent) std::memcpy(c->bqlen, P.qlen, sizeof c->bqlen);
-        }
-        FTTE_HIP(c, hipEventRecord(c->ev_fork, stream));
-        for (int lane = 0; lane < nlanes && !P.dataflow; ++lane) {
-            hipStream_t q = lane == 0 ? stream : c->lane_stream[(size_t)lane - 1];
-            if (lane) FTTE_HIP(c, hipStreamWaitEvent(q, c->ev_fork, 0));
-            const int gl = P.glanes > 1 ? lane : 0, nl = P.glanes > 1 ? 0 : lane;
-            const int nu0 = (int)((int64_t)nnu * nl / nulanes), nu1 = (int)((int64_t)nnu * (nl + 1) / nulanes);
-            const size_t *off = &P.stage_off[(size_t)gl * per_lane];
-            const size_t slice0 = (size_t)nu0 * c->ncell, slice_bytes = sizeof(double) * (size_t)(nu1 - nu0) * c->ncell;
-            if (pipe) {
-                // this lane's opacities: after the lane before (one transfer at a time has the link to itself), then its layouts
-                while (c->pipe_up.size() < (size_t)nlanes) {
-                    Event e;
-                    FTTE_HIP(c, e.create(hipEventDisableTiming));
-                    c->pipe_up.push_back(std::move(e));
-                }
-                if (lane) FTTE_HIP(c, hipStreamWaitEvent(q, c->pipe_up[(size_t)lane - 1], 0));
-                if ((rc = upload_on(c, q, c->kappa.source() + slice0, pipe->kappa + slice0, slice_bytes))) return rc;
-                FTTE_HIP(c, hipEventRecord(c->pipe_up[(size_t)lane], q));
-            }
-            if (lane_ends) {
-                for (int l = 1; l < 3; ++l)
-                    if (lane_layout[l] && launch_to_layout(l, c->kappa.source() + slice0, c->kappa.in_layout(l) + slice0, n, nu1 - nu0, (long)c->ncell, q))
-                        return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
-                FTTE_HIP(c, hipEventRecord(T.first[(size_t)lane], q));
-            }
-            for (size_t st = 0, mp = 0; st < nstages; ++st) {
-                // (after the stage: this lane's part of the blocks merge point mp waits for, recorded even behind an empty stage)
-                auto merge_point = [&]() -> int {
-                    if (overlap && mp < npoints && (size_t)P.merge_stage[mp] == st) {
-                        FTTE_HIP(c, hipEventRecord(c->ev_merge_point[(size_t)lane * npoints + mp], q));
-                        ++mp;
-                    }
-                    return FTTE_OK;
-                };
-                if (off[st + 1] == off[st]) {
-                    if ((rc = merge_point())) return rc;
-                    continue;
-                }
-                BrickLaunch L;
-                std::memset(&L, 0, sizeof L);
-                L.groups = c->d_bgroups;
-                L.tasks = c->d_btasks + off[st];
-                L.uvb = c->d_uvb;
-                L.group_stride = c->ncell;
-                L.face_stride = P.face_elems;
-                L.vface_off = P.vface_off; L.iface_off = P.iface_off;
-                L.n = n; L.ntasks = (int)(off[st + 1] - off[st]); L.nnu = nu1 - nu0; L.nu0 = nu0; L.chunk = P.chunk;
-                L.up = P.up; L.vp = P.vp; L.uw = P.uw; L.ut = P.ut; L.nslot = P.nslot;
-                L.emit = c->emit_mode;
-                L.math = kMath;
-                L.tiled = tiled ? 1 : 0;
-                L.pad2_ = c->ablate;
-                L.atomic_acc = c->atomic_acc;
-                const int form = brick_form(c, nnu);
-                c->last_brick_form = form;
-                c->last_brick_dataflow = 0;
-                c->last_brick_whole = form != 2 && brick_whole_form(L, c->brick_waves);
-                const int lrc = form == 2 ? launch_brick_pair(L, P.max_dirs, c->pair_waves, q) : launch_brick(L, P.max_dirs, c->brick_waves, q);
-                if (lrc) return fail(c, lrc == -1 ? FTTE_ERR_ARG : FTTE_ERR_NO_DEVICE, "brick kernel launch failed");
-                if ((rc = merge_point())) return rc;
-            }
-            if (lane_ends) { // this lane's J: merged as soon as its stages are done, and on its way back (pinned arrays) behind that
-                FTTE_HIP(c, hipEventRecord(T.last[(size_t)lane], q));
-                const double *accs[3 * kMaxAcc];
-                int layouts[3 * kMaxAcc], count = 0;
-                for (int l = 0; l < 3; ++l)
-                    for (int s2 = 0; s2 < P.nacc[l]; ++s2) { accs[count] = c->acc[l][s2] + slice0; layouts[count++] = frame(l); }
-                if (launch_merge(accs, layouts, count, J_dev + slice0, n, nu1 - nu0, (long)c->ncell, false, q, nullptr, 0, tiled, tchunk))
-                    return fail(c, FTTE_ERR_NO_DEVICE, "merge kernel launch failed");
-                if (pipe && is_registered(c, pipe->J + slice0, slice_bytes))
-                    FTTE_HIP(c, hipMemcpyAsync(pipe->J + slice0, J_dev + slice0, slice_bytes, hipMemcpyDeviceToHost, q));
-            }
-            if (lane) {
-                FTTE_HIP(c, hipEventRecord(c->lane_done[(size_t)lane - 1], q));
-                FTTE_HIP(c, hipStreamWaitEvent(stream, c->lane_done[(size_t)lane - 1], 0));
-            }
-        }
-        if (pipe) { // pageable J: through the staging blocks, lane after lane (the later lanes are still being swept)
-            for (int lane = 0; lane < nlanes; ++lane) {
-                const int nu0 = (int)((int64_t)nnu * lane / nulanes), nu1 = (int)((int64_t)nnu * (lane + 1) / nulanes);
-                const size_t slice0 = (size_t)nu0 * c->ncell, slice_bytes = sizeof(double) * (size_t)(nu1 - nu0) * c->ncell;
-                if (is_registered(c, pipe->J + slice0, slice_bytes)) continue;
-                hipStream_t q = lane == 0 ? stream : c->lane_stream[(size_t)lane - 1];
-                if ((rc = download_on(c, q, pipe->J + slice0, J_dev + slice0, slice_bytes))) return rc;
-            }
-            c->kappa.set(); // every lane has brought its groups
-        }
-        if (lane_ends) {
-            for (int l = 1; l < 3; ++l) if (lane_layout[l]) c->kappa.made(MediumField::layout(l)); // ... and transposed them
-            T.lanes = nlanes;
-        }
-        FTTE_HIP(c, hipEventRecord(T.stop, stream));
-        c->timing_used = 1;
+// Every brick of the sweep in one launch (options "dataflow" 1..3); flags of the sweep's epoch mark the finished ones
+int BrickSweep::one_launch()
+{
+    BrickLaunch L = launch(0, P.tasks.size(), 0, nnu);
+    FTTE_HIP(c, c->bflow.prepare(L, c->btables, P.tasks.size() * (size_t)nnu, stream));
+    L.pad_ = c->dataflow == 2 ? 1 : 0;
+    int persistent = 0;
+    if (P.persistent) {
+        L.queue = c->btables.queue;
+        std::memcpy(L.qoff, P.qoff, sizeof L.qoff); std::memcpy(L.qlen, P.qlen, sizeof L.qlen); std::memcpy(L.xcc_queue, c->xcc_queue, sizeof L.xcc_queue);
+        // as many workgroups as the GPU holds (four waves per SIMD; fewer fit when LDS is padded: the rest start late and
+        // find the queues empty)
+        hipDeviceProp_t prop;
+        FTTE_HIP(c, hipGetDeviceProperties(&prop, c->device));
+        persistent = (int)std::min<size_t>((size_t)prop.multiProcessorCount * 16, P.queue.size());
     }
-    // J = the groups' accumulators, layout after layout
+    c->last_brick_form = 0; c->last_brick_dataflow = P.persistent ? 3 : c->dataflow == 2 ? 2 : 1; c->last_brick_whole = 0;
+    const int lrc = launch_brick(L, P.max_dirs, c->brick_waves, stream, false, persistent);
+    if (lrc) return fail(c, lrc == -1 ? FTTE_ERR_ARG : FTTE_ERR_NO_DEVICE, "brick kernel launch failed");
+    FTTE_HIP(c, c->bflow.read_back(P, stream));
+    return FTTE_OK;
+}
+
+// The stages of one lane on its stream; with host arrays in front of them the lane's opacities and their layouts, behind them its
+// merge and its J on the way back
+int BrickSweep::lane_stages(int lane, LaunchTiming &T)
+{
+    const size_t nstages = (size_t)P.nstages;
+    int rc;
+    hipStream_t q = queue(lane);
+    if (lane) FTTE_HIP(c, hipStreamWaitEvent(q, c->ev_fork, 0));
+    const LaneSlice S = slice(lane);
+    const size_t *off = &P.stage_off[(size_t)(P.glanes > 1 ? lane : 0) * (nstages + 1)];
+    if (pipe) {
+        // this lane's opacities: after the lane before (one transfer at a time has the link to itself), then its layouts
+        FTTE_HIP(c, ensure_events(c->pipe_up, (size_t)nlanes, hipEventDisableTiming));
+        if (lane) FTTE_HIP(c, hipStreamWaitEvent(q, c->pipe_up[(size_t)lane - 1], 0));
+        if ((rc = upload_on(c, q, c->kappa.source() + S.first, pipe->kappa + S.first, S.bytes))) return rc;
+        FTTE_HIP(c, hipEventRecord(c->pipe_up[(size_t)lane], q));
+    }
+    if (lane_ends) {
+        for (int l = 1; l < 3; ++l)
+            if (lane_layout[l] && launch_to_layout(l, c->kappa.source() + S.first, c->kappa.in_layout(l) + S.first, n, S.nu1 - S.nu0, (long)c->ncell, q))
+                return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
+        FTTE_HIP(c, hipEventRecord(T.first[(size_t)lane], q));
+    }
+    for (size_t st = 0, mp = 0; st < nstages; ++st) {
+        if (off[st + 1] != off[st]) {
+            const BrickLaunch L = launch(off[st], off[st + 1], S.nu0, S.nu1);
+            const int form = brick_form(c, nnu);
+            c->last_brick_form = form; c->last_brick_dataflow = 0; c->last_brick_whole = form != 2 && brick_whole_form(L, c->brick_waves);
+            const int lrc = form == 2 ? launch_brick_pair(L, P.max_dirs, c->pair_waves, q) : launch_brick(L, P.max_dirs, c->brick_waves, q);
+            if (lrc) return fail(c, lrc == -1 ? FTTE_ERR_ARG : FTTE_ERR_NO_DEVICE, "brick kernel launch failed");
+        }
+        // (after the stage: this lane's part of the blocks merge point mp waits for, recorded even behind an empty stage)
+        if (overlap && mp < npoints && (size_t)P.merge_stage[mp] == st) {
+            FTTE_HIP(c, hipEventRecord(c->ev_merge_point[(size_t)lane * npoints + mp], q));
+            ++mp;
+        }
+    }
+    if (lane_ends) { // this lane's J: merged as soon as its stages are done, and on its way back (pinned arrays) behind that
+        FTTE_HIP(c, hipEventRecord(T.last[(size_t)lane], q));
+        const AccList A = acc_list(c->acc, P.nacc, frame, S.first);
+        if (launch_merge(A.acc, A.layout, A.count, J_dev + S.first, n, S.nu1 - S.nu0, (long)c->ncell, false, q, nullptr, 0, tiled, tchunk))
+            return fail(c, FTTE_ERR_NO_DEVICE, "merge kernel launch failed");
+        if (pipe && is_registered(c, pipe->J + S.first, S.bytes))
+            FTTE_HIP(c, hipMemcpyAsync(pipe->J + S.first, J_dev + S.first, S.bytes, hipMemcpyDeviceToHost, q));
+    }
+    if (lane) {
+        FTTE_HIP(c, hipEventRecord(c->lane_done[(size_t)lane - 1], q));
+        FTTE_HIP(c, hipStreamWaitEvent(stream, c->lane_done[(size_t)lane - 1], 0));
+    }
+    return FTTE_OK;
+}
+
+// J = the groups' accumulators, layout after layout
+int BrickSweep::merge()
+{
     if (overlap) {
         // block by block as the stages finish them: merge point after merge point, each lane's frequency groups behind that lane's
         // stage; the caller's stream goes on once the last blocks are in
-        const double *accs[3 * kMaxAcc];
-        int layouts[3 * kMaxAcc], count = 0;
-        for (int l = 0; l < 3; ++l)
-            for (int s = 0; s < P.nacc[l]; ++s) { accs[count] = c->acc[l][s]; layouts[count++] = frame(l); }
         for (size_t mp = 0; mp < npoints; ++mp)
             for (int lane = 0; lane < nlanes; ++lane) {
-                const int nu0 = (int)((int64_t)nnu * lane / nulanes), nu1 = (int)((int64_t)nnu * (lane + 1) / nulanes);
-                const size_t slice0 = (size_t)nu0 * c->ncell;
-                const double *lane_accs[3 * kMaxAcc];
-                for (int a = 0; a < count; ++a) lane_accs[a] = accs[a] + slice0;
+                const LaneSlice S = slice(lane);
+                const AccList A = acc_list(c->acc, P.nacc, frame, S.first);
                 FTTE_HIP(c, hipStreamWaitEvent(c->merge_stream, c->ev_merge_point[(size_t)lane * npoints + mp], 0));
-                if (launch_merge_blocks(lane_accs, layouts, count, J_dev + slice0, n, nu1 - nu0, (long)c->ncell, c->d_mblocks + P.merge_off[mp],
+                if (launch_merge_blocks(A.acc, A.layout, A.count, J_dev + S.first, n, S.nu1 - S.nu0, (long)c->ncell, c->btables.merge_blocks + P.merge_off[mp],
                                         (int)(P.merge_off[mp + 1] - P.merge_off[mp]), P.nmb, c->merge_stream, tiled, tchunk))
                     return fail(c, FTTE_ERR_NO_DEVICE, "merge kernel launch failed");
             }
         FTTE_HIP(c, hipEventRecord(c->ev_merge_done, c->merge_stream));
         FTTE_HIP(c, hipStreamWaitEvent(stream, c->ev_merge_done, 0));
     } else if (!lane_ends || P.groups.empty()) {
-        const double *accs[3 * kMaxAcc];
-        int layouts[3 * kMaxAcc], count = 0;
-        for (int l = 0; l < 3; ++l)
-            for (int s = 0; s < P.nacc[l]; ++s) { accs[count] = c->acc[l][s]; layouts[count++] = frame(l); }
-        if (count) {
-            if (launch_merge(accs, layouts, count, J_dev, n, nnu, (long)c->ncell, false, stream, nullptr, 0, tiled, tchunk))
+        const AccList A = acc_list(c->acc, P.nacc, frame);
+        if (A.count) {
+            if (launch_merge(A.acc, A.layout, A.count, J_dev, n, nnu, (long)c->ncell, false, stream, nullptr, 0, tiled, tchunk))
                 return fail(c, FTTE_ERR_NO_DEVICE, "merge kernel launch failed");
         } else FTTE_HIP(c, hipMemsetAsync(J_dev, 0, sizeof(double) * (size_t)nnu * c->ncell, stream)); // no directions
     }
+    return FTTE_OK;
+}
+
+} // namespace
+
+int brick_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, const double *w, const double *uvb, double *J_dev,
+                hipStream_t stream, const HostPipe *pipe)
+{
+    int rc;
+    if ((rc = build_brick_plan(c, ndir, phi, theta, w))) return rc;
+    // everything below overwrites device tables the previous sweep may still be reading
+    if ((rc = wait_sweep(c))) return rc;
+    FTTE_HIP(c, hipStreamSynchronize(stream));
+    if (stream != c->stream) FTTE_HIP(c, hipStreamSynchronize(c->stream));
+
+    BrickSweep R{c, c->bplan, J_dev, stream, pipe};
+    const BrickPlan &P = R.P;
+    if ((rc = R.prepare(ndir, uvb))) return rc;
+    if (!P.groups.empty()) {
+        // One pair of events brackets the whole phase: with kernels of several streams in flight together the time of a single
+        // launch says little.
+        LaunchTiming &T = c->timing[0];
+        T.updates = P.updates * c->nnu; T.lanes = 0;
+        if (R.lane_ends) {
+            FTTE_HIP(c, ensure_events(T.first, (size_t)R.nlanes, hipEventDefault));
+            FTTE_HIP(c, ensure_events(T.last, (size_t)R.nlanes, hipEventDefault));
+        }
+        FTTE_HIP(c, hipEventRecord(T.start, stream));
+        if (P.dataflow && (rc = R.one_launch())) return rc;
+        FTTE_HIP(c, hipEventRecord(c->ev_fork, stream));
+        for (int lane = 0; lane < R.nlanes && !P.dataflow; ++lane)
+            if ((rc = R.lane_stages(lane, T))) return rc;
+        if (pipe) { // pageable J: through the staging blocks, lane after lane (the later lanes are still being swept)
+            for (int lane = 0; lane < R.nlanes; ++lane) {
+                const LaneSlice S = R.slice(lane);
+                if (is_registered(c, pipe->J + S.first, S.bytes)) continue;
+                if ((rc = download_on(c, R.queue(lane), pipe->J + S.first, J_dev + S.first, S.bytes))) return rc;
+            }
+            c->kappa.set(); // every lane has brought its groups
+        }
+        if (R.lane_ends) {
+            for (int l = 1; l < 3; ++l) if (R.lane_layout[l]) c->kappa.made(MediumField::layout(l)); // ... and transposed them
+            T.lanes = R.nlanes;
+        }
+        FTTE_HIP(c, hipEventRecord(T.stop, stream));
+        c->timing_used = 1;
+    }
+    if ((rc = R.merge())) return rc;
     return mark_sweep(c, stream);
 }
 
@@ -826,16 +716,11 @@ int tile_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, co
     if (stream != c->stream) FTTE_HIP(c, hipStreamSynchronize(c->stream));
 
     if (!c->plan_uploaded) {
-        FTTE_HIP(c, c->d_layers.reserve(P.layers.size()));
-        FTTE_HIP(c, c->d_items.reserve(P.items.size()));
-        if (!P.layers.empty())
-            FTTE_HIP(c, hipMemcpy(c->d_layers, P.layers.data(), sizeof(LayerRec) * P.layers.size(), hipMemcpyHostToDevice));
-        if (!P.items.empty())
-            FTTE_HIP(c, hipMemcpy(c->d_items, P.items.data(), sizeof(WorkItem) * P.items.size(), hipMemcpyHostToDevice));
+        FTTE_HIP(c, to_device(c->d_layers, P.layers));
+        FTTE_HIP(c, to_device(c->d_items, P.items));
         c->plan_uploaded = true;
     }
-    FTTE_HIP(c, c->d_uvb.reserve((size_t)nnu));
-    FTTE_HIP(c, hipMemcpy(c->d_uvb, uvb, sizeof(double) * nnu, hipMemcpyHostToDevice)); c->uvb_sent.clear();
+    FTTE_HIP(c, c->d_uvb.send(uvb, (size_t)nnu));
 
     // accumulators sized for this nnu
     const size_t acc_size = accumulator_size(c->acc, per_acc);
@@ -891,7 +776,6 @@ int tile_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, co
         L.nitems = LP.nitems;
         L.nnu = nnu;
         L.emit = c->emit_mode;
-        static const ftte_consts kMath = FTTE_CONSTS_INIT;
         L.math = kMath;
         LaunchTiming &T = c->timing[li];
         T.updates = LP.updates * nnu; T.lanes = 0;
