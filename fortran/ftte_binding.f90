@@ -365,6 +365,35 @@ module ftte_binding
        real(c_double), intent(out) :: neutral_msun, total_msun
      end function ftte_hydrogen_mass
 
+     ! computeExpansionParameters(nh), equiSources.f90:4395-4429 (host, no context)
+     integer(c_int) function ftte_expansion_parameters(nh, final_radius_cm, density_coefficient) &
+          bind(C, name='ftte_expansion_parameters')
+       import :: c_int, c_double
+       real(c_double), value :: nh
+       real(c_double), intent(out) :: final_radius_cm, density_coefficient
+     end function ftte_expansion_parameters
+
+     ! equiSources.f90:1035-1069 (expansion of HII regions) on the device-resident medium: src_cell(nsrc) the host leaves of the
+     ! stars with weight > 0 (ftte_locate_cell), params = c_null_ptr (computed from the host leaves' densities) or c_loc of
+     ! params(3,nsrc) = finalRadius, densityCoefficient, sourceTotalHydrogenDensity; rho_coef(ncell) = rhoCoef
+     integer(c_int) function ftte_expand_hii_regions(ctx, nsrc, src_cell, params, rho_coef, nchanged) &
+          bind(C, name='ftte_expand_hii_regions')
+       import :: c_ptr, c_int, c_int64_t, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: nsrc
+       integer(c_int64_t), intent(in) :: src_cell(*)
+       type(c_ptr), value :: params
+       real(c_double), intent(out) :: rho_coef(*)
+       integer(c_int64_t), intent(out) :: nchanged
+     end function ftte_expand_hii_regions
+
+     ! rho of the device-resident medium
+     integer(c_int) function ftte_get_density(ctx, rho) bind(C, name='ftte_get_density')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       real(c_double), intent(out) :: rho(*)
+     end function ftte_get_density
+
      integer(c_int) function ftte_compute_opacities(ctx, nnu, beta) bind(C, name='ftte_compute_opacities')
        import :: c_ptr, c_int, c_double
        type(c_ptr), value :: ctx

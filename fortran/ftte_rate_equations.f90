@@ -5,12 +5,15 @@
 ! against oracle/_ref/definitions.mod (fortran/Makefile: target `dropin-check`).
 !
 !   call ftteInitialIonizationEquilibrium(nx)        ! replaces :1008-1022 (both passes, computeMass, the printed fraction)
+!   call ftteExpandHIIRegions(nx, nStars, star)      ! replaces :1035-1069, inside `if (expansionFlag)` (off in the shipped source)
 !   call ftteSolveRateEquations(nx, runUVBTransfer)  ! replaces the solveRateEquations calls of :1824-1831
 !   call ftteComputeMass(nx)                         ! replaces the computeMass calls of :1824-1831
 !
 ! On entry the leaves hold rho, tgas, HI, HeI, HeII, krate24..26 (the point-source block) and Jmean1..3 (the diffuse
 ! block); on return HI, HeI, HeII are the reference's new equilibrium values.  ftteInitialIonizationEquilibrium and
-! ftteComputeMass set neutralHydrogenMass and totalHydrogenMass.  ftteComputeMass works on the medium the last of the
+! ftteComputeMass set neutralHydrogenMass and totalHydrogenMass.  ftteExpandHIIRegions works on the medium the start-up
+! equilibrium left on the device (before it has run it takes the tree) and leaves rhoCoef, rho, HI, HeI, HeII of every leaf as the
+! reference's findExpansion and applyExpansion do.  ftteComputeMass works on the medium the last of the
 ! other two left on the device (the tree's HI and rho unchanged since); before either has run it takes the tree.
 module ftte_rate_equations
 
@@ -147,6 +150,79 @@ contains
     call ftteCheck(ctx, ftte_hydrogen_mass(ctx, neutralHydrogenMass, totalHydrogenMass), 'ftte_hydrogen_mass')
     write(*,'("ionization equilibrium:", es18.8)') neutralHydrogenMass/totalHydrogenMass
   end subroutine ftteInitialIonizationEquilibrium
+
+  ! equiSources.f90:1035-1069: the density drop of the HII regions around every star with weight > 0.  The device computes
+  ! rhoCoef and scales its own medium; the tree takes rhoCoef and the reference's own applyExpansion rule (:4495-4500), the same
+  ! four multiplications, so its fields equal the device's bit for bit.
+  subroutine ftteExpandHIIRegions(nx, nStars, star)
+    integer, intent(in) :: nx, nStars
+    type(starType), intent(in) :: star(:)
+    real(c_double), allocatable :: f(:,:), coef(:)
+    integer(c_int64_t), allocatable :: host(:)
+    integer(c_int32_t), allocatable :: pos(:)
+    integer(c_int64_t) :: ncell, nchanged
+    integer(c_int) :: nsrc
+    integer :: i, j, k, iStar
+
+    print*, 'computing expansion of HII regions'
+    if (.not. resident) then
+       call loadTree(nx, f)
+       resident = .true.
+    endif
+    ncell = 0
+    do i = 1, nx
+       do j = 1, nx
+          do k = 1, nx
+             call countChemCells(baseGrid%cell(i,j,k), ncell)
+          enddo
+       enddo
+    enddo
+    allocate(host(max(nStars,1)), coef(ncell))
+    nsrc = 0
+    do iStar = 1, nStars
+       if (star(iStar)%weight .gt. 0) then
+          allocate(pos(3*star(iStar)%level+3))
+          pos = star(iStar)%position(1:3*star(iStar)%level+3)
+          nsrc = nsrc + 1
+          call ftteCheck(ctx, ftte_locate_cell(ctx, star(iStar)%level, pos, host(nsrc)), 'ftte_locate_cell')
+          deallocate(pos)
+       endif
+    enddo
+    call ftteCheck(ctx, ftte_expand_hii_regions(ctx, nsrc, host, c_null_ptr, coef, nchanged), 'ftte_expand_hii_regions')
+    cursor = 0
+    do i = 1, nx
+       do j = 1, nx
+          do k = 1, nx
+             call scatterExpansion(baseGrid%cell(i,j,k), coef)
+          enddo
+       enddo
+    enddo
+  end subroutine ftteExpandHIIRegions
+
+  ! rhoCoef into the tree, then applyExpansion's rule (equiSources.f90:4495-4500)
+  recursive subroutine scatterExpansion(c, coef)
+    type(zoneType) :: c
+    real(c_double), intent(in) :: coef(:)
+    integer :: a, b, d
+    if (c%refined) then
+       do a = 1, 2
+          do b = 1, 2
+             do d = 1, 2
+                call scatterExpansion(c%cell(a,b,d), coef)
+             enddo
+          enddo
+       enddo
+    else
+       cursor = cursor + 1
+       c%rhoCoef = coef(cursor)
+       if (c%rhoCoef.lt.1.) then
+          c%rho  = c%rho  * c%rhoCoef
+          c%HI   = c%HI   * c%rhoCoef
+          c%HeI  = c%HeI  * c%rhoCoef
+          c%HeII = c%HeII * c%rhoCoef
+       endif
+    endif
+  end subroutine scatterExpansion
 
   ! computeMass (equiSources.f90:4369-4393) over every leaf: neutralHydrogenMass, totalHydrogenMass [msun]
   subroutine ftteComputeMass(nx)

@@ -349,6 +349,31 @@ int ftte_initial_ionization_equilibrium(ftte_ctx *ctx, const double *uniform, do
  * Every term is the reference's; the sums are deterministic (a fixed order, not the reference's sequential one). */
 int ftte_hydrogen_mass(ftte_ctx *ctx, double *neutral_msun, double *total_msun);
 
+/* ---- start-up expansion of HII regions ---------------------------------------------------------------
+ * equiSources.f90:1035-1069, behind `expansionFlag` (definitionsModule.f90:86: .false. in the shipped source, a compile-time
+ * switch; the code behind it is complete and called from the driver).  For every star with weight > 0 the reference lowers
+ * rhoCoef in every leaf inside the star's final HII radius that is not denser than 1.0001 times the star's host leaf
+ * (findExpansion, :4431-4474), then scales rho, HI, HeI, HeII by rhoCoef where it is below 1 (applyExpansion, :4476-4503). */
+
+/* computeExpansionParameters(nh), equiSources.f90:4395-4429 (host, no context) */
+int ftte_expansion_parameters(double nh, double *final_radius_cm, double *density_coefficient);
+
+/* equiSources.f90:1035-1069 on the device-resident medium of ftte_set_medium (needs rho).
+ * src_cell[nsrc]: host leaves of the stars with weight > 0 (what ftte_locate_cell returns; duplicates allowed).
+ * params: NULL, or [nsrc][3] = finalRadius [cm], densityCoefficient, sourceTotalHydrogenDensity per star, used as given.
+ * rho_coef (may be NULL): [ncell], the reference's rhoCoef.  nchanged (may be NULL): leaves with rhoCoef < 1.
+ * With params == NULL the host leaves' rho is fetched from the device and the parameters are computed on the host (libm) from
+ * nh = psi rho / mh; a host leaf whose density is not positive and finite is FTTE_ERR_ARG naming the source, as are nsrc < 0 and a
+ * src_cell outside [0, ncell).  FTTE_ERR_STATE without a grid or a medium with rho.  On any error the medium is unchanged.
+ * nsrc == 0 succeeds: nothing changes, rho_coef is all ones.  tgas and abun2 are not touched.  The opacities are the caller's
+ * (ftte_compute_opacities), as after ftte_solve_rate_equations.  The result is the same bits run after run: rhoCoef is a minimum
+ * over the stars.  ftte_counter(ctx, "expansion_exact_tests"): star-leaf pairs the last call put through the exact test (the
+ * rest were ruled out a workgroup of leaves at a time). */
+int ftte_expand_hii_regions(ftte_ctx *ctx, int nsrc, const int64_t *src_cell, const double *params,
+                            double *rho_coef, int64_t *nchanged);
+/* rho of the device-resident medium, ncell */
+int ftte_get_density(ftte_ctx *ctx, double *rho);
+
 /* ---- grid ingest (no device needed) -----------------------------------------------------------------
  * What the reference does between reading its grid file and the first transfer (equiSources.f90:427-618,
  * placeCellProjectWithVelocity :1870-1974): per refinement level a list of SPH-projected cells -- position [kpc], log10 of
@@ -399,7 +424,7 @@ int ftte_host_unregister(ftte_ctx *ctx, void *ptr);
  * the J accumulators they share (0 without a plan), "brick_chunk" (layers per brick of that plan) and "brick_queue_mix" (the
  * option "queue_mix" the persistent form's queues were laid out by; -1 when the plan has no queues); "brick_stages" (stages of that
  * plan), "merge_points" and "merge_blocks" (its block-wise merge: points and 32^3-cell blocks), "merge_stage_K" and "merge_final_K"
- * (the stage after which point K runs, the blocks final by then); "devices"; of a multi-device context also "frequency_slices",
+ * (the stage after which point K runs, the blocks final by then); "expansion_exact_tests" (ftte_expand_hii_regions); "devices"; of a multi-device context also "frequency_slices",
  * "direction_slices" and "multi_rccl" (1: the last direction-split sweep was summed over RCCL), "rccl_loadable", "rccl_selftest" (runs the
  * direction sum's RCCL calls on a clique of one rank, the first device: 1 = the piece came back unchanged; negative = it could not
  * run), the rest from its first device.

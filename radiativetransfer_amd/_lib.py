@@ -82,6 +82,9 @@ SIGNATURES = {
     "ftte_rate_equation_steps": (C.c_longlong, [_vp]),
     "ftte_initial_ionization_equilibrium": (C.c_int, [_vp, _dp, C.c_double, C.c_int, _dp]),
     "ftte_hydrogen_mass": (C.c_int, [_vp, _dp, _dp]),
+    "ftte_expansion_parameters": (C.c_int, [C.c_double, _dp, _dp]),
+    "ftte_expand_hii_regions": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int64), _dp, _dp, C.POINTER(C.c_int64)]),
+    "ftte_get_density": (C.c_int, [_vp, _dp]),
     "ftte_point_ray_steps": (C.c_longlong, [_vp]),
     "ftte_rmax": (C.c_int, [_dp]),
     "ftte_uvb_beta_table": (C.c_int, [C.c_int, C.c_double, _dp, _dp, _dp, _dp]),

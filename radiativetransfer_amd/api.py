@@ -17,7 +17,7 @@ from . import _lib
 from ._lib import FtteError, Pattern
 
 __all__ = ["DiffuseTransfer", "StellarTransfer", "rmax", "dust_cross_section", "uvb_beta_table", "uniform_table", "coll_rates", "rate_coefficient_tables", "FtteError", "Pattern", "pix2ang_nest", "healpix_directions", "fold_direction",
-           "rotate_indices", "set_pattern", "layer_patterns", "compute_cell_intensity"]
+           "rotate_indices", "set_pattern", "layer_patterns", "compute_cell_intensity", "expansion_parameters"]
 
 
 def _f64(a) -> np.ndarray:
@@ -590,3 +590,38 @@ class StellarTransfer(DiffuseTransfer):
         neutral, total = C.c_double(), C.c_double()
         self._ok(self._lib.ftte_hydrogen_mass(self._ctx, C.byref(neutral), C.byref(total)))
         return neutral.value, total.value
+
+    # -- the start-up expansion of HII regions (equiSources.f90:1035-1069; off in the shipped reference, expansionFlag)
+    @staticmethod
+    def expansion_parameters(nh: float) -> Tuple[float, float]:
+        """computeExpansionParameters(nh) (equiSources.f90:4395): (finalRadius [cm], densityCoefficient); host, no context."""
+        radius, coef = C.c_double(), C.c_double()
+        _check(_lib.load().ftte_expansion_parameters(float(nh), C.byref(radius), C.byref(coef)), "ftte_expansion_parameters")
+        return radius.value, coef.value
+
+    def expand_hii_regions(self, src_cells, params=None, want_rho_coef: bool = True) -> Tuple[Optional[np.ndarray], int]:
+        """findExpansion for every star and leaf, then applyExpansion, on the device-resident medium: src_cells are the host
+        leaves of the stars with weight > 0 (locate_cell); params[nsrc][3] = finalRadius [cm], densityCoefficient,
+        sourceTotalHydrogenDensity per star, or None to have them computed from the host leaves' densities.  Returns
+        (rhoCoef[ncell], number of leaves with rhoCoef < 1); want_rho_coef = False leaves rhoCoef on the device and returns None
+        in its place."""
+        cells = np.ascontiguousarray(src_cells, dtype=np.int64).reshape(-1)
+        if params is not None:
+            params = _f64(params)
+            if params.shape != (cells.size, 3):
+                raise ValueError("params must have shape [nsrc][3]")
+        coef = np.empty(max(self.ncell, 1)) if want_rho_coef else None
+        changed = C.c_int64()
+        self._ok(self._lib.ftte_expand_hii_regions(self._ctx, cells.size, cells.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                   None if params is None else _dp(params), None if coef is None else _dp(coef),
+                                                   C.byref(changed)))
+        return coef, changed.value
+
+    def density(self) -> np.ndarray:
+        """rho of the device-resident medium."""
+        out = np.empty(max(self.ncell, 1))
+        self._ok(self._lib.ftte_get_density(self._ctx, _dp(out)))
+        return out
+
+
+expansion_parameters = StellarTransfer.expansion_parameters

@@ -436,6 +436,7 @@ long long ftte_counter(const ftte_ctx *c, const char *name)
     if (!std::strcmp(name, "forest_builds")) return c->n_forest_builds;
     if (!std::strcmp(name, "device_objects")) return g_device_objects.load();
     if (!std::strcmp(name, "population_slots")) return c->point.slots.count;
+    if (!std::strcmp(name, "expansion_exact_tests")) return c->chem.expansion_tests;
     if (!std::strcmp(name, "hybrid_boxes")) return (c->hplan.valid && c->hplan.worthwhile) ? c->hplan.most_boxes : 0;
     if (!std::strcmp(name, "hybrid_passes")) return (c->hplan.valid && c->hplan.worthwhile) ? c->hplan.npass : 0;
     if (!std::strcmp(name, "fine_block")) return (c->hplan.valid && c->hplan.worthwhile && c->hplan.fine.active) ? c->hplan.fine.n : 0;

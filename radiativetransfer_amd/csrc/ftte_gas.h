@@ -2,12 +2,15 @@
 // HeI, HeII, rho, abun2 in cell-array order), with the packed copy the tracer reads.  The species have a version and the packed copy
 // remembers the version it was made from, as a MediumField's copies do (ftte_medium.h): whoever writes the species says
 // species_changed(), and the tracer asks packed_current().  Launches nothing and copies nothing: point_set_medium fills it.
-// ChemState: what the ionisation chemistry keeps beside the gas (ftte_chem.cpp).
+// ChemState: what the ionisation chemistry and the expansion of HII regions keep beside the gas (ftte_chem.cpp).
 #pragma once
 
 #include <cstdint>
 
+#include <vector>
+
 #include "ftte_device.h"
+#include "ftte_expansion.h"
 
 namespace ftte {
 
@@ -79,10 +82,19 @@ struct ChemState {
     DeviceBuffer<unsigned long long> counters; // first bad cell, bits of the largest change, bisection steps
     long long steps = 0;          // of the last update
     DeviceBuffer<double> mass;    // computeMass: per-workgroup partial sums, then the two totals (kMassParts)
+    // expansion of HII regions (ftte_expansion.h): where each leaf of a refined cell array lies, uploaded on first use after
+    // ftte_set_grid like `level`, with each leaf's tree node on the host; the stars of the last call; its exact star-leaf tests
+    DeviceBuffer<LeafPos> leaf_pos;
+    std::vector<int32_t> leaf_node;
+    DeviceBuffer<ExpStar> exp_star;
+    DeviceBuffer<ExpStarTest> exp_test;
+    DeviceBuffer<int64_t> exp_cells;
+    long long expansion_tests = 0;
 
     void drop_grid() // after ftte_set_grid: what is sized by the old grid; the rate coefficients stay
     {
-        level.reset(); logtem.reset(); out.reset(); J.reset();
+        level.reset(); logtem.reset(); out.reset(); J.reset(); leaf_pos.reset();
+        leaf_node.clear();
         temperature_set = false;
     }
 };
