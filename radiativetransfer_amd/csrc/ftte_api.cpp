@@ -26,11 +26,6 @@ int check_single(ftte_ctx *c)
     return c ? FTTE_OK : FTTE_ERR_ARG;
 }
 
-int fold_status(int rc)
-{
-    return rc == 1 ? FTTE_ERR_PHI : rc == 2 ? FTTE_ERR_THETA : FTTE_ERR_DOMINANT_AXIS;
-}
-
 } // namespace ftte
 
 
@@ -114,14 +109,14 @@ int ftte_set_grid(ftte_ctx *c, int nx, int ny, int nz, int64_t ncell, const int3
         for (auto &layout : c->acc)
             for (auto &a : layout) a.reset();
         c->emit_mode = 0;
-        c->amr_Iout.reset(); c->amr_mean.reset();
+        c->fscratch.drop();
         c->nnu = 0;
     }
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    free_forests(c);
-    free_hybrid(c);
-    c->d_leaf_of_base.reset();
+    c->forests.drop();
+    c->hplan = HybridPlan();
+    c->hdev.drop_grid();
     c->gas.drop();
     c->point.drop_grid();
     c->chem.drop_grid();
@@ -258,30 +253,28 @@ int ftte_set_option(ftte_ctx *c, const char *key, int value)
         c->group = value;
     } else if (!std::strcmp(key, "hybrid")) {
         if (value != 0 && value != 1) return fail(c, FTTE_ERR_ARG, "hybrid must be 0 (a refined cell array goes through the forest path as a whole) or 1 (bricks outside a box around the refined cells)");
-        c->hybrid = value;
-        c->hplan.valid = false;
+        c->hopt.hybrid = value;
     } else if (!std::strcmp(key, "hybrid_slots")) {
         if (value < 0 || value > 2) return fail(c, FTTE_ERR_ARG, "hybrid_slots must be 0 (phases), 1 (slots where there are several passes) or 2 (slots always)");
-        c->hybrid_slots = value;
+        c->hopt.slots = value;
     } else if (!std::strcmp(key, "graph")) {
         if (value != 0 && value != 1) return fail(c, FTTE_ERR_ARG, "graph must be 0 (every launch of the hybrid sweep issued every time) or 1 (captured once, replayed)");
-        c->use_graph = value;
+        c->hopt.graph = value;
     } else if (!std::strcmp(key, "box_lanes")) {
         if (value < 1 || value > 64 || 64 % value) return fail(c, FTTE_ERR_ARG, "box_lanes (the boxes of the hybrid sweep end on multiples of it along a brick's 64 lanes) must divide 64");
-        c->hybrid_lanes = value;
+        c->hopt.lanes = value;
     } else if (!std::strcmp(key, "forest_batch")) {
         if (value < 0 || value > 65535) return fail(c, FTTE_ERR_ARG, "forest_batch (directions per launch of the segment forests) must be 1..65535, or 0 for the default");
-        c->forest_batch = value;
+        c->hopt.forest_batch = value;
     } else if (!std::strcmp(key, "pipelines")) {
-        if (value < 1 || value > ftte_ctx::kMaxPipes) return fail(c, FTTE_ERR_ARG, "pipelines (independent bricks-forests-bricks sequences of the hybrid sweep, each on a stream of its own) must be 1..4");
-        c->halves = value;
-        c->hplan.valid = false;
+        if (value < 1 || value > kMaxPipes) return fail(c, FTTE_ERR_ARG, "pipelines (independent bricks-forests-bricks sequences of the hybrid sweep, each on a stream of its own) must be 1..4");
+        c->hopt.pipelines = value;
     } else if (!std::strcmp(key, "fine_bricks")) {
         if (value < 0 || value > 1) return fail(c, FTTE_ERR_ARG, "fine_bricks must be 0 (a fully refined block stays in the segment forest) or 1 (bricks of its own on the fine level where the block allows it)");
-        c->fine_bricks = value;
+        c->hopt.fine_bricks = value;
     } else if (!std::strcmp(key, "fine_chunk")) {
         if (value < 0 || value > 4096) return fail(c, FTTE_ERR_ARG, "fine_chunk (layers per brick on the fine level of a refined block) must be 1..4096, or 0 for the base bricks' chunk");
-        c->fine_chunk = value;
+        c->hopt.fine_chunk = value;
     } else if (!std::strcmp(key, "atomic_acc")) {
         if (value < 0 || value > 1) return fail(c, FTTE_ERR_ARG, "atomic_acc must be 0 or 1");
         c->atomic_acc = value;
@@ -324,7 +317,7 @@ int ftte_set_option(ftte_ctx *c, const char *key, int value)
     } else return fail(c, FTTE_ERR_ARG, std::string("unknown option: ") + key);
     c->plan.valid = false;
     c->bplan.valid = false;
-    c->hplan.valid = false;
+    c->hplan.invalidate();
     return FTTE_OK;
 }
 
@@ -339,7 +332,7 @@ int ftte_diffuse_sweep_device(ftte_ctx *c, int ndir, const double *phi, const do
     hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
 
     if (c->use_forest) {
-        if (c->hybrid && c->tree.refined() && !c->force_forest && ndir > 0) {
+        if (c->hopt.hybrid && c->tree.refined() && !c->force_forest && ndir > 0) {
             bool done = false;
             if ((rc = hybrid_sweep(c, ndir, phi, theta, w, uvb, J_dev, stream, &done)) || done) return rc;
         }
@@ -437,9 +430,9 @@ long long ftte_counter(const ftte_ctx *c, const char *name)
     if (!std::strcmp(name, "device_objects")) return g_device_objects.load();
     if (!std::strcmp(name, "population_slots")) return c->point.slots.count;
     if (!std::strcmp(name, "expansion_exact_tests")) return c->chem.expansion_tests;
-    if (!std::strcmp(name, "hybrid_boxes")) return (c->hplan.valid && c->hplan.worthwhile) ? c->hplan.most_boxes : 0;
-    if (!std::strcmp(name, "hybrid_passes")) return (c->hplan.valid && c->hplan.worthwhile) ? c->hplan.npass : 0;
-    if (!std::strcmp(name, "fine_block")) return (c->hplan.valid && c->hplan.worthwhile && c->hplan.fine.active) ? c->hplan.fine.n : 0;
+    if (!std::strcmp(name, "hybrid_boxes")) return c->hplan.boxes();
+    if (!std::strcmp(name, "hybrid_passes")) return c->hplan.passes();
+    if (!std::strcmp(name, "fine_block")) return c->hplan.fine_block();
     if (!std::strcmp(name, "brick_form")) return c->last_brick_form;
     if (!std::strcmp(name, "brick_dataflow")) return c->last_brick_dataflow;
     if (!std::strcmp(name, "brick_whole")) return c->last_brick_whole; // 1: the last sweep's stage launches took the whole-brick form

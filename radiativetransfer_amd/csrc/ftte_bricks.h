@@ -1,14 +1,18 @@
 // ftte_bricks.h -- the host side of a brick sweep (ftte_brick.hip): the plan, the device tables that hold a plan (BrickTables), a
 // buffer that knows the bytes it was sent (Sent<T>), the launch record filled from plan and tables (brick_launch), the accumulator
-// list of a merge (acc_list), a lane's frequency slice (lane_slice), the lanes' streams and events, and what the one-launch forms
-// keep between a sweep and the wait for it (BrickDataflow).  Host only; launches nothing.
+// list of a merge (acc_list), a lane's frequency slice (lane_slice), the lanes' streams and events, what the one-launch forms
+// keep between a sweep and the wait for it (BrickDataflow), and the entry points of the context-free planners (ftte_planner.cpp).
+// Host only; launches nothing.
 #pragma once
 
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
+#include <string>
 #include <vector>
 
+#include "../../include/ftte.h"
 #include "ftte_device.h"
 #include "ftte_internal.h"
 
@@ -65,6 +69,21 @@ struct BrickPlan {
     std::vector<int> merge_stage;
     std::vector<size_t> merge_off;
 };
+
+// ---- ftte_planner.cpp: the part of the planners that reads no context.  0, or an ftte_status with *err saying why.
+// A cubic sub-grid planned like a grid of its own (the fine cells of a fully refined block): side, cell size, and where the layers'
+// patterns come from (`patterns` fills n of them for direction d, folded to phi, theta, izone; returns 0 or an ftte_status)
+struct SubGridPlan {
+    int n = 0;
+    double cell = 0;
+    std::function<int(int d, double phi, double theta, int izone, ftte_pattern *out)> patterns;
+};
+int plan_direction(int n, double box, int d, double phi_d, double theta_d, double w_d, int tile_rows, std::vector<ftte_pattern> &pat,
+                   std::vector<int> &du_cum, std::vector<int> &dv_cum, DirPlan &D, LayerRec *layers, size_t layer_off, const SubGridPlan *sub,
+                   std::string *err);
+// (the plan's id stays 0: whoever counts the plans of a context stamps it)
+int plan_brick_groups(BrickPlan &P, int n, double box, int ndir, const double *phi, const double *theta, const double *w, int chunk, int gmax,
+                      int share, int want_dataflow, bool whole_faces, const SubGridPlan *sub, std::string *err);
 
 inline const ftte_consts kMath = FTTE_CONSTS_INIT; // the constants of ftte_math.h as the launch records carry them
 

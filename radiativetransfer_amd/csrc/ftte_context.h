@@ -1,12 +1,15 @@
 // ftte_context.h -- what the translation units behind include/ftte.h share: the sweep plans, the context, and the internal
-// entry points of the planners (ftte_plan.cpp), the sweeps (ftte_sweeps.cpp: segment forests, cell-fixed bricks), the hybrid sweep
-// of refined cell arrays (ftte_hybrid.cpp) and the host-array transfers (ftte_host_arrays.cpp).  ftte_api.cpp is the C ABI itself,
-// ftte_chem.cpp its part that reads or writes the species medium.
+// entry points of the planners that cache in the context (ftte_plan.cpp; the context-free ones are ftte_planner.cpp), the sweeps
+// (ftte_sweeps.cpp: segment forests, cell-fixed bricks), the hybrid sweep of refined cell arrays (ftte_hybrid.cpp) and the
+// host-array transfers (ftte_host_arrays.cpp).  ftte_api.cpp is the C ABI itself, ftte_chem.cpp its part that reads or writes the
+// species medium.
 //
 // Every device buffer, pinned buffer, stream, event and graph of the context is a member that owns it (ftte_device.h): a buffer's
 // capacity travels with its pointer, `delete c` releases everything, and a new buffer is added by declaring it.  What a buffer
-// holds has an owner as well: the medium's fields (ftte_medium.h), the gas (ftte_gas.h), and for the brick sweeps the tables of a
-// plan, the buffers that remember what they were sent and the state of the one-launch forms (ftte_bricks.h).
+// holds has an owner as well: the medium's fields (ftte_medium.h), the gas (ftte_gas.h), for the brick sweeps the tables of a
+// plan, the buffers that remember what they were sent and the state of the one-launch forms (ftte_bricks.h), and for the sweeps of
+// a refined cell array the forests, their scratch and their cache (ftte_forests.h) and the hybrid sweep's options, plan and device
+// state (ftte_hybrid.h).
 //
 // There is no CPU fallback behind any of this: every entry point that computes on the grid needs a HIP device and fails with
 // FTTE_ERR_NO_DEVICE otherwise.
@@ -29,6 +32,7 @@
 #include "ftte_bricks.h"
 #include "ftte_gas.h"
 #include "ftte_geometry.h"
+#include "ftte_hybrid.h"
 #include "ftte_kernels.h"
 #include "ftte_lambda.h"
 #include "ftte_medium.h"
@@ -140,18 +144,8 @@ struct ftte_ctx {
     AmrTree tree;
     bool use_forest = false;  // refined grid (or option "forest" = 1 on a uniform one, for cross-checks)
     int force_forest = 0;
-    struct ForestDev {
-        DeviceBuffer<SegRec> rec;
-        DeviceBuffer<uint8_t> active;
-        std::vector<int64_t> depth_off;
-        double w = 0;
-    };
-    std::vector<ForestDev> forests;
-    std::vector<double> forest_key; // phi, theta, w of the cached forests (+ box)
-    DeviceBuffer<AmrDirRec> d_amr_dirs;     // per-direction records of the forest batches
-    DeviceBuffer<int64_t> d_amr_tables;     // per batch and depth: count[], begin[]
-    DeviceBuffer<double> amr_Iout, amr_mean; // segment scratch, the same number of elements each (amr_scratch)
-    size_t amr_scratch() const { return std::min(amr_Iout.capacity(), amr_mean.capacity()); }
+    ForestCache forests;      // the whole tree's, per direction (forest_sweep)
+    ForestScratch fscratch;   // segment scratch, batch records and per-depth tables of both paths
 
     // partial merges run beside the sweeps of the next layout on their own (non-blocking) stream
     Stream merge_stream;
@@ -166,62 +160,11 @@ struct ftte_ctx {
     bool sweep_pending = false;
 
     // Hybrid sweep of a refined cell array: bricks outside a box around the refined cells, the segment forest inside it
-    int hybrid = 1;                       // option: 0 = the whole tree through the forest path
-    int hybrid_slots = 1;                 // option "slots": 0 = a phase of brick stages per pass even with several passes
-    int use_graph = 0;                    // option "graph": replay the hybrid sweep's launches from a captured hipGraph (measured slower)
-    int forest_batch = 0;                 // option: most directions per forest batch (0: what the path and the memory allow)
-    int hybrid_lanes = 1;                 // option "box_lanes": along u the boxes of the hybrid sweep end on multiples of this many lanes
-    int halves = 3;                       // option "pipelines": the hybrid sweep as this many independent pipelines on streams of their own (1..kMaxPipes)
-    static constexpr int kMaxPipes = 4;
-    Event ev_combine[kMaxPipes]; // hybrid sweep: pipeline k's forest means are in J
-    struct HybridPlan {
-        bool valid = false, worthwhile = false;
-        std::vector<double> key;          // box, chunk, group, share, then phi, theta, w
-        BrickPlan bricks;                 // groups, tasks of the bricks outside the regions (phase 1, then phase 3)
-        size_t phase1_stages = 0;         // stage lists per phase
-        GraphExec graph_exec;             // the launches of one sweep, captured (hybrid_sweep)
-        std::vector<uintptr_t> graph_sig;    // what they name: J, the buffers, the tables
-        bool slots = false;               // several passes: launch lists by slot (earliest launch a brick's inputs allow), not by phase
-        std::vector<std::vector<int>> pass_at; // [pipeline][pass] the list in front of which the pass's forests are launched
-        int most_boxes = 0;               // boxes of the izone that has most
-        int npass = 1;                    // passes of the forests (boxes behind other boxes wait for the bricks in between); the
-                                          // bricks run in npass + 1 phases: before pass 0, after pass 0, ..., after the last
-        size_t nlist = 0;                 // stage lists per half ((npass + 1) x phase1_stages)
-        int nhalves = 1;                  // the groups of an accumulator stay in one half; halves share nothing but kappa and J
-        std::vector<std::vector<int>> half_dirs; // directions of each half, list order
-        std::vector<size_t> stage_off;    // into bricks.tasks: [half][list]
-        int64_t brick_updates = 0;        // cell.direction updates the bricks perform (per frequency group)
-        struct Dir { DeviceBuffer<SegRec> rec; DeviceBuffer<uint8_t> active; DeviceBuffer<AmrExport> exports; int64_t nexports = 0;
-                     DeviceBuffer<AmrImport> imports; int64_t nimports = 0; // into the face rings of a fine block's bricks
-                     std::vector<int64_t> depth_off; std::vector<int32_t> pass_first; std::vector<int64_t> export_first; };
-        std::vector<Dir> dirs;
-        DeviceBuffer<int32_t> cells; int64_t ncells = 0; // the leaves inside the box of at least one direction
-        long long cells_id = 0;           // which list of this context that is (ftte_ctx::leaf_lists): what the medium's cell-major copies follow
-        // A fully refined block swept by bricks of its own on the fine level (option "fine_bricks"; one cluster that is a cube of
-        // base cells refined exactly once, twice its side a multiple of 64): inside it the fine cells are a uniform grid
-        // with a pattern per sub-layer, and the forest keeps only what lies around it (ftte_amr.h: ForestRegion::has_fine)
-        struct Fine {
-            bool active = false;
-            int n = 0;                          // fine cells a side
-            int lo[3] = {0, 0, 0};              // the block's first base cell, storage coordinates (1-based)
-            BrickPlan plan;                     // the fine grid's groups (those of `bricks`, an accumulator each) and tasks
-            std::vector<size_t> stage_off;      // into plan.tasks: list l = pipeline * nstages + stage is [stage_off[l], stage_off[l + 1])
-            int nstages = 0;
-            int64_t face_base = 0;              // where the fine face block starts inside a direction's face block (= bricks.face_elems)
-            int64_t updates = 0;                // cell.direction updates the fine bricks perform (per frequency group)
-            DeviceBuffer<int32_t> leaf_of_fine; // device: [n^3], fine cell in storage order -> leaf
-            BrickTables tables;                 // device: the side of `plan` (uploaded when the plan is built)
-        } fine;
-    } hplan;
-    long long leaf_lists = 0;         // leaf lists built so far (HybridPlan::cells_id counts from 1)
+    HybridOptions hopt;
+    HybridPlan hplan;
+    HybridDevice hdev;                // what hplan and the tree put on the device
+    long long leaf_lists = 0;         // leaf lists built so far (HybridDevice::cells_id counts from 1)
     int forest_fuse = 4096;           // option "forest_fuse": levels of a forest with at most this many (segment, group) pairs in one launch (0: a launch per level)
-    int fine_bricks = 1, fine_chunk = 0;  // options "fine_bricks", "fine_chunk" (0: the base bricks' chunk)
-    DeviceBuffer<double> fine_kappa[3];   // the fine block's opacities, dense, in the three layouts
-    DeviceBuffer<double> fine_emis[3];    // its emissivity / source function
-    DeviceBuffer<double> fine_acc[3][kMaxAcc]; // its groups' J accumulators
-    DeviceBuffer<int32_t> d_leaf_of_base;
-    DeviceBuffer<double> base_kappa[3];
-    DeviceBuffer<double> base_emis[3];    // emissivity / source function of the base cells (hybrid sweep with emission)
 
     // The species medium (ftte_gas.h): ftte_set_medium fills it; the tracer, the chemistry, the census, ftte_compute_opacities and
     // the thin limit read it; the chemistry's updates write its species and say so
@@ -279,25 +222,12 @@ int fail(ftte_ctx *c, int code, const std::string &msg);
             return fail((c), FTTE_ERR_NO_DEVICE, std::string(#call) + ": " + hipGetErrorString(e_));               \
     } while (0)
 
-int fold_status(int rc);
 // For the entry points that need no grid: 0, or what a missing or a multi-device context is refused with (check_ready does the
 // same as its first act)
 int check_single(ftte_ctx *c);
 
 // ---- ftte_plan.cpp
-// A cubic sub-grid planned like a grid of its own (the fine cells of a fully refined block): side, cell size, and where the layers'
-// patterns come from (`patterns` fills n of them for direction d, folded to phi, theta, izone; returns 0 or an ftte_status)
-struct SubGridPlan {
-    int n = 0;
-    double cell = 0;
-    std::function<int(int d, double phi, double theta, int izone, ftte_pattern *out)> patterns;
-};
-int plan_direction(ftte_ctx *c, int d, double phi_d, double theta_d, double w_d, int tile_rows, std::vector<ftte_pattern> &pat,
-                   std::vector<int> &du_cum, std::vector<int> &dv_cum, DirPlan &D, LayerRec *layers, size_t layer_off,
-                   const SubGridPlan *sub = nullptr);
 int build_plan(ftte_ctx *c, int rows, int stack, int ndir, const double *phi, const double *theta, const double *w);
-int plan_brick_groups(ftte_ctx *c, BrickPlan &P, int ndir, const double *phi, const double *theta, const double *w, int chunk, int gmax,
-                      int want_dataflow, bool whole_faces, const SubGridPlan *sub = nullptr);
 int build_brick_plan(ftte_ctx *c, int ndir, const double *phi, const double *theta, const double *w);
 int xcc_census(ftte_ctx *c); // fills ftte_ctx::xcc_count, xcc_queue (once per context)
 
@@ -306,27 +236,16 @@ int ensure_kappa(ftte_ctx *c, int nnu);
 int check_ready(ftte_ctx *c, bool need_kappa);
 int wait_sweep(ftte_ctx *c);
 int mark_sweep(ftte_ctx *c, hipStream_t stream);
-void free_forests(ftte_ctx *c);
 int ensure_timing(ftte_ctx *c, size_t count); // at least `count` launch records with both events
-// The cell-major copy of a field current on `stream`: every leaf in cell-array order, or (list: HybridPlan::cells_id) the leaves `cells`
+// The cell-major copy of a field current on `stream`: every leaf in cell-array order, or (list: HybridDevice::cells_id) the leaves `cells`
 int make_cell_major(ftte_ctx *c, MediumField &f, hipStream_t stream, const int32_t *cells = nullptr, int64_t ncells = 0, long long list = 0);
 // Group g of a brick plan as the kernel reads it: its arrays in the layout it marches through, its directions' layer tables from
 // `layers` and face blocks from `faces`, face_stride elements per direction
 void fill_brick_group(BrickGroup &G, const BrickPlan &P, size_t g, const double *kappa, const double *emis, double *J, const LayerRec *layers,
                       double *faces, size_t face_stride);
-// The accumulators of a set (ftte_ctx::acc, fine_acc) have one size.  Where that is less than per_acc elements every one of them is
+// The accumulators of a set (ftte_ctx::acc, HybridDevice::fine_acc) have one size.  Where that is less than per_acc elements every one of them is
 // released; returns the size to reserve for those a sweep uses.
 size_t accumulator_size(DeviceBuffer<double> (&acc)[3][kMaxAcc], size_t per_acc);
-
-// One direction of a forest pass as the host knows it
-struct ForestDirHost {
-    const SegRec *rec; const uint8_t *active; double w;
-    double *faces; const AmrExport *exports; int64_t nexports; // hybrid sweep only, else null / 0
-    const std::vector<int64_t> *depth_off;
-    const std::vector<int32_t> *pass_first;    // the passes of depth_off (AmrForest::pass_first), or null: one pass
-    const std::vector<int64_t> *export_first;  // the passes of exports, or null: all in the first
-    const AmrImport *imports = nullptr; int64_t nimports = 0;  // hybrid sweep with a fine block swept by bricks
-};
 
 // A forest pass made ready: the per-direction records and the per-depth tables are in device memory (a batch of 96 would not
 // fit the kernel arguments), what is left is a list of launches.
@@ -338,13 +257,13 @@ struct ForestRun {
     size_t dir_at = 0;
 };
 
-int prepare_forests(ftte_ctx *c, hipStream_t stream, const std::vector<std::vector<ForestDirHost>> &sets, const std::vector<int> &slot0,
+int prepare_forests(ftte_ctx *c, hipStream_t stream, const std::vector<std::vector<ForestDir>> &sets, const std::vector<int> &slot0,
                     int batch, size_t per_dir, std::vector<ForestRun> *runs);
 int launch_forest_pass(ftte_ctx *c, hipStream_t stream, const ForestRun &R, size_t b, size_t p, AmrLevelRec A);
 int launch_forest_combine(ftte_ctx *c, hipStream_t stream, const ForestRun &R, size_t b, AmrLevelRec A, double *J_dev, bool zero_first);
 int launch_forests(ftte_ctx *c, hipStream_t stream, const ForestRun &R, AmrLevelRec A, double *J_dev, bool zero_first, bool time_batches,
                    hipEvent_t before_combine, hipEvent_t after_combine);
-int run_forests(ftte_ctx *c, hipStream_t stream, const std::vector<ForestDirHost> &dirs, int batch, size_t per_dir, AmrLevelRec A,
+int run_forests(ftte_ctx *c, hipStream_t stream, const std::vector<ForestDir> &dirs, int batch, size_t per_dir, AmrLevelRec A,
                 double *J_dev, bool zero_first, bool time_batches);
 int forest_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, const double *w, const double *uvb,
                  double *J_dev, hipStream_t stream);
@@ -362,7 +281,6 @@ int tile_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, co
                hipStream_t stream);
 
 // ---- ftte_hybrid.cpp
-void free_hybrid(ftte_ctx *c);
 int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, const double *w, const double *uvb, double *J_dev,
                  hipStream_t stream, bool *done);
 

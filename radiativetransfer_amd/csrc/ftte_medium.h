@@ -6,6 +6,8 @@
 // current(), launches, and says made().
 #pragma once
 
+#include <cstdint>
+
 #include "ftte_device.h"
 
 namespace ftte {
@@ -14,7 +16,7 @@ class MediumField {
 public:
     // The copies.  Layouts 1 ([jc][ic][kc]) and 2 ([kc][ic][jc]): no parameter.  Brick order per axis order (option "tiled"): the
     // layers per piece.  Cell-major (the forests; all groups of a cell side by side): 0 = every leaf in cell-array order, else the
-    // id of the hybrid plan's leaf list (ftte_ctx::HybridPlan::cells_id).
+    // id of the hybrid plan's leaf list (HybridDevice::cells_id).
     enum Copy { kLayout1, kLayout2, kBricks0, kBricks1, kBricks2, kCellMajor, kCopies };
     static Copy layout(int l) { return Copy(kLayout1 + l - 1); } // l = 1, 2
     static Copy bricks(int l) { return Copy(kBricks0 + l); }     // l = 0, 1, 2
@@ -24,6 +26,8 @@ public:
     bool valid() const { return valid_; } // the source holds what the caller set last (nothing in the library asks; for assertions)
     double *copy(Copy x) const { return copy_[x].buf; }
     double *in_layout(int l) const { return l ? copy(layout(l)) : source(); }
+    // the addresses a captured hybrid sweep names: the source and its cell-major copy
+    template <typename Sig> void sign(Sig &sig) const { sig.push_back((uintptr_t)source()); sig.push_back((uintptr_t)copy(kCellMajor)); }
 
     // Room for `need` elements in the source.  One that has to grow is released first together with every copy (they are sized
     // by it); on failure the field is empty.

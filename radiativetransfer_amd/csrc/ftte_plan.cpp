@@ -1,101 +1,9 @@
-// ftte_plan.cpp -- the host planners of the uniform-grid sweeps: directions -> per-layer tables, then either ray-following
-// tiles and launches (build_plan, ftte::sweep_kernel) or cell-fixed bricks, groups, accumulators and stages (plan_brick_groups,
-// build_brick_plan, ftte::brick_kernel).  Pure host work, cached in the context.
+// ftte_plan.cpp -- the host planners of the uniform-grid sweeps: directions -> per-layer tables (plan_direction, ftte_planner.cpp),
+// then either ray-following tiles and launches (build_plan, ftte::sweep_kernel) or cell-fixed bricks, groups, accumulators
+// (plan_brick_groups, ftte_planner.cpp) and stages (build_brick_plan, ftte::brick_kernel).  Pure host work, cached in the context.
 #include "ftte_context.h"
 
 namespace ftte {
-
-// ---- planner ------------------------------------------------------------------------------------
-// One direction: fold it (equiSources.f90:1395-1454), build its per-layer patterns (:1495-1534, setPattern) and turn them
-// into what the kernels read: the memory frame of its izone and one LayerRec per layer.
-int plan_direction(ftte_ctx *c, int d, double phi_d, double theta_d, double w_d, int tile_rows, std::vector<ftte_pattern> &pat,
-                   std::vector<int> &du_cum, std::vector<int> &dv_cum, DirPlan &D, LayerRec *layers_of_d, size_t layer_off,
-                   const SubGridPlan *sub)
-{
-    // sub: the planes of a cubic sub-grid of `sub->n` cells a side and cell size sub->cell, whose layers carry the patterns
-    // sub->patterns(d) instead of a ray's own march from (0.5, 0.5): the fine cells of a fully refined block (ftte_hybrid.cpp)
-    const int n = sub ? sub->n : c->n;
-    const double cell = sub ? sub->cell : c->box / (double)n; // cellSizeAbsoluteUnits, equiSources.f90:1570
-    const long nn = (long)n * n;
-    D.w = w_d;
-
-    int rc = fold_direction(phi_d, theta_d, &D.phi, &D.theta, &D.izone);
-    if (rc) {
-        char buf[160];
-        std::snprintf(buf, sizeof buf, "direction %d (phi=%.17g, theta=%.17g) cannot be folded: %s", d, phi_d, theta_d,
-                      rc == 1 ? "phi on a quadrant boundary" : rc == 2 ? "theta outside (-pi/2,0)u(0,pi/2)"
-                                                                       : "tie between dominant axes");
-        return fail(c, fold_status(rc), buf);
-    }
-    if (sub) {
-        const int src = sub->patterns(d, D.phi, D.theta, D.izone, pat.data());
-        if (src) return fail(c, src, "direction " + std::to_string(d) + ": ray pattern left the unit cell (sub-layer patterns of a refined block)");
-    } else if (layer_patterns(n, D.phi, D.theta, pat.data())) {
-        char buf[128];
-        std::snprintf(buf, sizeof buf, "direction %d: ray pattern left the unit cell (setPattern consistency check)", d);
-        return fail(c, FTTE_ERR_PATTERN, buf);
-    }
-
-    // memory frame of this izone: which storage axis the march runs along decides the layout;
-    // within it u = the sweep axis that lands on the contiguous storage axis
-    ZoneMap zm;
-    zone_map(D.izone, &zm);
-    int march_c = 0;
-    for (int a = 0; a < 3; ++a) if (zm.src[a] == 0) march_c = a;
-    D.layout = march_c;
-    const int fast_c = (march_c == 2) ? 1 : 2;
-    const int mid_c = (march_c == 0) ? 1 : 0;
-    const bool u_is_k = zm.src[fast_c] == 2;
-    D.su = zm.mirror[fast_c] ? -1 : 1;
-    D.sv = zm.mirror[mid_c] ? -n : n;
-    D.si = (int)(zm.mirror[march_c] ? -nn : nn);
-    // the column enters as a position p = u (or n+1-u when mirrored) with stride +1: offset p - 1
-    D.org = -1 + (zm.mirror[mid_c] ? (long)n * n : -(long)n) +
-            (zm.mirror[march_c] ? (long)n * nn : -nn);
-
-    // layers: reference chain -> kernel-frame class, lengths in chain order, cumulative drift
-    D.layer_off = layer_off;
-    int du = 0, dv = 0;
-    for (int i = 0; i < n; ++i) {
-        const ftte_pattern &p = pat[i];
-        LayerRec &R = layers_of_d[i];
-        R.dpath[0] = cell * p.xy_len;
-        R.dpath[1] = R.dpath[2] = 0.0;
-        int rc_class = RC_ONE, step_k = 0, step_j = 0;
-        if (p.xz_active && p.yz_active) {
-            step_k = step_j = 1;
-            if (p.xy_top == 3) { // xy -> yz -> xz (the xz piece reaches the top)
-                R.dpath[1] = cell * p.yz_len; R.dpath[2] = cell * p.xz_len;
-                rc_class = u_is_k ? RC_THREE_U_SWAP : RC_THREE_V_SWAP; // mean adds xy, xz, yz: 3rd piece before 2nd
-            } else {             // xy -> xz -> yz
-                R.dpath[1] = cell * p.xz_len; R.dpath[2] = cell * p.yz_len;
-                rc_class = u_is_k ? RC_THREE_V : RC_THREE_U;
-            }
-        } else if (p.yz_active) { // xy -> yz: one cell further along sweep-k
-            step_k = 1;
-            R.dpath[1] = cell * p.yz_len;
-            rc_class = u_is_k ? RC_TWO_U : RC_TWO_V;
-        } else if (p.xz_active) { // xy -> xz: one cell further along sweep-j
-            step_j = 1;
-            R.dpath[1] = cell * p.xz_len;
-            rc_class = u_is_k ? RC_TWO_V : RC_TWO_U;
-        }
-        R.info = rc_class;
-        R.drift = (du & 0xffff) | (dv << 16);
-        du_cum[i] = du; dv_cum[i] = dv;
-        du += u_is_k ? step_k : step_j;
-        dv += u_is_k ? step_j : step_k;
-    }
-    // rays present at the last layer start at label -drift (base cell 0, second piece in cell 1)
-    D.u_lo = 1 - du_cum[n - 1];
-    D.v_lo = 1 - dv_cum[n - 1];
-    D.du_mid = du_cum[n / 2];
-    D.dv_mid = dv_cum[n / 2];
-    D.ntu = (n - D.u_lo + 1 + 62) / 63;
-    D.ntv = (n - D.v_lo + 1 + tile_rows - 1) / tile_rows;
-
-    return FTTE_OK;
-}
 
 // Turns the direction list into what the kernel consumes.  O(ndir * (n + tiles)) host work,
 // cached in the context for as long as the directions, the grid and the tuning stay the same.
@@ -124,8 +32,9 @@ int build_plan(ftte_ctx *c, int rows, int stack, int ndir, const double *phi, co
 
     for (int d = 0; d < ndir; ++d) {
         DirPlan &D = P.dirs[d];
-        const int rc = plan_direction(c, d, phi[d], theta[d], w[d], tile_rows, pat, du_cum, dv_cum, D, &P.layers[(size_t)d * n], (size_t)d * n);
-        if (rc) return rc;
+        std::string why;
+        const int rc = plan_direction(n, c->box, d, phi[d], theta[d], w[d], tile_rows, pat, du_cum, dv_cum, D, &P.layers[(size_t)d * n], (size_t)d * n, nullptr, &why);
+        if (rc) return fail(c, rc, why);
         D.slot = in_layout[D.layout]++ % slots;
     }
 
@@ -203,110 +112,6 @@ int build_plan(ftte_ctx *c, int rows, int stack, int ndir, const double *phi, co
     return FTTE_OK;
 }
 
-// The part of a brick plan that does not depend on which bricks are swept: the directions, the brick geometry and the face
-// block layout, the groups and their accumulators.
-int plan_brick_groups(ftte_ctx *c, BrickPlan &P, int ndir, const double *phi, const double *theta, const double *w, int chunk, int gmax,
-                      int want_dataflow, bool whole_faces, const SubGridPlan *sub)
-{
-    const int n = sub ? sub->n : c->n;
-    ++c->n_plan_builds;
-    P = BrickPlan();
-    P.id = ++c->brick_plans; // (a new plan: no BrickTables holds it)
-    P.n = n; P.chunk = chunk; P.gmax = gmax; P.share = c->share; P.want_dataflow = want_dataflow; P.box = c->box;
-    P.phi.assign(phi, phi + ndir); P.theta.assign(theta, theta + ndir); P.w.assign(w, w + ndir);
-    P.dirs.resize(ndir);
-    P.layers.resize((size_t)ndir * n);
-
-    std::vector<ftte_pattern> pat(n);
-    std::vector<int> du_cum(n + 1), dv_cum(n + 1);
-    for (int d = 0; d < ndir; ++d) {
-        const int rc = plan_direction(c, d, phi[d], theta[d], w[d], 7, pat, du_cum, dv_cum, P.dirs[d], &P.layers[(size_t)d * n], (size_t)d * n, sub);
-        if (rc) return rc;
-    }
-    P.ntu = (n + 63) / 64; P.ntv = (n + kBrickRows - 1) / kBrickRows; P.nti = (n + chunk - 1) / chunk;
-    P.up = 64 * P.ntu; P.vp = kBrickRows * P.ntv;
-    P.dataflow = want_dataflow != 0;
-    P.ut = P.dataflow ? 16 : kBrickRows; // a 128-byte line of its own per brick and layer when bricks of one launch exchange rays
-    P.uw = P.ntv * P.ut;
-    // rings over two chunks, or every chunk's faces kept (hybrid sweep); a sub-grid keeps one slot more (the chunk before its first)
-    // and one ring more along u and v (the brick columns / rows before its first): BrickLaunch::sub
-    P.nslot = sub ? P.nti + 1 : whole_faces ? P.nti : 2;
-    const int edge = sub ? 1 : 0;
-    P.vface_off = (int64_t)(P.ntu + edge) * P.nslot * chunk * P.uw;
-    P.iface_off = P.vface_off + (int64_t)(P.ntv + edge) * P.nslot * chunk * P.up;
-    P.uqface_off = P.iface_off + (int64_t)P.nslot * P.vp * P.up;
-    // (the faces inside a brick are used by the hybrid sweep only, which keeps every chunk's faces)
-    P.face_elems = P.uqface_off + (whole_faces ? 2 * (int64_t)P.nslot * chunk * P.uw : 0);
-
-    if (P.nti >= kBrickAccumulate) return fail(c, FTTE_ERR_UNSUPPORTED, "brick engine: more than 16383 chunks along the march axis: raise option \"chunk\"");
-
-    // Groups: layout after layout (the order in which the merge adds the accumulators), izone after izone, at most gmax
-    // directions each.  Accumulators: a group stores its J contribution once per cell, and every accumulator costs the merge
-    // one more read of the grid, so groups share an accumulator where they provably never meet in a brick in the same launch
-    // (the later one then reads, adds and stores, BrickTask):
-    //   * the passes of one izone sweep the bricks in the same order: started in different launches they never meet;
-    //   * two izones of one layout differ by reflections of the brick order along some axes; with t -> N-1-t along an axis
-    //     of even brick count N the difference of their stage numbers in a brick changes by an odd amount, so if an odd number
-    //     of such axes is reflected the difference is odd in every brick, and start launches that differ by an even number
-    //     never bring them together.  Needs bricks that coincide under reflection: n a multiple of 64, 8 and the chunk.
-    const bool aligned = n % 64 == 0 && n % kBrickRows == 0 && n % chunk == 0;
-    const int nbricks[3] = {P.ntu, P.ntv, P.nti};
-    for (int layout = 0; layout < 3; ++layout) {
-        struct Zone { int izone, parity; std::vector<std::vector<int>> passes; };
-        std::vector<Zone> zones;
-        for (int izone = 1; izone <= 24; ++izone) {
-            std::vector<int> members;
-            for (int d = 0; d < ndir; ++d)
-                if (P.dirs[d].izone == izone && P.dirs[d].layout == layout) members.push_back(d);
-            if (members.empty()) continue;
-            Zone Z;
-            Z.izone = izone;
-            const DirPlan &D0 = P.dirs[members[0]];
-            const bool mirror[3] = {D0.su < 0, D0.sv < 0, D0.si < 0};
-            Z.parity = 0;
-            for (int a = 0; a < 3; ++a) if (mirror[a] && nbricks[a] % 2 == 0) Z.parity ^= 1;
-            // as few passes as gmax allows, of equal size where possible (5 directions, gmax 4: 3 + 2, not 4 + 1)
-            const size_t npass = (members.size() + (size_t)gmax - 1) / (size_t)gmax;
-            for (size_t b = 0, q = 0; q < npass; ++q) {
-                const size_t len = members.size() / npass + (q < members.size() % npass ? 1 : 0);
-                Z.passes.emplace_back(members.begin() + (long)b, members.begin() + (long)(b + len));
-                b += len;
-            }
-            zones.push_back(Z);
-        }
-        // pair the izones of opposite parity (share = 2); share = 1: only the passes of one izone share; 0: nobody shares
-        std::vector<int> partner(zones.size(), -1);
-        if (aligned && c->share >= 2)
-            for (size_t x = 0; x < zones.size(); ++x) {
-                if (partner[x] >= 0) continue;
-                for (size_t y = x + 1; y < zones.size(); ++y)
-                    if (partner[y] < 0 && zones[y].parity != zones[x].parity) { partner[x] = (int)y; partner[y] = (int)x; break; }
-            }
-        std::vector<int> acc_of(zones.size(), -1);
-        for (size_t x = 0; x < zones.size(); ++x) {
-            const bool paired = partner[x] >= 0;
-            if (c->share >= 1) {
-                if (acc_of[x] < 0) {
-                    acc_of[x] = P.nacc[layout]++;
-                    if (paired) acc_of[(size_t)partner[x]] = acc_of[x];
-                }
-            }
-            for (size_t p = 0; p < zones[x].passes.size(); ++p) {
-                BrickPlan::Group G;
-                G.izone = zones[x].izone; G.layout = layout;
-                G.acc = c->share >= 1 ? acc_of[x] : P.nacc[layout]++;
-                G.offset = c->share >= 1 ? (int)p * (paired ? 2 : 1) : 0;
-                G.dirs = zones[x].passes[p];
-                P.max_dirs = std::max(P.max_dirs, (int)G.dirs.size());
-                P.groups.push_back(G);
-            }
-        }
-    }
-    for (int layout = 0; layout < 3; ++layout)
-        if (P.nacc[layout] > kMaxAcc) return fail(c, FTTE_ERR_UNSUPPORTED, "too many direction groups for one memory layout: raise option \"group\"");
-
-    return FTTE_OK;
-}
 
 // Bricks: group the directions by izone (input order within an izone, at most `group` per group), cut the grid into
 // bricks of 64 x kBrickRows x chunk cells, and order the bricks of every group into stages tu + tv + ti: a brick's three
@@ -337,7 +142,12 @@ int build_brick_plan(ftte_ctx *c, int ndir, const double *phi, const double *the
                        !std::memcmp(P.w.data(), w, sizeof(double) * ndir))))
         return FTTE_OK;
 
-    if ((rc = plan_brick_groups(c, P, ndir, phi, theta, w, chunk, gmax, want_dataflow, false))) return rc;
+    ++c->n_plan_builds;
+    const long long id = ++c->brick_plans; // (a new plan: no BrickTables holds it)
+    std::string why;
+    rc = plan_brick_groups(P, n, c->box, ndir, phi, theta, w, chunk, gmax, c->share, want_dataflow, false, nullptr, &why);
+    P.id = id;
+    if (rc) return fail(c, rc, why);
     P.want_glanes = want_glanes;
 
     // streams: the groups of one accumulator stay on one stream (their launches are ordered against each other)

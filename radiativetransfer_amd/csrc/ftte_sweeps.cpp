@@ -111,12 +111,6 @@ int mark_sweep(ftte_ctx *c, hipStream_t stream)
     return FTTE_OK;
 }
 
-void free_forests(ftte_ctx *c)
-{
-    c->forests.clear();
-    c->forest_key.clear();
-}
-
 size_t accumulator_size(DeviceBuffer<double> (&acc)[3][kMaxAcc], size_t per_acc)
 {
     size_t have = 0;
@@ -132,14 +126,14 @@ size_t accumulator_size(DeviceBuffer<double> (&acc)[3][kMaxAcc], size_t per_acc)
 // scratch slots from slot0[q] on), `batch` directions at a time each; built and uploaded in one go on `stream`.  A direction's
 // forest may come in passes (hybrid sweep with several boxes): every batch gets per-depth tables pass by pass, and per pass the
 // range of the rays that leave its boxes.
-int prepare_forests(ftte_ctx *c, hipStream_t stream, const std::vector<std::vector<ForestDirHost>> &sets, const std::vector<int> &slot0,
+int prepare_forests(ftte_ctx *c, hipStream_t stream, const std::vector<std::vector<ForestDir>> &sets, const std::vector<int> &slot0,
                     int batch, size_t per_dir, std::vector<ForestRun> *runs)
 {
     std::vector<AmrDirRec> recs;
     std::vector<int64_t> tables;
     runs->assign(sets.size(), ForestRun());
     for (size_t q = 0; q < sets.size(); ++q) {
-        const std::vector<ForestDirHost> &dirs = sets[q];
+        const std::vector<ForestDir> &dirs = sets[q];
         ForestRun &R = (*runs)[q];
         const int ndir = (int)dirs.size();
         R.dir_at = recs.size();
@@ -149,29 +143,29 @@ int prepare_forests(ftte_ctx *c, hipStream_t stream, const std::vector<std::vect
             B.d0 = d0; B.nb = nb;
             size_t npass = 1;
             for (int t = 0; t < nb; ++t) {
-                const ForestDirHost &D = dirs[(size_t)(d0 + t)];
+                const ForestTables &D = *dirs[(size_t)(d0 + t)].tables;
                 AmrDirRec rec;
                 std::memset(&rec, 0, sizeof rec);
                 rec.rec = D.rec; rec.active = D.active; rec.w = D.w;
-                rec.Iout = c->amr_Iout + per_dir * (size_t)(slot0[q] + t);
-                rec.mean = c->amr_mean + per_dir * (size_t)(slot0[q] + t);
-                rec.faces = D.faces; rec.exports = D.exports; rec.nexports = D.nexports;
+                rec.Iout = c->fscratch.Iout + per_dir * (size_t)(slot0[q] + t);
+                rec.mean = c->fscratch.mean + per_dir * (size_t)(slot0[q] + t);
+                rec.faces = dirs[(size_t)(d0 + t)].faces; rec.exports = D.exports; rec.nexports = D.nexports;
                 rec.imports = D.imports; rec.nimports = D.nimports;
                 recs.push_back(rec);
-                if (D.pass_first) npass = std::max(npass, D.pass_first->size() - 1);
+                if (!D.pass_first.empty()) npass = std::max(npass, D.pass_first.size() - 1);
             }
             for (size_t p = 0; p < npass; ++p) {
                 ForestRun::Pass P;
                 // depth d of pass p is entry first(p) + d of the direction's depth_off, while that lies inside the pass
-                auto range = [&](const ForestDirHost &D, size_t *first, size_t *count) {
-                    const size_t all = D.depth_off->size() - 1;
-                    if (!D.pass_first) { *first = 0; *count = p == 0 ? all : 0; return; }
-                    if (p + 1 >= D.pass_first->size()) { *first = all; *count = 0; return; }
-                    *first = (size_t)(*D.pass_first)[p]; *count = (size_t)((*D.pass_first)[p + 1] - (*D.pass_first)[p]);
+                auto range = [&](const ForestTables &D, size_t *first, size_t *count) {
+                    const size_t all = D.depth_off.size() - 1;
+                    if (D.pass_first.empty()) { *first = 0; *count = p == 0 ? all : 0; return; }
+                    if (p + 1 >= D.pass_first.size()) { *first = all; *count = 0; return; }
+                    *first = (size_t)D.pass_first[p]; *count = (size_t)(D.pass_first[p + 1] - D.pass_first[p]);
                 };
                 for (int t = 0; t < nb; ++t) {
                     size_t first, count;
-                    range(dirs[(size_t)(d0 + t)], &first, &count);
+                    range(*dirs[(size_t)(d0 + t)].tables, &first, &count);
                     P.maxdepth = std::max(P.maxdepth, count);
                 }
                 P.table_at = tables.size();
@@ -181,11 +175,11 @@ int prepare_forests(ftte_ctx *c, hipStream_t stream, const std::vector<std::vect
                     const size_t at = tables.size();
                     tables.resize(at + 2 * (size_t)nb, 0);
                     for (int t = 0; t < nb; ++t) {
-                        const ForestDirHost &D = dirs[(size_t)(d0 + t)];
+                        const ForestTables &D = *dirs[(size_t)(d0 + t)].tables;
                         size_t first, count;
                         range(D, &first, &count);
                         if (depth < count) {
-                            const std::vector<int64_t> &off = *D.depth_off;
+                            const std::vector<int64_t> &off = D.depth_off;
                             tables[at + (size_t)t] = off[first + depth + 1] - off[first + depth];
                             tables[at + (size_t)nb + (size_t)t] = off[first + depth];
                             most = std::max(most, off[first + depth + 1] - off[first + depth]);
@@ -197,11 +191,11 @@ int prepare_forests(ftte_ctx *c, hipStream_t stream, const std::vector<std::vect
                 P.export_at = tables.size();
                 tables.resize(P.export_at + 2 * (size_t)nb, 0);
                 for (int t = 0; t < nb; ++t) {
-                    const ForestDirHost &D = dirs[(size_t)(d0 + t)];
+                    const ForestTables &D = *dirs[(size_t)(d0 + t)].tables;
                     int64_t first = 0, count = p == 0 ? D.nexports : 0;
-                    if (D.export_first) {
-                        first = p + 1 < D.export_first->size() ? (*D.export_first)[p] : D.nexports;
-                        count = p + 1 < D.export_first->size() ? (*D.export_first)[p + 1] - first : 0;
+                    if (!D.export_first.empty()) {
+                        first = p + 1 < D.export_first.size() ? D.export_first[p] : D.nexports;
+                        count = p + 1 < D.export_first.size() ? D.export_first[p + 1] - first : 0;
                     }
                     tables[P.export_at + (size_t)t] = count;
                     tables[P.export_at + (size_t)nb + (size_t)t] = first;
@@ -212,10 +206,10 @@ int prepare_forests(ftte_ctx *c, hipStream_t stream, const std::vector<std::vect
             R.batches.push_back(B);
         }
     }
-    FTTE_HIP(c, c->d_amr_dirs.reserve(recs.size()));
-    FTTE_HIP(c, c->d_amr_tables.reserve(tables.size()));
-    if (!recs.empty()) FTTE_HIP(c, hipMemcpyAsync(c->d_amr_dirs, recs.data(), sizeof(AmrDirRec) * recs.size(), hipMemcpyHostToDevice, stream));
-    if (!tables.empty()) FTTE_HIP(c, hipMemcpyAsync(c->d_amr_tables, tables.data(), sizeof(int64_t) * tables.size(), hipMemcpyHostToDevice, stream));
+    FTTE_HIP(c, c->fscratch.dirs.reserve(recs.size()));
+    FTTE_HIP(c, c->fscratch.tables.reserve(tables.size()));
+    if (!recs.empty()) FTTE_HIP(c, hipMemcpyAsync(c->fscratch.dirs, recs.data(), sizeof(AmrDirRec) * recs.size(), hipMemcpyHostToDevice, stream));
+    if (!tables.empty()) FTTE_HIP(c, hipMemcpyAsync(c->fscratch.tables, tables.data(), sizeof(int64_t) * tables.size(), hipMemcpyHostToDevice, stream));
     FTTE_HIP(c, hipStreamSynchronize(stream)); // the host vectors leave scope; pageable copies are staged anyway
     return FTTE_OK;
 }
@@ -227,7 +221,7 @@ int launch_forest_pass(ftte_ctx *c, hipStream_t stream, const ForestRun &R, size
     const ForestRun::Batch &B = R.batches[b];
     if (p >= B.passes.size()) return FTTE_OK;
     const ForestRun::Pass &P = B.passes[p];
-    A.dir = c->d_amr_dirs + R.dir_at + (size_t)B.d0;
+    A.dir = c->fscratch.dirs + R.dir_at + (size_t)B.d0;
     A.ndir = B.nb;
     // Runs of thin levels (option "forest_fuse": at most that many (segment, frequency group) pairs in the fullest direction) go in
     // one launch, a workgroup per direction and a barrier per level; a thick level gets a launch of its own, a thread per pair.
@@ -237,18 +231,18 @@ int launch_forest_pass(ftte_ctx *c, hipStream_t stream, const ForestRun &R, size
         while (end < P.maxdepth && R.most_of[P.most_at + end] * (int64_t)c->nnu <= thin) ++end;
         if (end > depth + 1) {
             A.count = A.begin = nullptr; A.most = 0;
-            if (launch_amr_levels(A, c->d_amr_tables + P.table_at + depth * 2 * (size_t)B.nb, (int)(end - depth), stream))
+            if (launch_amr_levels(A, c->fscratch.tables + P.table_at + depth * 2 * (size_t)B.nb, (int)(end - depth), stream))
                 return fail(c, FTTE_ERR_NO_DEVICE, "forest level kernel launch failed");
             depth = end;
             continue;
         }
-        A.count = c->d_amr_tables + P.table_at + depth * 2 * (size_t)B.nb;
+        A.count = c->fscratch.tables + P.table_at + depth * 2 * (size_t)B.nb;
         A.begin = A.count + B.nb;
         A.most = R.most_of[P.most_at + depth];
         if (launch_amr_level(A, stream)) return fail(c, FTTE_ERR_NO_DEVICE, "forest level kernel launch failed");
         ++depth;
     }
-    A.count = c->d_amr_tables + P.export_at;
+    A.count = c->fscratch.tables + P.export_at;
     A.begin = A.count + B.nb;
     if (launch_amr_export(A, P.most_exports, stream)) return fail(c, FTTE_ERR_NO_DEVICE, "forest export kernel launch failed");
     return FTTE_OK;
@@ -258,7 +252,7 @@ int launch_forest_pass(ftte_ctx *c, hipStream_t stream, const ForestRun &R, size
 int launch_forest_combine(ftte_ctx *c, hipStream_t stream, const ForestRun &R, size_t b, AmrLevelRec A, double *J_dev, bool zero_first)
 {
     const ForestRun::Batch &B = R.batches[b];
-    A.dir = c->d_amr_dirs + R.dir_at + (size_t)B.d0;
+    A.dir = c->fscratch.dirs + R.dir_at + (size_t)B.d0;
     A.ndir = B.nb;
     if (launch_amr_combine(A, J_dev, zero_first, stream)) return fail(c, FTTE_ERR_NO_DEVICE, "forest combine kernel launch failed");
     return FTTE_OK;
@@ -292,7 +286,7 @@ int launch_forests(ftte_ctx *c, hipStream_t stream, const ForestRun &R, AmrLevel
 }
 
 // The forests of `dirs`, `batch` directions at a time (A.dir / A.count / A.begin are filled here).
-int run_forests(ftte_ctx *c, hipStream_t stream, const std::vector<ForestDirHost> &dirs, int batch, size_t per_dir, AmrLevelRec A,
+int run_forests(ftte_ctx *c, hipStream_t stream, const std::vector<ForestDir> &dirs, int batch, size_t per_dir, AmrLevelRec A,
                 double *J_dev, bool zero_first, bool time_batches)
 {
     std::vector<ForestRun> runs;
@@ -317,9 +311,9 @@ int forest_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     key.insert(key.end(), phi, phi + ndir);
     key.insert(key.end(), theta, theta + ndir);
     key.insert(key.end(), w, w + ndir);
-    if (key != c->forest_key || (int)c->forests.size() != ndir) {
+    if (!c->forests.current(key, ndir)) {
         FTTE_HIP(c, hipStreamSynchronize(stream));
-        free_forests(c);
+        c->forests.drop();
         ++c->n_forest_builds;
         std::vector<double> fphi(ndir), ftheta(ndir);
         std::vector<int> fzone(ndir);
@@ -331,7 +325,7 @@ int forest_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
                 return fail(c, fold_status(frc), buf);
             }
         }
-        c->forests.resize(ndir);
+        c->forests.dirs.resize(ndir);
         // link on the host, a few directions at a time on separate threads, upload, drop the host copy
         const int nthreads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
         for (int d0 = 0; d0 < ndir; d0 += nthreads) {
@@ -346,54 +340,34 @@ int forest_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
                 pool.emplace_back([&, t] {
                     st[t] = build_forest(c->tree, fphi[d0 + t], ftheta[d0 + t], fzone[d0 + t], c->box, &F[t], &msg[t]);
                     if (st[t]) return;
-                    // pack what the device reads per segment into one record, in processing order
                     const AmrForest &f = F[t];
-                    const size_t nact = f.order.size();
-                    rec[t].resize(std::max<size_t>(nact, 1));
-                    for (size_t q = 0; q < nact; ++q) {
-                        const int32_t sg = f.order[q];
-                        rec[t][q].seg = sg; rec[t][q].up = f.up[sg]; rec[t][q].up2 = f.up2[sg]; rec[t][q].at = 0;
-                        rec[t][q].dpath = f.dpath[sg];
-                    }
+                    rec[t] = pack_segments(f);
                     active[t].resize((size_t)ncell);
                     for (int64_t q = 0; q < ncell; ++q)
                         active[t][q] = (uint8_t)((f.up[3 * q + 1] != AmrForest::kInactive ? 1 : 0) | (f.up[3 * q + 2] != AmrForest::kInactive ? 2 : 0));
                 });
             for (auto &th : pool) th.join();
             for (int t = 0; t < nb; ++t) {
-                if (st[t]) { free_forests(c); return fail(c, st[t], "direction " + std::to_string(d0 + t) + ": " + msg[t]); }
-                ftte_ctx::ForestDev &D = c->forests[d0 + t];
+                if (st[t]) { c->forests.drop(); return fail(c, st[t], "direction " + std::to_string(d0 + t) + ": " + msg[t]); }
+                ForestTables &D = c->forests.dirs[d0 + t];
                 D.w = w[d0 + t];
                 D.depth_off = F[t].depth_off;
                 FTTE_HIP(c, to_device(D.rec, rec[t]));
                 FTTE_HIP(c, to_device(D.active, active[t]));
             }
         }
-        c->forest_key = key;
+        c->forests.key = key;
     }
 
     // Scratch: outgoing intensity and mean of every segment of every direction of a batch.  The batch is as large as the
     // direction list, kAmrBatch and the free memory allow (two arrays of 3 ncell nnu doubles per direction: 38 GB for 48
     // directions of a 128^3 x 8 tree), and shrinks once more if the allocation still fails.
     const size_t per_dir = (size_t)nseg * nnu;
-    const int most = c->forest_batch > 0 ? c->forest_batch : kAmrBatch;
-    int batch = std::max(1, std::min(ndir, most));
-    if (c->amr_scratch() < per_dir * (size_t)batch) {
-        FTTE_HIP(c, hipStreamSynchronize(stream));
-        c->amr_Iout.reset(); c->amr_mean.reset();
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const size_t fits = (size_t)(0.9 * (double)free_b) / (2 * sizeof(double) * per_dir);
-            batch = (int)std::max<size_t>(1, std::min<size_t>((size_t)batch, fits));
-        }
-        for (;;) {
-            if (c->amr_Iout.reserve(per_dir * (size_t)batch) == hipSuccess && c->amr_mean.reserve(per_dir * (size_t)batch) == hipSuccess) break;
-            c->amr_Iout.reset(); c->amr_mean.reset();
-            (void)hipGetLastError();
-            if (batch == 1) return fail(c, FTTE_ERR_MEMORY, "refined-grid sweep: not enough device memory for the segment scratch of one direction");
-            batch = (batch + 1) / 2;
-        }
-    } else batch = (int)std::min<size_t>((size_t)most, c->amr_scratch() / per_dir);
+    const int most = c->hopt.forest_batch > 0 ? c->hopt.forest_batch : kAmrBatch;
+    if (!c->fscratch.fits(per_dir, ndir, most)) FTTE_HIP(c, hipStreamSynchronize(stream));
+    hipError_t why;
+    const int batch = c->fscratch.reserve_batch(per_dir, ndir, most, 0.9, true, &why);
+    if (!batch) return fail(c, FTTE_ERR_MEMORY, "refined-grid sweep: not enough device memory for the segment scratch of one direction");
     FTTE_HIP(c, hipStreamSynchronize(stream)); // d_uvb below may still be read by the previous sweep
     FTTE_HIP(c, c->d_uvb.send(uvb, (size_t)nnu));
 
@@ -419,11 +393,8 @@ int forest_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
         A.ncell = ncell;
         A.nnu = nnu;
         A.math = kMath;
-        std::vector<ForestDirHost> dirs((size_t)ndir);
-        for (int d = 0; d < ndir; ++d) {
-            const ftte_ctx::ForestDev &D = c->forests[(size_t)d];
-            dirs[(size_t)d] = ForestDirHost{D.rec, D.active, D.w, nullptr, nullptr, 0, &D.depth_off, nullptr, nullptr};
-        }
+        std::vector<ForestDir> dirs((size_t)ndir);
+        for (int d = 0; d < ndir; ++d) dirs[(size_t)d] = ForestDir{&c->forests.dirs[(size_t)d], nullptr};
         if ((rc = run_forests(c, stream, dirs, batch, per_dir, A, J_dev, true, true))) return rc;
     }
     return mark_sweep(c, stream);

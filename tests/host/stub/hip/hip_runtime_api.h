@@ -1,6 +1,6 @@
 // A stand-in for <hip/hip_runtime_api.h> on the CPU: the calls the owners of ftte_device.h use, backed by malloc, with a count of
 // live objects, a count of releases, and a switch that makes the next allocation or creation fail; the copies and fills that
-// ftte_bricks.h issues, as memcpy / memset with a count of the copies.  tests/host/ only.
+// ftte_bricks.h issues, as memcpy / memset with a count of the copies; the free memory that ftte_forests.h asks for.  tests/host/ only.
 #pragma once
 
 #include <cstddef>
@@ -19,7 +19,9 @@ struct stub_state {
     long live = 0, released = 0;
     long live_at_last_request = -1; // objects alive when the last allocation was asked for
     bool fail_next = false;
+    int fail_countdown = 0;         // k > 0: the k-th allocation or creation from now fails
     long copies = 0;                // hipMemcpy / hipMemcpyAsync calls so far
+    size_t free_bytes = (size_t)1 << 30; // what hipMemGetInfo reports
 };
 inline stub_state &stub() { static stub_state s; return s; }
 
@@ -27,6 +29,7 @@ inline hipError_t stub_make(void **out, size_t bytes)
 {
     stub().live_at_last_request = stub().live;
     *out = nullptr;
+    if (stub().fail_countdown > 0 && --stub().fail_countdown == 0) stub().fail_next = true;
     if (stub().fail_next) { stub().fail_next = false; return hipErrorOutOfMemory; }
     *out = std::malloc(bytes ? bytes : 1);
     ++stub().live;
@@ -57,3 +60,5 @@ inline hipGraphExec_t stub_new_graph_exec() { void *p; stub_make(&p, 1); return 
 inline hipError_t hipMemcpy(void *dst, const void *src, size_t bytes, hipMemcpyKind) { std::memcpy(dst, src, bytes); ++stub().copies; return hipSuccess; }
 inline hipError_t hipMemcpyAsync(void *dst, const void *src, size_t bytes, hipMemcpyKind kind, hipStream_t) { return hipMemcpy(dst, src, bytes, kind); }
 inline hipError_t hipMemsetAsync(void *dst, int value, size_t bytes, hipStream_t) { std::memset(dst, value, bytes); return hipSuccess; }
+inline hipError_t hipMemGetInfo(size_t *free_b, size_t *total_b) { *free_b = stub().free_bytes; *total_b = 2 * stub().free_bytes; return hipSuccess; }
+inline hipError_t hipGetLastError() { return hipSuccess; }

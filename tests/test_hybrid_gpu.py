@@ -311,6 +311,45 @@ def test_fine_block_swept_by_bricks_of_its_own_every_izone_bitwise(lo):
             assert np.array_equal(J, ref), f"izone {O.fold_direction(p, t)[2]}"
 
 
+def test_the_two_refined_grid_paths_share_their_scratch_and_their_owners():
+    """One context, the 24 one-per-izone directions, two frequency groups: the hybrid sweep of a patch, the same tree through the
+    forest path for the whole tree (which resizes the segment scratch both paths use), the hybrid sweep again, another tree whose
+    fully refined cube is swept by fine bricks (other buffer sizes all round), and the first tree again.  The hybrid J of the
+    patch is the same every time, the forest path equals the oracle, and a second round leaves as many device objects as the
+    first."""
+    n = 64
+    patch = patch_case(n, [(30 + a, 31 + b, 33 + c) for a in range(3) for b in range(2) for c in range(4)], 1, 2, seed=n)
+    block = _cube_case(n, 32, (8, 24, 12), 2, seed=41)
+    dirs = one_per_izone()
+    phi, theta = np.array([d[0] for d in dirs]), np.array([d[1] for d in dirs])
+    w = np.full(len(dirs), 1.0 / len(dirs))
+    ref = O.sweep_tree(n, patch[0], patch[1], 1.0, phi, theta, w, patch[2], arith=O.ARITH_DEVICE)
+    with rt.DiffuseTransfer() as e:
+        def sweep(case):
+            level, kappa, uvb = case
+            e.set_grid(n, level, 1.0)
+            e.set_opacity(kappa)
+            return e.transport(phi, theta, w, uvb)
+        objects = []
+        for _ in range(2):
+            J1 = sweep(patch)
+            assert e.counter("hybrid_boxes") == 1 and e.counter("fine_block") == 0
+            e.set_option("hybrid", 0)
+            J_forest = e.transport(phi, theta, w, patch[2])
+            assert e.counter("hybrid_boxes") == 0
+            e.set_option("hybrid", 1)
+            J3 = e.transport(phi, theta, w, patch[2])
+            J_block = sweep(block)
+            assert e.counter("fine_block") == 64
+            J5 = sweep(patch)
+            assert np.array_equal(J1, J3) and np.array_equal(J1, J5)
+            assert np.array_equal(J_forest, ref)
+            assert np.allclose(J1, J_forest, rtol=SUM_RTOL, atol=0)
+            assert np.all(J_block > 0) and np.all(J_block <= block[2][:, None] * (1 + 1e-12))
+            objects.append(e.counter("device_objects"))
+        assert objects[1] == objects[0]
+
+
 def test_fine_block_many_directions_pipelines_and_the_forest_for_it():
     """The same with 48 directions in three pipelines: reproducible, equal to the sweep that keeps the block in the forest
     (fine_bricks = 0) and to the forest path for the whole tree to the rounding of the sum; a block the bricks cannot take (30^3:

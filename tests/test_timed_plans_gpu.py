@@ -2,7 +2,7 @@
 
 bench.py's default run (256^3 cells x 8 frequency groups x 96 directions) takes a brick plan in which direction groups share
 J accumulators: above 64 cells a side, where every brick count is even, izones of opposite brick-stage parity are paired on one
-accumulator and the later group reads, adds and stores without atomics (csrc/ftte_plan.cpp, plan_brick_groups).  Determinism
+accumulator and the later group reads, adds and stores without atomics (csrc/ftte_planner.cpp, plan_brick_groups).  Determinism
 and linearity cannot see a contribution that is lost the same way on every run; these tests compare J with the oracle (device
 arithmetic, ARITH_DEVICE) to the rounding of the sum over directions, per cell, with no absolute slack:
   * the headline run end to end: what bench.py itself timed and dumped;
