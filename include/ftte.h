@@ -104,7 +104,8 @@ int ftte_set_opacity_device(ftte_ctx *ctx, int nnu, const double *kappa_dev);
  * HeI = beta26, HeII = beta25 of the reference's group tables). */
 int ftte_set_species(ftte_ctx *ctx, int nnu, const double *HI, const double *HeI, const double *HeII,
                      const double *beta);
-/* Emissivity eta[nnu][ncell] (call after the opacities are set; sized by their nnu).  NULL selects the reference's
+/* Emissivity eta[nnu][ncell] (call after the opacities are set; sized by their nnu: opacities with another nnu switch
+ * emission off until it is set again).  NULL selects the reference's
  * hard-wired zero emissivity (transportRoutinesModule.f90:673-675).  Non-NULL switches the sweep to the reference's
  * emission term as written at :676,   Iout = Iin*tmpabs + nemi*tmpemi/dpath   with tmpemi = (1-tmpabs)/kappa
  * (dpath below tau = 1e-10), and to its log-mean (:1044-1048) for the cell intensity.  Replaces any source function. */

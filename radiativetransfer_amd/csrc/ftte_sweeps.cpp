@@ -7,6 +7,9 @@ namespace ftte {
 int ensure_kappa(ftte_ctx *c, int nnu)
 {
     const size_t need = (size_t)nnu * c->ncell;
+    // the emissivity or source function holds the groups it was set for: with another number of groups the sweep is the plain one,
+    // whether the buffers have to grow or not
+    if (nnu != c->nnu) c->emit_mode = 0;
     if (c->kappa.source() && c->kappa.capacity() >= need) return FTTE_OK;
     c->emis.release(); c->emit_mode = 0; // sized by the old number of groups: has to be set again
     FTTE_HIP(c, c->kappa.reserve_source(need));

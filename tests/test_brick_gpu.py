@@ -100,7 +100,7 @@ def test_bricks_equal_tiles_on_the_full_direction_set(engine, n, chunk):
 def test_one_wavefront_and_a_pair_per_brick_same_bits(engine):
     """The pair form splits a brick's rows between two wavefronts and changes nothing else: the same bits as one wavefront per
     brick, on whole and ragged grids, with shared accumulators (96 directions in groups of three), without emission and with
-    either form of it."""
+    either form of it.  Both forms with emission against the oracle: tests/test_brick_emission_gpu.py."""
     phi, theta, w = O.healpix_directions(2)
     engine.set_option("engine", 2)
     try:
