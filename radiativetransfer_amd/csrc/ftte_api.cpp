@@ -67,7 +67,6 @@ int ftte_destroy(ftte_ctx *c)
     if (c->multi) return multi_destroy(c);
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (auto &r : c->registered) (void)hipHostUnregister((void *)r.base); // the caller's arrays: pinned here, not owned
     delete c;
     return FTTE_OK;
 }
@@ -351,9 +350,9 @@ int ftte_diffuse_sweep(ftte_ctx *c, int ndir, const double *phi, const double *t
     if (!J) return fail(c, FTTE_ERR_ARG, "ftte_diffuse_sweep: J is NULL");
     FTTE_HIP(c, hipSetDevice(c->device));
     const size_t elems = (size_t)c->nnu * c->ncell;
-    FTTE_HIP(c, c->host_J_dev.reserve(elems)); // kept from call to call
-    if ((rc = ftte_diffuse_sweep_device(c, ndir, phi, theta, w, uvb, c->host_J_dev, nullptr))) return rc;
-    if ((rc = download(c, J, c->host_J_dev, sizeof(double) * elems))) return rc;
+    FTTE_HIP(c, c->host.J_dev.reserve(elems)); // kept from call to call
+    if ((rc = ftte_diffuse_sweep_device(c, ndir, phi, theta, w, uvb, c->host.J_dev, nullptr))) return rc;
+    if ((rc = download(c, J, c->host.J_dev, sizeof(double) * elems))) return rc;
     return wait_sweep(c); // the sweep has drained: report a dataflow sweep that gave up now rather than at the next call
 }
 
@@ -381,9 +380,9 @@ int ftte_diffuse_iteration(ftte_ctx *c, int nnu, const double *kappa, int ndir, 
     c->nnu = nnu;
     c->kappa.invalidate(); // the lanes bring it: set() when the last one has been issued (brick_sweep)
     const size_t elems = (size_t)nnu * c->ncell;
-    FTTE_HIP(c, c->host_J_dev.reserve(elems));
+    FTTE_HIP(c, c->host.J_dev.reserve(elems));
     const HostPipe pipe{kappa, J};
-    if ((rc = brick_sweep(c, ndir, phi, theta, w, uvb, c->host_J_dev, c->stream, &pipe))) {
+    if ((rc = brick_sweep(c, ndir, phi, theta, w, uvb, c->host.J_dev, c->stream, &pipe))) {
         c->kappa.invalidate();
         return rc;
     }
@@ -397,10 +396,8 @@ int ftte_host_register(ftte_ctx *c, void *ptr, size_t bytes)
     if (!c) return FTTE_ERR_ARG;
     if (!ptr || !bytes) return fail(c, FTTE_ERR_ARG, "ftte_host_register: bad argument");
     if (c->multi) return multi_host_register(c, ptr, bytes, true);
-    if (is_registered(c, ptr, bytes)) return FTTE_OK;
     FTTE_HIP(c, hipSetDevice(c->device));
-    FTTE_HIP(c, hipHostRegister(ptr, bytes, hipHostRegisterPortable)); // (portable: pinned for every device of the process)
-    c->registered.push_back({(const char *)ptr, bytes});
+    FTTE_HIP(c, c->host.pin(ptr, bytes));
     return FTTE_OK;
 }
 
@@ -408,15 +405,11 @@ int ftte_host_unregister(ftte_ctx *c, void *ptr)
 {
     if (!c) return FTTE_ERR_ARG;
     if (c->multi) return multi_host_register(c, ptr, 0, false);
-    for (size_t q = 0; q < c->registered.size(); ++q)
-        if (c->registered[q].base == (const char *)ptr) {
-            FTTE_HIP(c, hipSetDevice(c->device));
-            FTTE_HIP(c, hipStreamSynchronize(c->stream));
-            FTTE_HIP(c, hipHostUnregister(ptr));
-            c->registered.erase(c->registered.begin() + (long)q);
-            return FTTE_OK;
-        }
-    return fail(c, FTTE_ERR_ARG, "ftte_host_unregister: not a registered array");
+    if (!c->host.pinned(ptr)) return fail(c, FTTE_ERR_ARG, "ftte_host_unregister: not a registered array");
+    FTTE_HIP(c, hipSetDevice(c->device));
+    FTTE_HIP(c, hipStreamSynchronize(c->stream));
+    FTTE_HIP(c, c->host.unpin(ptr));
+    return FTTE_OK;
 }
 
 long long ftte_counter(const ftte_ctx *c, const char *name)

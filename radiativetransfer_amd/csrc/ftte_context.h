@@ -9,7 +9,7 @@
 // holds has an owner as well: the medium's fields (ftte_medium.h), the gas (ftte_gas.h), for the brick sweeps the tables of a
 // plan, the buffers that remember what they were sent and the state of the one-launch forms (ftte_bricks.h), and for the sweeps of
 // a refined cell array the forests, their scratch and their cache (ftte_forests.h) and the hybrid sweep's options, plan and device
-// state (ftte_hybrid.h).
+// state (ftte_hybrid.h), and for host arrays the staging blocks and the registered ranges (ftte_host.h).
 //
 // There is no CPU fallback behind any of this: every entry point that computes on the grid needs a HIP device and fails with
 // FTTE_ERR_NO_DEVICE otherwise.
@@ -25,13 +25,12 @@
 #include <string>
 #include <vector>
 
-#include <thread>
-
 #include "../../include/ftte.h"
 #include "ftte_amr.h"
 #include "ftte_bricks.h"
 #include "ftte_gas.h"
 #include "ftte_geometry.h"
+#include "ftte_host.h"
 #include "ftte_hybrid.h"
 #include "ftte_kernels.h"
 #include "ftte_lambda.h"
@@ -113,7 +112,6 @@ struct ftte_ctx {
     int engine = 0, chunk = 0, group = 0, brick_waves = 4, pair_waves = 4, last_brick_form = -1, last_brick_dataflow = -1, last_brick_whole = 0, share = 2, team = -1, lanes = 2; // chunk, group: 0 = by the parallelism (build_brick_plan)
     std::vector<Stream> lane_stream;        // extra streams of the brick sweep (frequency groups are independent)
     std::vector<Event> pipe_up;             // ftte_diffuse_iteration: lane k's opacities have arrived
-    bool stage_used[2] = {false, false};    // the pinned staging block has a transfer recorded on stage_ev
     std::vector<Event> lane_done;
     Event ev_fork;
     // option: 0 = a launch per stage; 1, 2 = the bricks of a sweep in ONE launch where the grid allows it, a workgroup per brick,
@@ -171,15 +169,7 @@ struct ftte_ctx {
     GasState gas;
     PointState point; // point sources: tree, rate tables, rates, tracer scratch
 
-    // host-array boundary (ftte_set_opacity / ftte_diffuse_sweep): J lives in a device buffer the context keeps, and
-    // pageable host arrays cross PCIe through two pinned staging blocks filled by a few host threads while the other
-    // block is in flight; arrays the caller has registered (ftte_host_register) are copied by the DMA engine directly
-    DeviceBuffer<double> host_J_dev;
-    PinnedBuffer<char> stage[2];
-    Event stage_ev[2];
-    struct HostRange { const char *base; size_t bytes; };
-    std::vector<HostRange> registered;
-    std::vector<HostRange> registered_elsewhere; // pinned by another context of the same process (the devices of one multi-device context)
+    HostBoundary host; // host arrays (ftte_set_opacity / ftte_diffuse_sweep): staging blocks, registered arrays, J on the device (ftte_host.h)
 
     // instrumentation (ftte_counter): how often the expensive host-side builds ran
     long long n_grid_builds = 0, n_plan_builds = 0, n_forest_builds = 0;

@@ -393,11 +393,9 @@ int multi_host_register(ftte_ctx *c, void *ptr, size_t bytes, bool on)
     Multi &M = *c->multi;
     const int rc = on ? ftte_host_register(M.sub[0], ptr, bytes) : ftte_host_unregister(M.sub[0], ptr);
     if (rc) return adopt(c, M.sub[0], rc);
-    for (size_t k = 1; k < M.sub.size(); ++k) {
-        auto &R = M.sub[k]->registered_elsewhere;
-        if (on) R.push_back({(const char *)ptr, bytes});
-        else R.erase(std::remove_if(R.begin(), R.end(), [&](const ftte_ctx::HostRange &r) { return r.base == (const char *)ptr; }), R.end());
-    }
+    for (size_t k = 1; k < M.sub.size(); ++k)
+        if (on) M.sub[k]->host.learn(ptr, bytes);
+        else M.sub[k]->host.forget(ptr);
     return FTTE_OK;
 }
 

@@ -86,11 +86,15 @@ def test_registered_and_pageable_host_arrays_give_the_same_bits():
                                rtol=64 * np.finfo(float).eps, atol=0)
 
 
-@pytest.mark.parametrize("n,nnu", [(70, 3), (64, 8), (33, 2)])
+@pytest.mark.parametrize("n,nnu", [(70, 3), (64, 8), (33, 2), (130, 8)])
 def test_iteration_in_one_call_equals_the_two_calls(n, nnu):
     """ftte_diffuse_iteration = ftte_set_opacity + ftte_diffuse_sweep with the frequency groups crossing PCIe and being swept in
     overlapping lanes: the same bits, with pageable arrays (through the staging blocks) and with registered ones (DMA in place),
-    and a later device-side sweep finds the opacities the call left behind."""
+    and a later device-side sweep finds the opacities the call left behind.  At (130, 8) a lane of the default two is 4 groups x
+    130^3 x 8 B = 70.3 MB, just over one 64 MiB staging block: a lane's opacities and its pageable J each hand over from one block
+    to the next.  With one of the two arrays registered the blocks are used one way only -- pageable opacities and a registered J
+    leave the lanes' staged uploads recorded and no staged download behind them -- and what follows goes through the same blocks:
+    ftte_set_opacity of a pageable array (staged from 1 MiB on) and a sweep."""
     kappa, uvb, box = synthetic.uniform_workload(n, nnu, seed=n, tau_median=0.3)
     phi, theta, w = O.healpix_directions(2)
     with rt.DiffuseTransfer() as e:
@@ -108,6 +112,15 @@ def test_iteration_in_one_call_equals_the_two_calls(n, nnu):
         e.set_opacity(k2)
         assert np.array_equal(J_reg, e.transport(phi, theta, w, uvb))
         e.host_unregister(k2); e.host_unregister(J_reg)
+        for registered in ("J", "kappa"):
+            k1, J_mixed = kappa.copy(), np.full_like(J_two, np.nan)
+            pinned = J_mixed if registered == "J" else k1
+            e.host_register(pinned)
+            e.iterate_into(k1, phi, theta, w, uvb, J_mixed)
+            assert np.array_equal(J_mixed, J_two)
+            e.set_opacity(k2)
+            assert np.array_equal(e.transport(phi, theta, w, uvb), J_reg)
+            e.host_unregister(pinned)
         e.set_option("lanes", 1)                        # no lanes: the two calls internally
         J_seq = np.empty_like(J_two)
         e.iterate_into(kappa, phi, theta, w, uvb, J_seq)
