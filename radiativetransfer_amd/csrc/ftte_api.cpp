@@ -246,10 +246,10 @@ int ftte_set_option(ftte_ctx *c, const char *key, int value)
         c->engine = value;
     } else if (!std::strcmp(key, "chunk")) {
         if (value < 0 || value > 4096) return fail(c, FTTE_ERR_ARG, "chunk (layers per brick) must be 1..4096, or 0 for the default");
-        c->chunk = value;
+        c->bopt.chunk = value;
     } else if (!std::strcmp(key, "group")) {
         if (value < 0 || value > kBrickMaxDirs) return fail(c, FTTE_ERR_ARG, "group (directions sharing a brick pass) must be 1..8, or 0 for the default");
-        c->group = value;
+        c->bopt.group = value;
     } else if (!std::strcmp(key, "hybrid")) {
         if (value != 0 && value != 1) return fail(c, FTTE_ERR_ARG, "hybrid must be 0 (a refined cell array goes through the forest path as a whole) or 1 (bricks outside a box around the refined cells)");
         c->hopt.hybrid = value;
@@ -285,19 +285,19 @@ int ftte_set_option(ftte_ctx *c, const char *key, int value)
         c->forest_fuse = value;
     } else if (!std::strcmp(key, "queue_mix")) {
         if (value < 0 || value > 2) return fail(c, FTTE_ERR_ARG, "queue_mix must be 0, 1 or 2");
-        c->queue_mix = value;
+        c->bopt.queue_mix = value;
     } else if (!std::strcmp(key, "dataflow")) {
         if (value < 0 || value > 3) return fail(c, FTTE_ERR_ARG, "dataflow must be 0 (a launch per stage), 1 (one launch, bricks wait for each other), 2 (the same with write-through stores) or 3 (persistent workgroups, a task queue per XCD)");
-        c->dataflow = value;
+        c->bopt.dataflow = value;
     } else if (!std::strcmp(key, "merge_overlap")) {
         if (value != 0 && value != 1) return fail(c, FTTE_ERR_ARG, "merge_overlap must be 0 (the brick sweep merges J after its last stage) or 1 (block by block as the stages finish them)");
         c->merge_overlap = value;
     } else if (!std::strcmp(key, "lanes")) {
         if (value < 1 || value > 16) return fail(c, FTTE_ERR_ARG, "lanes (streams the brick sweep spreads its frequency groups over) must be 1..16");
-        c->lanes = value;
+        c->bopt.lanes = value;
     } else if (!std::strcmp(key, "team")) {
         if (value < -1 || value > 2 || value == 1) return fail(c, FTTE_ERR_ARG, "team must be -1 (by the number of frequency groups: 2 up to four, else 0), 0 (one wavefront sweeps a group's directions in turn) or 2 (two wavefronts per brick, four rows each); 1 (a wavefront per direction) lost everywhere and is gone");
-        c->team = value;
+        c->bopt.team = value;
     } else if (!std::strcmp(key, "tiled")) {
         if (value < 0 || value > 2) return fail(c, FTTE_ERR_ARG, "tiled must be 0 (default), 1 (bricks: opacities and accumulators stored brick by brick where the grid is made of whole bricks: a brick's layer in one piece) or 2 (the whole brick in one piece)");
         c->tiled_opt = value;
@@ -306,7 +306,7 @@ int ftte_set_option(ftte_ctx *c, const char *key, int value)
         c->pair_waves = value;
     } else if (!std::strcmp(key, "share")) {
         if (value < 0 || value > 2) return fail(c, FTTE_ERR_ARG, "share (groups sharing a J accumulator) must be 0 (none), 1 (passes of one izone) or 2 (and izone pairs)");
-        c->share = value;
+        c->bopt.share = value;
     } else if (!std::strcmp(key, "brick_waves")) {
         if (value < 2 || value > 4) return fail(c, FTTE_ERR_ARG, "brick_waves must be 2..4");
         c->brick_waves = value;
@@ -367,8 +367,8 @@ int ftte_diffuse_iteration(ftte_ctx *c, int nnu, const double *kappa, int ndir, 
     if (rc) return rc;
     if (nnu < 1 || !kappa || !J || ndir < 0 || (ndir > 0 && (!phi || !theta || !w)) || !uvb)
         return fail(c, FTTE_ERR_ARG, "ftte_diffuse_iteration: bad argument");
-    const bool lanes_apply = !c->use_forest && c->engine != 1 && !c->emit_mode && brick_form(c, nnu) != 1 && !c->dataflow && ndir > 0 && c->lanes >= 2 &&
-                             nnu >= c->lanes;
+    const bool lanes_apply = !c->use_forest && c->engine != 1 && !c->emit_mode && c->bopt.brick_form(nnu, c->emit_mode) != 1 && !c->bopt.dataflow && ndir > 0 &&
+                             c->bopt.lanes >= 2 && nnu >= c->bopt.lanes;
     if (!lanes_apply) {
         if ((rc = ftte_set_opacity(c, nnu, kappa))) return rc;
         return ftte_diffuse_sweep(c, ndir, phi, theta, w, uvb, J);
@@ -430,7 +430,7 @@ long long ftte_counter(const ftte_ctx *c, const char *name)
     if (!std::strcmp(name, "brick_dataflow")) return c->last_brick_dataflow;
     if (!std::strcmp(name, "brick_whole")) return c->last_brick_whole; // 1: the last sweep's stage launches took the whole-brick form
     if (!std::strcmp(name, "brick_chunk")) return c->bplan.valid ? c->bplan.chunk : 0;
-    if (!std::strcmp(name, "brick_queue_mix")) return (c->bplan.valid && c->bplan.persistent) ? c->bplan.qmix : -1;
+    if (!std::strcmp(name, "brick_queue_mix")) return (c->bplan.valid && c->bplan.persistent) ? c->bplan.key.queue_mix : -1;
     if (!std::strcmp(name, "brick_groups")) return c->bplan.valid ? (long long)c->bplan.groups.size() : 0;
     if (!std::strcmp(name, "brick_accumulators")) return c->bplan.valid ? c->bplan.nacc[0] + c->bplan.nacc[1] + c->bplan.nacc[2] : 0;
     if (!std::strcmp(name, "brick_accumulators_0")) return c->bplan.valid ? c->bplan.nacc[0] : 0;

@@ -1,10 +1,12 @@
-// ftte_bricks.h -- the host side of a brick sweep (ftte_brick.hip): the plan, the device tables that hold a plan (BrickTables), a
-// buffer that knows the bytes it was sent (Sent<T>), the launch record filled from plan and tables (brick_launch), the accumulator
-// list of a merge (acc_list), a lane's frequency slice (lane_slice), the lanes' streams and events, what the one-launch forms
-// keep between a sweep and the wait for it (BrickDataflow), and the entry points of the context-free planners (ftte_planner.cpp).
+// ftte_bricks.h -- the host side of a brick sweep (ftte_brick.hip): the options a brick plan depends on and what they resolve to
+// (BrickOptions, BrickKey), the plan, the device tables that hold a plan (BrickTables), a buffer that knows the bytes it was sent
+// (Sent<T>), the launch record filled from plan and tables (brick_launch), the accumulator list of a merge (acc_list), a lane's
+// frequency slice (lane_slice), the lanes' streams and events, what the one-launch forms keep between a sweep and the wait for it
+// (BrickDataflow), and the entry points of the context-free planners (ftte_planner.cpp).
 // Host only; launches nothing.
 #pragma once
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -30,15 +32,86 @@ struct DirPlan {
     int slot = 0;
 };
 
+// What a brick plan of the uniform grid depends on beside its directions: the grid, and what the options resolve to for it
+// (BrickOptions::resolve).  Two sweeps with equal keys and direction lists share a plan.
+struct BrickKey {
+    int n = 0;
+    double box = 0;
+    int chunk = 0, gmax = 0, share = 0;        // layers per brick, most directions per group, who shares an accumulator
+    int want_dataflow = 0, want_glanes = 0;    // 0 a launch per stage, 1 one launch, 3 persistent workgroups; streams the groups are dealt to
+    int nnu = 0, xcc_count = 0, queue_mix = 0; // what the persistent form's queues are cut for (want_dataflow == 3), else 0
+    bool operator==(const BrickKey &o) const
+    {
+        return n == o.n && box == o.box && chunk == o.chunk && gmax == o.gmax && share == o.share && want_dataflow == o.want_dataflow &&
+               want_glanes == o.want_glanes && nnu == o.nnu && xcc_count == o.xcc_count && queue_mix == o.queue_mix;
+    }
+};
+
+// The options a brick plan depends on (ftte_set_option; 0 or -1: by the parallelism there is), and the rules that turn them into
+// a plan's parameters.  The launch-time options (brick_waves, pair_waves, atomic_acc, ablate, merge_overlap) are the context's.
+struct BrickOptions {
+    int chunk = 0, group = 0; // layers per brick, most directions per group
+    int share = 2, team = -1, lanes = 2;
+    // 0 = a launch per stage; 1, 2 = the bricks of a sweep in ONE launch where the grid allows it, a workgroup per brick, waiting
+    // for each other through flags (cross-XCD hand-overs: L2 write-back per brick, or write-through stores); 3 = one launch of
+    // persistent workgroups that draw bricks from a queue per XCD (hand-overs stay behind one L2: plain stores)
+    int dataflow = 0;
+    int queue_mix = 0;        // persistent form: 0 = a frequency group per queue where they divide, else by load; 1 = by load; 2 = (group + accumulator) mod queues
+
+    // Which form of the brick kernel sweeps: 0 one wavefront per brick, 2 a pair of wavefronts per brick.
+    // Option "team" = -1 (the default) leaves it to the parallelism: with four frequency groups or fewer on this GPU (a rank of a
+    // frequency-sharded run) the stages are narrow, and the pair form's twice as many wavefronts fill them better (5 / 7 / 9 %
+    // at 4 / 2 / 1 groups); at eight the single wavefront is 1.5 % ahead.  The dataflow launch is built for form 0 only.
+    // (With the reference's emissivity term -- its log-mean needs a division and two polynomials per piece -- the pair form is ahead
+    // at eight groups as well: 103 instead of 162 VGPRs; a source function costs three instructions per piece and goes as no emission.)
+    int brick_form(int nnu, int emit_mode) const { return team >= 0 ? team : (((nnu <= 4 || emit_mode) && !dataflow) ? 2 : 0); }
+
+    // The uniform grid's plan.  Unset options follow the parallelism there is: a stage offers (bricks of a plane) x groups x
+    // frequency groups tasks, and with few frequency groups on this GPU shorter bricks and smaller groups keep the stages wide
+    // enough; the groups are then dealt to the streams instead of the frequency groups.  One launch (want_dataflow 1) needs whole
+    // bricks, form 0 and no emission; whether it becomes the persistent form is settled by persistent() once the XCDs are counted.
+    // (key.box is the caller's.)
+    BrickKey resolve(int n, int nnu, int emit_mode) const
+    {
+        BrickKey k;
+        const int form = brick_form(nnu, emit_mode);
+        k.n = n;
+        k.chunk = std::min(chunk > 0 ? chunk : (nnu >= 4 ? 16 : nnu >= 2 ? 8 : 4), n);
+        k.gmax = group > 0 ? group : (nnu >= 2 || form == 2 ? 3 : 2);
+        k.share = share;
+        k.want_dataflow = (dataflow && n % 64 == 0 && n % kBrickRows == 0 && n % k.chunk == 0 && form == 0 && !emit_mode) ? 1 : 0;
+        k.want_glanes = k.want_dataflow ? 1 : (nnu >= lanes ? 1 : lanes);
+        return k;
+    }
+    // Option "dataflow" = 3 on a grid that allows one launch: persistent workgroups, a queue per XCD, where the device reports
+    // 1 .. kBrickQueues of them; else the one-launch form stays
+    void persistent(BrickKey &k, int nnu, int xcc_count) const
+    {
+        if (!k.want_dataflow || dataflow != 3 || xcc_count < 1 || xcc_count > kBrickQueues) return;
+        k.want_dataflow = 3; k.nnu = nnu; k.xcc_count = xcc_count; k.queue_mix = queue_mix;
+    }
+    // The hybrid sweep's base plan: short bricks (the box is widened by one brick on every side, and what lies inside it costs
+    // several times a brick's bytes), the group size by the frequency groups alone (the pair form does not sweep it), a launch
+    // per stage: its chunk, gmax and share enter HybridOptions::plan_key
+    BrickKey resolve_hybrid(int n, int nnu) const
+    {
+        BrickKey k;
+        k.n = n;
+        k.chunk = std::min(chunk > 0 ? chunk : 4, n);
+        k.gmax = group > 0 ? group : (nnu >= 2 ? 3 : 2);
+        k.share = share;
+        return k;
+    }
+};
+
 // The brick organisation of the same sweep (ftte_brick.hip): directions grouped by izone, bricks ordered into stages
 struct BrickPlan {
     bool valid = false;
     long long id = 0;                  // which plan built in this context this is (ftte_ctx::brick_plans): what BrickTables::holds compares
-    // key
-    int n = 0, chunk = 0, gmax = 0, share = 0, want_glanes = 0, want_dataflow = 0;
-    double box = 0;
+    BrickKey key;                      // the uniform grid's plan: what it was built for, with the directions (a hybrid sweep's plans: HybridPlan::key)
     std::vector<double> phi, theta, w;
     // content
+    int n = 0, chunk = 0;              // cells a side, layers per brick
     std::vector<DirPlan> dirs;
     std::vector<LayerRec> layers;
     struct Group { int izone = 0, layout = 0, acc = 0, offset = 0, lane = 0; std::vector<int> dirs; };
@@ -47,8 +120,7 @@ struct BrickPlan {
     bool dataflow = false;             // one launch, bricks wait for each other through flags (needs whole bricks: n % 64 == 0)
     std::vector<int32_t> deps;         // [tasks][kBrickDeps]
     // persistent form (option "dataflow" = 3): one queue of (task, frequency slot) pairs per XCD, whole dependency chains each
-    bool persistent = false;
-    int qnnu = 0, nq = 0, qmix = 0;    // frequency groups and XCDs the queues were cut for, option "queue_mix"
+    bool persistent = false;           // (cut for key.nnu frequency groups, key.xcc_count XCDs and key.queue_mix)
     std::vector<uint32_t> queue;       // work ids task * nnu + slot, queue after queue
     uint32_t qoff[kBrickQueues] = {}, qlen[kBrickQueues] = {};
     int64_t qload[kBrickQueues] = {};  // cell.direction.frequency updates per queue (balance: instrumentation)
@@ -81,9 +153,19 @@ struct SubGridPlan {
 int plan_direction(int n, double box, int d, double phi_d, double theta_d, double w_d, int tile_rows, std::vector<ftte_pattern> &pat,
                    std::vector<int> &du_cum, std::vector<int> &dv_cum, DirPlan &D, LayerRec *layers, size_t layer_off, const SubGridPlan *sub,
                    std::string *err);
+// The uniform grid's brick plan, step by step: groups, lanes of groups, stage lists, what a brick waits for (one-launch forms),
+// merge blocks and merge points, the persistent form's queues.  P.valid with the outcome.
+struct BrickInputs { BrickKey key; int ndir; const double *phi, *theta, *w; };
+int plan_bricks(const BrickInputs &in, BrickPlan &P, std::string *err);
 // (the plan's id stays 0: whoever counts the plans of a context stamps it)
 int plan_brick_groups(BrickPlan &P, int n, double box, int ndir, const double *phi, const double *theta, const double *w, int chunk, int gmax,
                       int share, int want_dataflow, bool whole_faces, const SubGridPlan *sub, std::string *err);
+
+// whether a plan's copy of a direction array is the caller's list
+inline bool same_list(const std::vector<double> &held, const double *now, int ndir)
+{
+    return (int)held.size() == ndir && (ndir == 0 || !std::memcmp(held.data(), now, sizeof(double) * ndir));
+}
 
 inline const ftte_consts kMath = FTTE_CONSTS_INIT; // the constants of ftte_math.h as the launch records carry them
 

@@ -1,13 +1,14 @@
-// ftte_context.h -- what the translation units behind include/ftte.h share: the sweep plans, the context, and the internal
-// entry points of the planners that cache in the context (ftte_plan.cpp; the context-free ones are ftte_planner.cpp), the sweeps
+// ftte_context.h -- what the translation units behind include/ftte.h share: the context, and the internal entry points of the
+// planners' cached callers (ftte_plan.cpp; the planners themselves read no context: ftte_planner.cpp), the sweeps
 // (ftte_sweeps.cpp: segment forests, cell-fixed bricks), the hybrid sweep of refined cell arrays (ftte_hybrid.cpp) and the
 // host-array transfers (ftte_host_arrays.cpp).  ftte_api.cpp is the C ABI itself, ftte_chem.cpp its part that reads or writes the
 // species medium.
 //
 // Every device buffer, pinned buffer, stream, event and graph of the context is a member that owns it (ftte_device.h): a buffer's
 // capacity travels with its pointer, `delete c` releases everything, and a new buffer is added by declaring it.  What a buffer
-// holds has an owner as well: the medium's fields (ftte_medium.h), the gas (ftte_gas.h), for the brick sweeps the tables of a
-// plan, the buffers that remember what they were sent and the state of the one-launch forms (ftte_bricks.h), and for the sweeps of
+// holds has an owner as well: the medium's fields (ftte_medium.h), the gas (ftte_gas.h), for the brick sweeps the options a plan
+// depends on with the rules that resolve them, the plan, its tables, the buffers that remember what they were sent and the state of
+// the one-launch forms (ftte_bricks.h), for the ray-following tiles their plan (ftte_tiles.h), and for the sweeps of
 // a refined cell array the forests, their scratch and their cache (ftte_forests.h) and the hybrid sweep's options, plan and device
 // state (ftte_hybrid.h), and for host arrays the staging blocks and the registered ranges (ftte_host.h).
 //
@@ -36,36 +37,13 @@
 #include "ftte_lambda.h"
 #include "ftte_medium.h"
 #include "ftte_point.h"
+#include "ftte_tiles.h"
 
 
 namespace ftte {
 
 
 extern std::string g_create_error; // what ftte_last_error(NULL) returns
-
-struct LaunchPlan {
-    int layout = 0;
-    bool first = false;
-    std::vector<int> dirs; // indices into Plan::dirs, position = slot
-    int acc_base = 0;      // slot s of this launch accumulates into acc[layout][acc_base + s]
-    size_t item_off = 0;
-    int nitems = 0;
-    int64_t updates = 0;
-};
-
-struct Plan {
-    bool valid = false;
-    // key
-    int n = 0, rows = 0, slots = 0, stack = 0;
-    double box = 0;
-    std::vector<double> phi, theta, w;
-    // content
-    std::vector<DirPlan> dirs;
-    std::vector<LayerRec> layers;
-    std::vector<WorkItem> items;
-    std::vector<LaunchPlan> launches;
-    bool used[3][kMaxSlots] = {};
-};
 
 struct LaunchTiming {
     Event start, stop;
@@ -109,18 +87,14 @@ struct ftte_ctx {
 
     // which organisation sweeps a uniform grid: 0 = the default = 2 = cell-fixed bricks (brick_kernel), 1 = ray-following tiles
     // (sweep_kernel)
-    int engine = 0, chunk = 0, group = 0, brick_waves = 4, pair_waves = 4, last_brick_form = -1, last_brick_dataflow = -1, last_brick_whole = 0, share = 2, team = -1, lanes = 2; // chunk, group: 0 = by the parallelism (build_brick_plan)
+    int engine = 0, brick_waves = 4, pair_waves = 4, last_brick_form = -1, last_brick_dataflow = -1, last_brick_whole = 0;
+    BrickOptions bopt;                      // the options a brick plan depends on: chunk, group, share, team, lanes, dataflow, queue_mix
     std::vector<Stream> lane_stream;        // extra streams of the brick sweep (frequency groups are independent)
     std::vector<Event> pipe_up;             // ftte_diffuse_iteration: lane k's opacities have arrived
     std::vector<Event> lane_done;
     Event ev_fork;
-    // option: 0 = a launch per stage; 1, 2 = the bricks of a sweep in ONE launch where the grid allows it, a workgroup per brick,
-    // waiting for each other through flags (cross-XCD hand-overs: L2 write-back per brick, or write-through stores); 3 = one launch of
-    // persistent workgroups that draw bricks from a queue per XCD (hand-overs stay behind one L2: plain stores)
-    int dataflow = 0;
     int atomic_acc = 0;               // option "atomic_acc": later visitors of an accumulator add with fp64 atomics instead of read-add-store
     int ablate = 0;                   // diagnostic option "ablate": parts of the brick kernel's memory traffic left out (wrong J; timing only)
-    int queue_mix = 0;                // persistent form: 0 = a frequency group per queue where they divide, else by load; 1 = by load; 2 = (group + accumulator) mod queues
     BrickDataflow bflow;              // flags, tickets and error word of the one-launch forms: brick_sweep prepares, wait_sweep checks
     int xcc_count = -1;               // XCC ids this device reports (census, ftte_brick.hip); -1: not taken yet
     int8_t xcc_queue[16] = {};        // XCC id -> 0 .. xcc_count - 1, or -1
@@ -188,18 +162,6 @@ struct ftte_ctx {
     DeviceBuffer<unsigned long long> d_update_stats;
     PinnedBuffer<unsigned long long> h_update_stats;
 };
-
-// Which form of the brick kernel sweeps: 0 one wavefront per brick, 2 a pair of wavefronts per brick.
-// Option "team" = -1 (the default) leaves it to the parallelism: with four frequency groups or fewer on this GPU (a rank of a
-// frequency-sharded run) the stages are narrow, and the pair form's twice as many wavefronts fill them better (5 / 7 / 9 %
-// at 4 / 2 / 1 groups); at eight the single wavefront is 1.5 % ahead.  The dataflow launch is built for form 0 only.
-inline int brick_form(const ftte_ctx *c, int nnu)
-{
-    // (with the reference's emissivity term -- its log-mean needs a division and two polynomials per piece -- the pair form is ahead at
-    // eight groups as well: 103 instead of 162 VGPRs; a source function costs three instructions per piece and goes as no emission)
-    return c->team >= 0 ? c->team : (((nnu <= 4 || c->emit_mode) && !c->dataflow) ? 2 : 0);
-}
-
 
 namespace ftte {
 

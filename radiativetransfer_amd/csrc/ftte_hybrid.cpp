@@ -32,16 +32,14 @@ static int gather_layouts(ftte_ctx *c, const MediumField &f, const int32_t *leaf
 static int build_hybrid_plan(ftte_ctx *c, int ndir, const double *phi, const double *theta, const double *w)
 {
     HybridPlan &H = c->hplan;
-    // short bricks: the box is widened by one brick on every side, and what lies inside it costs several times a brick's bytes
-    const int chunk = std::min(c->chunk > 0 ? c->chunk : 4, c->n);
-    const int gmax = c->group > 0 ? c->group : (c->nnu >= 2 ? 3 : 2);
-    std::vector<double> key = c->hopt.plan_key(c->box, chunk, gmax, c->share, ndir, phi, theta, w);
+    const BrickKey K = c->bopt.resolve_hybrid(c->n, c->nnu);
+    std::vector<double> key = c->hopt.plan_key(c->box, K.chunk, K.gmax, K.share, ndir, phi, theta, w);
     if (H.valid && H.key == key) return FTTE_OK;
     c->hdev.drop_plan();
     H = HybridPlan();
     H.key = std::move(key);
     std::string why;
-    const int rc = plan_hybrid(HybridInputs{c->n, c->box, &c->tree, c->hopt, chunk, gmax, c->share, ndir, phi, theta, w}, H, &why);
+    const int rc = plan_hybrid(HybridInputs{c->n, c->box, &c->tree, c->hopt, K.chunk, K.gmax, K.share, ndir, phi, theta, w}, H, &why);
     c->n_plan_builds += H.brick_plans_made;
     H.bricks.id = ++c->brick_plans; // (new plans: no BrickTables holds them)
     if (H.brick_plans_made > 1) H.fine.plan.id = ++c->brick_plans;

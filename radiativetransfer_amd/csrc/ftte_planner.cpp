@@ -1,14 +1,18 @@
 // ftte_planner.cpp -- the planners that read no context: one direction's layer tables (plan_direction), the groups, accumulators
-// and face blocks of a brick plan (plan_brick_groups), and the hybrid sweep's plan for a refined cell array (plan_hybrid: boxes
-// around the clusters of refined cells, pipelines, the fine block, slots, task lists, the forests restricted to the boxes).  Pure
-// host work against the owners' headers only; failure is a status and a text, as build_forest reports it.
+// and face blocks of a brick plan (plan_brick_groups), the one builder of stage-ordered task lists (build_task_lists: count, offsets,
+// fill, and who stores and who accumulates), the uniform grid's brick plan in steps (plan_bricks: groups, lanes of groups, stage
+// lists, dependencies, merge points, queues) and its tile plan (plan_tiles), and the hybrid sweep's plan for a refined cell array
+// (plan_hybrid: boxes around the clusters of refined cells, pipelines, the fine block, slots, task lists, the forests restricted to
+// the boxes).  Pure host work against the owners' headers only; failure is a status and a text, as build_forest reports it.
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <thread>
 
 #include "ftte_geometry.h"
 #include "ftte_hybrid.h"
+#include "ftte_tiles.h"
 
 namespace ftte {
 
@@ -117,7 +121,7 @@ int plan_brick_groups(BrickPlan &P, int n_grid, double box, int ndir, const doub
 {
     const int n = sub ? sub->n : n_grid;
     P = BrickPlan();
-    P.n = n; P.chunk = chunk; P.gmax = gmax; P.share = share; P.want_dataflow = want_dataflow; P.box = box;
+    P.n = n; P.chunk = chunk;
     P.phi.assign(phi, phi + ndir); P.theta.assign(theta, theta + ndir); P.w.assign(w, w + ndir);
     P.dirs.resize(ndir);
     P.layers.resize((size_t)ndir * n);
@@ -210,6 +214,361 @@ int plan_brick_groups(BrickPlan &P, int n_grid, double box, int ndir, const doub
     for (int layout = 0; layout < 3; ++layout)
         if (P.nacc[layout] > kMaxAcc) return fail(err, FTTE_ERR_UNSUPPORTED, "too many direction groups for one memory layout: raise option \"group\"");
 
+    return FTTE_OK;
+}
+
+// ---- task lists ------------------------------------------------------------------------------------------------------------------
+namespace {
+
+size_t brick_index(const BrickPlan &P, int tu, int tv, int ti) { return ((size_t)ti * P.ntv + tv) * P.ntu + tu; }
+// the physical brick under brick (tu, tv, ti) of group G: counted from the far end along the axes the group's frame mirrors
+size_t brick_index(const BrickPlan &P, const BrickPlan::Group &G, int tu, int tv, int ti)
+{
+    const DirPlan &D0 = P.dirs[G.dirs[0]];
+    return brick_index(P, D0.su < 0 ? P.ntu - 1 - tu : tu, D0.sv < 0 ? P.ntv - 1 - tv : tv, D0.si < 0 ? P.nti - 1 - ti : ti);
+}
+template <typename F> void for_each_brick(const BrickPlan &P, F fn)
+{
+    for (int ti = 0; ti < P.nti; ++ti)
+        for (int tv = 0; tv < P.ntv; ++tv)
+            for (int tu = 0; tu < P.ntu; ++tu) fn(tu, tv, ti);
+}
+std::vector<size_t> groups_in_order(const BrickPlan &P)
+{
+    std::vector<size_t> order(P.groups.size());
+    for (size_t g = 0; g < order.size(); ++g) order[g] = g;
+    return order;
+}
+// within a list the groups with the most directions first: their bricks take longest, the short ones fill the tail
+std::vector<size_t> largest_groups_first(const BrickPlan &P)
+{
+    std::vector<size_t> order = groups_in_order(P);
+    std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return P.groups[x].dirs.size() > P.groups[y].dirs.size(); });
+    return order;
+}
+
+// The one builder of task lists.  visit(g, put) names every task of group g in the order it is to stand in its list:
+// put(list, launch, tu, tv, ti, task) -- `list` of the `nlists` it goes into, `launch` the place of that list in the launch order of
+// its accumulator's stream, `task` as the kernel reads it but for the accumulate bit.  Counts per list, turns the counts into offsets
+// (returned: nlists + 1), fills P.tasks with the groups in `order`, and sets kBrickAccumulate exactly where an earlier launch visits
+// the same physical brick of the same accumulator: whoever comes first stores, whoever comes later reads, adds and stores.
+// (Two pieces of one brick in one launch write different lanes of rows that start from zero: either may come first.)
+template <typename Visit> std::vector<size_t> build_task_lists(BrickPlan &P, const std::vector<size_t> &order, size_t nlists, Visit visit)
+{
+    const size_t nb = (size_t)P.ntu * P.ntv * P.nti;
+    std::vector<std::vector<size_t>> first(3 * (size_t)kMaxAcc); // per accumulator and physical brick: the earliest launch that writes it
+    std::vector<size_t> off(nlists + 1, 0);
+    for (size_t g : order) {
+        const BrickPlan::Group &G = P.groups[g];
+        std::vector<size_t> &F = first[(size_t)G.layout * kMaxAcc + G.acc];
+        if (F.empty()) F.assign(nb, ~(size_t)0);
+        visit(g, [&](size_t list, size_t launch, int tu, int tv, int ti, const BrickTask &) {
+            ++off[list + 1];
+            size_t &f = F[brick_index(P, G, tu, tv, ti)];
+            f = std::min(f, launch);
+        });
+    }
+    for (size_t l = 0; l < nlists; ++l) off[l + 1] += off[l];
+    P.tasks.resize(off[nlists]);
+    std::vector<size_t> fill(off.begin(), off.end() - 1);
+    for (size_t g : order) {
+        const BrickPlan::Group &G = P.groups[g];
+        const std::vector<size_t> &F = first[(size_t)G.layout * kMaxAcc + G.acc];
+        visit(g, [&](size_t list, size_t launch, int tu, int tv, int ti, BrickTask T) {
+            if (launch > F[brick_index(P, G, tu, tv, ti)]) T.ti = (int16_t)(T.ti | kBrickAccumulate);
+            P.tasks[fill[list]++] = T;
+        });
+    }
+    return off;
+}
+
+// ---- the uniform grid's brick plan, step by step ------------------------------------------------------------------------------------
+
+// Streams: the groups of one accumulator stay on one stream (their launches are ordered against each other)
+void deal_group_lanes(BrickPlan &P, int want_glanes)
+{
+    P.glanes = std::max(1, std::min(want_glanes, P.nacc[0] + P.nacc[1] + P.nacc[2]));
+    int next = 0;
+    std::vector<int> lane_of(3 * (size_t)kMaxAcc, -1);
+    for (auto &G : P.groups) {
+        int &l = lane_of[(size_t)G.layout * kMaxAcc + G.acc];
+        if (l < 0) l = next++ % P.glanes;
+        G.lane = l;
+    }
+}
+
+// Stages: brick (tu, tv, ti) of a group runs in stage tu + tv + ti + the group's offset of its lane.  Fills P.tasks, P.nstages,
+// P.stage_off ([glanes][nstages + 1], the lanes one after the other) and P.updates.
+void write_stage_lists(BrickPlan &P, int ndir)
+{
+    int max_offset = 0;
+    for (const auto &G : P.groups) max_offset = std::max(max_offset, G.offset);
+    const size_t nstages = P.groups.empty() ? 0 : (size_t)(P.ntu + P.ntv + P.nti - 2 + max_offset);
+    P.nstages = (int)nstages;
+    const std::vector<size_t> off = build_task_lists(P, largest_groups_first(P), (size_t)P.glanes * nstages, [&](size_t g, auto put) {
+        const BrickPlan::Group &G = P.groups[g];
+        for_each_brick(P, [&](int tu, int tv, int ti) {
+            const size_t st = (size_t)(tu + tv + ti + G.offset);
+            put((size_t)G.lane * nstages + st, st, tu, tv, ti, BrickTask{(int16_t)g, (int16_t)tu, (int16_t)tv, (int16_t)ti});
+        });
+    });
+    P.stage_off.resize((size_t)P.glanes * (nstages + 1));
+    for (size_t l = 0; l < (size_t)P.glanes; ++l)
+        for (size_t st = 0; st <= nstages; ++st) P.stage_off[l * (nstages + 1) + st] = off[l * nstages + st];
+    P.updates = (int64_t)P.n * P.n * P.n * ndir; // (every group's bricks cover the grid)
+}
+
+// One-launch forms: what each brick waits for -- its three upstream neighbours, the readers of the two face slots it rewrites (the
+// rings hold two chunks), and the previous visitor of its J tile.  All of them lie earlier in the (stage-ordered) list.
+int link_dependencies(BrickPlan &P, std::string *err)
+{
+    const size_t nt = P.tasks.size(), nb = (size_t)P.ntu * P.ntv * P.nti;
+    std::vector<int32_t> index(P.groups.size() * nb, -1);
+    auto at = [&](size_t g, int tu, int tv, int ti) -> int32_t & { return index[g * nb + brick_index(P, tu, tv, ti)]; };
+    for (size_t q = 0; q < nt; ++q) at((size_t)P.tasks[q].group, P.tasks[q].tu, P.tasks[q].tv, P.tasks[q].ti & (kBrickAccumulate - 1)) = (int32_t)q;
+    P.deps.assign(nt * kBrickDeps, -1);
+    // the visitors of every J tile, per accumulator, in launch order
+    struct Visit { int launch; int32_t task; };
+    std::vector<std::vector<std::vector<Visit>>> visits(3 * (size_t)kMaxAcc);
+    for (size_t q = 0; q < nt; ++q) {
+        const BrickTask &T = P.tasks[q];
+        const size_t g = (size_t)T.group;
+        const BrickPlan::Group &G = P.groups[g];
+        const int ti = T.ti & (kBrickAccumulate - 1);
+        int32_t *D = &P.deps[q * kBrickDeps];
+        if (T.tu > 0) D[0] = at(g, T.tu - 1, T.tv, ti);
+        if (T.tv > 0) D[1] = at(g, T.tu, T.tv - 1, ti);
+        if (ti > 0) D[2] = at(g, T.tu, T.tv, ti - 1);
+        if (ti >= 2 && T.tu + 1 < P.ntu) D[4] = at(g, T.tu + 1, T.tv, ti - 2); // read the u-face slot this brick rewrites
+        if (ti >= 2 && T.tv + 1 < P.ntv) D[5] = at(g, T.tu, T.tv + 1, ti - 2); // the v-face slot
+        auto &V = visits[(size_t)G.layout * kMaxAcc + G.acc];
+        if (V.empty()) V.resize(nb);
+        V[brick_index(P, G, T.tu, T.tv, ti)].push_back({T.tu + T.tv + ti + G.offset, (int32_t)q});
+    }
+    for (auto &V : visits)
+        for (auto &list : V) {
+            std::sort(list.begin(), list.end(), [](const Visit &x, const Visit &y) { return x.launch < y.launch; });
+            for (size_t k = 1; k < list.size(); ++k) P.deps[(size_t)list[k].task * kBrickDeps + 3] = list[k - 1].task;
+        }
+    for (size_t q = 0; q < nt; ++q)
+        for (int k = 0; k < kBrickDeps; ++k)
+            if (P.deps[q * kBrickDeps + k] >= (int32_t)q) return fail(err, FTTE_ERR_STATE, "brick plan: a dependency does not precede its brick");
+    return FTTE_OK;
+}
+
+// Merge blocks: the stage of the last task that writes into each kMergeBlock^3 block of cells, in any accumulator.  A brick holds,
+// along the storage axes (ic, jc, kc) of its layout, the layers chunk * ti + 1 .. of the march axis, the rows kBrickRows * tv + 1 ..
+// of the middle one and the columns 64 tu + 1 .. of the contiguous one, each counted from the far end where the frame mirrors it.
+// The blocks are then cut into merge points: after the stages by which half, three quarters, ... of them are final, and after the
+// last stage.  (Points from an eighth of the blocks on: 0.3 ms per 256^3 x 8 x 96 step slower -- the early merges only take
+// bandwidth from wide stages -- and three points: 0.1 ms slower; profiles/README.md.)
+void cut_merge_points(BrickPlan &P)
+{
+    const int n = P.n, nstages = P.nstages, nmb = (n + kMergeBlock - 1) / kMergeBlock;
+    const size_t nblk = (size_t)nmb * nmb * nmb;
+    P.nmb = nmb;
+    std::vector<int> last(nblk, nstages - 1); // (every block is written; the default only keeps a gap safe)
+    std::vector<char> seen(nblk, 0);
+    for (int st = 0; st < nstages; ++st)
+        for (size_t q = P.stage_off[(size_t)st]; q < P.stage_off[(size_t)st + 1]; ++q) {
+            const BrickTask &T = P.tasks[q];
+            const BrickPlan::Group &G = P.groups[(size_t)T.group];
+            const DirPlan &D0 = P.dirs[G.dirs[0]];
+            const int march_c = G.layout, fast_c = march_c == 2 ? 1 : 2, mid_c = march_c == 0 ? 1 : 0;
+            int lo[3], hi[3];
+            auto span = [&](int axis, int first, int len, bool mirror) { // cells first .. first + len - 1 (0-based) of the frame axis
+                const int a = first, b = std::min(first + len, n) - 1;
+                lo[axis] = (mirror ? n - 1 - b : a) / kMergeBlock;
+                hi[axis] = (mirror ? n - 1 - a : b) / kMergeBlock;
+            };
+            span(march_c, P.chunk * (T.ti & (kBrickAccumulate - 1)), P.chunk, D0.si < 0);
+            span(mid_c, kBrickRows * T.tv, kBrickRows, D0.sv < 0);
+            span(fast_c, 64 * T.tu, 64, D0.su < 0);
+            for (int bi = lo[0]; bi <= hi[0]; ++bi)
+                for (int bj = lo[1]; bj <= hi[1]; ++bj)
+                    for (int bk = lo[2]; bk <= hi[2]; ++bk) {
+                        const size_t b = ((size_t)bi * nmb + bj) * nmb + bk;
+                        last[b] = seen[b] ? std::max(last[b], st) : st;
+                        seen[b] = 1;
+                    }
+        }
+    std::vector<int32_t> order(nblk);
+    for (size_t b = 0; b < nblk; ++b) order[b] = (int32_t)b;
+    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return last[(size_t)x] < last[(size_t)y]; });
+    static const double kFrac[] = {4. / 8, 6. / 8, 7. / 8, 15. / 16, 31. / 32, 1.};
+    P.merge_off.push_back(0);
+    for (double f : kFrac) {
+        const size_t want = std::min(nblk, std::max<size_t>(1, (size_t)std::ceil(f * (double)nblk)));
+        const int st = f >= 1. ? nstages - 1 : last[(size_t)order[want - 1]];
+        if (!P.merge_stage.empty() && st <= P.merge_stage.back()) continue;
+        size_t end = P.merge_off.back();
+        while (end < nblk && last[(size_t)order[end]] <= st) ++end;
+        if (end == P.merge_off.back() && st != nstages - 1) continue;
+        P.merge_stage.push_back(st);
+        P.merge_off.push_back(end);
+    }
+    P.merge_blocks = std::move(order);
+}
+
+// Queues of the persistent form.  What a brick waits for belongs to its own frequency group and to the groups of directions that share
+// its accumulator, so (frequency group, accumulator) pairs are the units that can be dealt out.  With a multiple of the queue count
+// in frequency groups, queue = group mod queues (all direction groups of a frequency group read the same opacities: one L2 for them);
+// else the units go, largest first, to the queue with the least work so far.
+void deal_queues(BrickPlan &P, int nnu, int nq, int queue_mix)
+{
+    const int64_t n = P.n;
+    P.persistent = true;
+    std::vector<int64_t> acc_dirs(3 * (size_t)kMaxAcc, 0);
+    for (const auto &G : P.groups) acc_dirs[(size_t)G.layout * kMaxAcc + G.acc] += (int64_t)G.dirs.size();
+    std::vector<int> queue_of((size_t)nnu * 3 * kMaxAcc, -1);
+    int64_t load[kBrickQueues] = {};
+    if (nnu % nq == 0 && queue_mix == 0) {
+        for (int nu = 0; nu < nnu; ++nu)
+            for (size_t a = 0; a < acc_dirs.size(); ++a)
+                if (acc_dirs[a]) { queue_of[(size_t)nu * acc_dirs.size() + a] = nu % nq; load[nu % nq] += acc_dirs[a]; }
+    } else if (queue_mix == 2) { // every queue a share of every frequency group: accumulator a of group nu to queue (nu + a) mod queues
+        for (int nu = 0; nu < nnu; ++nu) {
+            int k = 0;
+            for (size_t a = 0; a < acc_dirs.size(); ++a)
+                if (acc_dirs[a]) { const int q = (nu + k++) % nq; queue_of[(size_t)nu * acc_dirs.size() + a] = q; load[q] += acc_dirs[a]; }
+        }
+    } else {
+        std::vector<std::pair<int64_t, size_t>> units;
+        for (int nu = 0; nu < nnu; ++nu)
+            for (size_t a = 0; a < acc_dirs.size(); ++a)
+                if (acc_dirs[a]) units.push_back({acc_dirs[a], (size_t)nu * acc_dirs.size() + a});
+        std::stable_sort(units.begin(), units.end(), [](const auto &x, const auto &y) { return x.first > y.first; });
+        for (const auto &u : units) {
+            int q = 0;
+            for (int k = 1; k < nq; ++k) if (load[k] < load[q]) q = k;
+            queue_of[u.second] = q;
+            load[q] += u.first;
+        }
+    }
+    std::vector<std::vector<uint32_t>> lists((size_t)nq);
+    for (size_t t = 0; t < P.tasks.size(); ++t) {
+        const BrickPlan::Group &G = P.groups[(size_t)P.tasks[t].group];
+        const size_t a = (size_t)G.layout * kMaxAcc + G.acc;
+        for (int nu = 0; nu < nnu; ++nu)
+            lists[(size_t)queue_of[(size_t)nu * acc_dirs.size() + a]].push_back((uint32_t)(t * (size_t)nnu + (size_t)nu));
+    }
+    for (int q = 0; q < kBrickQueues; ++q) {
+        P.qoff[q] = (uint32_t)P.queue.size();
+        P.qlen[q] = q < nq ? (uint32_t)lists[(size_t)q].size() : 0;
+        P.qload[q] = q < nq ? load[q] * n * n * n : 0;
+        if (q < nq) P.queue.insert(P.queue.end(), lists[(size_t)q].begin(), lists[(size_t)q].end());
+    }
+}
+
+} // namespace
+
+// Bricks: group the directions by izone (input order within an izone, at most gmax per group), cut the grid into bricks of
+// 64 x kBrickRows x chunk cells, and order the bricks of every group into stages tu + tv + ti: a brick's three upstream neighbours
+// lie one stage earlier, its consumers exactly one stage later (which is what lets the face buffers be rings over two chunks).
+int plan_bricks(const BrickInputs &in, BrickPlan &P, std::string *err)
+{
+    const BrickKey &K = in.key;
+    int rc;
+    if ((rc = plan_brick_groups(P, K.n, K.box, in.ndir, in.phi, in.theta, in.w, K.chunk, K.gmax, K.share, K.want_dataflow, false, nullptr, err))) return rc;
+    P.key = K;
+    deal_group_lanes(P, K.want_glanes);
+    write_stage_lists(P, in.ndir);
+    if (P.dataflow && !P.tasks.empty() && (rc = link_dependencies(P, err))) return rc;
+    if (!P.dataflow && P.glanes == 1 && !P.tasks.empty()) cut_merge_points(P); // (merge points: stages on one lane of groups)
+    if (P.dataflow && K.want_dataflow == 3 && !P.tasks.empty()) deal_queues(P, K.nnu, K.xcc_count, K.queue_mix);
+    P.valid = true;
+    return FTTE_OK;
+}
+
+// Ray-following tiles: turns the direction list into what the tile kernel consumes.  O(ndir * (n + tiles)) host work.
+int plan_tiles(const TileInputs &in, Plan &P, std::string *err)
+{
+    const int n = in.n, slots = in.slots, ndir = in.ndir;
+    const int tile_rows = in.stack * in.rows - 1; // owned rows of one work item
+    P = Plan();
+    P.n = n; P.rows = in.rows; P.slots = slots; P.stack = in.stack; P.box = in.box;
+    P.phi.assign(in.phi, in.phi + ndir); P.theta.assign(in.theta, in.theta + ndir); P.w.assign(in.w, in.w + ndir);
+    P.dirs.resize(ndir);
+    P.layers.resize((size_t)ndir * n);
+
+    std::vector<ftte_pattern> pat(n);
+    std::vector<int> du_cum(n + 1), dv_cum(n + 1);
+    int in_layout[3] = {0, 0, 0};
+
+    for (int d = 0; d < ndir; ++d) {
+        DirPlan &D = P.dirs[d];
+        const int rc = plan_direction(n, in.box, d, in.phi[d], in.theta[d], in.w[d], tile_rows, pat, du_cum, dv_cum, D, &P.layers[(size_t)d * n], (size_t)d * n, nullptr, err);
+        if (rc) return rc;
+        D.slot = in_layout[D.layout]++ % slots;
+    }
+
+    // launches: per layout, batches of `slots` directions in input order
+    for (int layout = 0; layout < 3; ++layout) {
+        std::vector<int> members;
+        for (int d = 0; d < ndir; ++d) if (P.dirs[d].layout == layout) members.push_back(d);
+        for (size_t b = 0; b < members.size(); b += slots) {
+            LaunchPlan LP;
+            LP.layout = layout;
+            LP.first = (b == 0);
+            // a short last batch takes the highest accumulators: the lower ones are final one launch earlier and can be
+            // merged while it runs, without changing the order in which the accumulators are added up
+            const int in_batch = (int)(std::min(members.size(), b + (size_t)slots) - b);
+            LP.acc_base = (b > 0 && in_batch < slots) ? slots - in_batch : 0;
+            LP.item_off = P.items.size();
+            std::vector<uint32_t> where; // per item of this launch: the tile's place in the plane halfway through the march
+            for (size_t s = b; s < std::min(members.size(), b + (size_t)slots); ++s) {
+                const int d = members[s];
+                const DirPlan &D = P.dirs[d];
+                const int slot = (int)(s - b);
+                LP.dirs.push_back(d);
+                P.used[layout][LP.acc_base + slot] = true;
+                const LayerRec *Ls = &P.layers[D.layer_off];
+                for (int tv = 0; tv < D.ntv; ++tv) {
+                    for (int tu = 0; tu < D.ntu; ++tu) {
+                        // owned labels of this tile; a layer is active when any owned ray, or the cell one
+                        // step beyond it, is inside the domain
+                        const int ul_min = D.u_lo + 63 * tu, ul_max = ul_min + 62;
+                        const int vl_min = D.v_lo + tile_rows * tv, vl_max = vl_min + tile_rows - 1;
+                        int i_first = 0, i_last = -1;
+                        for (int i = 1; i <= n; ++i) {
+                            const int cu_d = (int)(short)(Ls[i - 1].drift & 0xffff), cv_d = Ls[i - 1].drift >> 16;
+                            const bool act = ul_min + cu_d <= n && ul_max + cu_d + 1 >= 1 && vl_min + cv_d <= n &&
+                                             vl_max + cv_d + 1 >= 1;
+                            if (act) { if (!i_first) i_first = i; i_last = i; }
+                        }
+                        if (!i_first) continue;
+                        WorkItem it;
+                        it.slot = (int16_t)slot; it.tu = (int16_t)tu; it.tv = (int16_t)tv;
+                        it.i_first = (int16_t)i_first; it.i_last = (int16_t)i_last; it.pad = 0;
+                        P.items.push_back(it);
+                        const int pu = std::max(0, ul_min + D.du_mid + 64) / 64, pv = std::max(0, vl_min + D.dv_mid + 64) / std::max(tile_rows, 1);
+                        where.push_back(((uint32_t)pv << 16) | (uint32_t)(pu & 0xffff));
+                    }
+                }
+                LP.updates += (int64_t)n * n * n;
+            }
+            LP.nitems = (int)(P.items.size() - LP.item_off);
+            // longest marches first, so that the short corner tiles fill the tail of the launch; among equally long ones, tiles
+            // of the directions in flight that cross the same part of the grid side by side, so that they read the same part of
+            // a kappa plane at about the same time (+2 %; the place is taken halfway through the march).  (Grouping the tiles of
+            // one direction together instead -- hoping for L2 hits on shared halo rows -- was measured: no drop in FETCH_SIZE,
+            // 6 % slower through worse load balance.)
+            std::vector<uint32_t> idx(where.size());
+            for (size_t q = 0; q < idx.size(); ++q) idx[q] = (uint32_t)q;
+            const WorkItem *base = P.items.data() + LP.item_off;
+            std::stable_sort(idx.begin(), idx.end(), [&](uint32_t x, uint32_t y) {
+                const int lx = base[x].i_last - base[x].i_first, ly = base[y].i_last - base[y].i_first;
+                if (lx != ly) return lx > ly;
+                if (where[x] != where[y]) return where[x] < where[y];
+                return base[x].slot < base[y].slot;
+            });
+            std::vector<WorkItem> sorted(idx.size());
+            for (size_t q = 0; q < idx.size(); ++q) sorted[q] = base[idx[q]];
+            std::copy(sorted.begin(), sorted.end(), P.items.begin() + LP.item_off);
+            P.launches.push_back(LP);
+        }
+    }
+    P.valid = true;
     return FTTE_OK;
 }
 
@@ -503,28 +862,16 @@ int plan_fine_block(const HybridInputs &in, const Extent &cluster, int fine_chun
     if (Q.groups.size() != P.groups.size()) return fail(err, FTTE_ERR_STATE, "hybrid plan: the fine block's groups differ from the base grid's");
     Q.face_elems = Q.uqface_off; // (no boxes inside the fine grid)
     FN.face_base = P.face_elems;
-    // stage lists per pipeline: stage = tu + tv + ti, the groups with the most directions first
+    // stage lists per pipeline: list l = pipeline * nstages + stage, stage = tu + tv + ti, the groups with the most directions first
+    // (an accumulator per group: nobody accumulates)
     FN.nstages = Q.ntu + Q.ntv + Q.nti - 2;
-    const size_t nst = (size_t)FN.nstages, nl = (size_t)H.nhalves * nst;
-    FN.stage_off.assign(nl + 1, 0); // list l = pipeline * nstages + stage: tasks [stage_off[l], stage_off[l + 1])
-    for (size_t g = 0; g < Q.groups.size(); ++g)
-        for (int ti = 0; ti < Q.nti; ++ti)
-            for (int tv = 0; tv < Q.ntv; ++tv)
-                for (int tu = 0; tu < Q.ntu; ++tu) ++FN.stage_off[(size_t)half_of_group[g] * nst + (size_t)(tu + tv + ti) + 1];
-    for (size_t l = 0; l < nl; ++l) FN.stage_off[l + 1] += FN.stage_off[l];
-    Q.tasks.resize(FN.stage_off[nl]);
-    std::vector<size_t> at(FN.stage_off.begin(), FN.stage_off.end() - 1);
-    std::vector<size_t> by_size(Q.groups.size());
-    for (size_t g = 0; g < by_size.size(); ++g) by_size[g] = g;
-    std::stable_sort(by_size.begin(), by_size.end(), [&](size_t x, size_t y) { return Q.groups[x].dirs.size() > Q.groups[y].dirs.size(); });
-    for (size_t g : by_size)
-        for (int ti = 0; ti < Q.nti; ++ti)
-            for (int tv = 0; tv < Q.ntv; ++tv)
-                for (int tu = 0; tu < Q.ntu; ++tu) {
-                    BrickTask T;
-                    T.group = (int16_t)g; T.tu = (int16_t)tu; T.tv = (int16_t)tv; T.ti = (int16_t)ti;
-                    Q.tasks[at[(size_t)half_of_group[g] * nst + (size_t)(tu + tv + ti)]++] = T;
-                }
+    const size_t nst = (size_t)FN.nstages;
+    FN.stage_off = build_task_lists(Q, largest_groups_first(Q), (size_t)H.nhalves * nst, [&](size_t g, auto put) {
+        for_each_brick(Q, [&](int tu, int tv, int ti) {
+            const size_t st = (size_t)(tu + tv + ti);
+            put((size_t)half_of_group[g] * nst + st, st, tu, tv, ti, BrickTask{(int16_t)g, (int16_t)tu, (int16_t)tv, (int16_t)ti});
+        });
+    });
     FN.updates = (int64_t)nf * nf * nf * in.ndir;
     // the boxes learn about the block: its extent in their sweep frame (the refined cells' own) and the fine face block
     for (auto &BX : boxes)
@@ -585,7 +932,6 @@ template <typename F> void for_each_piece(int n, const BrickPlan &P, const std::
                 for (int q = 0; q < np; ++q) fn(tu, tv, ti, q, pc[q]);
             }
 }
-size_t brick_index(const BrickPlan &P, int tu, int tv, int ti) { return ((size_t)ti * P.ntv + tv) * P.ntu + tu; }
 
 // the box that holds lanes [lane_lo, lane_hi] of brick (tu, tv, ti), or -1
 int box_over(const std::vector<HybridBox> &BX, int tu, int tv, int ti, int lane_lo, int lane_hi)
@@ -683,56 +1029,32 @@ int assign_slots(int n, const BrickPlan &P, const Boxes &boxes, const std::vecto
 void write_task_lists(int n, BrickPlan &P, const Boxes &boxes, const std::vector<int> &half_of_group, const std::vector<std::vector<int32_t>> &slot,
                       int per_phase, HybridPlan &H)
 {
-    const size_t nlist = (size_t)H.nhalves * H.nlist, nb = (size_t)P.ntu * P.ntv * P.nti;
+    const size_t nlist = (size_t)H.nhalves * H.nlist;
     auto list_of = [&](size_t g, const Piece &pc, int tu, int tv, int ti, int q) {
         if (H.slots) return (size_t)half_of_group[g] * H.nlist + (size_t)slot[g][2 * brick_index(P, tu, tv, ti) + (size_t)q];
         return (size_t)half_of_group[g] * H.nlist + (size_t)pc.phase * (size_t)per_phase + (size_t)(tu + tv + ti + P.groups[g].offset);
     };
-    // the list in which each accumulator's cells are first written, per physical brick: whoever comes later accumulates
-    std::vector<std::vector<size_t>> first(3 * (size_t)kMaxAcc);
-    auto brick_of = [&](const BrickPlan::Group &G, int tu, int tv, int ti) {
-        const DirPlan &D0 = P.dirs[G.dirs[0]];
-        const int bu = D0.su < 0 ? P.ntu - 1 - tu : tu, bv = D0.sv < 0 ? P.ntv - 1 - tv : tv, bi = D0.si < 0 ? P.nti - 1 - ti : ti;
-        return ((size_t)bi * P.ntv + bv) * P.ntu + bu;
-    };
+    // the lists in which some brick is cut by a box go to the masked half, all of their tasks with a lane range
     std::vector<uint8_t> cut(nlist, 0);
+    H.brick_updates = 0;
     for (size_t g = 0; g < P.groups.size(); ++g)
         for_each_piece(n, P, boxes[g], [&](int tu, int tv, int ti, int q, const Piece &pc) {
             if (pc.masked) cut[list_of(g, pc, tu, tv, ti, q)] = 1;
+            const int64_t cu = std::max(0, std::min(pc.lane_hi, n - 64 * tu - 1) - pc.lane_lo + 1), cv = std::min(kBrickRows, n - kBrickRows * tv),
+                          ci = std::min(P.chunk, n - P.chunk * ti);
+            H.brick_updates += cu * cv * ci * (int64_t)P.groups[g].dirs.size();
         });
-    H.stage_off.assign(2 * nlist + 1, 0);
-    for (size_t g = 0; g < P.groups.size(); ++g) {
-        const BrickPlan::Group &G = P.groups[g];
-        std::vector<size_t> &F = first[(size_t)G.layout * kMaxAcc + G.acc];
-        if (F.empty()) F.assign(nb, ~(size_t)0);
-        for_each_piece(n, P, boxes[g], [&](int tu, int tv, int ti, int q, const Piece &pc) {
-            const size_t l = list_of(g, pc, tu, tv, ti, q);
-            ++H.stage_off[(cut[l] ? nlist : 0) + l + 1];
-            size_t &f = F[brick_of(G, tu, tv, ti)];
-            f = std::min(f, l);
-        });
-    }
-    for (size_t l = 0; l < 2 * nlist; ++l) H.stage_off[l + 1] += H.stage_off[l];
-    P.tasks.resize(H.stage_off[2 * nlist]);
-    std::vector<size_t> fill(H.stage_off.begin(), H.stage_off.end() - 1);
-    H.brick_updates = 0;
-    for (size_t g = 0; g < P.groups.size(); ++g) {
-        const BrickPlan::Group &G = P.groups[g];
-        const std::vector<size_t> &F = first[(size_t)G.layout * kMaxAcc + G.acc];
+    H.stage_off = build_task_lists(P, groups_in_order(P), 2 * nlist, [&](size_t g, auto put) {
         for_each_piece(n, P, boxes[g], [&](int tu, int tv, int ti, int q, const Piece &pc) {
             const size_t l = list_of(g, pc, tu, tv, ti, q);
             BrickTask T;
             T.tv = (int16_t)(cut[l] ? tv | (pc.box << kBrickBoxShift) : tv);
             T.group = (int16_t)(cut[l] ? (int)g | (pc.lane_hi << kBrickLaneHiShift) : (int)g);
             T.tu = (int16_t)(uint16_t)(cut[l] ? tu | (pc.lane_lo << kBrickLaneLoShift) : tu);
-            // (two pieces of one brick write different lanes of rows that start from zero: either may come first)
-            T.ti = (int16_t)(ti | (l > F[brick_of(G, tu, tv, ti)] ? kBrickAccumulate : 0));
-            P.tasks[fill[(cut[l] ? nlist : 0) + l]++] = T;
-            const int64_t cu = std::max(0, std::min(pc.lane_hi, n - 64 * tu - 1) - pc.lane_lo + 1), cv = std::min(kBrickRows, n - kBrickRows * tv),
-                          ci = std::min(P.chunk, n - P.chunk * ti);
-            H.brick_updates += cu * cv * ci * (int64_t)G.dirs.size();
+            T.ti = (int16_t)ti;
+            put((cut[l] ? nlist : 0) + l, l, tu, tv, ti, T);
         });
-    }
+    });
 }
 
 // The forests, restricted to the boxes: linked on the host a few directions at a time.  Once the leaves that lie in any box are

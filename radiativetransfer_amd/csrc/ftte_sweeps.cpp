@@ -507,7 +507,7 @@ int BrickSweep::prepare(int ndir, const double *uvb)
     FTTE_HIP(c, c->btables.groups.send(G.data(), G.size()));
     FTTE_HIP(c, c->d_uvb.send(uvb, (size_t)nnu));
 
-    nulanes = P.glanes > 1 ? 1 : std::max(1, std::min(c->lanes, nnu)); // streams over frequency groups ...
+    nulanes = P.glanes > 1 ? 1 : std::max(1, std::min(c->bopt.lanes, nnu)); // streams over frequency groups ...
     nlanes = nulanes * P.glanes;                                        // ... or over the groups of directions
     FTTE_HIP(c, ensure_lanes(c->lane_stream, c->lane_done, (size_t)nlanes - 1));
     FTTE_HIP(c, c->ev_fork.create(hipEventDisableTiming));
@@ -525,7 +525,7 @@ int BrickSweep::one_launch()
 {
     BrickLaunch L = launch(0, P.tasks.size(), 0, nnu);
     FTTE_HIP(c, c->bflow.prepare(L, c->btables, P.tasks.size() * (size_t)nnu, stream));
-    L.pad_ = c->dataflow == 2 ? 1 : 0;
+    L.pad_ = c->bopt.dataflow == 2 ? 1 : 0;
     int persistent = 0;
     if (P.persistent) {
         L.queue = c->btables.queue;
@@ -536,7 +536,7 @@ int BrickSweep::one_launch()
         FTTE_HIP(c, hipGetDeviceProperties(&prop, c->device));
         persistent = (int)std::min<size_t>((size_t)prop.multiProcessorCount * 16, P.queue.size());
     }
-    c->last_brick_form = 0; c->last_brick_dataflow = P.persistent ? 3 : c->dataflow == 2 ? 2 : 1; c->last_brick_whole = 0;
+    c->last_brick_form = 0; c->last_brick_dataflow = P.persistent ? 3 : c->bopt.dataflow == 2 ? 2 : 1; c->last_brick_whole = 0;
     const int lrc = launch_brick(L, P.max_dirs, c->brick_waves, stream, false, persistent);
     if (lrc) return fail(c, lrc == -1 ? FTTE_ERR_ARG : FTTE_ERR_NO_DEVICE, "brick kernel launch failed");
     FTTE_HIP(c, c->bflow.read_back(P, stream));
@@ -569,7 +569,7 @@ int BrickSweep::lane_stages(int lane, LaunchTiming &T)
     for (size_t st = 0, mp = 0; st < nstages; ++st) {
         if (off[st + 1] != off[st]) {
             const BrickLaunch L = launch(off[st], off[st + 1], S.nu0, S.nu1);
-            const int form = brick_form(c, nnu);
+            const int form = c->bopt.brick_form(nnu, c->emit_mode);
             c->last_brick_form = form; c->last_brick_dataflow = 0; c->last_brick_whole = form != 2 && brick_whole_form(L, c->brick_waves);
             const int lrc = form == 2 ? launch_brick_pair(L, P.max_dirs, c->pair_waves, q) : launch_brick(L, P.max_dirs, c->brick_waves, q);
             if (lrc) return fail(c, lrc == -1 ? FTTE_ERR_ARG : FTTE_ERR_NO_DEVICE, "brick kernel launch failed");
