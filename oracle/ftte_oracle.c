@@ -790,3 +790,72 @@ void fo_device_cell_mean(int64_t count, const double *acc, int nseg, double w, d
 {
     for (int64_t i = 0; i < count; ++i) out[i] = ftte_cell_mean(acc[i], nseg, w);
 }
+
+/* ------------------------------------------ the device's chemistry (csrc/ftte_chem_math.h) on the host
+ * The per-cell statement the kernels of ftte_chem.hip call, looped over the cells, with the library's bookkeeping: the species
+ * of the cells that pass (the others keep what they held), the bisection steps summed over what the kernel counts, and
+ * 1 + the first cell at which the reference stops (0: none).  The logarithm of the temperature is libm's, taken here as
+ * ftte_set_temperature takes it.  On the host FTTE_DIV is `/` and FTTE_ANY is per element: this pins the control flow, the
+ * operation order, the constants and the branch logic, not the trimmed division or the wavefront vote.
+ * Arguments as fo_solve_rate_equations (krate: [3][ncell] or NULL). */
+#include "../radiativetransfer_amd/csrc/ftte_chem_math.h"
+
+long fo_device_solve_rate_equations(int n, long ncell, const int32_t *level, double box, const double *rho, const double *tgas,
+                                    double *HI_io, double *HeI_io, double *HeII_io, const double *krate, int run_uvb, const double *J,
+                                    const double *ksi, const double *uniform, double threshold, int nratec, double logtem0,
+                                    double logtem9, double dlogtem, const double *k, long *steps)
+{
+    const ChemTable T = {k, nratec, logtem0, logtem9, dlogtem};
+    long first_bad = 0, all_steps = 0;
+    for (long c = 0; c < ncell; ++c) {
+        double HI, HeI, HeII, change;
+        unsigned s;
+        int tame;
+        const int ok = chem_solve_cell(&T, rho[c], log(tgas[c]), HI_io[c], HeI_io[c], HeII_io[c], chem_cell_volume(box, level[c], n),
+                                       krate != NULL, krate ? krate[c] : 0., krate ? krate[ncell + c] : 0., krate ? krate[2 * ncell + c] : 0.,
+                                       run_uvb ? J + c : NULL, ncell, ksi, uniform, threshold, &HI, &HeI, &HeII, &s, &change, &tame);
+        if (!ok) { if (!first_bad) first_bad = c + 1; }
+        else { all_steps += (long)s; HI_io[c] = HI; HeI_io[c] = HeI; HeII_io[c] = HeII; }
+    }
+    if (steps) *steps = all_steps;
+    return first_bad;
+}
+
+/* chem_tame of every cell's equation over solveRateEquations' bracket, as chem_solve_cell reports it: whether the kernel takes
+ * the cell's residuals through the trimmed division */
+void fo_device_chem_tame(int n, long ncell, const int32_t *level, double box, const double *rho, const double *tgas, const double *HI,
+                         const double *HeI, const double *HeII, const double *krate, int run_uvb, const double *J, const double *ksi,
+                         const double *uniform, double threshold, int nratec, double logtem0, double logtem9, double dlogtem,
+                         const double *k, int32_t *tame)
+{
+    const ChemTable T = {k, nratec, logtem0, logtem9, dlogtem};
+    for (long c = 0; c < ncell; ++c) {
+        double out[4];
+        unsigned s;
+        int t;
+        (void)chem_solve_cell(&T, rho[c], log(tgas[c]), HI[c], HeI[c], HeII[c], chem_cell_volume(box, level[c], n), krate != NULL,
+                              krate ? krate[c] : 0., krate ? krate[ncell + c] : 0., krate ? krate[2 * ncell + c] : 0.,
+                              run_uvb ? J + c : NULL, ncell, ksi, uniform, threshold, &out[0], &out[1], &out[2], &s, &out[3], &t);
+        tame[c] = t;
+    }
+}
+
+/* the start-up equilibrium, `passes` times per cell; the steps of every pass run count, as in the kernel */
+long fo_device_initial_equilibrium(long ncell, const double *rho, const double *tgas, double *HI_io, double *HeI_io, double *HeII_io,
+                                   const double *uniform, double threshold, int passes, int nratec, double logtem0, double logtem9,
+                                   double dlogtem, const double *k, long *steps)
+{
+    const ChemTable T = {k, nratec, logtem0, logtem9, dlogtem};
+    long first_bad = 0, all_steps = 0;
+    for (long c = 0; c < ncell; ++c) {
+        double HI, HeI, HeII;
+        unsigned long long s;
+        const int ok = chem_initial_cell(&T, rho[c], log(tgas[c]), HI_io[c], HeI_io[c], HeII_io[c], uniform, threshold, passes, &HI, &HeI,
+                                         &HeII, &s);
+        all_steps += (long)s;
+        if (!ok) { if (!first_bad) first_bad = c + 1; }
+        else { HI_io[c] = HI; HeI_io[c] = HeI; HeII_io[c] = HeII; }
+    }
+    if (steps) *steps = all_steps;
+    return first_bad;
+}

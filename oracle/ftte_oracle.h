@@ -140,6 +140,21 @@ void fo_device_segment_emit(int64_t count, double *I, const double *tau, const d
 /* ftte_segment_source element-wise (a source function: the exact path mean) */
 void fo_device_segment_source(int64_t count, double *I, const double *tau, const double *src, double *mean);
 
+/* radiativetransfer_amd/csrc/ftte_chem_math.h, the per-cell chemistry of the kernels, looped over the cells on the host
+ * (ftte_oracle.c).  Arguments as fo_solve_rate_equations; return 0 or 1 + the first cell at which the reference stops, the
+ * species of the cells that pass in place, *steps the bisection steps as the kernel counts them.  tame[c]: chem_tame. */
+long fo_device_solve_rate_equations(int n, long ncell, const int32_t *level, double box, const double *rho, const double *tgas,
+                                    double *HI_io, double *HeI_io, double *HeII_io, const double *krate, int run_uvb, const double *J,
+                                    const double *ksi, const double *uniform, double threshold, int nratec, double logtem0,
+                                    double logtem9, double dlogtem, const double *k, long *steps);
+void fo_device_chem_tame(int n, long ncell, const int32_t *level, double box, const double *rho, const double *tgas, const double *HI,
+                         const double *HeI, const double *HeII, const double *krate, int run_uvb, const double *J, const double *ksi,
+                         const double *uniform, double threshold, int nratec, double logtem0, double logtem9, double dlogtem,
+                         const double *k, int32_t *tame);
+long fo_device_initial_equilibrium(long ncell, const double *rho, const double *tgas, double *HI_io, double *HeI_io, double *HeII_io,
+                                   const double *uniform, double threshold, int passes, int nratec, double logtem0, double logtem9,
+                                   double dlogtem, const double *k, long *steps);
+
 /* ---- ionisation equilibrium (ftte_oracle_chem.c): solveRateEquations, equiSources.f90:3459-3677 ---- */
 long fo_solve_rate_equations(int n, long ncell, const int32_t *level, double box, const double *rho, const double *tgas,
                              double *HI_io, double *HeI_io, double *HeII_io, const double *krate, int run_uvb, const double *J,

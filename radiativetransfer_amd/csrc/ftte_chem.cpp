@@ -2,6 +2,7 @@
 // ionisation chemistry (rate coefficients, temperature, the equilibrium update, the start-up equilibrium, the hydrogen census), the
 // species' way out, the opacities and the thin-limit radiation made from them, and the start-up expansion of HII regions (kernel:
 // ftte_expansion.hip).  The chemistry's own state is ftte_ctx::chem.
+#include "ftte_chem_math.h"
 #include "ftte_context.h"
 
 using namespace ftte;
@@ -364,7 +365,6 @@ int ftte_expand_hii_regions(ftte_ctx *c, int nsrc, const int64_t *src_cell, cons
     const size_t ns = (size_t)nsrc;
 
     // per star: finalRadius, densityCoefficient, sourceTotalHydrogenDensity (:1048), given or from the host leaf's density
-    const double psi = (double)0.76f, mh = (double)1.6726231e-24f; // definitionsModule.f90:25-27, 261
     std::vector<double> own;
     if (!params) {
         std::vector<double> rho(ns);
@@ -380,7 +380,7 @@ int ftte_expand_hii_regions(ftte_ctx *c, int nsrc, const int64_t *src_cell, cons
             if (!(rho[s] > 0.0) || !std::isfinite(rho[s]))
                 return fail(c, FTTE_ERR_ARG, who + "the density of the host cell of source " + std::to_string(s) + " (cell " +
                                                  std::to_string(src_cell[s]) + ") is not positive and finite");
-            const double nh = psi * rho[s] / mh;
+            const double nh = chem_nh(rho[s]);
             expansion_parameters(nh, &own[3 * s], &own[3 * s + 1]);
             own[3 * s + 2] = nh;
         }

@@ -1,0 +1,190 @@
+// ftte_chem.hip -- the kernels behind ftte_chem.cpp: the ionisation equilibrium of every leaf (solveRateEquations,
+// initialIonizationEquilibrium), the optically thin radiation field, the hydrogen census and the opacities.  The chemistry of a
+// cell is ftte_chem_math.h, compiled here for the device and by the tests' host library for the host; an equilibrium kernel is the
+// grid-stride loop, the cell's loads, one call into that header and the cell's stores, and then the fold of its statistics.
+#include <hip/hip_runtime.h>
+
+#include "ftte_chem_math.h"
+#include "ftte_internal.h"
+#include "ftte_kernels.h"
+
+namespace ftte {
+
+// The statistics of an update -- the largest change (kChange), the bisection steps, the first cell the reference would stop at --
+// are combined per wavefront, then per workgroup, before they go to their single words in memory with one atomic each: a
+// quarter of a million atomics on ONE address each cost more than all the arithmetic of the kernel.
+template <bool kChange>
+__device__ __forceinline__ void fold_statistics(const ChemRec &R, unsigned long long my_change, unsigned long long my_steps,
+                                                unsigned long long my_bad)
+{
+    __shared__ unsigned long long blk_change[4], blk_steps[4], blk_bad[4];
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned long long oc = kChange ? __shfl_xor(my_change, off) : 0ull, os = __shfl_xor(my_steps, off), ob = __shfl_xor(my_bad, off);
+        my_change = oc > my_change ? oc : my_change;
+        my_steps += os;
+        my_bad = ob < my_bad ? ob : my_bad;
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { if (kChange) blk_change[wave] = my_change; blk_steps[wave] = my_steps; blk_bad[wave] = my_bad; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < 4; ++k) {
+            if (kChange) my_change = blk_change[k] > my_change ? blk_change[k] : my_change;
+            my_steps += blk_steps[k];
+            my_bad = blk_bad[k] < my_bad ? blk_bad[k] : my_bad;
+        }
+        if (my_bad != ~0ull) atomicMin(R.first_bad, my_bad);
+        if (kChange && my_change) atomicMax(R.max_change, my_change);
+        if (my_steps) atomicAdd(R.steps, my_steps);
+    }
+}
+
+// solveRateEquations, equiSources.f90:3459-3677, per leaf (chem_solve_cell)
+__global__ void __launch_bounds__(256) rate_equations_kernel(const ChemRec R)
+{
+    unsigned long long my_change = 0ull, my_steps = 0ull, my_bad = ~0ull;
+    const ChemTable T = {R.k, R.nratec, R.logtem0, R.logtem9, R.dlogtem};
+    for (long c = (long)blockIdx.x * blockDim.x + threadIdx.x; c < R.ncell; c += (long)gridDim.x * blockDim.x) { // (a few cells per thread)
+        double p24 = 0., p25 = 0., p26 = 0., HI, HeI, HeII, change;
+        if (R.krate) { p24 = R.krate[c * kCellRec]; p25 = R.krate[c * kCellRec + 1]; p26 = R.krate[c * kCellRec + 2]; }
+        unsigned steps; int tame;
+        const int ok = chem_solve_cell(&T, R.rho[c], R.logtem[c], R.HI[c], R.HeI[c], R.HeII[c], chem_cell_volume(R.box, R.level[c], R.n),
+                                       R.krate != nullptr, p24, p25, p26, R.run_uvb ? R.J + c : nullptr, R.ncell, R.ksi, R.uniform, R.threshold,
+                                       &HI, &HeI, &HeII, &steps, &change, &tame);
+        if (!ok) my_bad = (unsigned long long)c < my_bad ? (unsigned long long)c : my_bad;
+        else {
+            const unsigned long long bits = (unsigned long long)__double_as_longlong(change); // non-negative doubles order like their bits
+            my_change = bits > my_change ? bits : my_change;
+            my_steps += (unsigned long long)steps;
+            R.HI_out[c] = HI; R.HeI_out[c] = HeI; R.HeII_out[c] = HeII;
+        }
+    }
+    fold_statistics<true>(R, my_change, my_steps, my_bad);
+}
+
+// The start-up ionisation equilibrium, initialIonizationEquilibrium (equiSources.f90:3679-3868), R.passes times per leaf
+// (chem_initial_cell).  R.krate, R.J, R.run_uvb, R.ksi are not used.
+__global__ void __launch_bounds__(256) initial_equilibrium_kernel(const ChemRec R)
+{
+    unsigned long long my_steps = 0ull, my_bad = ~0ull;
+    const ChemTable T = {R.k, R.nratec, R.logtem0, R.logtem9, R.dlogtem};
+    for (long c = (long)blockIdx.x * blockDim.x + threadIdx.x; c < R.ncell; c += (long)gridDim.x * blockDim.x) {
+        double HI, HeI, HeII;
+        unsigned long long steps;
+        const int ok = chem_initial_cell(&T, R.rho[c], R.logtem[c], R.HI[c], R.HeI[c], R.HeII[c], R.uniform, R.threshold, R.passes, &HI, &HeI,
+                                         &HeII, &steps);
+        my_steps += steps;
+        if (!ok) my_bad = (unsigned long long)c < my_bad ? (unsigned long long)c : my_bad;
+        else { R.HI_out[c] = HI; R.HeI_out[c] = HeI; R.HeII_out[c] = HeII; }
+    }
+    fold_statistics<false>(R, 0ull, my_steps, my_bad);
+}
+
+// (enough workgroups to fill the GPU several times over, few enough that their atomics are nothing)
+static int launch_equilibrium(void (*kernel)(const ChemRec), const ChemRec &R, hipStream_t stream)
+{
+    if (R.ncell <= 0) return 0;
+    const long blocks = (R.ncell + 255) / 256;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, stream, R);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+int launch_rate_equations(const ChemRec &R, hipStream_t stream) { return launch_equilibrium(rate_equations_kernel, R, stream); }
+
+int launch_initial_equilibrium(const ChemRec &R, hipStream_t stream)
+{
+    return R.ncell > 0 && R.passes < 1 ? -1 : launch_equilibrium(initial_equilibrium_kernel, R, stream);
+}
+
+// assignUvbRadiation, transportRoutinesModule.f90:1056-1093: the optically thin alternative to the sweep.  J_g = uvb_g where the
+// Lyman-limit mean free path of the cell is at least the self-shielding threshold, else 0.
+__global__ void __launch_bounds__(256) thin_limit_kernel(const double *__restrict__ HI, const double *__restrict__ HeI,
+                                                         const double *__restrict__ HeII, const double *__restrict__ rho,
+                                                         const double *__restrict__ uvb, double threshold, double *__restrict__ J,
+                                                         long ncell, int nnu)
+{
+    const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= ncell) return;
+    const bool lit = chem_mean_free_path(fmin(HI[c], chem_nh(rho[c])), HeI[c], HeII[c]) >= threshold;
+    for (int g = 0; g < nnu; ++g) J[(long)g * ncell + c] = lit ? uvb[g] : 0.0;
+}
+
+int launch_thin_limit(const double *HI, const double *HeI, const double *HeII, const double *rho, const double *uvb, double threshold,
+                      double *J, long ncell, int nnu, hipStream_t stream)
+{
+    hipLaunchKernelGGL(thin_limit_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, stream, HI, HeI, HeII, rho, uvb, threshold, J,
+                       ncell, nnu);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// computeMass (equiSources.f90:4369-4393) per leaf: HI mh cs3/msun and psi rho cs3/msun, cs3 the cube of the cell's size, each
+// term with the reference's operations in its order.  The sums are the code's own and deterministic: every thread adds its
+// cells in grid-stride order, the workgroup folds its 256 sums as a fixed tree, and mass_total_kernel adds the workgroups'
+// partial sums in a fixed order too.  No floating-point atomics.
+__device__ __forceinline__ void tree_sum_256(double *a, double *b)
+{
+    for (int w = 128; w > 0; w >>= 1) {
+        __syncthreads();
+        if ((int)threadIdx.x < w) { a[threadIdx.x] += a[threadIdx.x + w]; b[threadIdx.x] += b[threadIdx.x + w]; }
+    }
+    __syncthreads();
+}
+
+__global__ void __launch_bounds__(256) hydrogen_mass_kernel(const int8_t *__restrict__ level, const double *__restrict__ HI,
+                                                            const double *__restrict__ rho, long ncell, int n, double box,
+                                                            double *__restrict__ part)
+{
+    __shared__ double sn[256], st[256];
+    double an = 0., at = 0.;
+    for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < ncell; c += (long)gridDim.x * 256) {
+        const double cs3 = chem_cell_volume(box, level[c], n);
+        an += HI[c] * FTTE_MH * cs3 / FTTE_MSUN;
+        at += FTTE_PSI * rho[c] * cs3 / FTTE_MSUN;
+    }
+    sn[threadIdx.x] = an; st[threadIdx.x] = at;
+    tree_sum_256(sn, st);
+    if (threadIdx.x == 0) { part[blockIdx.x] = sn[0]; part[kMassBlocks + blockIdx.x] = st[0]; }
+}
+
+__global__ void __launch_bounds__(256) mass_total_kernel(double *part, int nblocks)
+{
+    __shared__ double sn[256], st[256];
+    double an = 0., at = 0.;
+    for (int b = threadIdx.x; b < nblocks; b += 256) { an += part[b]; at += part[kMassBlocks + b]; }
+    sn[threadIdx.x] = an; st[threadIdx.x] = at;
+    tree_sum_256(sn, st);
+    if (threadIdx.x == 0) { part[2 * kMassBlocks] = sn[0]; part[2 * kMassBlocks + 1] = st[0]; }
+}
+
+int launch_hydrogen_mass(const int8_t *level, const double *HI, const double *rho, long ncell, int n, double box, double *part,
+                         hipStream_t stream)
+{
+    if (ncell < 1 || n < 1 || !part) return -1;
+    const long want = (ncell + 255) / 256;
+    const int blocks = (int)(want < kMassBlocks ? want : kMassBlocks);
+    hipLaunchKernelGGL(hydrogen_mass_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, level, HI, rho, ncell, n, box, part);
+    if (hipGetLastError() != hipSuccess) return -2;
+    hipLaunchKernelGGL(mass_total_kernel, dim3(1), dim3(256), 0, stream, part, blocks);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// kappa[g][c] = HI[c]*beta[0][g] + HeI[c]*beta[1][g] + HeII[c]*beta[2][g]   (equiSources.f90:4977-4980)
+__global__ void __launch_bounds__(256) opacity_kernel(const double *__restrict__ HI, const double *__restrict__ HeI,
+                                                      const double *__restrict__ HeII, const double *__restrict__ beta,
+                                                      double *__restrict__ kappa, long ncell, int nnu)
+{
+    for (long c = (long)blockIdx.x * blockDim.x + threadIdx.x; c < ncell; c += (long)gridDim.x * blockDim.x) {
+        const double a = HI[c], b = HeI[c], d = HeII[c];
+        for (int g = 0; g < nnu; ++g) kappa[(long)g * ncell + c] = a * beta[g] + b * beta[nnu + g] + d * beta[2 * nnu + g];
+    }
+}
+
+int launch_opacity(const double *HI, const double *HeI, const double *HeII, const double *beta, double *kappa, long ncell,
+                   int nnu, hipStream_t stream)
+{
+    const int blocks = (int)((ncell + 255) / 256 < 8192 ? (ncell + 255) / 256 : 8192);
+    hipLaunchKernelGGL(opacity_kernel, dim3(blocks), dim3(256), 0, stream, HI, HeI, HeII, beta, kappa, ncell, nnu);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+} // namespace ftte

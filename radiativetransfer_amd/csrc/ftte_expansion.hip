@@ -9,6 +9,7 @@
 // the test is the leaf's own before any expansion -- so neither the cull nor the order of the stars can change a bit of it.
 #include <hip/hip_runtime.h>
 
+#include "ftte_chem_math.h"
 #include "ftte_expansion.h"
 
 namespace ftte {
@@ -38,7 +39,6 @@ __global__ void __launch_bounds__(kExpGroup) expansion_kernel(const ExpandRec R)
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t c = (int64_t)blockIdx.x * kExpGroup + tid;
     const bool live = c < R.ncell;
-    const double psi = (double)0.76f, mh = (double)1.6726231e-24f; // definitionsModule.f90:25-27, 261
 
     // the leaf's centre (findExpansion's xcell, ycell, zcell) and its hydrogen density before any expansion
     double x = 0., y = 0., z = 0., nh = 0.;
@@ -50,7 +50,7 @@ __global__ void __launch_bounds__(kExpGroup) expansion_kernel(const ExpandRec R)
             const int i0 = (int)(c / nn), j0 = (int)((c / R.n) % R.n), k0 = (int)(c % R.n);
             x = expansion_base_centre(i0, R.n); y = expansion_base_centre(j0, R.n); z = expansion_base_centre(k0, R.n);
         }
-        nh = psi * R.rho[c] / mh;
+        nh = chem_nh(R.rho[c]);
     }
 
     // the box around the workgroup's centres

@@ -5,6 +5,8 @@
 // are to /root/reference files.
 #include "ftte_geometry.h"
 
+#include "ftte_chem_math.h"
+
 #include <cmath>
 #include <cstring>
 
@@ -12,7 +14,7 @@ namespace ftte {
 
 // definitionsModule.f90:8-10.  `pi = 3.141592654` is a default-real literal: the binary64
 // constant is the float32 value 3.1415927410125732, and halfPi/twoPi derive from it.
-const double kPi = static_cast<double>(3.141592654f);
+const double kPi = FTTE_PI;
 const double kHalfPi = 0.5 * kPi;
 const double kTwoPi = 2.0 * kPi;
 

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/ftte.h"
+#include "ftte_chem_math.h"
 
 namespace {
 
@@ -136,8 +137,7 @@ int ftte_ingest_levels(int nlevels, const ftte_level_list *lists, ftte_cellarray
 
     // the tree: base cells zeroed (:495-521), every listed cell placed (:580-618)
     std::vector<Node> T((size_t)nx * nx * nx);
-    const double mp = W(1.6726231e-24f), mn = W(1.67492728e-24f), psi = W(0.76f);
-    const double mh = mp, mhe = 2. * (mp + mn);
+    const double psi = FTTE_PSI, mh = FTTE_MH, mhe = FTTE_MHE;
     for (int l = 0; l < nlevels; ++l) {
         const int64_t nc = lists[l].ncell;
         for (int64_t c = 0; c < nc; ++c) {

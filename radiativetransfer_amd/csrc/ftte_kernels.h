@@ -1,5 +1,5 @@
-// ftte_kernels.h -- launch wrappers of ftte_kernels.hip (all asynchronous on `stream`;
-// return 0, -1 bad argument, -2 launch failure)
+// ftte_kernels.h -- launch wrappers of ftte_kernels.hip, ftte_brick.hip and, from launch_opacity and launch_rate_equations on,
+// ftte_chem.hip (all asynchronous on `stream`; return 0, -1 bad argument, -2 launch failure)
 #pragma once
 #include <hip/hip_runtime_api.h>
 

@@ -1,6 +1,12 @@
-// ftte_kernels.hip -- CDNA4 (gfx950) kernels of the diffuse long-characteristics sweep.
+// ftte_kernels.hip -- CDNA4 (gfx950) kernels of the diffuse long-characteristics sweep and what grew around it.
 //
-// What is computed (per direction, per frequency group): the reference's cell transfer,
+// What the file holds, in its order: the ray-following tile sweep of round 1 (sweep_kernel, described below); the moves between
+// cell-array order and the sweep layouts and the merge of the accumulators; the segment forest of refined cell arrays (amr_*);
+// the point sources (rate tables, the splitting tracer, the packed medium and rates); the sum of the devices' pieces of J.  The
+// chemistry's kernels -- equilibrium, thin limit, hydrogen census, opacities -- are ftte_chem.hip; the brick sweep is
+// ftte_brick.hip.
+//
+// The tile sweep.  What is computed (per direction, per frequency group): the reference's cell transfer,
 //   transportRoutinesModule.f90:587-961  /  equiSources.f90:1580-1788,
 // on a uniform grid.  How it is organised has nothing in common with the reference's serial
 // pointer walk:
@@ -30,7 +36,7 @@
 
 #include "ftte_internal.h"
 #include "ftte_kernels.h"
-#include "ftte_math.h"
+#include "ftte_chem_math.h"
 
 namespace ftte {
 
@@ -1134,10 +1140,10 @@ __global__ void __launch_bounds__(64) point_trace_kernel(const TraceRec T)
         const long c = node_leaf(T, cell);
         const double *M = T.medium + c * kCellRec; // HI, HeI, HeII, rho, abun2
         const double hi = M[0];
-        const double tau1 = path * hi * (double)6.3e-18f, tau2 = path * M[1] * (double)7.42e-18f, tau3 = path * M[2] * (double)1.58e-18f;
+        const double tau1 = path * hi * FTTE_SIGMA_HI, tau2 = path * M[1] * FTTE_SIGMA_HEI, tau3 = path * M[2] * FTTE_SIGMA_HEII;
         double taud = 0.0;
         if (T.dust == 1) taud = path * hi * (double)5.4116737e-22f * M[4] / (double)0.2f;
-        else if (T.dust == 2) taud = path * (double)0.76f * M[3] / (double)1.6726231e-24f * (double)5.4116737e-22f * M[4] / (double)0.2f;
+        else if (T.dust == 2) taud = path * FTTE_PSI * M[3] / FTTE_MH * (double)5.4116737e-22f * M[4] / (double)0.2f;
         if (T.escape) { // :3198-3233: what is left of the ray where it crosses the output radii, what leaves through the box faces
             double *E = T.escape + (size_t)src * kEscapeRec;
             const double tmp1 = old_radius * T.box / fn, tmp2 = radius * T.box / fn;
@@ -1312,381 +1318,6 @@ int launch_point_trace(const TraceRec &T, hipStream_t stream)
 {
     if (T.nrays <= 0) return 0;
     hipLaunchKernelGGL(point_trace_kernel, dim3((T.nrays + 63) / 64), dim3(64), 0, stream, T);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Ionisation equilibrium per leaf: solveRateEquations, equiSources.f90:3459-3677.  The reference's arithmetic statement by
-// statement (every operation is an IEEE add, multiply or divide; the logarithm of the temperature comes from the host),
-// bisection on the electron density until HeI moves by less than 1e-10 of the helium density.
-// ------------------------------------------------------------------------------------------------
-struct ChemEq { double k1, k2, k3, k4, k5, k6, nh, nhe, kr24, kr25, kr26; };
-
-template <bool kIeee> __device__ __forceinline__ double chem_div(double a, double b) { return kIeee ? a / b : FTTE_DIV(a, b); }
-
-template <bool kIeee> __device__ __forceinline__ double chem_residual_as(const ChemEq &q, double de, double &HeI, double &HX)
-{
-    // :3592-3596 (repeated at :3600-3604 and :3618-3622)
-    const double X = q.k3 * de + q.kr26, Y = q.k4 * de;
-    const double XY = chem_div<kIeee>(X, Y);
-    const double HII = chem_div<kIeee>(q.nh, 1. + chem_div<kIeee>(q.k2 * de, q.k1 * de + q.kr24));
-    HeI = chem_div<kIeee>(de - HII - 2. * q.nhe, XY - 2. - chem_div<kIeee>(2. * X, Y));
-    HX = HeI * X;
-    const double HeII = chem_div<kIeee>(HX, Y);
-    return q.k3 * HeI * de + q.k6 * (q.nhe - HeI - HeII) * de + q.kr26 * HeI - HeII * (q.k4 * de + q.k5 * de + q.kr25);
-}
-
-// The residual's six divisions through FTTE_DIV, the trimmed sequence of ftte_math.h (a quarter fewer instructions, some forty
-// evaluations per cell), where that gives IEEE's quotient; the plain division where it might not.  `tame` (per cell,
-// chem_tame): every operand that depends on the rate coefficients lies in [2^-250, 2^250] for every de of the bracket -- then
-// every divisor, and every quotient but the last, is far from both ends of the range.  Left to check per evaluation: the last
-// numerator, HeI X (too small: HeII near the underflow), and NaN from an overflowing quotient.  Any lane outside takes the whole
-// wavefront through IEEE division, which gives the same bits in the lanes that did not need it.
-__device__ __forceinline__ double chem_residual(const ChemEq &q, double de, double &HeI, bool tame)
-{
-    double HX;
-    if (!FTTE_ANY(!tame)) {
-        double h;
-        const double r = chem_residual_as<false>(q, de, h, HX);
-        if (!FTTE_ANY(!(r == r) || (HX != 0. && fabs(HX) < 0x1p-700))) { HeI = h; return r; }
-    }
-    return chem_residual_as<true>(q, de, HeI, HX);
-}
-
-// Whether the divisors and numerators of chem_residual that depend on the rate coefficients stay in [2^-250, 2^250] over the
-// bracket [de1, de2] (each is a non-decreasing function of de when the coefficients are not negative, so its ends bound it), X
-// either there or 0 throughout, and nh, nhe there too.  False for a table whose coefficients vanish or come close to it where
-// nothing else ionises the cell: k1 de + kr24 or k4 de is then subnormal or 0 at de = 1e-30, where the trimmed division
-// returns NaN and IEEE's carries on with inf and 0.
-__device__ __forceinline__ bool chem_tame(const ChemEq &q, double de1, double de2)
-{
-    const auto in = [](double v) { return v >= 0x1p-250 && v <= 0x1p250; };
-    const double X1 = q.k3 * de1 + q.kr26, X2 = q.k3 * de2 + q.kr26;
-    return q.k1 >= 0. && q.k2 >= 0. && q.k3 >= 0. && q.k4 >= 0. && in(q.nh) && in(q.nhe) && in(q.k1 * de1 + q.kr24) &&
-           in(q.k1 * de2 + q.kr24) && in(q.k2 * de1) && in(q.k2 * de2) && in(q.k4 * de1) && in(q.k4 * de2) &&
-           ((X1 == 0. && X2 == 0.) || (in(X1) && in(X2)));
-}
-
-__global__ void __launch_bounds__(256) rate_equations_kernel(const ChemRec R)
-{
-    // (the sweep's three statistics -- the largest change, the bisection steps, the first cell the reference would stop at -- are
-    // combined per workgroup before they go to their single words in memory: a quarter of a million atomics on ONE address each
-    // cost more than all the arithmetic of the kernel)
-    __shared__ unsigned long long blk_change[4], blk_steps[4], blk_bad[4];
-    unsigned long long my_change = 0ull, my_steps = 0ull, my_bad = ~0ull;
-    for (long c = (long)blockIdx.x * blockDim.x + threadIdx.x; c < R.ncell; c += (long)gridDim.x * blockDim.x) { // (a few cells per thread)
-    const double psi = (double)0.76f, mp = (double)1.6726231e-24f, mn = (double)1.67492728e-24f; // definitionsModule.f90:25-28, 261
-    const double mh = mp, mhe = 2. * (mp + mn), pi = (double)3.141592654f;
-    ChemEq q;
-    const double rho = R.rho[c];
-    q.nh = psi * rho / mh;
-    q.nhe = (1. - psi) * rho / mhe;
-    const double HI0 = R.HI[c], HeI0 = R.HeI[c], HeII0 = R.HeII[c];
-    double HI = fmin(HI0, q.nh), HeI = HeI0, HeII = HeII0;
-    if (q.nhe - HeI0 - HeII0 < 0. && HeII < 0.) HeII = 0.; // :3504-3513: only this survives of the branch
-    // rates per cell -> per absorber, :3520-3542
-    const double size = R.box / (double)((float)(1 << R.level[c]) * (float)R.n);
-    const double vol = size * size * size;
-    q.kr24 = (R.krate && HI > 0.) ? R.krate[c * kCellRec] / (vol * HI) : 0.;
-    q.kr25 = (R.krate && HeII > 0.) ? R.krate[c * kCellRec + 1] / (vol * HeII) : 0.;
-    q.kr26 = (R.krate && HeI > 0.) ? R.krate[c * kCellRec + 2] / (vol * HeI) : 0.;
-    q.kr24 = fmax(q.kr24, 0.); q.kr25 = fmax(q.kr25, 0.); q.kr26 = fmax(q.kr26, 0.);
-    if (R.run_uvb) { // :3545-3553
-        const double t1 = 4. * pi * R.J[c], t2 = 4. * pi * R.J[R.ncell + c], t3 = 4. * pi * R.J[2 * R.ncell + c];
-        q.kr24 = q.kr24 + t1 * R.ksi[0] + t2 * R.ksi[3] + t3 * R.ksi[6];
-        q.kr25 = q.kr25 + t3 * R.ksi[7];
-        q.kr26 = q.kr26 + t2 * R.ksi[5] + t3 * R.ksi[8];
-    } else { // :3554-3562
-        const double mfp = 1. / (HI * (double)6.3e-18f + HeI * (double)7.42e-18f + HeII * (double)1.58e-18f);
-        if (mfp >= R.threshold) {
-            q.kr24 = q.kr24 + 4. * pi * R.uniform[0];
-            q.kr25 = q.kr25 + 4. * pi * R.uniform[1];
-            q.kr26 = q.kr26 + 4. * pi * R.uniform[2];
-        }
-    }
-    // rate coefficients at this temperature, :3568-3587
-    double logtem = R.logtem[c];
-    logtem = fmax(logtem, R.logtem0);
-    logtem = fmin(logtem, R.logtem9);
-    int ix = (int)((logtem - R.logtem0) / R.dlogtem) + 1;
-    ix = ix < 1 ? 1 : ix;
-    ix = ix > R.nratec - 1 ? R.nratec - 1 : ix;
-    const double t1 = R.logtem0 + (double)(ix - 1) * R.dlogtem, t2 = R.logtem0 + (double)ix * R.dlogtem, tdef = t2 - t1;
-    double kk[6];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-        const double *ka = R.k + (size_t)r * R.nratec;
-        kk[r] = ka[ix - 1] + (logtem - t1) * (ka[ix] - ka[ix - 1]) / tdef;
-    }
-    q.k1 = kk[0]; q.k2 = kk[1]; q.k3 = kk[2]; q.k4 = kk[3]; q.k5 = kk[4]; q.k6 = kk[5];
-
-    // bisection on the electron density, :3589-3633
-    double de1 = (double)1.e-30f, de2 = q.nh + 2. * q.nhe;
-    const bool tame = chem_tame(q, de1, de2);
-    double res1 = chem_residual(q, de1, HeI, tame);
-    double de = de2;
-    (void)chem_residual(q, de2, HeI, tame);
-    double HeIprev = -1.;
-    unsigned steps = 0;
-    while (fabs(HeI - HeIprev) / q.nhe > 1.e-10 && steps < 4096u) {
-        HeIprev = HeI;
-        de = 0.5 * (de1 + de2);
-        const double res = chem_residual(q, de, HeI, tame);
-        const bool opposite = (res > 0. && res1 < 0.) || (res < 0. && res1 > 0.); // :5044-5058
-        if (opposite) de2 = de;
-        else { de1 = de; res1 = res; }
-        ++steps;
-    }
-    const double X = q.k3 * de + q.kr26, Y = q.k4 * de;
-    HeII = HeI * X / Y;
-    const double HII = q.nh / (1. + q.k2 * de / (q.k1 * de + q.kr24));
-    HI = q.k2 * HII * de / (q.k1 * de + q.kr24);
-    // where the reference prints the species and stops, :3637-3654
-    const bool ok = (HI / q.nh >= 0. && HI / q.nh <= 1.) && (HeI / q.nhe >= 0. && HeI / q.nhe <= 1.) && steps < 4096u;
-    if (!ok) my_bad = (unsigned long long)c < my_bad ? (unsigned long long)c : my_bad;
-    else {
-        // the reference's (unused) convergence measure, :3671-3674
-        const double c1 = fabs(HI - HI0) * mh / (psi * rho), c2 = fabs(HeI - HeI0) * mhe / ((1. - psi) * rho),
-                     c3 = fabs(HeII - HeII0) * mhe / ((1. - psi) * rho);
-        const double change = fmax(c1, fmax(c2, c3));
-        const unsigned long long bits = (unsigned long long)__double_as_longlong(change); // non-negative doubles order like their bits
-        my_change = bits > my_change ? bits : my_change;
-        my_steps += (unsigned long long)steps;
-        R.HI_out[c] = HI; R.HeI_out[c] = HeI; R.HeII_out[c] = HeII;
-    }
-    }
-    // wavefront, then workgroup, then one atomic each
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long oc = __shfl_xor(my_change, off), os = __shfl_xor(my_steps, off), ob = __shfl_xor(my_bad, off);
-        my_change = oc > my_change ? oc : my_change;
-        my_steps += os;
-        my_bad = ob < my_bad ? ob : my_bad;
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { blk_change[wave] = my_change; blk_steps[wave] = my_steps; blk_bad[wave] = my_bad; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < 4; ++k) {
-            my_change = blk_change[k] > my_change ? blk_change[k] : my_change;
-            my_steps += blk_steps[k];
-            my_bad = blk_bad[k] < my_bad ? blk_bad[k] : my_bad;
-        }
-        if (my_bad != ~0ull) atomicMin(R.first_bad, my_bad);
-        if (my_change) atomicMax(R.max_change, my_change);
-        if (my_steps) atomicAdd(R.steps, my_steps);
-    }
-}
-
-// assignUvbRadiation, transportRoutinesModule.f90:1056-1093: the optically thin alternative to the sweep.  J_g = uvb_g where the
-// Lyman-limit mean free path of the cell is at least the self-shielding threshold, else 0.
-__global__ void __launch_bounds__(256) thin_limit_kernel(const double *__restrict__ HI, const double *__restrict__ HeI,
-                                                         const double *__restrict__ HeII, const double *__restrict__ rho,
-                                                         const double *__restrict__ uvb, double threshold, double *__restrict__ J,
-                                                         long ncell, int nnu)
-{
-    const long c = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (c >= ncell) return;
-    const double psi = (double)0.76f, mh = (double)1.6726231e-24f;
-    const double hi = fmin(HI[c], psi * rho[c] / mh);
-    const double mfp = 1. / (hi * (double)6.3e-18f + HeI[c] * (double)7.42e-18f + HeII[c] * (double)1.58e-18f);
-    const bool lit = mfp >= threshold;
-    for (int g = 0; g < nnu; ++g) J[(long)g * ncell + c] = lit ? uvb[g] : 0.0;
-}
-
-int launch_thin_limit(const double *HI, const double *HeI, const double *HeII, const double *rho, const double *uvb, double threshold,
-                      double *J, long ncell, int nnu, hipStream_t stream)
-{
-    hipLaunchKernelGGL(thin_limit_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, stream, HI, HeI, HeII, rho, uvb, threshold, J,
-                       ncell, nnu);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-int launch_rate_equations(const ChemRec &R, hipStream_t stream)
-{
-    if (R.ncell <= 0) return 0;
-    // (enough workgroups to fill the GPU several times over, few enough that their atomics are nothing)
-    const long blocks = (R.ncell + 255) / 256;
-    hipLaunchKernelGGL(rate_equations_kernel, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, stream, R);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-// ------------------------------------------------------------------------------------------------
-// The start-up ionisation equilibrium, initialIonizationEquilibrium (equiSources.f90:3679-3868), `passes` times per leaf
-// (the reference: twice, :1016), the next pass starting from the last one's HI, HeI, HeII -- in registers, since the routine
-// reads nothing outside its own cell.  The residual is solveRateEquations' (chem_residual_as, IEEE divisions throughout); what
-// differs from rate_equations_kernel is spelled out at each place.  R.krate, R.J, R.run_uvb are not used: the rates are the
-// uniform background's behind the self-shielding test alone (:3731-3743).
-// ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) initial_equilibrium_kernel(const ChemRec R)
-{
-    __shared__ unsigned long long blk_steps[4], blk_bad[4];
-    unsigned long long my_steps = 0ull, my_bad = ~0ull;
-    const double psi = (double)0.76f, mp = (double)1.6726231e-24f, mn = (double)1.67492728e-24f; // definitionsModule.f90:25-28, 261
-    const double mh = mp, mhe = 2. * (mp + mn), pi = (double)3.141592654f;
-    for (long c = (long)blockIdx.x * blockDim.x + threadIdx.x; c < R.ncell; c += (long)gridDim.x * blockDim.x) {
-    const double rho = R.rho[c];
-    ChemEq q;
-    q.nh = psi * rho / mh;
-    q.nhe = (1. - psi) * rho / mhe;
-    // rate coefficients at this temperature (:3747-3766): the same in every pass
-    double logtem = R.logtem[c];
-    logtem = fmax(logtem, R.logtem0);
-    logtem = fmin(logtem, R.logtem9);
-    int ix = (int)((logtem - R.logtem0) / R.dlogtem) + 1;
-    ix = ix < 1 ? 1 : ix;
-    ix = ix > R.nratec - 1 ? R.nratec - 1 : ix;
-    const double t1 = R.logtem0 + (double)(ix - 1) * R.dlogtem, t2 = R.logtem0 + (double)ix * R.dlogtem, tdef = t2 - t1;
-    double kk[6];
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-        const double *ka = R.k + (size_t)r * R.nratec;
-        kk[r] = ka[ix - 1] + (logtem - t1) * (ka[ix] - ka[ix - 1]) / tdef;
-    }
-    q.k1 = kk[0]; q.k2 = kk[1]; q.k3 = kk[2]; q.k4 = kk[3]; q.k5 = kk[4]; q.k6 = kk[5];
-
-    double cHI = R.HI[c], cHeI = R.HeI[c], cHeII = R.HeII[c]; // currentCell%HI, %HeI, %HeII on entry to the pass
-    bool ok = true;
-    for (int pass = 0; pass < R.passes && ok; ++pass) {
-        // :3710-3726.  HII is dead (de is reassigned before use).  Of the HeIII clip only this survives: currentCell%HeI and
-        // %HeII are overwritten at the end, so the local HeII = 0 of the inner branch is its one effect, and that branch tests
-        // the REASSIGNED currentCell%HeII = nhe - HeI0 (unlike :3504-3513)
-        double HI = fmin(cHI, q.nh), HeI = cHeI;
-        const double HeII = (q.nhe - cHeI - cHeII < 0. && q.nhe - cHeI < 0.) ? 0. : cHeII;
-        // uniform background only, behind the self-shielding test (:3731-3743); HI clipped, HeI unclipped
-        const double mfp = 1. / (HI * (double)6.3e-18f + HeI * (double)7.42e-18f + HeII * (double)1.58e-18f);
-        const bool lit = mfp >= R.threshold;
-        q.kr24 = lit ? 4. * pi * R.uniform[0] : 0.;
-        q.kr25 = lit ? 4. * pi * R.uniform[1] : 0.;
-        q.kr26 = lit ? 4. * pi * R.uniform[2] : 0.;
-        // bisection, :3771-3807: bracket from a default-real 1.e-20, res1 taken once at de1 and never updated, run until HeI
-        // stops changing at all
-        double de1 = (double)1.e-20f, de2 = q.nh + 2. * q.nhe;
-        double HX;
-        const double res1 = chem_residual_as<true>(q, de1, HeI, HX);
-        (void)chem_residual_as<true>(q, de2, HeI, HX);
-        double de = de2, HeIprev = -1.;
-        unsigned steps = 0;
-        while (HeI != HeIprev && steps < 4096u) { // (the reference loops forever on a NaN HeI: capped, and a failure)
-            HeIprev = HeI;
-            de = 0.5 * (de1 + de2);
-            const double res = chem_residual_as<true>(q, de, HeI, HX);
-            const bool opposite = (res > 0. && res1 < 0.) || (res < 0. && res1 > 0.); // :5044-5058
-            if (opposite) de2 = de;
-            else de1 = de;
-            ++steps;
-        }
-        my_steps += (unsigned long long)steps;
-        // :3808-3818: HIprev, HeIIprev are HI, HeII (unchanged inside the loop) once the loop has run, -1 if it has not
-        const double HIprev = steps ? HI : -1., HeIIprev = steps ? HeII : -1.;
-        const bool converged = HeI == HeIprev && !(HIprev != HI) && !(HeIIprev != HeII);
-        // :3820-3823
-        const double X = q.k3 * de + q.kr26, Y = q.k4 * de;
-        const double HII = q.nh / (1. + q.k2 * de / (q.k1 * de + q.kr24));
-        HI = q.k2 * HII * de / (q.k1 * de + q.kr24);
-        // :3832-3843
-        ok = converged && (HI / q.nh >= 0. && HI / q.nh <= 1.) && (HeI / q.nhe >= 0. && HeI / q.nhe <= 1.);
-        cHI = HI; cHeI = HeI; cHeII = HeI * X / Y;
-    }
-    if (!ok) my_bad = (unsigned long long)c < my_bad ? (unsigned long long)c : my_bad;
-    else { R.HI_out[c] = cHI; R.HeI_out[c] = cHeI; R.HeII_out[c] = cHeII; }
-    }
-    // wavefront, then workgroup, then one atomic each (as rate_equations_kernel)
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long os = __shfl_xor(my_steps, off), ob = __shfl_xor(my_bad, off);
-        my_steps += os;
-        my_bad = ob < my_bad ? ob : my_bad;
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { blk_steps[wave] = my_steps; blk_bad[wave] = my_bad; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < 4; ++k) {
-            my_steps += blk_steps[k];
-            my_bad = blk_bad[k] < my_bad ? blk_bad[k] : my_bad;
-        }
-        if (my_bad != ~0ull) atomicMin(R.first_bad, my_bad);
-        if (my_steps) atomicAdd(R.steps, my_steps);
-    }
-}
-
-int launch_initial_equilibrium(const ChemRec &R, hipStream_t stream)
-{
-    if (R.ncell <= 0) return 0;
-    if (R.passes < 1) return -1;
-    const long blocks = (R.ncell + 255) / 256;
-    hipLaunchKernelGGL(initial_equilibrium_kernel, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, stream, R);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-// computeMass (equiSources.f90:4369-4393) per leaf: HI mh cs3/msun and psi rho cs3/msun, cs3 the cube of the cell's size, each
-// term with the reference's operations in its order.  The sums are the code's own and deterministic: every thread adds its
-// cells in grid-stride order, the workgroup folds its 256 sums as a fixed tree, and mass_total_kernel adds the workgroups'
-// partial sums in a fixed order too.  No floating-point atomics.
-__device__ __forceinline__ void tree_sum_256(double *a, double *b)
-{
-    for (int w = 128; w > 0; w >>= 1) {
-        __syncthreads();
-        if ((int)threadIdx.x < w) { a[threadIdx.x] += a[threadIdx.x + w]; b[threadIdx.x] += b[threadIdx.x + w]; }
-    }
-    __syncthreads();
-}
-
-__global__ void __launch_bounds__(256) hydrogen_mass_kernel(const int8_t *__restrict__ level, const double *__restrict__ HI,
-                                                            const double *__restrict__ rho, long ncell, int n, double box,
-                                                            double *__restrict__ part)
-{
-    __shared__ double sn[256], st[256];
-    const double psi = (double)0.76f, mh = (double)1.6726231e-24f, msun = (double)1.98892e33f; // definitionsModule.f90:25-29, 261
-    double an = 0., at = 0.;
-    for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < ncell; c += (long)gridDim.x * 256) {
-        const double size = box / (double)((float)(1 << level[c]) * (float)n);
-        const double cs3 = size * size * size;
-        an += HI[c] * mh * cs3 / msun;
-        at += psi * rho[c] * cs3 / msun;
-    }
-    sn[threadIdx.x] = an; st[threadIdx.x] = at;
-    tree_sum_256(sn, st);
-    if (threadIdx.x == 0) { part[blockIdx.x] = sn[0]; part[kMassBlocks + blockIdx.x] = st[0]; }
-}
-
-__global__ void __launch_bounds__(256) mass_total_kernel(double *part, int nblocks)
-{
-    __shared__ double sn[256], st[256];
-    double an = 0., at = 0.;
-    for (int b = threadIdx.x; b < nblocks; b += 256) { an += part[b]; at += part[kMassBlocks + b]; }
-    sn[threadIdx.x] = an; st[threadIdx.x] = at;
-    tree_sum_256(sn, st);
-    if (threadIdx.x == 0) { part[2 * kMassBlocks] = sn[0]; part[2 * kMassBlocks + 1] = st[0]; }
-}
-
-int launch_hydrogen_mass(const int8_t *level, const double *HI, const double *rho, long ncell, int n, double box, double *part,
-                         hipStream_t stream)
-{
-    if (ncell < 1 || n < 1 || !part) return -1;
-    const long want = (ncell + 255) / 256;
-    const int blocks = (int)(want < kMassBlocks ? want : kMassBlocks);
-    hipLaunchKernelGGL(hydrogen_mass_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, level, HI, rho, ncell, n, box, part);
-    if (hipGetLastError() != hipSuccess) return -2;
-    hipLaunchKernelGGL(mass_total_kernel, dim3(1), dim3(256), 0, stream, part, blocks);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-// kappa[g][c] = HI[c]*beta[0][g] + HeI[c]*beta[1][g] + HeII[c]*beta[2][g]   (equiSources.f90:4977-4980)
-__global__ void __launch_bounds__(256) opacity_kernel(const double *__restrict__ HI, const double *__restrict__ HeI,
-                                                      const double *__restrict__ HeII, const double *__restrict__ beta,
-                                                      double *__restrict__ kappa, long ncell, int nnu)
-{
-    for (long c = (long)blockIdx.x * blockDim.x + threadIdx.x; c < ncell; c += (long)gridDim.x * blockDim.x) {
-        const double a = HI[c], b = HeI[c], d = HeII[c];
-        for (int g = 0; g < nnu; ++g) kappa[(long)g * ncell + c] = a * beta[g] + b * beta[nnu + g] + d * beta[2 * nnu + g];
-    }
-}
-
-int launch_opacity(const double *HI, const double *HeI, const double *HeII, const double *beta, double *kappa, long ncell,
-                   int nnu, hipStream_t stream)
-{
-    const int blocks = (int)((ncell + 255) / 256 < 8192 ? (ncell + 255) / 256 : 8192);
-    hipLaunchKernelGGL(opacity_kernel, dim3(blocks), dim3(256), 0, stream, HI, HeI, HeII, beta, kappa, ncell, nnu);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

@@ -25,6 +25,7 @@
 #define FTTE_MATH_H
 
 #if defined(__HIPCC__)
+#include <hip/hip_runtime.h> /* the qualifiers of FTTE_HD, for a file that has not included it yet */
 #define FTTE_HD __host__ __device__ __forceinline__
 #define FTTE_FMA(a, b, c) __builtin_fma((a), (b), (c))
 #define FTTE_RINT(a) __builtin_rint(a)
@@ -38,8 +39,10 @@
  * 2^-1022 <= |b| <= 2^1021 (b and 1/b normal), a is 0 or 2^-969 <= |a|, and the quotient is normal and below 2^767.
  * Outside that it is not IEEE's: a zero or subnormal b gives NaN (not +-inf), a quotient near the underflow can be
  * off in its last bits.  Callers keep their operands inside (the attenuation pair: 0.29 <= a <= 1, 0.34 <= b < 1e300,
- * lanes outside discard the result) or check them (chem_residual).  Same bits as the host's `/` there: checked by
- * the bitwise parity tests. */
+ * lanes outside discard the result) or check them (chem_residual, ftte_chem_math.h: chem_tame bounds every operand that
+ * depends on the rate coefficients to [2^-250, 2^250] over the cell's whole bracket, and the last numerator and a NaN are
+ * checked per evaluation; a wavefront with a lane outside takes IEEE division).  Same bits as the host's `/` there: checked
+ * by the bitwise parity tests. */
 __device__ __forceinline__ double ftte_div(double a, double b)
 {
     double y = __builtin_amdgcn_rcp(b);

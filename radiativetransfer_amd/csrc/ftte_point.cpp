@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstring>
 
+#include "ftte_chem_math.h"
 #include "ftte_geometry.h"
 #include "ftte_kernels.h"
 
@@ -20,7 +21,7 @@ const double kHydrogen = W(13.598), kHeI = W(24.587), kHeII = W(54.418); // defi
 inline double c_light() { return W(2.99792458e10); }
 inline double ev_to_erg() { return 1.60217646e-12; }
 inline double ev_to_hz() { return 1.60217646e-12 / W(6.6260693e-27); }
-inline double pi_ref() { return (double)3.141592654f; }
+inline double pi_ref() { return FTTE_PI; }
 
 inline double pow4(double x) { return x * x * x * x; }
 
@@ -91,9 +92,9 @@ void uvb_beta_table(int nfreq, double freqdel, const double *alpha, double *beta
     std::vector<double> nu(nfreq), s24(nfreq), s25(nfreq), s26(nfreq);
     for (int i = 0; i < nfreq; ++i) {
         nu[i] = std::pow(10.0, (double)i * freqdel);
-        s24[i] = nu[i] > kHydrogen ? hydrogenic(W(6.3e-18), kHydrogen, nu[i]) : 0.0;
-        s25[i] = nu[i] > kHeII ? hydrogenic(W(1.58e-18), kHeII, nu[i]) : 0.0;
-        s26[i] = nu[i] > kHeI ? W(7.42e-18) * (W(1.66) * std::pow(nu[i] / kHeI, (double)(-2.05f)) -
+        s24[i] = nu[i] > kHydrogen ? hydrogenic(FTTE_SIGMA_HI, kHydrogen, nu[i]) : 0.0;
+        s25[i] = nu[i] > kHeII ? hydrogenic(FTTE_SIGMA_HEII, kHeII, nu[i]) : 0.0;
+        s26[i] = nu[i] > kHeI ? FTTE_SIGMA_HEI * (W(1.66) * std::pow(nu[i] / kHeI, (double)(-2.05f)) -
                                                W(0.66) * std::pow(nu[i] / kHeI, (double)(-3.05f)))
                               : 0.0;
     }
@@ -134,9 +135,9 @@ void uniform_table(int nfreq, double freqdel, double alpha_quasar, double alpha_
     double prev = 0.0;
     for (int i = 0; i < nfreq; ++i) {
         const double nu = std::pow(10.0, (double)i * freqdel);
-        const double s24 = nu > kHydrogen ? hydrogenic(W(6.3e-18), kHydrogen, nu) : 0.0;
-        const double s25 = nu > kHeII ? hydrogenic(W(1.58e-18), kHeII, nu) : 0.0;
-        const double s26 = nu > kHeI ? W(7.42e-18) * (W(1.66) * std::pow(nu / kHeI, (double)(-2.05f)) - W(0.66) * std::pow(nu / kHeI, (double)(-3.05f)))
+        const double s24 = nu > kHydrogen ? hydrogenic(FTTE_SIGMA_HI, kHydrogen, nu) : 0.0;
+        const double s25 = nu > kHeII ? hydrogenic(FTTE_SIGMA_HEII, kHeII, nu) : 0.0;
+        const double s26 = nu > kHeI ? FTTE_SIGMA_HEI * (W(1.66) * std::pow(nu / kHeI, (double)(-2.05f)) - W(0.66) * std::pow(nu / kHeI, (double)(-3.05f)))
                                      : 0.0;
         if (i >= 1) { // uniformTable.f90:136-190
             const double delta_nu = nu - prev;
@@ -243,9 +244,9 @@ void frequency_grid(const double *a_smc, FrequencyGrid &G)
         G.nu[i] = std::pow(10.0, (double)i * freqdel);
         const double lambda = c_light() / (G.nu[i] * ev_to_hz()) * W(1.e8); // Angstrom
         G.sd[i] = dust_cross_section(lambda / W(1.e4), a_smc) * W(1.e-22);
-        G.s24[i] = G.nu[i] > kHydrogen ? hydrogenic(W(6.3e-18), kHydrogen, G.nu[i]) : 0.0;
-        G.s25[i] = G.nu[i] > kHeII ? hydrogenic(W(1.58e-18), kHeII, G.nu[i]) : 0.0;
-        G.s26[i] = G.nu[i] > kHeI ? W(7.42e-18) * (W(1.66) * std::pow(G.nu[i] / kHeI, (double)(-2.05f)) -
+        G.s24[i] = G.nu[i] > kHydrogen ? hydrogenic(FTTE_SIGMA_HI, kHydrogen, G.nu[i]) : 0.0;
+        G.s25[i] = G.nu[i] > kHeII ? hydrogenic(FTTE_SIGMA_HEII, kHeII, G.nu[i]) : 0.0;
+        G.s26[i] = G.nu[i] > kHeI ? FTTE_SIGMA_HEI * (W(1.66) * std::pow(G.nu[i] / kHeI, (double)(-2.05f)) -
                                                    W(0.66) * std::pow(G.nu[i] / kHeI, (double)(-3.05f)))
                                   : 0.0;
     }
@@ -263,9 +264,9 @@ double population_bins(const FrequencyGrid &G, const double *spec, int nmetal, i
         FreqBin &B = bins[i - 1];
         B.dtmp = lum / (freq * ev_to_erg()) * delta_nu * ev_to_hz();
         if (freq >= kHydrogen) total = total + B.dtmp;
-        B.r24 = G.s24[i] / W(6.3e-18);
-        B.r26 = G.s26[i] / W(7.42e-18);
-        B.r25 = G.s25[i] / W(1.58e-18);
+        B.r24 = G.s24[i] / FTTE_SIGMA_HI;
+        B.r26 = G.s26[i] / FTTE_SIGMA_HEI;
+        B.r25 = G.s25[i] / FTTE_SIGMA_HEII;
         B.rdust = G.sd[i] / W(5.4116737e-22);
         for (int r = 0; r < 3; ++r) B.excess[r] = freq >= thr[r] ? (freq - thr[r]) * ev_to_erg() : -1.0;
     }
@@ -283,9 +284,9 @@ int output_sigma(PointState &P, hipStream_t stream, const double *a_smc, std::st
         const double freq = lower * std::exp((double)((float)(ie - 1) / (float)(kOutputEnergies - 1)) * (std::log(upper) - std::log(lower)));
         const double lambda = c_light() / (freq * ev_to_hz()) * W(1.e8);
         sigma[3 * kOutputEnergies + ie - 1] = dust_cross_section(lambda / W(1.e4), a_smc) * W(1.e-22);
-        sigma[0 * kOutputEnergies + ie - 1] = freq > kHydrogen ? hydrogenic(W(6.3e-18), kHydrogen, freq) : freq == kHydrogen ? W(6.3e-18) : 0.0;
-        sigma[1 * kOutputEnergies + ie - 1] = freq > kHeII ? hydrogenic(W(1.58e-18), kHeII, freq) : 0.0;
-        sigma[2 * kOutputEnergies + ie - 1] = freq > kHeI ? W(7.42e-18) * (W(1.66) * std::pow(freq / kHeI, (double)(-2.05f)) -
+        sigma[0 * kOutputEnergies + ie - 1] = freq > kHydrogen ? hydrogenic(FTTE_SIGMA_HI, kHydrogen, freq) : freq == kHydrogen ? FTTE_SIGMA_HI : 0.0;
+        sigma[1 * kOutputEnergies + ie - 1] = freq > kHeII ? hydrogenic(FTTE_SIGMA_HEII, kHeII, freq) : 0.0;
+        sigma[2 * kOutputEnergies + ie - 1] = freq > kHeI ? FTTE_SIGMA_HEI * (W(1.66) * std::pow(freq / kHeI, (double)(-2.05f)) -
                                                                            W(0.66) * std::pow(freq / kHeI, (double)(-3.05f)))
                                                           : 0.0;
     }
@@ -391,7 +392,7 @@ int point_set_output_sigma(PointState &P, hipStream_t stream, const double *sigm
 {
     // the tracer multiplies the threshold depths by sigma(E) / sigma(threshold), :3216-3219
     double ratio[4 * kOutputEnergies];
-    const double thr[4] = {W(6.30e-18), W(1.58e-18), W(7.42e-18), W(5.4116737e-22)};
+    const double thr[4] = {FTTE_SIGMA_HI, FTTE_SIGMA_HEII, FTTE_SIGMA_HEI, W(5.4116737e-22)};
     for (int q = 0; q < 4; ++q)
         for (int ie = 0; ie < kOutputEnergies; ++ie) ratio[q * kOutputEnergies + ie] = sigma[q * kOutputEnergies + ie] / thr[q];
     POINT_HIP(P.sigma_ratio.reserve((size_t)4 * kOutputEnergies));

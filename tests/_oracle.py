@@ -23,7 +23,7 @@ class Pattern(C.Structure):
 
 def build():
     src = [os.path.join(ORACLE_DIR, f) for f in ("ftte_oracle.c", "ftte_oracle_point.c", "ftte_oracle.h")]
-    src.append(os.path.join(ROOT, "radiativetransfer_amd", "csrc", "ftte_math.h"))
+    src += [os.path.join(ROOT, "radiativetransfer_amd", "csrc", f) for f in ("ftte_math.h", "ftte_chem_math.h")]
     if not os.path.exists(LIB) or any(os.path.getmtime(s) > os.path.getmtime(LIB) for s in src):
         subprocess.check_call(["make", "-C", ORACLE_DIR, "-B", "libftte_oracle.so"], stdout=subprocess.DEVNULL)
 
@@ -323,27 +323,62 @@ def point_sources(n, level, HI, HeI, HeII, rho, abun2, box, dust, src_leaf, src_
     return rates, hp.value
 
 
-def solve_rate_equations(n, level, box, rho, tgas, HI, HeI, HeII, krate, run_uvb, J, ksi, uniform, threshold, logtem0, logtem9,
-                         dlogtem, k):
-    """fo_solve_rate_equations: returns (HI, HeI, HeII, status, bisection steps); status 0 or 1 + first stopping cell."""
+def _rate_equation_call(name, restype, tail, n, level, box, rho, tgas, HI, HeI, HeII, krate, run_uvb, J, ksi, uniform, threshold, logtem0,
+                        logtem9, dlogtem, k):
+    """fo_solve_rate_equations' argument list in front of `tail` (ctypes type, value), for it and for the fo_device_ pair"""
     level = np.ascontiguousarray(level, dtype=np.int32)
-    nc = len(level)
     rho, tgas, k = _f64(rho), _f64(tgas), _f64(k)
-    HI, HeI, HeII = (np.array(a, dtype=np.float64, copy=True) for a in (HI, HeI, HeII))
     krate = None if krate is None else _f64(krate)
     J = None if J is None else _f64(J)
     ksi = _f64(ksi if ksi is not None else np.zeros(9))
     uniform = _f64(uniform if uniform is not None else np.zeros(3))
-    L = lib()
     dp = C.POINTER(C.c_double)
-    L.fo_solve_rate_equations.restype = C.c_long
-    L.fo_solve_rate_equations.argtypes = [C.c_int, C.c_long, C.POINTER(C.c_int32), C.c_double, dp, dp, dp, dp, dp, dp, C.c_int, dp, dp, dp,
-                                          C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, dp, C.POINTER(C.c_long)]
+    fn = getattr(lib(), name)
+    fn.restype = restype
+    fn.argtypes = [C.c_int, C.c_long, C.POINTER(C.c_int32), C.c_double, dp, dp, dp, dp, dp, dp, C.c_int, dp, dp, dp, C.c_double, C.c_int,
+                   C.c_double, C.c_double, C.c_double, dp, tail[0]]
+    return fn(n, len(level), level.ctypes.data_as(C.POINTER(C.c_int32)), box, _dp(rho), _dp(tgas), _dp(HI), _dp(HeI), _dp(HeII),
+              _dp(krate) if krate is not None else None, int(run_uvb), _dp(J) if J is not None else None, _dp(ksi), _dp(uniform),
+              float(threshold), k.shape[1], float(logtem0), float(logtem9), float(dlogtem), _dp(k), tail[1])
+
+
+def solve_rate_equations(n, level, box, rho, tgas, HI, HeI, HeII, krate, run_uvb, J, ksi, uniform, threshold, logtem0, logtem9,
+                         dlogtem, k, name="fo_solve_rate_equations"):
+    """fo_solve_rate_equations: returns (HI, HeI, HeII, status, bisection steps); status 0 or 1 + first stopping cell."""
+    HI, HeI, HeII = (np.array(a, dtype=np.float64, copy=True) for a in (HI, HeI, HeII))
     its = C.c_long()
-    st = L.fo_solve_rate_equations(n, nc, level.ctypes.data_as(C.POINTER(C.c_int32)), box, _dp(rho), _dp(tgas), _dp(HI), _dp(HeI), _dp(HeII),
-                                   _dp(krate) if krate is not None else None, int(run_uvb), _dp(J) if J is not None else None, _dp(ksi),
-                                   _dp(uniform), float(threshold), k.shape[1], float(logtem0), float(logtem9), float(dlogtem), _dp(k),
-                                   C.byref(its))
+    st = _rate_equation_call(name, C.c_long, (C.POINTER(C.c_long), C.byref(its)), n, level, box, rho, tgas, HI, HeI, HeII, krate, run_uvb,
+                             J, ksi, uniform, threshold, logtem0, logtem9, dlogtem, k)
+    return HI, HeI, HeII, int(st), its.value
+
+
+def device_solve_rate_equations(*args):
+    """fo_device_solve_rate_equations, csrc/ftte_chem_math.h on the host: arguments and return as solve_rate_equations; the cells
+    at which the reference stops keep their species, the steps are those of the cells that pass (what the kernel counts)."""
+    return solve_rate_equations(*args, name="fo_device_solve_rate_equations")
+
+
+def device_chem_tame(n, level, box, rho, tgas, HI, HeI, HeII, *rest):
+    """fo_device_chem_tame: per cell, whether the kernel takes its residuals through the trimmed division; arguments as
+    solve_rate_equations."""
+    tame = np.empty(len(level), np.int32)
+    _rate_equation_call("fo_device_chem_tame", None, (C.POINTER(C.c_int32), tame.ctypes.data_as(C.POINTER(C.c_int32))), n, level, box, rho,
+                        tgas, _f64(HI), _f64(HeI), _f64(HeII), *rest)
+    return tame.astype(bool)
+
+
+def device_initial_equilibrium(rho, tgas, HI, HeI, HeII, uniform, threshold, logtem0, logtem9, dlogtem, k, passes=2):
+    """fo_device_initial_equilibrium: (HI, HeI, HeII, status, bisection steps of all passes); arguments as
+    _initial_equilibrium.initial_equilibrium."""
+    rho, tgas, k, uniform = _f64(rho), _f64(tgas), _f64(k), _f64(uniform)
+    HI, HeI, HeII = (np.array(a, dtype=np.float64, copy=True) for a in (HI, HeI, HeII))
+    dp = C.POINTER(C.c_double)
+    fn = lib().fo_device_initial_equilibrium
+    fn.restype = C.c_long
+    fn.argtypes = [C.c_long, dp, dp, dp, dp, dp, dp, C.c_double, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, dp, C.POINTER(C.c_long)]
+    its = C.c_long()
+    st = fn(rho.size, _dp(rho), _dp(tgas), _dp(HI), _dp(HeI), _dp(HeII), _dp(uniform), float(threshold), int(passes), k.shape[1],
+            float(logtem0), float(logtem9), float(dlogtem), _dp(k), C.byref(its))
     return HI, HeI, HeII, int(st), its.value
 
 
