@@ -394,6 +394,108 @@ module ftte_binding
        real(c_double), intent(out) :: rho(*)
      end function ftte_get_density
 
+     ! ---- analysis of the device-resident medium: the reader's slice map (readCellArray.f90:116-140), the projection of mode
+     ! initialConfiguration (equiSources.f90:678-719), mode clumpingFactor (:661-676) and the PDFs of mode plotPDFs (:785-836)
+     ! i0 and xnew of equiSources.f90:703-709 for the columns (or rows) of a projected map (host, no context)
+     integer(c_int) function ftte_map_axis(n, nmap, centre, zoom, base, frac) bind(C, name='ftte_map_axis')
+       import :: c_int, c_int32_t, c_double
+       integer(c_int), value :: n, nmap
+       real(c_double), value :: centre, zoom
+       integer(c_int32_t), intent(out) :: base(*)
+       real(c_double), intent(out) :: frac(*)
+     end function ftte_map_axis
+
+     ! the same for the reader's loops, readCellArray.f90:126-132 (host, no context)
+     integer(c_int) function ftte_slice_axis(n, nmap, centre, zoom, base, frac) bind(C, name='ftte_slice_axis')
+       import :: c_int, c_int32_t, c_double
+       integer(c_int), value :: n, nmap
+       real(c_double), value :: centre, zoom
+       integer(c_int32_t), intent(out) :: base(*)
+       real(c_double), intent(out) :: frac(*)
+     end function ftte_slice_axis
+
+     ! kstart and kend of equiSources.f90:687-700 (host, no context)
+     integer(c_int) function ftte_map_depth(n, centre, zoom, kstart, kend) bind(C, name='ftte_map_depth')
+       import :: c_int, c_int32_t, c_double
+       integer(c_int), value :: n
+       real(c_double), value :: centre, zoom
+       integer(c_int32_t), intent(out) :: kstart, kend
+     end function ftte_map_depth
+
+     ! value: c_null_ptr (HI of the medium for a slice, abun2 for a projection) or c_loc of value(ncell); centre(2) / centre(3)
+     integer(c_int) function ftte_slice_map(ctx, izone, nxmap, nymap, centre, zoom, zslice, value, map) &
+          bind(C, name='ftte_slice_map')
+       import :: c_ptr, c_int, c_double, c_float
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: izone, nxmap, nymap
+       real(c_double), intent(in) :: centre(*)
+       real(c_double), value :: zoom
+       real(c_double), value :: zslice
+       type(c_ptr), value :: value           ! host array
+       real(c_float), intent(out) :: map(*)  ! mapArray(nxmap,nymap)
+     end function ftte_slice_map
+
+     integer(c_int) function ftte_slice_map_device(ctx, izone, nxmap, nymap, centre, zoom, zslice, value, map) &
+          bind(C, name='ftte_slice_map_device')
+       import :: c_ptr, c_int, c_double, c_float
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: izone, nxmap, nymap
+       real(c_double), intent(in) :: centre(*)
+       real(c_double), value :: zoom
+       real(c_double), value :: zslice
+       type(c_ptr), value :: value           ! device array
+       real(c_float), intent(out) :: map(*)  ! mapArray(nxmap,nymap)
+     end function ftte_slice_map_device
+
+     ! mode 0: the reference's mass-weighted mean; 1: the path integral sum value * leaf size [cm] (not in the reference)
+     integer(c_int) function ftte_project_map(ctx, izone, nxmap, nymap, centre, zoom, mode, value, map) &
+          bind(C, name='ftte_project_map')
+       import :: c_ptr, c_int, c_double, c_float
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: izone, nxmap, nymap
+       real(c_double), intent(in) :: centre(*)
+       real(c_double), value :: zoom
+       integer(c_int), value :: mode
+       type(c_ptr), value :: value           ! host array
+       real(c_float), intent(out) :: map(*)  ! mapArray(nxmap,nymap)
+     end function ftte_project_map
+
+     integer(c_int) function ftte_project_map_device(ctx, izone, nxmap, nymap, centre, zoom, mode, value, map) &
+          bind(C, name='ftte_project_map_device')
+       import :: c_ptr, c_int, c_double, c_float
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: izone, nxmap, nymap
+       real(c_double), intent(in) :: centre(*)
+       real(c_double), value :: zoom
+       integer(c_int), value :: mode
+       type(c_ptr), value :: value           ! device array
+       real(c_float), intent(out) :: map(*)  ! mapArray(nxmap,nymap)
+     end function ftte_project_map_device
+
+     ! equiSources.f90:661-676: clumping = volSumDensity2 / volSumDensity**2 after the division by volume = volSum
+     integer(c_int) function ftte_clumping(ctx, clumping, volume, mean_nh) bind(C, name='ftte_clumping')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       real(c_double), intent(out) :: clumping, volume, mean_nh
+     end function ftte_clumping
+
+     ! pdfGas(npdf) and pdfGasOutside, equiSources.f90:814-822
+     integer(c_int) function ftte_gas_pdf(ctx, pdf, outside) bind(C, name='ftte_gas_pdf')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       real(c_double), intent(out) :: pdf(50), outside
+     end function ftte_gas_pdf
+
+     ! pdfStar(npdf), pdfStarOutside and meanHostDensity/float(nStarsSpecificAge), :787-813; src_cell(nsrc) from ftte_locate_cell
+     integer(c_int) function ftte_star_pdf(ctx, nsrc, src_cell, pdf, outside, mean_host_HI) bind(C, name='ftte_star_pdf')
+       import :: c_ptr, c_int, c_int32_t, c_int64_t, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: nsrc
+       integer(c_int64_t), intent(in) :: src_cell(*)
+       integer(c_int32_t), intent(out) :: pdf(50), outside
+       real(c_double), intent(out) :: mean_host_HI
+     end function ftte_star_pdf
+
      integer(c_int) function ftte_compute_opacities(ctx, nnu, beta) bind(C, name='ftte_compute_opacities')
        import :: c_ptr, c_int, c_double
        type(c_ptr), value :: ctx

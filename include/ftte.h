@@ -400,6 +400,62 @@ int ftte_cellarray_fields(const ftte_cellarray *a, int32_t *level, double *HI, d
                           double *velx, double *vely, double *velz, double *abun2);
 void ftte_cellarray_free(ftte_cellarray *a);
 
+/* ---- analysis: how the reference looks at a result, on the device-resident medium ------------------
+ * Each call reads the medium's fields and the tree where they are (no copy is kept, so a map made after ftte_set_medium, an
+ * equilibrium update or ftte_expand_hii_regions shows the new medium) and needs a single-device context; a multi-device context
+ * never holds a medium (ftte_set_medium is refused on it), so all of them return FTTE_ERR_UNSUPPORTED there.
+ * What they keep on the device belongs to the context, is released by ftte_set_grid with another grid and counts in
+ * ftte_counter("device_objects").  Refusals: FTTE_ERR_IZONE for izone outside 1..24; FTTE_ERR_ARG for non-positive map sizes,
+ * zoom <= 0, zslice outside [0, 1) or a window whose pixels leave the box (the reference indexes out of bounds there);
+ * FTTE_ERR_STATE without a medium (ftte_set_medium), for the projection and the censuses without its density.
+ *
+ * Maps.  map[i + nxmap*j], i = 0..nxmap-1, is the reference's mapArray(nxmap,nymap): pixel i+1 along the sweep frame's first
+ * axis, j+1 along its second; izone turns the sweep frame into storage as rotateIndices does (ftte_rotate_indices), for base
+ * cells and for the children of a refined cell (the is/js/ks arrays of equiSources.f90:690-696).  The window is
+ * [start, end] = [max(centre - 0.5/zoom, 0), min(start + 1/zoom, 1)] on each map axis (:685-689). */
+
+/* The per-column (or per-row) quantities of the driver's pixel loops, equiSources.f90:703-709: base[i-1] = i0 (1-based base
+ * cell) and frac[i-1] = xnew (position inside it) for x0 = (end-start)*(float(i)-0.5)/float(nmap) + start, evaluated left to
+ * right in double as the compiled line is.  Context-free, host only.  FTTE_ERR_ARG where an i0 would leave 1..n. */
+int ftte_map_axis(int n, int nmap, double centre, double zoom, int32_t *base /*[nmap]*/, double *frac /*[nmap]*/);
+/* The same for the reader's loops, readCellArray.f90:126-132, whose x0 is the single-precision quotient (float(i)-0.5)/float(nmap)
+ * widened: x0 = (end-start)*quotient + start, which is the reader's own x0 for the whole box (centre 0.5, zoom 1; the reader
+ * has no window).  It differs from ftte_map_axis in the last bits of xnew. */
+int ftte_slice_axis(int n, int nmap, double centre, double zoom, int32_t *base /*[nmap]*/, double *frac /*[nmap]*/);
+/* kstart and kend of the projection, :687-700: the base cells (1-based, inclusive) between max(centre - 0.5/zoom, 0) and
+ * min(centre + 0.5/zoom, 1), clamped to 1..n. */
+int ftte_map_depth(int n, double centre, double zoom, int32_t *kstart, int32_t *kend);
+
+/* The slice map of the reader tool, readCellArray.f90:116-140 with sliceCell :189-230: every pixel is the value of the leaf that
+ * holds (x0, y0, zslice), rounded to float32.  value[ncell] (host; _device: any device array of ncell doubles, e.g. one group of
+ * a swept J or one plane of ftte_point_rates_device); NULL = HI of the medium, as in the reference.  Axes: ftte_slice_axis. */
+int ftte_slice_map(ftte_ctx *ctx, int izone, int nxmap, int nymap, const double centre[2], double zoom, double zslice,
+                   const double *value, float *map);
+int ftte_slice_map_device(ftte_ctx *ctx, int izone, int nxmap, int nymap, const double centre[2], double zoom, double zslice,
+                          const double *value_dev, float *map);
+/* mode 0: the projection of mode initialConfiguration, equiSources.f90:678-719 with projectVariableToMap :4914-4954 (the
+ * reference: izone 3, 1024^2, centre (.5,.5,.5), zoom 2): per pixel the leaves of base cells kstart..kend along the depth, both
+ * depth children of every refined cell, accumulated as :4948-4950 -- a float32 pixel, widened and rounded for every leaf, a
+ * double totalMass -- and divided at the end; a column of rho = 0 gives NaN, as there.  value NULL = abun2 of the medium.
+ * mode 1 is NOT in the reference; it is this build's own definition: the path integral sum value * leaf size [cm] over the same
+ * leaves in the same order (a column density where value is a number density), summed in double and rounded to float32 once.
+ * Axes: ftte_map_axis and ftte_map_depth. */
+int ftte_project_map(ftte_ctx *ctx, int izone, int nxmap, int nymap, const double centre[3], double zoom, int mode,
+                     const double *value, float *map);
+int ftte_project_map_device(ftte_ctx *ctx, int izone, int nxmap, int nymap, const double centre[3], double zoom, int mode,
+                            const double *value_dev, float *map);
+/* mode clumpingFactor, equiSources.f90:661-676 with computeClumping :4711-4735: volume = volSum, mean_nh = volSumDensity/volSum,
+ * clumping = (volSumDensity2/volSum) / mean_nh**2, nh = psi*rho/mh.  The sums are the library's own fixed-order sums (as
+ * ftte_hydrogen_mass): the same bits on every call, the reference's sequential sums to rounding.  Any output may be NULL. */
+int ftte_clumping(ftte_ctx *ctx, double *clumping, double *volume, double *mean_nh);
+/* pdfGas and pdfGasOutside of mode plotPDFs, equiSources.f90:814-822 with computeGasPDF :4682-4709: the volume (base cells) of
+ * the leaves in each of the 50 bins of log10(rho/msun*pc**3) between -8 and 3, and of those outside (rho = 0 among them).
+ * Counted as integers per bin and level on the device and weighed on the host, which is exact. */
+int ftte_gas_pdf(ftte_ctx *ctx, double pdf[50], double *outside);
+/* pdfStar, pdfStarOutside and meanHostDensity/float(nStarsSpecificAge) of :787-813 for the stars with weight > 0, which arrive as
+ * their host leaves (ftte_locate_cell), as they do for the tracer: a gather of nsrc leaves.  mean_host_HI may be NULL. */
+int ftte_star_pdf(ftte_ctx *ctx, int nsrc, const int64_t *src_cell, int32_t pdf[50], int32_t *outside, double *mean_host_HI);
+
 /* ---- host arrays ------------------------------------------------------------------------------
  * The reference keeps its fields in host memory (the zoneType tree, definitionsModule.f90:163-180); the drop-ins
  * flatten them into cell-array order and hand them over.  Pageable arrays cross PCIe through pinned staging blocks

@@ -85,6 +85,16 @@ SIGNATURES = {
     "ftte_expansion_parameters": (C.c_int, [C.c_double, _dp, _dp]),
     "ftte_expand_hii_regions": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int64), _dp, _dp, C.POINTER(C.c_int64)]),
     "ftte_get_density": (C.c_int, [_vp, _dp]),
+    "ftte_map_axis": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_int32), _dp]),
+    "ftte_slice_axis": (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_int32), _dp]),
+    "ftte_map_depth": (C.c_int, [C.c_int, C.c_double, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "ftte_slice_map": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, C.c_double, C.c_double, _dp, C.POINTER(C.c_float)]),
+    "ftte_slice_map_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, C.c_double, C.c_double, _vp, C.POINTER(C.c_float)]),
+    "ftte_project_map": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, C.c_double, C.c_int, _dp, C.POINTER(C.c_float)]),
+    "ftte_project_map_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, C.c_double, C.c_int, _vp, C.POINTER(C.c_float)]),
+    "ftte_clumping": (C.c_int, [_vp, _dp, _dp, _dp]),
+    "ftte_gas_pdf": (C.c_int, [_vp, _dp, _dp]),
+    "ftte_star_pdf": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp]),
     "ftte_point_ray_steps": (C.c_longlong, [_vp]),
     "ftte_rmax": (C.c_int, [_dp]),
     "ftte_uvb_beta_table": (C.c_int, [C.c_int, C.c_double, _dp, _dp, _dp, _dp]),

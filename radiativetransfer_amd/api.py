@@ -17,7 +17,7 @@ from . import _lib
 from ._lib import FtteError, Pattern
 
 __all__ = ["DiffuseTransfer", "StellarTransfer", "rmax", "dust_cross_section", "uvb_beta_table", "uniform_table", "coll_rates", "rate_coefficient_tables", "FtteError", "Pattern", "pix2ang_nest", "healpix_directions", "fold_direction",
-           "rotate_indices", "set_pattern", "layer_patterns", "compute_cell_intensity", "expansion_parameters"]
+           "rotate_indices", "set_pattern", "layer_patterns", "compute_cell_intensity", "expansion_parameters", "map_axis", "slice_axis", "map_depth"]
 
 
 def _f64(a) -> np.ndarray:
@@ -41,6 +41,30 @@ def rotate_indices(i: int, j: int, k: int, nx: int, ny: int, nz: int, izone: int
     _check(_lib.load().ftte_rotate_indices(i, j, k, nx, ny, nz, izone, C.byref(a), C.byref(b), C.byref(c)),
            f"izone {izone} outside 1..24")
     return a.value, b.value, c.value
+
+
+def _axis(fn, n: int, nmap: int, centre: float, zoom: float):
+    base, frac = np.empty(max(nmap, 1), dtype=np.int32), np.empty(max(nmap, 1))
+    _check(fn(int(n), int(nmap), float(centre), float(zoom), base.ctypes.data_as(C.POINTER(C.c_int32)), _dp(frac)),
+           f"bad map axis: n {n}, nmap {nmap}, centre {centre}, zoom {zoom}")
+    return base, frac
+
+
+def map_axis(n: int, nmap: int, centre: float = 0.5, zoom: float = 1.0):
+    """(i0[nmap] 1-based, xnew[nmap]) of the projection's pixel loops (equiSources.f90:703-709); host, no context."""
+    return _axis(_lib.load().ftte_map_axis, n, nmap, centre, zoom)
+
+
+def slice_axis(n: int, nmap: int, centre: float = 0.5, zoom: float = 1.0):
+    """(i0[nmap] 1-based, xnew[nmap]) of the reader's pixel loops (readCellArray.f90:126-132) inside a window; host, no context."""
+    return _axis(_lib.load().ftte_slice_axis, n, nmap, centre, zoom)
+
+
+def map_depth(n: int, centre: float = 0.5, zoom: float = 1.0) -> Tuple[int, int]:
+    """(kstart, kend) of the projection (equiSources.f90:687-700), 1-based and inclusive; host, no context."""
+    a, b = C.c_int32(), C.c_int32()
+    _check(_lib.load().ftte_map_depth(int(n), float(centre), float(zoom), C.byref(a), C.byref(b)), f"bad map depth: n {n}, centre {centre}, zoom {zoom}")
+    return a.value, b.value
 
 
 def pix2ang_nest(nside: int, ipix: int) -> Tuple[float, float]:
@@ -622,6 +646,61 @@ class StellarTransfer(DiffuseTransfer):
         out = np.empty(max(self.ncell, 1))
         self._ok(self._lib.ftte_get_density(self._ctx, _dp(out)))
         return out
+
+    # -- analysis: the reference's ways of looking at a result (readCellArray.f90:116-140; equiSources.f90:661-731, :785-836)
+    def _map(self, host_fn, device_fn, izone, shape, centre, zoom, extra, value, value_device_ptr):
+        nxmap, nymap = int(shape[0]), int(shape[1])
+        out = np.empty((max(nymap, 1), max(nxmap, 1)), dtype=np.float32)  # the reference's mapArray(nxmap,nymap) as it lies in memory
+        centre = _f64(centre).reshape(-1)
+        args = (self._ctx, int(izone), nxmap, nymap, _dp(centre), float(zoom), extra)
+        mp = out.ctypes.data_as(C.POINTER(C.c_float))
+        if value_device_ptr is not None:
+            self._ok(device_fn(*args, C.c_void_p(int(value_device_ptr)), mp))
+        else:
+            if value is not None:
+                value = _f64(value).reshape(-1)
+                if value.size != self.ncell:
+                    raise ValueError("value must have one entry per leaf")
+            self._ok(host_fn(*args, None if value is None else _dp(value), mp))
+        return out.T  # [nxmap][nymap]: map[i, j] is mapArray(i+1, j+1)
+
+    def slice_map(self, izone: int, shape, zslice: float, centre=(0.5, 0.5), zoom: float = 1.0, value=None,
+                  value_device_ptr: Optional[int] = None) -> np.ndarray:
+        """The reader's slice map (readCellArray.f90:116-140): float32 [nxmap][nymap], pixel = the value of the leaf at
+        (x0, y0, zslice) of izone's sweep frame.  value[ncell] (or a device array); None = HI of the medium."""
+        if len(centre) != 2:
+            raise ValueError("centre must have two entries")
+        return self._map(self._lib.ftte_slice_map, self._lib.ftte_slice_map_device, izone, shape, centre, zoom, float(zslice), value,
+                         value_device_ptr)
+
+    def project_map(self, izone: int, shape, centre=(0.5, 0.5, 0.5), zoom: float = 1.0, mode: int = 0, value=None,
+                    value_device_ptr: Optional[int] = None) -> np.ndarray:
+        """mode 0: the mass-weighted projection of mode initialConfiguration (equiSources.f90:678-719), float32 [nxmap][nymap];
+        mode 1 (not in the reference): the path integral sum value * leaf size [cm].  None = abun2 of the medium."""
+        if len(centre) != 3:
+            raise ValueError("centre must have three entries")
+        return self._map(self._lib.ftte_project_map, self._lib.ftte_project_map_device, izone, shape, centre, zoom, int(mode), value,
+                         value_device_ptr)
+
+    def clumping(self) -> dict:
+        """mode clumpingFactor (equiSources.f90:661-676): clumping, volume (volSum) and mean_nh (volSumDensity/volSum)."""
+        a, b, d = C.c_double(), C.c_double(), C.c_double()
+        self._ok(self._lib.ftte_clumping(self._ctx, C.byref(a), C.byref(b), C.byref(d)))
+        return dict(clumping=a.value, volume=b.value, mean_nh=d.value)
+
+    def gas_pdf(self) -> Tuple[np.ndarray, float]:
+        """(pdfGas[50], pdfGasOutside) of mode plotPDFs (equiSources.f90:814-822)."""
+        pdf, outside = np.empty(50), C.c_double()
+        self._ok(self._lib.ftte_gas_pdf(self._ctx, _dp(pdf), C.byref(outside)))
+        return pdf, outside.value
+
+    def star_pdf(self, src_cells) -> Tuple[np.ndarray, int, float]:
+        """(pdfStar[50], pdfStarOutside, mean HI of the host leaves) of :787-813; src_cells: the stars' host leaves."""
+        cells = np.ascontiguousarray(src_cells, dtype=np.int64).reshape(-1)
+        pdf, outside, mean = np.zeros(50, dtype=np.int32), C.c_int32(), C.c_double()
+        self._ok(self._lib.ftte_star_pdf(self._ctx, cells.size, cells.ctypes.data_as(C.POINTER(C.c_int64)),
+                                         pdf.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(outside), C.byref(mean)))
+        return pdf, outside.value, mean.value
 
 
 expansion_parameters = StellarTransfer.expansion_parameters

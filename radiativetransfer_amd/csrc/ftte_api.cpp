@@ -119,6 +119,7 @@ int ftte_set_grid(ftte_ctx *c, int nx, int ny, int nz, int64_t ncell, const int3
     c->gas.drop();
     c->point.drop_grid();
     c->chem.drop_grid();
+    c->analysis.drop_grid();
     c->leaf_level.assign(level, level + ncell);
     c->n = nx; c->ncell = ncell; c->box = box_cm; c->grid_set = true;
     c->kappa.invalidate();

@@ -7,7 +7,7 @@
 
 using namespace ftte;
 
-namespace {
+namespace ftte {
 
 // the leaves' levels on the device: uploaded on first use after ftte_set_grid
 int ensure_level(ftte_ctx *c)
@@ -17,6 +17,10 @@ int ensure_level(ftte_ctx *c)
     FTTE_HIP(c, hipMemcpyAsync(c->chem.level, c->leaf_level.data(), (size_t)c->ncell, hipMemcpyHostToDevice, c->stream));
     return FTTE_OK;
 }
+
+} // namespace ftte
+
+namespace {
 
 // What an update of the species has of its own, beside its arguments
 struct ChemUpdate {

@@ -7,6 +7,7 @@
 #include "ftte_chem_math.h"
 #include "ftte_internal.h"
 #include "ftte_kernels.h"
+#include "ftte_tree_sum.h"
 
 namespace ftte {
 
@@ -120,16 +121,7 @@ int launch_thin_limit(const double *HI, const double *HeI, const double *HeII, c
 // computeMass (equiSources.f90:4369-4393) per leaf: HI mh cs3/msun and psi rho cs3/msun, cs3 the cube of the cell's size, each
 // term with the reference's operations in its order.  The sums are the code's own and deterministic: every thread adds its
 // cells in grid-stride order, the workgroup folds its 256 sums as a fixed tree, and mass_total_kernel adds the workgroups'
-// partial sums in a fixed order too.  No floating-point atomics.
-__device__ __forceinline__ void tree_sum_256(double *a, double *b)
-{
-    for (int w = 128; w > 0; w >>= 1) {
-        __syncthreads();
-        if ((int)threadIdx.x < w) { a[threadIdx.x] += a[threadIdx.x + w]; b[threadIdx.x] += b[threadIdx.x + w]; }
-    }
-    __syncthreads();
-}
-
+// partial sums in a fixed order too.  No floating-point atomics (tree_sum_256: ftte_tree_sum.h).
 __global__ void __launch_bounds__(256) hydrogen_mass_kernel(const int8_t *__restrict__ level, const double *__restrict__ HI,
                                                             const double *__restrict__ rho, long ncell, int n, double box,
                                                             double *__restrict__ part)

@@ -28,6 +28,7 @@
 
 #include "../../include/ftte.h"
 #include "ftte_amr.h"
+#include "ftte_analysis.h"
 #include "ftte_bricks.h"
 #include "ftte_gas.h"
 #include "ftte_geometry.h"
@@ -150,6 +151,7 @@ struct ftte_ctx {
 
     std::vector<int8_t> leaf_level;  // per leaf, as handed to ftte_set_grid
     ChemState chem;                  // ionisation equilibrium (ftte_chem.cpp)
+    AnalysisState analysis;          // maps and censuses of the medium (ftte_analysis.cpp)
 
     // accelerated source iteration (ftte_lambda_host.cpp): the segment-length tables of the last direction list, the leaves' places on
     // their levels (made for the tree of grid build lambda_leaves_grid) with the sub-layers that hold a leaf, the update's statistics
@@ -250,6 +252,9 @@ long long multi_counter(const ftte_ctx *c, const char *name);
 const char *multi_how(const ftte_ctx *c);
 ftte_ctx *multi_first(const ftte_ctx *c);
 int multi_host_register(ftte_ctx *c, void *ptr, size_t bytes, bool on);
+
+// ---- ftte_chem.cpp
+int ensure_level(ftte_ctx *c); // the leaves' levels in ChemState::level (uploaded on first use after ftte_set_grid)
 
 // ---- ftte_host_arrays.cpp
 bool is_registered(const ftte_ctx *c, const void *p, size_t bytes);

@@ -471,6 +471,23 @@ int point_set_rates(PointState &P, hipStream_t stream, int64_t ncell, const doub
     return 0;
 }
 
+// the tree's nodes on the device: uploaded on first use after ftte_set_grid (nothing for a uniform grid)
+int point_ensure_tree(PointState &P, hipStream_t stream, const AmrTree &tree, std::string *err)
+{
+    if (P.tree_ready) return FTTE_OK;
+    const size_t nnode = tree.parent.size();
+    P.node.reset();
+    if (tree.refined()) {
+        std::vector<NodeRec> nodes(nnode);
+        for (size_t v = 0; v < nnode; ++v) nodes[v] = NodeRec{tree.child0[v], tree.leaf[v], tree.parent[v], (int32_t)tree.level[v]};
+        POINT_HIP(P.node.reserve(nnode));
+        POINT_HIP(hipMemcpyAsync(P.node, nodes.data(), sizeof(NodeRec) * nnode, hipMemcpyHostToDevice, stream));
+        POINT_HIP(hipStreamSynchronize(stream));
+    }
+    P.tree_ready = true;
+    return FTTE_OK;
+}
+
 int point_trace(PointState &P, GasState &G, hipStream_t stream, const AmrTree &tree, double box, int nsrc, const int64_t *src_cell,
                 const double *src_ndot, const int32_t *src_slot, int *highest_pixel_level, int *highest_per_star, std::string *err)
 {
@@ -482,17 +499,7 @@ int point_trace(PointState &P, GasState &G, hipStream_t stream, const AmrTree &t
         if ((rc = point_zero_rates(P, stream, tree.ncell, err))) return rc;
 
     const size_t nnode = tree.parent.size();
-    if (!P.tree_ready) {
-        P.node.reset();
-        if (tree.refined()) {
-            std::vector<NodeRec> nodes(nnode);
-            for (size_t v = 0; v < nnode; ++v) nodes[v] = NodeRec{tree.child0[v], tree.leaf[v], tree.parent[v], (int32_t)tree.level[v]};
-            POINT_HIP(P.node.reserve(nnode));
-            POINT_HIP(hipMemcpyAsync(P.node, nodes.data(), sizeof(NodeRec) * nnode, hipMemcpyHostToDevice, stream));
-            POINT_HIP(hipStreamSynchronize(stream));
-        }
-        P.tree_ready = true;
-    }
+    if ((rc = point_ensure_tree(P, stream, tree, err))) return rc;
     POINT_HIP(G.reserve_packed(kCellRec));
     if (!G.packed_current()) {
         const double *const fields[5] = {G.field(0), G.field(1), G.field(2), G.field(3), G.field(4)};

@@ -110,6 +110,8 @@ int point_zero_rates(PointState &P, hipStream_t stream, int64_t ncell, std::stri
 // rates in the interface's layout [6][ncell], in device memory (valid until the next trace)
 int point_rate_planes(PointState &P, hipStream_t stream, double **planes, std::string *err);
 int point_set_rates(PointState &P, hipStream_t stream, int64_t ncell, const double *planes_host, std::string *err);
+// PointState::node holds the tree (the tracer and the maps of ftte_analysis.cpp descend through it); no-op once uploaded
+int point_ensure_tree(PointState &P, hipStream_t stream, const AmrTree &tree, std::string *err);
 // src_slot[nsrc]: the population slot each star reads, or null: all read the current tables.  highest_pixel_level: the maximum
 // over the stars; highest_per_star[nsrc]: each star's own.  Either may be null.  Makes the gas's packed copy where it is not current.
 int point_trace(PointState &P, GasState &G, hipStream_t stream, const AmrTree &tree, double box, int nsrc, const int64_t *src_cell,
