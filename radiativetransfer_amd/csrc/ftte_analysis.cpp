@@ -127,8 +127,7 @@ int make_map(ftte_ctx *c, const MapCall &M)
 
     if ((rc = analysis_ready(c))) return rc;
     AnalysisState &A = c->analysis;
-    std::string err;
-    if ((rc = point_ensure_tree(c->point, c->stream, c->tree, &err))) return fail(c, rc, who + err);
+    FTTE_HIP(c, c->dtree.ensure(c->stream, c->tree));
     for (int a = 0; a < 2; ++a) {
         FTTE_HIP(c, A.base[a].reserve(base[a].size()));
         FTTE_HIP(c, A.frac[a].reserve(frac[a].size()));
@@ -144,7 +143,7 @@ int make_map(ftte_ctx *c, const MapCall &M)
     }
     if (!value) value = G.field(M.project ? GasState::kAbun2 : GasState::kHI);
 
-    R.node = c->tree.refined() ? c->point.node.get() : nullptr;
+    R.node = c->dtree.nodes();
     R.value = value;
     R.rho = G.field(GasState::kRho);
     R.ibase = A.base[0]; R.jbase = A.base[1]; R.ifrac = A.frac[0]; R.jfrac = A.frac[1];

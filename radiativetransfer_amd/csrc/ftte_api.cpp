@@ -1,7 +1,7 @@
 // ftte_api.cpp -- the C ABI of include/ftte.h: context life cycle, grid and field setters, options, the sweep entry points, point
 // sources, host helpers; the entry points that read or write the species medium are in ftte_chem.cpp.  The work behind them:
 // ftte_plan.cpp (planners), ftte_sweeps.cpp (launch sequences), ftte_hybrid.cpp (refined cell arrays), ftte_host_arrays.cpp (PCIe),
-// ftte_point.cpp, ftte_amr.cpp, ftte_ingest.cpp.
+// ftte_point.cpp, ftte_tables.cpp (the reference's table mathematics), ftte_amr.cpp, ftte_ingest.cpp.
 //
 // There is no CPU fallback: every entry point that computes on the grid needs a HIP device and fails with FTTE_ERR_NO_DEVICE
 // otherwise.
@@ -118,6 +118,7 @@ int ftte_set_grid(ftte_ctx *c, int nx, int ny, int nz, int64_t ncell, const int3
     c->hdev.drop_grid();
     c->gas.drop();
     c->point.drop_grid();
+    c->dtree.drop();
     c->chem.drop_grid();
     c->analysis.drop_grid();
     c->leaf_level.assign(level, level + ncell);
@@ -422,7 +423,7 @@ long long ftte_counter(const ftte_ctx *c, const char *name)
     if (!std::strcmp(name, "plan_builds")) return c->n_plan_builds;
     if (!std::strcmp(name, "forest_builds")) return c->n_forest_builds;
     if (!std::strcmp(name, "device_objects")) return g_device_objects.load();
-    if (!std::strcmp(name, "population_slots")) return c->point.slots.count;
+    if (!std::strcmp(name, "population_slots")) return c->point.tables.slot_count();
     if (!std::strcmp(name, "expansion_exact_tests")) return c->chem.expansion_tests;
     if (!std::strcmp(name, "hybrid_boxes")) return c->hplan.boxes();
     if (!std::strcmp(name, "hybrid_passes")) return c->hplan.passes();
@@ -526,7 +527,7 @@ int ftte_stellar_beta_table(ftte_ctx *c, const double *a_smc, int nwave, const d
     if (iSpectrum < 1 || iSpectrum + 1 > nspectrum || iMetal < 1 || iMetal + 1 > nmetal)
         return fail(c, FTTE_ERR_ARG, "ftte_stellar_beta_table: iSpectrum / iMetal outside the library");
     FTTE_HIP(c, hipSetDevice(c->device));
-    return point_stellar_beta_table(c->point, c->stream, a_smc, nwave, wavelength_cm, nspectrum, nmetal, specific_luminosity, iSpectrum,
+    return point_stellar_beta_table(c->point.tables, c->stream, a_smc, nwave, wavelength_cm, nspectrum, nmetal, specific_luminosity, iSpectrum,
                                     coefSpectrum, iMetal, coefMetal, total_integral, &c->err);
 }
 
@@ -543,7 +544,7 @@ int ftte_stellar_beta_tables(ftte_ctx *c, const double *a_smc, int nwave, const 
         if (iSpectrum[p] < 1 || iSpectrum[p] + 1 > nspectrum || iMetal[p] < 1 || iMetal[p] + 1 > nmetal)
             return fail(c, FTTE_ERR_ARG, "ftte_stellar_beta_tables: iSpectrum / iMetal of population " + std::to_string(p) + " outside the library");
     FTTE_HIP(c, hipSetDevice(c->device));
-    return point_stellar_beta_tables(c->point, c->stream, a_smc, nwave, wavelength_cm, nspectrum, nmetal, specific_luminosity, npop,
+    return point_stellar_beta_tables(c->point.tables, c->stream, a_smc, nwave, wavelength_cm, nspectrum, nmetal, specific_luminosity, npop,
                                      iSpectrum, coefSpectrum, iMetal, coefMetal, total_integral, &c->err);
 }
 
@@ -553,7 +554,7 @@ int ftte_set_population_tables(ftte_ctx *c, int npop, const double *tables)
     if (rc) return rc;
     if (npop < 1 || !tables) return fail(c, FTTE_ERR_ARG, "ftte_set_population_tables: bad argument");
     FTTE_HIP(c, hipSetDevice(c->device));
-    return point_set_population_tables(c->point, c->stream, npop, tables, &c->err);
+    return c->point.tables.set_slots(c->stream, npop, tables, &c->err);
 }
 
 int ftte_get_population_tables(ftte_ctx *c, int slot, double *tables)
@@ -561,12 +562,13 @@ int ftte_get_population_tables(ftte_ctx *c, int slot, double *tables)
     int rc = check_single(c);
     if (rc) return rc;
     if (!tables) return fail(c, FTTE_ERR_ARG, "ftte_get_population_tables: bad argument");
-    const TableSets &S = c->point.slots;
-    if (!S.count) return fail(c, FTTE_ERR_STATE, "no population slots: call ftte_stellar_beta_tables or ftte_set_population_tables first");
-    if (slot < 0 || slot >= S.count)
-        return fail(c, FTTE_ERR_ARG, "ftte_get_population_tables: slot " + std::to_string(slot) + " outside 0.." + std::to_string(S.count - 1));
+    const RateTables &R = c->point.tables;
+    if ((rc = R.missing(true, &c->err))) return rc;
+    const int count = R.slot_count();
+    if (slot < 0 || slot >= count)
+        return fail(c, FTTE_ERR_ARG, "ftte_get_population_tables: slot " + std::to_string(slot) + " outside 0.." + std::to_string(count - 1));
     FTTE_HIP(c, hipSetDevice(c->device));
-    return point_get_tables(S, c->stream, slot, tables, &c->err);
+    return R.get(c->stream, true, slot, tables, &c->err);
 }
 
 int ftte_set_rate_tables(ftte_ctx *c, const double *tables)
@@ -575,7 +577,7 @@ int ftte_set_rate_tables(ftte_ctx *c, const double *tables)
     if (rc) return rc;
     if (!tables) return fail(c, FTTE_ERR_ARG, "ftte_set_rate_tables: bad argument");
     FTTE_HIP(c, hipSetDevice(c->device));
-    return point_set_tables(c->point, c->stream, tables, &c->err);
+    return c->point.tables.set_current(c->stream, tables, &c->err);
 }
 
 int ftte_get_rate_tables(ftte_ctx *c, double *tables)
@@ -583,9 +585,9 @@ int ftte_get_rate_tables(ftte_ctx *c, double *tables)
     int rc = check_single(c);
     if (rc) return rc;
     if (!tables) return fail(c, FTTE_ERR_ARG, "ftte_get_rate_tables: bad argument");
-    if (!c->point.current.count) return fail(c, FTTE_ERR_STATE, "no rate tables: call ftte_stellar_beta_table or ftte_set_rate_tables first");
+    if ((rc = c->point.tables.missing(false, &c->err))) return rc;
     FTTE_HIP(c, hipSetDevice(c->device));
-    return point_get_tables(c->point.current, c->stream, 0, tables, &c->err);
+    return c->point.tables.get(c->stream, false, 0, tables, &c->err);
 }
 
 int ftte_get_rates_hydrogen_helium(ftte_ctx *c, int dust_approximation, int nsample, const double *tau, double *rates)
@@ -628,7 +630,7 @@ int ftte_set_zero_rates(ftte_ctx *c)
     int rc = check_ready(c, false);
     if (rc) return rc;
     FTTE_HIP(c, hipSetDevice(c->device));
-    if ((rc = point_zero_rates(c->point, c->stream, c->ncell, &c->err))) return rc;
+    if ((rc = c->point.rates.zero(c->stream, c->ncell, &c->err))) return rc;
     FTTE_HIP(c, hipStreamSynchronize(c->stream));
     return FTTE_OK;
 }
@@ -663,7 +665,7 @@ int ftte_point_sources(ftte_ctx *c, int nsrc, const int64_t *src_cell, const dou
     if (highest_pixel_level) *highest_pixel_level = 0;
     if (!nsrc) return FTTE_OK;
     FTTE_HIP(c, hipSetDevice(c->device));
-    return point_trace(c->point, c->gas, c->stream, c->tree, c->box, nsrc, src_cell, src_ndot, nullptr, highest_pixel_level, nullptr, &c->err);
+    return point_trace(c->point, c->dtree, c->gas, c->stream, c->tree, c->box, nsrc, src_cell, src_ndot, nullptr, highest_pixel_level, nullptr, &c->err);
 }
 
 int ftte_point_sources_populations(ftte_ctx *c, int nsrc, const int64_t *src_cell, const double *src_ndot, const int32_t *src_slot,
@@ -672,32 +674,21 @@ int ftte_point_sources_populations(ftte_ctx *c, int nsrc, const int64_t *src_cel
     int rc = check_ready(c, false);
     if (rc) return rc;
     if (nsrc < 0 || (nsrc && (!src_cell || !src_ndot || !src_slot))) return fail(c, FTTE_ERR_ARG, "ftte_point_sources_populations: bad argument");
-    if (!c->point.slots.count)
-        return fail(c, FTTE_ERR_STATE, "no population slots: call ftte_stellar_beta_tables or ftte_set_population_tables first");
+    if ((rc = c->point.tables.missing(true, &c->err))) return rc;
     if (highest_pixel_level) std::fill(highest_pixel_level, highest_pixel_level + nsrc, 0);
     if (!nsrc) return FTTE_OK;
     FTTE_HIP(c, hipSetDevice(c->device));
-    return point_trace(c->point, c->gas, c->stream, c->tree, c->box, nsrc, src_cell, src_ndot, src_slot, nullptr, highest_pixel_level, &c->err);
+    return point_trace(c->point, c->dtree, c->gas, c->stream, c->tree, c->box, nsrc, src_cell, src_ndot, src_slot, nullptr, highest_pixel_level, &c->err);
 }
 
 int ftte_point_escape(ftte_ctx *c, int nsrc, double *remaining, double *boundary, double *dust, double *spectrum, double *fraction)
 {
     int rc = check_single(c);
     if (rc) return rc;
-    const PointState &P = c->point;
-    if (nsrc < 0 || (size_t)nsrc * kEscapeRec != P.escape_host.size())
+    const EscapeRecord &E = c->point.escape;
+    if (nsrc != E.stars())
         return fail(c, FTTE_ERR_ARG, "ftte_point_escape: nsrc is not the number of stars of the last ftte_point_sources");
-    for (int s = 0; s < nsrc; ++s) {
-        const double *E = P.escape_host.data() + (size_t)s * kEscapeRec;
-        for (int ir = 0; ir < kOutputRadii; ++ir) {
-            if (remaining) remaining[s * kOutputRadii + ir] = E[ir];
-            if (boundary) boundary[s * kOutputRadii + ir] = E[kOutputRadii + ir];
-            // equiSources.f90:1342-1348
-            if (fraction) fraction[s * kOutputRadii + ir] = E[kOutputRadii + ir] < 1. ? E[ir] / (P.escape_ndot[(size_t)s] - E[kOutputRadii + ir]) : 0.;
-        }
-        if (dust) dust[s] = E[2 * kOutputRadii];
-        if (spectrum) std::memcpy(spectrum + (size_t)s * kOutputEnergies, E + 2 * kOutputRadii + 1, sizeof(double) * kOutputEnergies);
-    }
+    for (int s = 0; s < nsrc; ++s) E.unpack(s, remaining, boundary, dust, spectrum, fraction);
     return FTTE_OK;
 }
 
@@ -707,7 +698,7 @@ int ftte_set_output_sigma(ftte_ctx *c, const double *sigma)
     if (rc) return rc;
     if (!sigma) return fail(c, FTTE_ERR_ARG, "ftte_set_output_sigma: bad argument");
     FTTE_HIP(c, hipSetDevice(c->device));
-    return point_set_output_sigma(c->point, c->stream, sigma, &c->err);
+    return c->point.tables.set_sigma(c->stream, sigma, &c->err);
 }
 
 int ftte_get_point_rates(ftte_ctx *c, double *rates)
@@ -715,10 +706,10 @@ int ftte_get_point_rates(ftte_ctx *c, double *rates)
     int rc = check_ready(c, false);
     if (rc) return rc;
     if (!rates) return fail(c, FTTE_ERR_ARG, "ftte_get_point_rates: bad argument");
-    if (!c->point.rates || c->point.rates_cells != c->ncell) return fail(c, FTTE_ERR_STATE, "no rates: call ftte_set_zero_rates / ftte_point_sources first");
+    if (!c->point.rates.ready(c->ncell)) return fail(c, FTTE_ERR_STATE, "no rates: call ftte_set_zero_rates / ftte_point_sources first");
     FTTE_HIP(c, hipSetDevice(c->device));
     double *planes = nullptr;
-    if ((rc = point_rate_planes(c->point, c->stream, &planes, &c->err))) return rc;
+    if ((rc = c->point.rates.planes(c->stream, &planes, &c->err))) return rc;
     FTTE_HIP(c, hipMemcpyAsync(rates, planes, sizeof(double) * 6 * c->ncell, hipMemcpyDeviceToHost, c->stream));
     FTTE_HIP(c, hipStreamSynchronize(c->stream));
     return FTTE_OK;
@@ -730,7 +721,7 @@ int ftte_set_point_rates(ftte_ctx *c, const double *rates)
     if (rc) return rc;
     if (!rates) return fail(c, FTTE_ERR_ARG, "ftte_set_point_rates: bad argument");
     FTTE_HIP(c, hipSetDevice(c->device));
-    return point_set_rates(c->point, c->stream, c->ncell, rates, &c->err);
+    return c->point.rates.set(c->stream, c->ncell, rates, &c->err);
 }
 
 int ftte_point_rates_device(ftte_ctx *c, double **rates_dev)
@@ -738,14 +729,14 @@ int ftte_point_rates_device(ftte_ctx *c, double **rates_dev)
     int rc = check_ready(c, false);
     if (rc) return rc;
     if (!rates_dev) return fail(c, FTTE_ERR_ARG, "ftte_point_rates_device: bad argument");
-    if (!c->point.rates || c->point.rates_cells != c->ncell) return fail(c, FTTE_ERR_STATE, "no rates: call ftte_set_zero_rates / ftte_point_sources first");
+    if (!c->point.rates.ready(c->ncell)) return fail(c, FTTE_ERR_STATE, "no rates: call ftte_set_zero_rates / ftte_point_sources first");
     FTTE_HIP(c, hipSetDevice(c->device));
-    if ((rc = point_rate_planes(c->point, c->stream, rates_dev, &c->err))) return rc;
+    if ((rc = c->point.rates.planes(c->stream, rates_dev, &c->err))) return rc;
     FTTE_HIP(c, hipStreamSynchronize(c->stream));
     return FTTE_OK;
 }
 
-long long ftte_point_ray_steps(const ftte_ctx *c) { return c ? c->point.ray_steps : 0; }
+long long ftte_point_ray_steps(const ftte_ctx *c) { return c ? c->point.escape.ray_steps() : 0; }
 
 int ftte_rmax(double *rmax30)
 {

@@ -81,10 +81,10 @@ int solve_rates(ftte_ctx *c, int run_uvb, const double *J, bool J_on_device, con
 {
     const ChemUpdate U{who, "species fraction outside [0, 1]", launch_rate_equations};
     return chem_update(c, U, [&](ChemRec &R) -> int {
-        const PointState &P = c->point;
+        const PointRates &P = c->point.rates;
         if (run_uvb && (!J || !ksi)) return fail(c, FTTE_ERR_ARG, std::string(who) + ": the transfer-driven update needs J and ksi");
         if (!run_uvb && !uniform) return fail(c, FTTE_ERR_ARG, std::string(who) + ": the uniform-background update needs the background rates");
-        if (use_point_rates && (!P.rates || P.rates_cells != c->ncell))
+        if (use_point_rates && !P.ready(c->ncell))
             return fail(c, FTTE_ERR_STATE, std::string(who) + ": no point-source rates (ftte_set_zero_rates / ftte_point_sources)");
         if (run_uvb && !J_on_device) {
             const size_t nc = (size_t)c->ncell;
@@ -93,7 +93,7 @@ int solve_rates(ftte_ctx *c, int run_uvb, const double *J, bool J_on_device, con
             J = c->chem.J;
         }
         R.J = run_uvb ? J : nullptr;
-        R.krate = use_point_rates ? P.rates.get() : nullptr;
+        R.krate = use_point_rates ? P.packed() : nullptr;
         R.run_uvb = run_uvb ? 1 : 0;
         if (ksi) std::memcpy(R.ksi, ksi, sizeof R.ksi);
         if (uniform) std::memcpy(R.uniform, uniform, sizeof R.uniform);

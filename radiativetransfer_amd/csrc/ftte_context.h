@@ -10,7 +10,10 @@
 // depends on with the rules that resolve them, the plan, its tables, the buffers that remember what they were sent and the state of
 // the one-launch forms (ftte_bricks.h), for the ray-following tiles their plan (ftte_tiles.h), and for the sweeps of
 // a refined cell array the forests, their scratch and their cache (ftte_forests.h) and the hybrid sweep's options, plan and device
-// state (ftte_hybrid.h), and for host arrays the staging blocks and the registered ranges (ftte_host.h).
+// state (ftte_hybrid.h), for host arrays the staging blocks and the registered ranges (ftte_host.h), for the tree its copy on the
+// device (ftte_device_tree.h), and for point sources the rate tables with their output cross-sections, the accumulated rates, the
+// tracer's scratch and the escape record of the last trace (ftte_point.h).  The reference's table mathematics reads no context and
+// no HIP (ftte_tables.cpp).
 //
 // There is no CPU fallback behind any of this: every entry point that computes on the grid needs a HIP device and fails with
 // FTTE_ERR_NO_DEVICE otherwise.
@@ -115,6 +118,7 @@ struct ftte_ctx {
 
     // refined cell arrays: the tree, and the per-direction segment forests resident on the device
     AmrTree tree;
+    DeviceTree dtree;         // its nodes on the device, for the point-source tracer and the maps (ftte_device_tree.h)
     bool use_forest = false;  // refined grid (or option "forest" = 1 on a uniform one, for cross-checks)
     int force_forest = 0;
     ForestCache forests;      // the whole tree's, per direction (forest_sweep)
@@ -142,7 +146,7 @@ struct ftte_ctx {
     // The species medium (ftte_gas.h): ftte_set_medium fills it; the tracer, the chemistry, the census, ftte_compute_opacities and
     // the thin limit read it; the chemistry's updates write its species and say so
     GasState gas;
-    PointState point; // point sources: tree, rate tables, rates, tracer scratch
+    PointState point; // point sources: rate tables, rates, tracer scratch, escape record (ftte_point.h)
 
     HostBoundary host; // host arrays (ftte_set_opacity / ftte_diffuse_sweep): staging blocks, registered arrays, J on the device (ftte_host.h)
 

@@ -1,0 +1,263 @@
+// The owners of the point-source path (radiativetransfer_amd/csrc/ftte_point.h: RateTables, PointRates, TraceScratch, EscapeRecord),
+// the tree on the device (ftte_device_tree.h) and the tracer's steps that read no device, against a stub of the HIP runtime
+// (tests/host/stub), under the address and undefined-behaviour sanitizers with leak detection.  ftte_point.cpp is linked as it is; the
+// kernels it launches are stand-ins here that count their calls.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "ftte_kernels.h"
+#include "ftte_point.h"
+
+using namespace ftte;
+
+#define CHECK(cond)                                                                                                \
+    do {                                                                                                           \
+        if (!(cond)) { std::fprintf(stderr, "ERROR %s:%d: %s\n", __FILE__, __LINE__, #cond); std::exit(1); }       \
+    } while (0)
+
+static struct { long rate_table, log_table, lookup, pack, repack, trace; } launches;
+namespace ftte {
+int launch_rate_table(const FreqBin *, int, int, double *, double *, hipStream_t) { ++launches.rate_table; return 0; }
+int launch_rate_lookup(const double *, int, int, const double *, double *, hipStream_t) { ++launches.lookup; return 0; }
+int launch_log_table(const double *, int, double *, hipStream_t) { ++launches.log_table; return 0; }
+int launch_point_trace(const TraceRec &, hipStream_t) { ++launches.trace; return 0; } // (no ray splits: the queue length stays 0)
+int launch_pack_medium(const double *const[5], double *, long, hipStream_t) { ++launches.pack; return 0; }
+int launch_repack_rates(double *, double *, long, bool, hipStream_t) { ++launches.repack; return 0; }
+} // namespace ftte
+
+static bool has(const std::string &text, const char *part) { return text.find(part) != std::string::npos; }
+
+static void rate_tables()
+{
+    const hipStream_t q = nullptr;
+    std::string err;
+    const std::vector<double> host(3 * kSetDoubles, 1.0), sigma(4 * kOutputEnergies, 1e-18);
+    const std::vector<FreqBin> bins(kFrequencies - 1);
+    RateTables R;
+    // nothing yet: the state error of each set, each text where it belongs
+    CHECK(R.missing(false, &err) == FTTE_ERR_STATE && err == "no rate tables: call ftte_stellar_beta_table or ftte_set_rate_tables first");
+    CHECK(R.missing(true, &err) == FTTE_ERR_STATE && err == "no population slots: call ftte_stellar_beta_tables or ftte_set_population_tables first");
+    CHECK(R.sigma() == nullptr);
+
+    // current tables, then cross-sections; new tables from the host take the cross-sections away; a population brings its own
+    CHECK(R.set_current(q, host.data(), &err) == 0 && launches.log_table == 1);
+    CHECK(R.missing(false, &err) == 0 && R.missing(true, &err) == FTTE_ERR_STATE && R.by_slot(false).count == 1);
+    CHECK(R.set_sigma(q, sigma.data(), &err) == 0 && R.sigma() != nullptr);
+    CHECK(R.sigma()[0] == 1e-18 / (double)6.3e-18f); // what the tracer multiplies with: sigma / threshold
+    double *const current = R.by_slot(false).tables;
+    CHECK(R.set_current(q, host.data(), &err) == 0 && R.sigma() == nullptr && R.by_slot(false).tables == current);
+    CHECK(R.current_from_bins(q, bins, sigma.data(), &err) == 0 && R.sigma() != nullptr && launches.rate_table == 1);
+    CHECK(R.by_slot(false).count == 1 && R.by_slot(false).tables == current);
+
+    // slots from 1 to 3 and back: the larger buffers stay
+    CHECK(R.set_slots(q, 1, host.data(), &err) == 0 && R.by_slot(true).count == 1 && R.missing(true, &err) == 0);
+    CHECK(R.set_slots(q, 3, host.data(), &err) == 0 && R.by_slot(true).count == 3);
+    double *const t3 = R.by_slot(true).tables, *const l3 = R.by_slot(true).logtab;
+    long released = stub().released;
+    CHECK(R.set_slots(q, 1, host.data(), &err) == 0 && R.by_slot(true).count == 1);
+    CHECK(R.by_slot(true).tables == t3 && R.by_slot(true).logtab == l3 && stub().released == released);
+    CHECK(R.by_slot(true).tables.capacity() == 3 * kSetDoubles);
+    std::vector<double> back(kSetDoubles, 0.0);
+    CHECK(R.get(q, true, 0, back.data(), &err) == 0 && back[kSetDoubles - 1] == 1.0);
+
+    // more slots than the device has room for, counting what the two replaced buffers give back: refused before anything is released
+    const size_t free_bytes = stub().free_bytes;
+    stub().free_bytes = 2 * 4 * kSetDoubles * sizeof(double) - 2 * 3 * kSetDoubles * sizeof(double) - 1;
+    const long live = stub().live;
+    CHECK(R.set_slots(q, 4, host.data(), &err) == FTTE_ERR_MEMORY && has(err, "population slots: 4 slots need "));
+    CHECK(R.by_slot(true).count == 1 && R.by_slot(true).tables == t3 && stub().released == released && stub().live == live);
+    ++stub().free_bytes; // (exactly enough)
+    stub().fail_next = true; // ... and the allocation itself fails: no slot is held
+    CHECK(R.set_slots(q, 4, host.data(), &err) == FTTE_ERR_MEMORY && has(err, "could not be allocated"));
+    CHECK(R.by_slot(true).count == 0 && R.missing(true, &err) == FTTE_ERR_STATE && !R.by_slot(true).tables && !R.by_slot(true).logtab);
+    CHECK(R.by_slot(false).count == 1); // (the current tables are another set)
+    stub().free_bytes = free_bytes;
+    std::vector<FreqBin> two(2 * (kFrequencies - 1));
+    CHECK(R.slots_from_bins(q, two, 2, sigma.data(), &err) == 0 && R.by_slot(true).count == 2 && launches.rate_table == 2);
+}
+
+static void rates()
+{
+    const hipStream_t q = nullptr;
+    std::string err;
+    const long base = stub().live;
+    PointRates P;
+    CHECK(!P.ready(64) && !P.ready(0) && P.packed() == nullptr);
+    CHECK(P.zero(q, 64, &err) == 0 && P.ready(64) && !P.ready(65) && !P.ready(0) && stub().live == base + 1);
+    CHECK(P.packed()[kCellRec * 64 - 1] == 0.0);
+    double *planes = nullptr;
+    CHECK(P.planes(q, &planes, &err) == 0 && planes && stub().live == base + 2 && launches.repack == 1);
+    CHECK(P.planes(q, &planes, &err) == 0 && stub().live == base + 2 && launches.repack == 2);
+    CHECK(P.zero(q, 64, &err) == 0 && stub().live == base + 2); // the same grid: the planes stay
+    CHECK(P.zero(q, 27, &err) == 0 && P.ready(27) && !P.ready(64) && stub().live == base + 1); // another one: they go
+    const std::vector<double> host(6 * 27, 2.0);
+    CHECK(P.set(q, 27, host.data(), &err) == 0 && P.ready(27) && stub().live == base + 2 && launches.repack == 3);
+    P.drop();
+    CHECK(stub().live == base && !P.ready(27) && P.packed() == nullptr);
+    P.drop();
+    CHECK(stub().live == base);
+}
+
+// a 2^3 base grid: uniform, or with its first base cell refined (16 nodes, 15 leaves)
+static AmrTree tree_of(bool refined)
+{
+    std::vector<int32_t> level(refined ? 15 : 8, 0);
+    if (refined) std::fill(level.begin(), level.begin() + 8, 1);
+    AmrTree tree;
+    CHECK(tree.build(2, (int64_t)level.size(), level.data()).empty());
+    CHECK(tree.refined() == refined && tree.parent.size() == (refined ? 16u : 8u));
+    return tree;
+}
+
+static void device_tree_and_sources()
+{
+    const hipStream_t q = nullptr;
+    std::string err;
+    const long base = stub().live;
+    DeviceTree D;
+    const AmrTree uniform = tree_of(false), refined = tree_of(true);
+    long copies = stub().copies;
+    CHECK(D.ensure(q, uniform) == hipSuccess && D.nodes() == nullptr && stub().live == base && stub().copies == copies);
+    for (int64_t c = 0; c < uniform.ncell; ++c) CHECK(D.node_of(c) == c);
+
+    D.drop(); // ftte_set_grid
+    CHECK(D.ensure(q, refined) == hipSuccess && D.nodes() != nullptr && stub().live == base + 1 && stub().copies == copies + 1);
+    CHECK(D.ensure(q, refined) == hipSuccess && stub().live == base + 1 && stub().copies == copies + 1); // found
+    for (int64_t c = 0; c < refined.ncell; ++c) CHECK(refined.leaf[(size_t)D.node_of(c)] == c);
+    CHECK(D.nodes()[15].leaf == refined.leaf[15] && D.nodes()[0].child0 == refined.child0[0]);
+    D.drop();
+    CHECK(stub().live == base && D.nodes() == nullptr);
+    stub().fail_next = true;
+    CHECK(D.ensure(q, refined) == hipErrorOutOfMemory && D.nodes() == nullptr && stub().live == base);
+    CHECK(D.ensure(q, refined) == hipSuccess && stub().copies == copies + 2 && stub().live == base + 1);
+
+    // the stars of a call on that tree
+    const int64_t ncell = refined.ncell;
+    int32_t node[3];
+    const int64_t below[3] = {0, -1, 3}, above[3] = {0, 3, ncell}, good[3] = {14, 0, 7};
+    CHECK(check_sources(D, ncell, 3, below, nullptr, 0, node, &err) == FTTE_ERR_ARG && err == "ftte_point_sources: source cell outside the cell array");
+    err.clear();
+    CHECK(check_sources(D, ncell, 3, above, nullptr, 0, node, &err) == FTTE_ERR_ARG && err == "ftte_point_sources: source cell outside the cell array");
+    const int32_t low[3] = {0, -1, 2}, high[3] = {0, 2, 3}, fine[3] = {2, 0, 1};
+    CHECK(check_sources(D, ncell, 3, good, low, 3, node, &err) == FTTE_ERR_ARG);
+    CHECK(err == "ftte_point_sources_populations: star 1 names slot -1, outside 0..2");
+    CHECK(check_sources(D, ncell, 3, good, high, 3, node, &err) == FTTE_ERR_ARG);
+    CHECK(err == "ftte_point_sources_populations: star 2 names slot 3, outside 0..2");
+    for (const int32_t *slot : {(const int32_t *)nullptr, fine}) {
+        node[0] = node[1] = node[2] = -7;
+        CHECK(check_sources(D, ncell, 3, good, slot, 3, node, &err) == 0);
+        for (int s = 0; s < 3; ++s) CHECK(refined.leaf[(size_t)node[s]] == good[s]);
+    }
+    CHECK(check_sources(D, ncell, 0, good, nullptr, 0, node, &err) == 0);
+}
+
+static void scratch_and_ray_counts()
+{
+    const long base = stub().live;
+    {
+        TraceScratch S;
+        hipError_t why = hipSuccess;
+        CHECK(S.reserve(1, false, &why) == 1 && why == hipSuccess);
+        CHECK(S.queue[0].capacity() >= (size_t)kSplitsPerSource && S.queue[1].capacity() >= (size_t)kSplitsPerSource);
+        CHECK(kSplitsPerSource == 3072 && !S.src_slot && S.counters.capacity() == (size_t)TraceScratch::kCounters);
+        CHECK(S.reserve(1025, true, &why) == kSplitBatch && S.src_slot.capacity() == 1025 && S.escape.capacity() == (size_t)1025 * kEscapeRec);
+        CHECK(S.queue[0].capacity() == (size_t)kSplitBatch * kSplitsPerSource);
+        const long live = stub().live, released = stub().released;
+        CHECK(S.reserve(3, true, &why) == 3 && stub().live == live && stub().released == released && stub().live_at_last_request < live);
+        stub().fail_next = true;
+        CHECK(S.reserve(2000, true, &why) == 0 && why == hipErrorOutOfMemory);
+    }
+    CHECK(stub().live == base);
+
+    CHECK(rays_of_level(1, 3, 0) == 36 && rays_of_level(1, 3, 99) == 36);
+    CHECK(rays_of_level(2, 3, 5) == 20 && rays_of_level(6, 1024, 5) == 20);
+    CHECK(rays_of_level(2, 3, 0) == 0);
+    CHECK(!std::strcmp(trace_error_text(5), "split queue overflow") && !std::strcmp(trace_error_text(4), "ray did not terminate"));
+    CHECK(!std::strcmp(trace_error_text(1), "continuation cell outside the base grid") && !std::strcmp(trace_error_text(77), "error in checkPoint"));
+}
+
+static void escape_record()
+{
+    EscapeRecord E;
+    CHECK(E.stars() == 0 && E.ray_steps() == 0);
+    const double ndot[2] = {5.0, 8.0};
+    double *rec = E.receive(2, ndot);
+    for (int s = 0; s < 2; ++s)
+        for (int q = 0; q < kEscapeRec; ++q) rec[s * kEscapeRec + q] = 1000.0 * (s + 1) + q;
+    // the boundary losses: star 0 below 1 at radius 2 only, star 1 everywhere
+    for (int ir = 0; ir < kOutputRadii; ++ir) { rec[kOutputRadii + ir] = ir == 2 ? 0.25 : 1.0 + ir; rec[kEscapeRec + kOutputRadii + ir] = 0.125 * ir; }
+    E.counted(12345);
+    CHECK(E.stars() == 2 && E.ray_steps() == 12345);
+    CHECK(3 != E.stars() && 0 != E.stars()); // what ftte_point_escape refuses another star count with
+    double remaining[2 * kOutputRadii], boundary[2 * kOutputRadii], fraction[2 * kOutputRadii], dust[2], spectrum[2 * kOutputEnergies];
+    for (int s = 0; s < 2; ++s) E.unpack(s, remaining, boundary, dust, spectrum, fraction);
+    for (int s = 0; s < 2; ++s) {
+        const double *R = rec + s * kEscapeRec;
+        for (int ir = 0; ir < kOutputRadii; ++ir) {
+            CHECK(remaining[s * kOutputRadii + ir] == R[ir] && boundary[s * kOutputRadii + ir] == R[kOutputRadii + ir]);
+            const double b = R[kOutputRadii + ir];
+            CHECK(fraction[s * kOutputRadii + ir] == (b < 1. ? R[ir] / (ndot[s] - b) : 0.));
+        }
+        CHECK(dust[s] == R[2 * kOutputRadii]);
+        for (int ie = 0; ie < kOutputEnergies; ++ie) CHECK(spectrum[s * kOutputEnergies + ie] == R[2 * kOutputRadii + 1 + ie]);
+    }
+    CHECK(fraction[2] == 1002.0 / (5.0 - 0.25) && fraction[1] == 0. && fraction[kOutputRadii] == 2000.0 / 8.0);
+    E.unpack(1, nullptr, nullptr, nullptr, nullptr, nullptr); // every output may be missing
+    E.receive(1, ndot);
+    CHECK(E.stars() == 1);
+}
+
+// point_trace through its steps on the refined tree: the first call makes what is missing, the second finds everything
+static void steady_trace()
+{
+    const hipStream_t q = nullptr;
+    std::string err;
+    const AmrTree tree = tree_of(true);
+    const int64_t cells[3] = {14, 0, 7};
+    const double ndot[3] = {1.0, 2.0, 3.0};
+    const std::vector<double> host(kSetDoubles, 1.0);
+    PointState P;
+    DeviceTree D;
+    GasState G;
+    int highest = -1;
+    CHECK(point_trace(P, D, G, q, tree, 1.0, 3, cells, ndot, nullptr, &highest, nullptr, &err) == FTTE_ERR_STATE && has(err, "no rate tables"));
+    CHECK(P.tables.set_current(q, host.data(), &err) == 0);
+    CHECK(point_trace(P, D, G, q, tree, 1.0, 3, cells, ndot, nullptr, &highest, nullptr, &err) == FTTE_ERR_STATE && has(err, "no medium"));
+    CHECK(G.reserve(tree.ncell) == hipSuccess);
+    G.filled(tree.ncell, 0, false);
+    const int32_t slots[3] = {0, 0, 0};
+    CHECK(point_trace(P, D, G, q, tree, 1.0, 3, cells, ndot, slots, nullptr, &highest, &err) == FTTE_ERR_STATE && has(err, "no population slots"));
+
+    launches.pack = launches.trace = 0;
+    CHECK(point_trace(P, D, G, q, tree, 1.0, 3, cells, ndot, nullptr, &highest, nullptr, &err) == 0);
+    CHECK(launches.pack == 1 && launches.trace == 1 && highest == 0 && P.rates.ready(tree.ncell) && D.nodes() && G.packed_current());
+    CHECK(P.escape.stars() == 3 && P.escape.ray_steps() == 0);
+    // steady: nothing is allocated or released, the medium is not packed again, and the copies are the batch's two uploads, the
+    // level's counter up and down, and the three downloads at the end
+    const long live = stub().live, released = stub().released, copies = stub().copies;
+    int each[3] = {-1, -1, -1};
+    CHECK(point_trace(P, D, G, q, tree, 1.0, 3, cells, ndot, nullptr, nullptr, each, &err) == 0);
+    CHECK(stub().live == live && stub().released == released && stub().copies == copies + 7 && stub().live_at_last_request < live);
+    CHECK(launches.pack == 1 && launches.trace == 2 && each[0] == 0 && each[2] == 0);
+    const int64_t outside[3] = {14, 15, 7};
+    CHECK(point_trace(P, D, G, q, tree, 1.0, 3, outside, ndot, nullptr, &highest, nullptr, &err) == FTTE_ERR_ARG && launches.trace == 2);
+    P.drop_grid();
+    CHECK(!P.rates.ready(tree.ncell) && stub().live == live - 1);
+}
+
+int main()
+{
+    const long base = stub().live;
+    rate_tables();
+    rates();
+    device_tree_and_sources();
+    scratch_and_ray_counts();
+    escape_record();
+    steady_trace();
+    CHECK(stub().live == base && g_device_objects.load() == stub().live);
+    std::printf("point state under the sanitizers: ok\n");
+    return 0;
+}

@@ -17,7 +17,7 @@ typedef struct stub_event *hipEvent_t;
 typedef struct stub_stream *hipStream_t;
 typedef struct stub_graph *hipGraph_t;
 typedef struct stub_graph_exec *hipGraphExec_t;
-typedef enum { hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2 } hipMemcpyKind;
+typedef enum { hipMemcpyHostToDevice = 1, hipMemcpyDeviceToHost = 2, hipMemcpyDeviceToDevice = 3 } hipMemcpyKind;
 enum { hipEventDefault = 0, hipEventDisableTiming = 2, hipStreamDefault = 0, hipStreamNonBlocking = 1, hipHostMallocDefault = 0, hipHostRegisterPortable = 1 };
 
 struct stub_state {
@@ -124,3 +124,4 @@ inline hipError_t hipHostRegister(void *p, size_t, unsigned)
 }
 inline hipError_t hipHostUnregister(void *p) { return stub().pinned.erase(p) ? hipSuccess : hipErrorHostMemoryNotRegistered; }
 inline hipError_t hipGetLastError() { return hipSuccess; }
+inline const char *hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : e == hipErrorOutOfMemory ? "out of memory" : "error"; }

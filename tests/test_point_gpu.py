@@ -93,6 +93,40 @@ def test_tracer_against_reference(stellar, golden, name):
     assert np.array_equal(rates == 0, g["krate"] == 0)
 
 
+def test_tracer_and_maps_share_the_device_tree(golden):
+    """The tracer and the slice map descend through one copy of the tree on the device, made by whichever comes first.  Either
+    order gives the same map (a look-up: bit for bit) and rates that meet the reference; a uniform grid afterwards drops it."""
+    import radiativetransfer_amd as rt
+    g = golden("point10_refined_dust")
+
+    def medium(st, g):
+        st.set_grid(int(g["n"]), g["level"], float(g["box"]))
+        st.set_medium(g["HI"], g["HeI"], g["HeII"], g["rho"], g["abun2"], int(g["dust"]))
+        st.set_rate_tables(g["tables"])
+
+    def trace(st, g):
+        hp = st.point_sources(g["src_leaf"], g["src_weight"].astype(float))
+        rates = st.rates()
+        assert hp == int(g["highestPixelLevel"])
+        _close(rates, g["krate"])
+        assert np.array_equal(rates == 0, g["krate"] == 0)
+
+    shape = (4 * int(g["n"]), 4 * int(g["n"]))
+    with rt.StellarTransfer() as a, rt.StellarTransfer() as b:
+        medium(a, g)
+        map_first = a.slice_map(1, shape, 0.53)   # the map makes the tree, the trace finds it
+        trace(a, g)
+        medium(b, g)
+        trace(b, g)                               # the trace makes it, the map finds it
+        map_second = b.slice_map(1, shape, 0.53)
+        assert np.array_equal(map_first, map_second)
+        assert np.unique(map_first).size > int(g["n"])  # (not a constant map: the medium varies from leaf to leaf)
+        u = golden("point16_homogeneous")
+        assert not u["level"].any()
+        medium(a, u)
+        trace(a, u)
+
+
 def _random_tree(rng, n, p1, p2):
     level = []
     for _ in range(n ** 3):
