@@ -476,7 +476,7 @@ int ftte_host_unregister(ftte_ctx *ctx, void *ptr);
  * stage, 1 one launch with flags, 2 the same with write-through stores, 3 persistent workgroups with a queue per XCD; the form
  * option "dataflow" asks for falls back to 1 or 0 where the XCD census or the grid size does not allow it; -1 before the first);
  * "brick_whole": 1 when that sweep's stage launches took the whole-brick form of the brick kernel (every brick whole, four waves, no
- * emission, no diagnostic option), else 0;
+ * emission, no diagnostic option), else 0; "nu_deal": option "nu_deal" as it stands (the library's default until it is set);
  * "brick_groups" and "brick_accumulators" (also "_0", "_1", "_2" per memory layout): direction groups of the current brick plan and
  * the J accumulators they share (0 without a plan), "brick_chunk" (layers per brick of that plan) and "brick_queue_mix" (the
  * option "queue_mix" the persistent form's queues were laid out by; -1 when the plan has no queues); "brick_stages" (stages of that
@@ -503,6 +503,11 @@ long long ftte_counter(const ftte_ctx *ctx, const char *name);
  *                   write-through stores, 3 one launch of persistent workgroups with a task queue per XCD
  *     "tiled"       bricks: 1 = opacities and accumulators stored brick by brick (a brick's layer in one piece; grids of whole
  *                   bricks), 2 = the whole brick in one piece; same results, measured without gain; 0 = in frames (default)
+ *     "nu_deal"     bricks, a launch per stage: how a launch's workgroups are dealt to its (brick, frequency group) pairs.  0:
+ *                   workgroup b sweeps group b mod nnu, so each group always runs on the same XCDs; K >= 1: the groups are turned
+ *                   by one after every run of K bricks per XCD round, so every XCD sweeps every group equally often.
+ *                   Same results bit for bit; no plan depends on it.  0..4096, default 16 (1 puts every group's opacities behind
+ *                   every L2 and gains nothing with two streams; 4 to 64 measured alike)
  *     "merge_overlap" bricks: 1 (default) = J merged block by block (32^3 cells) while the last stages run, 0 = one merge after
  *                   the last stage; same results
  *     "team"        bricks: 0 = one wavefront per brick, 2 = two wavefronts per

@@ -279,6 +279,10 @@ int ftte_set_option(ftte_ctx *c, const char *key, int value)
     } else if (!std::strcmp(key, "atomic_acc")) {
         if (value < 0 || value > 1) return fail(c, FTTE_ERR_ARG, "atomic_acc must be 0 or 1");
         c->atomic_acc = value;
+    } else if (!std::strcmp(key, "nu_deal")) {
+        if (value < 0 || value > 4096) return fail(c, FTTE_ERR_ARG, "nu_deal (tasks of one frequency group that follow each other on an XCD) must be 1..4096, or 0 for workgroup b -> group b mod nnu");
+        c->nu_deal = value;
+        return FTTE_OK; // (a launch-time choice: no plan depends on it; a captured hybrid sweep, option "graph", keeps the placement it was captured with -- same J)
     } else if (!std::strcmp(key, "ablate")) {
         if (value < 0 || value > 63) return fail(c, FTTE_ERR_ARG, "ablate is a mask of 6 bits");
         c->ablate = value;
@@ -431,6 +435,7 @@ long long ftte_counter(const ftte_ctx *c, const char *name)
     if (!std::strcmp(name, "brick_form")) return c->last_brick_form;
     if (!std::strcmp(name, "brick_dataflow")) return c->last_brick_dataflow;
     if (!std::strcmp(name, "brick_whole")) return c->last_brick_whole; // 1: the last sweep's stage launches took the whole-brick form
+    if (!std::strcmp(name, "nu_deal")) return c->nu_deal; // the option as it stands (its default before anybody set it)
     if (!std::strcmp(name, "brick_chunk")) return c->bplan.valid ? c->bplan.chunk : 0;
     if (!std::strcmp(name, "brick_queue_mix")) return (c->bplan.valid && c->bplan.persistent) ? c->bplan.key.queue_mix : -1;
     if (!std::strcmp(name, "brick_groups")) return c->bplan.valid ? (long long)c->bplan.groups.size() : 0;

@@ -314,8 +314,10 @@ __global__ void __launch_bounds__(64, WAVES) brick_kernel(const BrickLaunch L)
     // dataflow with write-through stores (sc1: the line goes to memory and leaves this XCD's L2) instead of an L2 write-back
     // before the flag
     const bool through = FLOW == 1 && L.pad_ != 0;
-    const int nu = L.nu0 + (int)(work % (unsigned)nnu);
-    const unsigned task_index = work / (unsigned)nnu;
+    // (the one-launch forms keep slot = work % nnu: their queues and flags are indexed by it)
+    const BrickWork W = brick_deal(work, (unsigned)nnu, FLOW ? 0u : (unsigned)L.deal);
+    const int nu = L.nu0 + (int)W.slot;
+    const unsigned task_index = W.task;
     // (the task list, the inflow and the group records are read-only for the launch and wave-uniform: scalar loads, address space 4)
     BrickTask T;
     {
@@ -672,10 +674,11 @@ __global__ void __launch_bounds__(128, WAVES) brick_pair_kernel(const BrickLaunc
     double *state = pair_lds + (size_t)wv * (max_dirs - 1) * H * 64; // this wave's parked rays
     double *handover = pair_lds + (size_t)2 * (max_dirs - 1) * H * 64; // [step parity][lane]
     const int nnu = L.nnu;
-    const int nu = L.nu0 + blockIdx.x % nnu;
+    const BrickWork W = brick_deal(blockIdx.x, (unsigned)nnu, (unsigned)L.deal);
+    const int nu = L.nu0 + (int)W.slot;
     BrickTask T;
     {
-        const unsigned long raw = ((const __attribute__((address_space(4))) unsigned long *)(unsigned long)L.tasks)[blockIdx.x / nnu];
+        const unsigned long raw = ((const __attribute__((address_space(4))) unsigned long *)(unsigned long)L.tasks)[W.task];
         T.group = (int16_t)(raw & 0xffffu); T.tu = (int16_t)((raw >> 16) & 0xffffu); T.tv = (int16_t)((raw >> 32) & 0xffffu); T.ti = (int16_t)(raw >> 48);
     }
     const int tu = uniform((int)T.tu), tv = uniform((int)T.tv), ti = uniform((int)T.ti) & (kBrickAccumulate - 1);

@@ -98,6 +98,7 @@ struct ftte_ctx {
     std::vector<Event> lane_done;
     Event ev_fork;
     int atomic_acc = 0;               // option "atomic_acc": later visitors of an accumulator add with fp64 atomics instead of read-add-store
+    int nu_deal = 16;                 // option "nu_deal": run length of the deal of a stage launch's frequency groups over the XCDs (brick_deal); 0: work % nnu
     int ablate = 0;                   // diagnostic option "ablate": parts of the brick kernel's memory traffic left out (wrong J; timing only)
     BrickDataflow bflow;              // flags, tickets and error word of the one-launch forms: brick_sweep prepares, wait_sweep checks
     int xcc_count = -1;               // XCC ids this device reports (census, ftte_brick.hip); -1: not taken yet

@@ -191,7 +191,8 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
         for (int masked = 0; masked < 2; ++masked) { // the stage's whole bricks, then those a box cuts through
             const size_t *off = &H.stage_off[(masked ? masked_lists : 0) + (size_t)half * H.nlist];
             if (off[l + 1] == off[l]) continue;
-            const BrickLaunch L = brick_launch(P, c->btables, off[l], off[l + 1], 0, nnu, nbase, face_elems, c->d_uvb, emit);
+            BrickLaunch L = brick_launch(P, c->btables, off[l], off[l + 1], 0, nnu, nbase, face_elems, c->d_uvb, emit);
+            L.deal = c->nu_deal;
             const int lrc = launch_brick(L, P.max_dirs, c->brick_waves, q, masked != 0);
             if (lrc) return fail(c, lrc == -1 ? FTTE_ERR_ARG : FTTE_ERR_NO_DEVICE, "brick kernel launch failed");
         }
@@ -211,7 +212,7 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
             const size_t l = (size_t)half * (size_t)FN.nstages + (size_t)st;
             if (FN.stage_off[l + 1] == FN.stage_off[l]) continue;
             BrickLaunch L = brick_launch(Q, V.fine_tables, FN.stage_off[l], FN.stage_off[l + 1], 0, nnu, (int64_t)FN.n * FN.n * FN.n, face_elems, c->d_uvb, emit);
-            L.sub = 1;
+            L.sub = 1; L.deal = c->nu_deal;
             const int lrc = launch_brick(L, Q.max_dirs, c->brick_waves, q, false);
             if (lrc) return fail(c, lrc == -1 ? FTTE_ERR_ARG : FTTE_ERR_NO_DEVICE, "brick kernel launch failed");
         }

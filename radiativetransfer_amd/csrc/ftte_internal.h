@@ -163,8 +163,31 @@ struct BrickLaunch {
     // chunk before the first; somebody has filled them (amr_fine_import_kernel) --, and the bricks at its downstream faces leave
     // theirs in their own rings and in chunk slot nti (nslot = nti + 1: no wrap), where the forest behind picks them up.
     int32_t sub;
+    // Stage launches (no ticket, no queue): how the launch's workgroups are dealt to (task, frequency slot) pairs, brick_deal below
+    // (option "nu_deal"; 0: workgroup b sweeps slot b % nnu of task b / nnu)
+    int32_t deal;
     ftte_consts math;
 };
+
+// Which (task, frequency slot) pair workgroup `work` of a stage launch sweeps.  Workgroups are dealt round-robin over the XCDs
+// (observed behaviour, not a contract), so with slot = work % nnu a launch of 4 groups always puts group nu0 + k on XCDs k and
+// k + 4, and the groups are not equally expensive: the optically thick ones pay the thick path of the segment.  Here the slots are
+// turned by one after every run of P * deal tasks, P = kXcds / gcd(nnu, kXcds) the tasks after which work % kXcds comes round
+// again: over a launch every XCD then sweeps every slot equally often, to within `deal` workgroups, and `deal` neighbouring tasks
+// of a slot stay behind one L2.  A bijection on (task, slot) for any nnu and deal; deal = 0: slot = work % nnu.
+constexpr unsigned kXcds = 8; // XCDs of gfx950 (MI355X).  Only the balance depends on it, no result does.
+struct BrickWork { unsigned task, slot; };
+FTTE_HD BrickWork brick_deal(unsigned work, unsigned nnu, unsigned deal)
+{
+    BrickWork W;
+    W.task = work / nnu;
+    W.slot = work - W.task * nnu;
+    if (deal) {
+        const unsigned low = nnu & (0u - nnu), g = low < kXcds ? low : kXcds; // gcd(nnu, kXcds): kXcds is a power of two
+        W.slot = (W.slot + W.task / (kXcds / g * deal)) % nnu;
+    }
+    return W;
+}
 
 // ---- refined cell arrays (ftte_amr.h) ------------------------------------------------------------------
 constexpr int kAmrBatch = 96; // most directions in flight in the forest path (what fits the device memory decides)

@@ -432,7 +432,7 @@ struct BrickSweep {
     BrickLaunch launch(size_t task0, size_t task1, int nu0, int nu1) const
     {
         BrickLaunch L = brick_launch(P, c->btables, task0, task1, nu0, nu1, c->ncell, P.face_elems, c->d_uvb, c->emit_mode);
-        L.tiled = tiled ? 1 : 0; L.pad2_ = c->ablate; L.atomic_acc = c->atomic_acc;
+        L.tiled = tiled ? 1 : 0; L.pad2_ = c->ablate; L.atomic_acc = c->atomic_acc; L.deal = c->nu_deal;
         return L;
     }
     int prepare(int ndir, const double *uvb), one_launch(), lane_stages(int lane, LaunchTiming &T), merge();
