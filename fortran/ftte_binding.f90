@@ -340,6 +340,35 @@ module ftte_binding
        real(c_double), intent(out) :: max_change
      end function ftte_solve_rate_equations
 
+     ! time-dependent ionisation: the species advanced over dt_s seconds in `substeps` implicit steps at the rates of the state on
+     ! entry, instead of replaced by their equilibrium; the other arguments as ftte_solve_rate_equations
+     integer(c_int) function ftte_advance_rate_equations(ctx, dt_s, substeps, run_uvb_transfer, J, ksi, uniform, &
+          self_shielding_threshold, use_point_rates, max_change) bind(C, name='ftte_advance_rate_equations')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       real(c_double), value :: dt_s
+       integer(c_int), value :: substeps, run_uvb_transfer, use_point_rates
+       real(c_double), intent(in) :: J(*)          ! (ncell, 3): Jmean1..3
+       real(c_double), intent(in) :: ksi(3,3)      ! (ksi24, ksi25, ksi26) x (group1, group2, group3)
+       real(c_double), intent(in) :: uniform(3)
+       real(c_double), value :: self_shielding_threshold
+       real(c_double), intent(out) :: max_change
+     end function ftte_advance_rate_equations
+
+     ! same with J in device memory (e.g. what ftte_diffuse_sweep_device wrote)
+     integer(c_int) function ftte_advance_rate_equations_device(ctx, dt_s, substeps, run_uvb_transfer, J_dev, ksi, uniform, &
+          self_shielding_threshold, use_point_rates, max_change) bind(C, name='ftte_advance_rate_equations_device')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       real(c_double), value :: dt_s
+       integer(c_int), value :: substeps, run_uvb_transfer, use_point_rates
+       type(c_ptr), value :: J_dev
+       real(c_double), intent(in) :: ksi(3,3)
+       real(c_double), intent(in) :: uniform(3)
+       real(c_double), value :: self_shielding_threshold
+       real(c_double), intent(out) :: max_change
+     end function ftte_advance_rate_equations_device
+
      integer(c_int) function ftte_get_medium(ctx, HI, HeI, HeII) bind(C, name='ftte_get_medium')
        import :: c_ptr, c_int, c_double
        type(c_ptr), value :: ctx

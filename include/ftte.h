@@ -322,6 +322,23 @@ int ftte_solve_rate_equations(ftte_ctx *ctx, int run_uvb_transfer, const double 
 int ftte_solve_rate_equations_device(ftte_ctx *ctx, int run_uvb_transfer, const double *J_dev, const double *ksi,
                                      const double *uniform, double self_shielding_threshold, int use_point_rates,
                                      double *max_change);
+/* Time-dependent ionisation at fixed temperature: HI, HeI, HeII of every leaf advanced over dt_s seconds instead of replaced by
+ * their equilibrium.  Arguments, preconditions and error texts those of ftte_solve_rate_equations.  Per cell: the incoming state
+ * clipped to the elements' budgets (HI <= nH, HeI <= nHe, HeII <= nHe - HeI, none negative); the rates per absorber formed from
+ * it exactly as the equilibrium update forms them, and held fixed for the whole call; `substeps` backward-Euler steps of
+ * dt_s / substeps, each closed by a bisection on the electron density run until its midpoint is an end of the bracket.  First
+ * order in the step; its stationary state is the equilibrium of the same rates (dt_s = 1e40 gives it to rounding).  The coupling
+ * to the transfer is explicit: J and the point-source rates are the caller's, from the state before the call.
+ * FTTE_ERR_ARG unless dt_s is finite and > 0 and 1 <= substeps <= 4096.  FTTE_ERR_RATES, the first failing cell named and the
+ * medium unchanged, where a species comes out not finite or outside its element's budget by more than rounding (an empty
+ * cell) or a bisection does not settle in 4096 steps.  max_change as there; ftte_rate_equation_steps counts the bisection
+ * steps of all substeps. */
+int ftte_advance_rate_equations(ftte_ctx *ctx, double dt_s, int substeps, int run_uvb_transfer, const double *J, const double *ksi,
+                                const double *uniform, double self_shielding_threshold, int use_point_rates, double *max_change);
+/* Same with J in device memory: a time step stays on the device */
+int ftte_advance_rate_equations_device(ftte_ctx *ctx, double dt_s, int substeps, int run_uvb_transfer, const double *J_dev,
+                                       const double *ksi, const double *uniform, double self_shielding_threshold,
+                                       int use_point_rates, double *max_change);
 /* HI, HeI, HeII of the device-resident medium, ncell each */
 int ftte_get_medium(ftte_ctx *ctx, double *HI, double *HeI, double *HeII);
 /* computeOpacities (equiSources.f90:4956-4983) on the device-resident medium: kappa[g] = HI beta[0][g] + HeI beta[1][g] +
@@ -332,7 +349,7 @@ int ftte_compute_opacities(ftte_ctx *ctx, int nnu, const double *beta);
  * HeII 1.58e-18) of the device-resident medium is at least the threshold, else 0.  J[nnu][ncell]. */
 int ftte_assign_uvb_radiation(ftte_ctx *ctx, int nnu, const double *uvb, double self_shielding_threshold, double *J);
 int ftte_assign_uvb_radiation_device(ftte_ctx *ctx, int nnu, const double *uvb, double self_shielding_threshold, double *J_dev);
-/* bisection steps of the last ftte_solve_rate_equations* or ftte_initial_ionization_equilibrium, summed over the cells (and
+/* bisection steps of the last ftte_solve_rate_equations*, ftte_advance_rate_equations* or ftte_initial_ionization_equilibrium, summed over the cells (and
  * over the passes of the latter) */
 long long ftte_rate_equation_steps(const ftte_ctx *ctx);
 /* The start-up ionisation equilibrium, equiSources.f90:1008-1022: initialIonizationEquilibrium (:3679-3868) `passes` times

@@ -577,6 +577,24 @@ class StellarTransfer(DiffuseTransfer):
         """Same with J[3][ncell] in device memory (e.g. what transport_device wrote)."""
         return self._solve(self._lib.ftte_solve_rate_equations_device, C.c_void_p(j_device_ptr), True, ksi, None, 0.0, use_point_rates)
 
+    # -- time-dependent ionisation: the same rates, the species advanced over dt instead of replaced by their equilibrium
+    def advance_rate_equations(self, dt: float, run_uvb: bool, J=None, ksi=None, uniform=None, threshold: float = 0.0,
+                               use_point_rates: bool = False, substeps: int = 1) -> float:
+        """HI, HeI, HeII of the device-resident medium advanced over dt seconds in `substeps` implicit steps at the rates of the
+        state on entry (arguments as solve_rate_equations).  Returns the largest change of a species fraction."""
+        J = None if J is None else _f64(J)
+        if J is not None and J.shape != (3, self.ncell):
+            raise ValueError("J must have shape [3][ncell]")
+        fn = self._lib.ftte_advance_rate_equations
+        return self._solve(lambda ctx, *rest: fn(ctx, float(dt), int(substeps), *rest), None if J is None else _dp(J), run_uvb, ksi, uniform,
+                           threshold, use_point_rates)
+
+    def advance_rate_equations_device(self, dt: float, j_device_ptr: int, ksi, use_point_rates: bool = False, substeps: int = 1) -> float:
+        """Same with J[3][ncell] in device memory (e.g. what transport_device wrote)."""
+        fn = self._lib.ftte_advance_rate_equations_device
+        return self._solve(lambda ctx, *rest: fn(ctx, float(dt), int(substeps), *rest), C.c_void_p(j_device_ptr), True, ksi, None, 0.0,
+                           use_point_rates)
+
     def medium(self):
         out = [np.empty(max(self.ncell, 1)) for _ in range(3)]
         self._ok(self._lib.ftte_get_medium(self._ctx, *[_dp(a) for a in out]))

@@ -1,5 +1,5 @@
 // ftte_chem.cpp -- the entry points of include/ftte.h that read or write the species medium (ftte_ctx::gas) outside the tracer: the
-// ionisation chemistry (rate coefficients, temperature, the equilibrium update, the start-up equilibrium, the hydrogen census), the
+// ionisation chemistry (rate coefficients, temperature, the equilibrium update, the advance over a time step, the start-up equilibrium, the hydrogen census), the
 // species' way out, the opacities and the thin-limit radiation made from them, and the start-up expansion of HII regions (kernel:
 // ftte_expansion.hip).  The chemistry's own state is ftte_ctx::chem.
 #include "ftte_chem_math.h"
@@ -75,30 +75,52 @@ template <typename Own> int chem_update(ftte_ctx *c, const ChemUpdate &U, Own ow
     return FTTE_OK;
 }
 
+// The fields of the record that name the rates of the moment -- the transfer's J or the uniform background, with or without the
+// point sources' rates -- from the arguments solveRateEquations and the advance over dt share; J goes to the device if it is not there
+int rate_arguments(ftte_ctx *c, ChemRec &R, const char *who, int run_uvb, const double *J, bool J_on_device, const double *ksi,
+                   const double *uniform, double threshold, int use_point_rates)
+{
+    const PointRates &P = c->point.rates;
+    if (run_uvb && (!J || !ksi)) return fail(c, FTTE_ERR_ARG, std::string(who) + ": the transfer-driven update needs J and ksi");
+    if (!run_uvb && !uniform) return fail(c, FTTE_ERR_ARG, std::string(who) + ": the uniform-background update needs the background rates");
+    if (use_point_rates && !P.ready(c->ncell))
+        return fail(c, FTTE_ERR_STATE, std::string(who) + ": no point-source rates (ftte_set_zero_rates / ftte_point_sources)");
+    if (run_uvb && !J_on_device) {
+        const size_t nc = (size_t)c->ncell;
+        FTTE_HIP(c, c->chem.J.reserve(3 * nc));
+        FTTE_HIP(c, hipMemcpyAsync(c->chem.J, J, sizeof(double) * 3 * nc, hipMemcpyHostToDevice, c->stream));
+        J = c->chem.J;
+    }
+    R.J = run_uvb ? J : nullptr;
+    R.krate = use_point_rates ? P.packed() : nullptr;
+    R.run_uvb = run_uvb ? 1 : 0;
+    if (ksi) std::memcpy(R.ksi, ksi, sizeof R.ksi);
+    if (uniform) std::memcpy(R.uniform, uniform, sizeof R.uniform);
+    R.threshold = threshold;
+    return FTTE_OK;
+}
+
 // solveRateEquations (equiSources.f90:3459-3677; it stops at :3637-3654)
 int solve_rates(ftte_ctx *c, int run_uvb, const double *J, bool J_on_device, const double *ksi, const double *uniform, double threshold,
                 int use_point_rates, double *max_change, const char *who)
 {
     const ChemUpdate U{who, "species fraction outside [0, 1]", launch_rate_equations};
     return chem_update(c, U, [&](ChemRec &R) -> int {
-        const PointRates &P = c->point.rates;
-        if (run_uvb && (!J || !ksi)) return fail(c, FTTE_ERR_ARG, std::string(who) + ": the transfer-driven update needs J and ksi");
-        if (!run_uvb && !uniform) return fail(c, FTTE_ERR_ARG, std::string(who) + ": the uniform-background update needs the background rates");
-        if (use_point_rates && !P.ready(c->ncell))
-            return fail(c, FTTE_ERR_STATE, std::string(who) + ": no point-source rates (ftte_set_zero_rates / ftte_point_sources)");
-        if (run_uvb && !J_on_device) {
-            const size_t nc = (size_t)c->ncell;
-            FTTE_HIP(c, c->chem.J.reserve(3 * nc));
-            FTTE_HIP(c, hipMemcpyAsync(c->chem.J, J, sizeof(double) * 3 * nc, hipMemcpyHostToDevice, c->stream));
-            J = c->chem.J;
-        }
-        R.J = run_uvb ? J : nullptr;
-        R.krate = use_point_rates ? P.packed() : nullptr;
-        R.run_uvb = run_uvb ? 1 : 0;
-        if (ksi) std::memcpy(R.ksi, ksi, sizeof R.ksi);
-        if (uniform) std::memcpy(R.uniform, uniform, sizeof R.uniform);
-        R.threshold = threshold;
-        return FTTE_OK;
+        return rate_arguments(c, R, who, run_uvb, J, J_on_device, ksi, uniform, threshold, use_point_rates);
+    }, max_change);
+}
+
+// The species advanced over dt in `substeps` implicit steps at the same rates (chem_advance_cell; the build's own, the reference
+// has no time step)
+int advance_rates(ftte_ctx *c, double dt, int substeps, int run_uvb, const double *J, bool J_on_device, const double *ksi, const double *uniform,
+                  double threshold, int use_point_rates, double *max_change, const char *who)
+{
+    const ChemUpdate U{who, "species not finite or outside their element's budget, or no convergence,", launch_advance_equations};
+    return chem_update(c, U, [&](ChemRec &R) -> int {
+        if (!std::isfinite(dt) || !(dt > 0.)) return fail(c, FTTE_ERR_ARG, std::string(who) + ": dt_s must be finite and positive");
+        if (substeps < 1 || substeps > 4096) return fail(c, FTTE_ERR_ARG, std::string(who) + ": substeps must lie in 1 .. 4096");
+        R.dt = dt; R.substeps = substeps;
+        return rate_arguments(c, R, who, run_uvb, J, J_on_device, ksi, uniform, threshold, use_point_rates);
     }, max_change);
 }
 
@@ -290,6 +312,20 @@ int ftte_solve_rate_equations_device(ftte_ctx *c, int run_uvb_transfer, const do
 {
     return solve_rates(c, run_uvb_transfer, J_dev, true, ksi, uniform, self_shielding_threshold, use_point_rates, max_change,
                        "ftte_solve_rate_equations_device");
+}
+
+int ftte_advance_rate_equations(ftte_ctx *c, double dt_s, int substeps, int run_uvb_transfer, const double *J, const double *ksi,
+                                const double *uniform, double self_shielding_threshold, int use_point_rates, double *max_change)
+{
+    return advance_rates(c, dt_s, substeps, run_uvb_transfer, J, false, ksi, uniform, self_shielding_threshold, use_point_rates, max_change,
+                         "ftte_advance_rate_equations");
+}
+
+int ftte_advance_rate_equations_device(ftte_ctx *c, double dt_s, int substeps, int run_uvb_transfer, const double *J_dev, const double *ksi,
+                                       const double *uniform, double self_shielding_threshold, int use_point_rates, double *max_change)
+{
+    return advance_rates(c, dt_s, substeps, run_uvb_transfer, J_dev, true, ksi, uniform, self_shielding_threshold, use_point_rates, max_change,
+                         "ftte_advance_rate_equations_device");
 }
 
 // initialIonizationEquilibrium (it stops at equiSources.f90:3809-3818, :3832-3843)

@@ -1,5 +1,5 @@
 // ftte_chem.hip -- the kernels behind ftte_chem.cpp: the ionisation equilibrium of every leaf (solveRateEquations,
-// initialIonizationEquilibrium), the optically thin radiation field, the hydrogen census and the opacities.  The chemistry of a
+// initialIonizationEquilibrium), its advance over a time step, the optically thin radiation field, the hydrogen census and the opacities.  The chemistry of a
 // cell is ftte_chem_math.h, compiled here for the device and by the tests' host library for the host; an equilibrium kernel is the
 // grid-stride loop, the cell's loads, one call into that header and the cell's stores, and then the fold of its statistics.
 #include <hip/hip_runtime.h>
@@ -81,6 +81,29 @@ __global__ void __launch_bounds__(256) initial_equilibrium_kernel(const ChemRec 
     fold_statistics<false>(R, 0ull, my_steps, my_bad);
 }
 
+// HI, HeI, HeII of every leaf advanced over R.dt in R.substeps implicit steps at the rates of the state on entry (chem_advance_cell)
+__global__ void __launch_bounds__(256) advance_equations_kernel(const ChemRec R)
+{
+    unsigned long long my_change = 0ull, my_steps = 0ull, my_bad = ~0ull;
+    const ChemTable T = {R.k, R.nratec, R.logtem0, R.logtem9, R.dlogtem};
+    for (long c = (long)blockIdx.x * blockDim.x + threadIdx.x; c < R.ncell; c += (long)gridDim.x * blockDim.x) {
+        double p24 = 0., p25 = 0., p26 = 0., HI, HeI, HeII, change;
+        if (R.krate) { p24 = R.krate[c * kCellRec]; p25 = R.krate[c * kCellRec + 1]; p26 = R.krate[c * kCellRec + 2]; }
+        unsigned long long steps;
+        const int ok = chem_advance_cell(&T, R.rho[c], R.logtem[c], R.HI[c], R.HeI[c], R.HeII[c], chem_cell_volume(R.box, R.level[c], R.n),
+                                         R.krate != nullptr, p24, p25, p26, R.run_uvb ? R.J + c : nullptr, R.ncell, R.ksi, R.uniform, R.threshold,
+                                         R.dt, R.substeps, &HI, &HeI, &HeII, &steps, &change);
+        my_steps += steps;
+        if (!ok) my_bad = (unsigned long long)c < my_bad ? (unsigned long long)c : my_bad;
+        else {
+            const unsigned long long bits = (unsigned long long)__double_as_longlong(change);
+            my_change = bits > my_change ? bits : my_change;
+            R.HI_out[c] = HI; R.HeI_out[c] = HeI; R.HeII_out[c] = HeII;
+        }
+    }
+    fold_statistics<true>(R, my_change, my_steps, my_bad);
+}
+
 // (enough workgroups to fill the GPU several times over, few enough that their atomics are nothing)
 static int launch_equilibrium(void (*kernel)(const ChemRec), const ChemRec &R, hipStream_t stream)
 {
@@ -95,6 +118,11 @@ int launch_rate_equations(const ChemRec &R, hipStream_t stream) { return launch_
 int launch_initial_equilibrium(const ChemRec &R, hipStream_t stream)
 {
     return R.ncell > 0 && R.passes < 1 ? -1 : launch_equilibrium(initial_equilibrium_kernel, R, stream);
+}
+
+int launch_advance_equations(const ChemRec &R, hipStream_t stream)
+{
+    return R.ncell > 0 && (R.substeps < 1 || !(R.dt > 0.)) ? -1 : launch_equilibrium(advance_equations_kernel, R, stream);
 }
 
 // assignUvbRadiation, transportRoutinesModule.f90:1056-1093: the optically thin alternative to the sweep.  J_g = uvb_g where the

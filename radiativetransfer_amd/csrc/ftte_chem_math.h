@@ -5,7 +5,8 @@
  * helium balance, and the closing statements for HII, HI, HeII with the reference's test of the fractions.  Every
  * statement keeps the reference's operation order (each operation an IEEE add, multiply or divide; the logarithm of the
  * temperature comes from the host) and its line reference.  What differs between the two routines is four parameters of
- * chem_bisect, literals at its two call sites.
+ * chem_bisect, literals at its two call sites.  Below them stands the build's own time-dependent step over dt
+ * (chem_advance_cell), on the same densities, coefficients and rates.
  *
  * Conventions of ftte_math.h: FTTE_HD functions, plain C11 plus HIP, no templates, lambdas or references -- the same
  * source is compiled by hipcc into the kernels of ftte_chem.hip and by gcc into the tests' host library (fo_device_solve_rate_equations,
@@ -167,6 +168,33 @@ FTTE_HD int chem_close(const ChemEq *q, double de, double HeI, double *HI_out, d
     return (HI / q->nh >= 0. && HI / q->nh <= 1.) && (HeI / q->nhe >= 0. && HeI / q->nhe <= 1.);
 }
 
+/* The photo-ionisation rates per absorber, in two parts that each take the absorbers HI, HeI, HeII as their caller sees them.
+ * First the point sources' rates per cell over the absorbers in the cell, :3520-3542; arguments as chem_solve_cell's. */
+FTTE_HD void chem_point_rates(ChemEq *q, double HI, double HeI, double HeII, double vol, int point, double p24, double p25, double p26)
+{
+    q->kr24 = (point && HI > 0.) ? p24 / (vol * HI) : 0.;
+    q->kr25 = (point && HeII > 0.) ? p25 / (vol * HeII) : 0.;
+    q->kr26 = (point && HeI > 0.) ? p26 / (vol * HeI) : 0.;
+    q->kr24 = fmax(q->kr24, 0.); q->kr25 = fmax(q->kr25, 0.); q->kr26 = fmax(q->kr26, 0.);
+}
+
+/* Then, added to them, either the transfer's J, :3545-3553, or the uniform background where the Lyman-limit mean free path
+ * of HI, HeI, HeII is at least the self-shielding threshold, :3554-3562 */
+FTTE_HD void chem_radiation_rates(ChemEq *q, double HI, double HeI, double HeII, const double *J, long J_stride, const double *ksi,
+                                  const double *uniform, double threshold)
+{
+    if (J) { /* :3545-3553 */
+        const double t1 = 4. * FTTE_PI * J[0], t2 = 4. * FTTE_PI * J[J_stride], t3 = 4. * FTTE_PI * J[2 * J_stride];
+        q->kr24 = q->kr24 + t1 * ksi[0] + t2 * ksi[3] + t3 * ksi[6];
+        q->kr25 = q->kr25 + t3 * ksi[7];
+        q->kr26 = q->kr26 + t2 * ksi[5] + t3 * ksi[8];
+    } else if (chem_mean_free_path(HI, HeI, HeII) >= threshold) { /* :3554-3562 */
+        q->kr24 = q->kr24 + 4. * FTTE_PI * uniform[0];
+        q->kr25 = q->kr25 + 4. * FTTE_PI * uniform[1];
+        q->kr26 = q->kr26 + 4. * FTTE_PI * uniform[2];
+    }
+}
+
 /* solveRateEquations for one cell.  In: the cell's state and its rates -- the point sources' rates per cell (point != 0: p24,
  * p25, p26 = krate24, krate25, krate26) plus either the transfer's J (J != NULL: the cell's three groups at J[0], J[J_stride],
  * J[2 J_stride]; ksi[group][ksi24, ksi25, ksi26]) or the uniform background behind the self-shielding test.  Out: whether the
@@ -184,21 +212,8 @@ FTTE_HD int chem_solve_cell(const ChemTable *T, double rho, double logtem, doubl
     q.nh = chem_nh(rho); q.nhe = chem_nhe(rho);
     double HI = fmin(HI0, q.nh), HeI = HeI0, HeII = HeII0, de, HeIprev;
     if (q.nhe - HeI0 - HeII0 < 0. && HeII < 0.) HeII = 0.; /* :3504-3513: only this survives of the branch */
-    /* rates per cell -> per absorber, :3520-3542 */
-    q.kr24 = (point && HI > 0.) ? p24 / (vol * HI) : 0.;
-    q.kr25 = (point && HeII > 0.) ? p25 / (vol * HeII) : 0.;
-    q.kr26 = (point && HeI > 0.) ? p26 / (vol * HeI) : 0.;
-    q.kr24 = fmax(q.kr24, 0.); q.kr25 = fmax(q.kr25, 0.); q.kr26 = fmax(q.kr26, 0.);
-    if (J) { /* :3545-3553 */
-        const double t1 = 4. * FTTE_PI * J[0], t2 = 4. * FTTE_PI * J[J_stride], t3 = 4. * FTTE_PI * J[2 * J_stride];
-        q.kr24 = q.kr24 + t1 * ksi[0] + t2 * ksi[3] + t3 * ksi[6];
-        q.kr25 = q.kr25 + t3 * ksi[7];
-        q.kr26 = q.kr26 + t2 * ksi[5] + t3 * ksi[8];
-    } else if (chem_mean_free_path(HI, HeI, HeII) >= threshold) { /* :3554-3562 */
-        q.kr24 = q.kr24 + 4. * FTTE_PI * uniform[0];
-        q.kr25 = q.kr25 + 4. * FTTE_PI * uniform[1];
-        q.kr26 = q.kr26 + 4. * FTTE_PI * uniform[2];
-    }
+    chem_point_rates(&q, HI, HeI, HeII, vol, point, p24, p25, p26); /* :3520-3542 */
+    chem_radiation_rates(&q, HI, HeI, HeII, J, J_stride, ksi, uniform, threshold);
     chem_coefficients(T, logtem, &q);
     const unsigned steps = *steps_out = chem_bisect(&q, (double)1.e-30f, 1, 1, 1, &de, &HeI, &HeIprev, tame_out);
     const int ok = chem_close(&q, de, HeI, &HI, &HeII) && steps < CHEM_MAX_STEPS;
@@ -244,6 +259,112 @@ FTTE_HD int chem_initial_cell(const ChemTable *T, double rho, double logtem, dou
         cHeI = HeI;
     }
     *HI_out = cHI; *HeI_out = cHeI; *HeII_out = cHeII;
+    return ok;
+}
+
+/* ---- time-dependent ionisation: one implicit step over dt ---------------------------------------------------------------
+ *
+ * The rate equations whose balance is the residual above (:3592-3602), at fixed temperature and fixed rates per absorber,
+ *   dHI/dt   = k2 de HII - (k1 de + kr24) HI
+ *   dHeI/dt  = Y HeII - X HeI                                   X = k3 de + kr26, Y = k4 de
+ *   dHeII/dt = X HeI - (Y + W) HeII + Z HeIII                   W = k5 de + kr25, Z = k6 de
+ * with HII = nh - HI and HeIII = nhe - HeI - HeII put in, stepped by backward Euler at a trial electron density de, and de
+ * closed by bisection on charge neutrality.  Nothing here is the reference's (it has no time step); the stationary state of
+ * the step is its equilibrium. */
+
+/* by how much a species fraction may leave [0, 1] and count as rounding */
+#define CHEM_ADVANCE_SLACK 0x1p-48
+
+/* One backward-Euler step of length h at electron density de.  Hydrogen is linear in HI.  Helium is the 2x2 system
+ *   (1 + hX) HeI' - hY HeII' = HeI,   -h(X - Z) HeI' + (1 + h(Y + W + Z)) HeII' = HeII + hZ nhe
+ * by Cramer's rule, the determinant 1 + h(X + Y + W + Z) + h^2 (XW + XZ + YZ) and both numerators multiplied out into sums of
+ * non-negative terms (HeI <= nhe on entry): no difference of products, nothing cancels, and HeI' + HeII' <= nhe to rounding.
+ * The powers of h stay inside the products hX, hY, hW, hZ, so that a step of 1e40 s overflows nothing. */
+FTTE_HD void chem_advance_step(const ChemEq *q, double h, double de, double HI, double HeI, double HeII, double *HI1, double *HeI1,
+                               double *HeII1)
+{
+    const double a = q->k1 * de + q->kr24, b = q->k2 * de;
+    *HI1 = (HI + h * b * q->nh) / (1. + h * (a + b));
+    const double hX = h * (q->k3 * de + q->kr26), hY = h * (q->k4 * de), hW = h * (q->k5 * de + q->kr25), hZ = h * (q->k6 * de);
+    const double det = 1. + (hX + hY + hW + hZ) + (hX * hW + hX * hZ + hY * hZ);
+    *HeI1 = (HeI * (1. + (hY + hW + hZ)) + hY * (HeII + hZ * q->nhe)) / det;
+    *HeII1 = (HeII + hZ * (q->nhe - HeI) + hX * (HeII + HeI) + hX * hZ * q->nhe) / det;
+}
+
+/* The step closed: bisection on de over [1e-30, nh + 2 nhe] of de - (HII' + HeII' + 2 HeIII'), until the midpoint is an end
+ * of the bracket (or CHEM_MAX_STEPS moves of the bracket).  Returns the moves; the species are those at the last midpoint. */
+FTTE_HD unsigned chem_advance_close(const ChemEq *q, double h, double *HI, double *HeI, double *HeII)
+{
+    double de1 = (double)1.e-30f, de2 = q->nh + 2. * q->nhe, HI1, HeI1, HeII1;
+    unsigned steps = 0;
+    for (;;) {
+        const double de = 0.5 * (de1 + de2);
+        chem_advance_step(q, h, de, *HI, *HeI, *HeII, &HI1, &HeI1, &HeII1);
+        if (de == de1 || de == de2 || steps >= CHEM_MAX_STEPS) break;
+        const double res = de - ((q->nh - HI1) + HeII1 + 2. * (q->nhe - HeI1 - HeII1));
+        if (res > 0.) de2 = de;
+        else de1 = de;
+        ++steps;
+    }
+    *HI = HI1; *HeI = HeI1; *HeII = HeII1;
+    return steps;
+}
+
+/* a state within the elements' budgets: HI <= nh, HeI <= nhe, HeII <= nhe - HeI, none negative */
+FTTE_HD void chem_advance_clip(const ChemEq *q, double *HI, double *HeI, double *HeII)
+{
+    *HI = fmax(fmin(*HI, q->nh), 0.);
+    *HeI = fmax(fmin(*HeI, q->nhe), 0.);
+    *HeII = fmax(fmin(*HeII, q->nhe - *HeI), 0.);
+}
+
+/* What a call fixes for a cell before its first step: the densities, the incoming state clipped to the elements' budgets
+ * (*HI, *HeI, *HeII on return), the rates per absorber and the coefficients.  The rates are formed by the statements that
+ * form chem_solve_cell's: the point sources' over the absorbers of the clipped state (none where there are none); the
+ * self-shielding test on the incoming state as the equilibrium routines take it -- HI no more than nh, HeI and HeII as they
+ * come -- so that a cell over its helium budget is shielded or lit here as it is there. */
+FTTE_HD void chem_advance_setup(const ChemTable *T, ChemEq *q, double rho, double logtem, double *HI, double *HeI, double *HeII, double vol,
+                                int point, double p24, double p25, double p26, const double *J, long J_stride, const double *ksi,
+                                const double *uniform, double threshold)
+{
+    q->nh = chem_nh(rho); q->nhe = chem_nhe(rho);
+    const double HI0 = fmin(*HI, q->nh), HeI0 = *HeI, HeII0 = *HeII;
+    chem_advance_clip(q, HI, HeI, HeII);
+    chem_point_rates(q, *HI, *HeI, *HeII, vol, point, p24, p25, p26);
+    chem_radiation_rates(q, HI0, HeI0, HeII0, J, J_stride, ksi, uniform, threshold);
+    chem_coefficients(T, logtem, q);
+}
+
+/* HI, HeI, HeII of one cell advanced over dt in `substeps` equal steps.  In: as chem_solve_cell, and dt [s].  The rates per
+ * absorber (chem_advance_setup) stay fixed for the whole call, substeps included.  Out: whether the cell got through (else: an
+ * output that is not finite, HI'/nh or (HeI' + HeII')/nhe outside [0, 1] by more than rounding, or a bisection that hit the
+ * cap), the new species, the bisection steps of all substeps, and chem_solve_cell's measure of the change. */
+FTTE_HD int chem_advance_cell(const ChemTable *T, double rho, double logtem, double HI0, double HeI0, double HeII0, double vol, int point,
+                              double p24, double p25, double p26, const double *J, long J_stride, const double *ksi, const double *uniform,
+                              double threshold, double dt, int substeps, double *HI_out, double *HeI_out, double *HeII_out,
+                              unsigned long long *steps_out, double *change_out)
+{
+    ChemEq q;
+    double HI = HI0, HeI = HeI0, HeII = HeII0;
+    chem_advance_setup(T, &q, rho, logtem, &HI, &HeI, &HeII, vol, point, p24, p25, p26, J, J_stride, ksi, uniform, threshold);
+    const double h = dt / (double)substeps;
+    unsigned long long steps = 0ull;
+    int ok = 1;
+    for (int s = 0; s < substeps && ok; ++s) {
+        if (s) chem_advance_clip(&q, &HI, &HeI, &HeII); /* a substep takes its state as a call does: the sums' rounding does not add up */
+        const unsigned n = chem_advance_close(&q, h, &HI, &HeI, &HeII);
+        steps += (unsigned long long)n;
+        ok = n < CHEM_MAX_STEPS;
+    }
+    const double fH = HI / q.nh, fHe = (HeI + HeII) / q.nhe;
+    /* (a NaN fails every comparison; an infinity the range) */
+    ok = ok && fH >= -CHEM_ADVANCE_SLACK && fH <= 1. + CHEM_ADVANCE_SLACK && fHe >= -CHEM_ADVANCE_SLACK && fHe <= 1. + CHEM_ADVANCE_SLACK &&
+         HeI >= -CHEM_ADVANCE_SLACK * q.nhe && HeII >= -CHEM_ADVANCE_SLACK * q.nhe;
+    const double c1 = fabs(HI - HI0) * FTTE_MH / (FTTE_PSI * rho), c2 = fabs(HeI - HeI0) * FTTE_MHE / ((1. - FTTE_PSI) * rho),
+                 c3 = fabs(HeII - HeII0) * FTTE_MHE / ((1. - FTTE_PSI) * rho);
+    *change_out = fmax(c1, fmax(c2, c3));
+    *HI_out = HI; *HeI_out = HeI; *HeII_out = HeII;
+    *steps_out = steps;
     return ok;
 }
 

@@ -320,6 +320,8 @@ struct ChemRec {
     unsigned long long *first_bad; // lowest cell index at which the reference would stop, or ~0
     unsigned long long *max_change; // bits of the largest change of a species fraction
     unsigned long long *steps;      // bisection steps taken, all cells
+    double dt;                 // advance_equations_kernel only: the time to advance over [s], in `substeps` equal steps
+    int32_t substeps;
 };
 
 } // namespace ftte

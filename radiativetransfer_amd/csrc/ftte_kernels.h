@@ -58,6 +58,8 @@ int launch_repack_rates(double *planes, double *packed, long ncell, bool to_pack
 int launch_rate_equations(const ChemRec &R, hipStream_t stream);
 // the start-up equilibrium (initialIonizationEquilibrium), R.passes times per leaf; R.krate, R.J, R.run_uvb, R.ksi unused
 int launch_initial_equilibrium(const ChemRec &R, hipStream_t stream);
+// HI, HeI, HeII of every leaf advanced over R.dt in R.substeps implicit steps; R.passes unused
+int launch_advance_equations(const ChemRec &R, hipStream_t stream);
 // computeMass over the leaves: part[kMassParts]; the neutral and the total hydrogen mass [msun] land in part[2 kMassBlocks], [+1]
 constexpr int kMassBlocks = 1024;
 constexpr int kMassParts = 2 * kMassBlocks + 2;

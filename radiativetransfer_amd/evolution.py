@@ -1,0 +1,62 @@
+"""Time-dependent ionisation: the reference's loop with its equilibrium update replaced by an advance over dt.
+
+A step is what an iteration of the reference's loop is (equiSources.f90:1811-1819) -- zero the rates, trace the point sources, make
+the opacities from the medium, sweep the diffuse field into J -- followed by StellarTransfer.advance_rate_equations_device in
+place of solveRateEquations.  Everything stays on the device; per step only the two masses of hydrogen_mass() come back.
+
+The coupling is explicit: the rates and J of a step are those of the state at its start, held fixed over dt.  The chemistry
+itself is implicit and stable for any dt; the ionisation front is not resolved in time unless dt is short against the time the
+front takes to cross a cell."""
+from __future__ import annotations
+
+from typing import Callable, Optional, Sequence, Tuple
+
+import numpy as np
+
+
+def evolve(st, dt: float, nsteps: int, sources: Optional[Tuple[Sequence[int], Sequence[float]]] = None, directions=None, beta=None, uvb=None,
+           ksi=None, substeps: int = 1, on_step: Optional[Callable] = None):
+    """Advance the medium of the StellarTransfer `st` over nsteps steps of dt seconds each.
+
+    st          a StellarTransfer with grid, medium (with rho), rate coefficients, temperature and, for sources, rate tables set
+    sources     (cells, ndot): 0-based cell-array indices of the stars and their photon rates, or None
+    directions  (phi, theta, weight) of the diffuse sweep
+    beta        [3][nnu] cross sections per species and frequency group (compute_opacities_from_medium); nnu must be 3
+    uvb         [nnu] the background's intensity entering the box
+    ksi         [3][3] = [group][ksi24, ksi25, ksi26]
+    substeps    implicit steps per dt, at the rates of the step's start
+    on_step     called as on_step(step, st, J) after each step, J the step's [3][ncell] device tensor (for inspection; the rates of
+                the step are still on the device)
+
+    Returns (times, neutral): times[nsteps + 1] in seconds from 0 and neutralHydrogenMass / totalHydrogenMass at each."""
+    import torch
+
+    if directions is None or beta is None or uvb is None or ksi is None:
+        raise ValueError("evolve needs directions, beta, uvb and ksi")
+    if nsteps < 0:
+        raise ValueError("nsteps must not be negative")
+    phi, theta, weight = directions
+    beta = np.ascontiguousarray(beta, dtype=np.float64)
+    if beta.ndim != 2 or beta.shape != (3, 3):
+        raise ValueError("beta must have shape [3][3]: the update takes J in three frequency groups")
+    J = torch.empty((3, st.ncell), dtype=torch.float64, device="cuda")  # (the current device, which is the context's by default)
+    stream = torch.cuda.current_stream()
+
+    def fraction():
+        neutral, total = st.hydrogen_mass()
+        return neutral / total
+
+    times, neutral = [0.0], [fraction()]
+    for step in range(nsteps):
+        st.set_zero_rates()
+        if sources is not None:
+            st.point_sources(*sources)
+        st.compute_opacities_from_medium(beta)
+        st.transport_device(phi, theta, weight, uvb, J.data_ptr(), stream.cuda_stream)
+        stream.synchronize()
+        st.advance_rate_equations_device(dt, J.data_ptr(), ksi, use_point_rates=True, substeps=substeps)
+        if on_step is not None:
+            on_step(step, st, J)
+        times.append((step + 1) * float(dt))
+        neutral.append(fraction())
+    return np.array(times), np.array(neutral)
