@@ -507,7 +507,7 @@ int ftte_host_unregister(ftte_ctx *ctx, void *ptr);
  * -1 for an unknown name. */
 long long ftte_counter(const ftte_ctx *ctx, const char *name);
 
-/* Tuning knobs.  0 means "automatic" where noted.  Results do not depend on any of them except through the order in which the
+/* Tuning knobs.  0 means automatic where noted.  Every option belongs to the context it is set on.  Results do not depend on any of them except through the order in which the
  * directions' contributions are added into J (last bits); unknown keys return FTTE_ERR_ARG.
  *   uniform grids
  *     "engine"      0 automatic = 2 cell-fixed bricks, 1 ray-following tiles (3a)
@@ -527,13 +527,16 @@ long long ftte_counter(const ftte_ctx *ctx, const char *name);
  *                   every L2 and gains nothing with two streams; 4 to 64 measured alike)
  *     "merge_overlap" bricks: 1 (default) = J merged block by block (32^3 cells) while the last stages run, 0 = one merge after
  *                   the last stage; same results
- *     "team"        bricks: 0 = one wavefront per brick, 2 = two wavefronts per
- *                   brick, four rows each ("pair_waves": workgroups per SIMD that form is compiled for, 2..4); -1 (default):
- *                   2 with up to four frequency groups on this GPU, else 0
+ *     "team"        bricks: 0 = one wavefront per brick, 2 = two wavefronts per brick, four rows each; -1 (default): 2 with up to
+ *                   four frequency groups on this GPU, else 0
+ *     "pair_waves"  bricks, two wavefronts per brick: workgroups per SIMD that form is compiled for, 2..4
  *     "rows", "stack", "slots", "waves"  tiles: rays per lane (4, 8, 16), wavefronts per workgroup (1, 2, 4, 8), directions in flight
  *                   per launch (1..16), waves per SIMD (2..6); built variants rows x stack = 4x{1,4,8}, 8x{1,2,4}, 16x1
  *   refined cell arrays
  *     "hybrid"      1 bricks outside boxes around the refined cells, segment forests inside (default; 3b), 0 forests for the whole tree
+ *     "hybrid_slots" hybrid: where the bricks' launches go around the passes of the forests: 0 = phases (a phase of brick stages per
+ *                   pass), 1 (default) = slots where there are several passes (every brick in the earliest launch its own inputs
+ *                   allow), 2 = slots always
  *     "pipelines"   hybrid: independent bricks-forests-bricks sequences on streams of their own, 1..4 (default 3)
  *     "box_lanes"   hybrid: along a brick's 64 lanes the boxes end on multiples of this (a divisor of 64; default 1: one cell beyond
  *                   the refined cells)
@@ -546,7 +549,8 @@ long long ftte_counter(const ftte_ctx *ctx, const char *name);
  *     "forest_fuse" runs of forest levels with at most this many (segment, frequency group) pairs in the fullest direction go in ONE
  *                   launch, a workgroup per direction and a barrier per level (default 4096; 0: a launch per level).  Same bits.
  *     "forest"      1: use the segment forests on a uniform grid too, for cross-checks
- *   "ldspad"        diagnostic: extra dynamic LDS per workgroup (bytes), to cap residency
+ *   "ldspad"        diagnostic, per context like every option: extra dynamic LDS per workgroup of this context's sweep launches
+ *                   (bytes, 0..163840), to cap residency
  *   "atomic_acc"    bricks: 1 = later visitors of a shared accumulator add with fp64 atomics instead of read-add-store (default 0)
  *   "queue_mix"     bricks, dataflow = 3: how (frequency group, accumulator) units are dealt to the XCDs' queues: 0 a frequency
  *                   group per queue where they divide, 1 by load, 2 (group + accumulator) mod queues

@@ -127,7 +127,6 @@ int ftte_set_grid(ftte_ctx *c, int nx, int ny, int nz, int64_t ncell, const int3
     c->plan.valid = false;
     c->bplan.valid = false;
     c->tree = std::move(tree);
-    c->use_forest = c->tree.refined() || c->force_forest;
     return FTTE_OK;
 }
 
@@ -158,7 +157,7 @@ int ftte_set_opacity_device(ftte_ctx *c, int nnu, const double *kappa_dev)
     // A uniform grid whose last sweep used the transposed layout 2 (the copy is there): the copy and the transposes in one pass over
     // the caller's array, layout 1 too where the last sweep used it (the tile engine; the brick engine marches layout 1 through
     // layout 0).  Else the copy alone; the sweep makes what it needs.
-    const bool same = !c->use_forest && c->nnu == nnu && !c->tiled_opt;
+    const bool same = !c->use_forest() && c->nnu == nnu && !c->opt.launch.tiled;
     const bool with2 = same && c->kappa.current(MediumField::kLayout2), with1 = with2 && c->kappa.current(MediumField::kLayout1);
     if (with2) {
         if (launch_set_layouts(kappa_dev, c->kappa.source(), with1 ? c->kappa.in_layout(1) : nullptr, c->kappa.in_layout(2), c->n, nnu, (long)c->ncell, c->stream))
@@ -227,102 +226,13 @@ int ftte_set_option(ftte_ctx *c, const char *key, int value)
 {
     if (!c || !key) return FTTE_ERR_ARG;
     if (c->multi) return multi_set_option(c, key, value);
-    if (!std::strcmp(key, "rows")) {
-        if (value != 4 && value != 8 && value != 16) return fail(c, FTTE_ERR_ARG, "rows must be 4, 8 or 16");
-        c->rows = value;
-    } else if (!std::strcmp(key, "slots")) {
-        if (value < 1 || value > kMaxSlots) return fail(c, FTTE_ERR_ARG, "slots must be 1..16");
-        c->slots = value;
-    } else if (!std::strcmp(key, "waves")) {
-        if (value < 2 || value > 6) return fail(c, FTTE_ERR_ARG, "waves must be 2..6");
-        c->waves = value;
-    } else if (!std::strcmp(key, "forest")) {
-        if (value != 0 && value != 1) return fail(c, FTTE_ERR_ARG, "forest must be 0 or 1");
-        c->force_forest = value;
-        c->use_forest = (c->grid_set && c->tree.refined()) || value;
-    } else if (!std::strcmp(key, "ldspad")) {
-        if (value < 0 || value > 160 * 1024) return fail(c, FTTE_ERR_ARG, "ldspad must be 0..163840 bytes");
-        set_lds_pad(value);
-    } else if (!std::strcmp(key, "engine")) {
-        if (value < 0 || value > 2) return fail(c, FTTE_ERR_ARG, "engine must be 0 (automatic), 1 (ray-following tiles) or 2 (cell-fixed bricks)");
-        c->engine = value;
-    } else if (!std::strcmp(key, "chunk")) {
-        if (value < 0 || value > 4096) return fail(c, FTTE_ERR_ARG, "chunk (layers per brick) must be 1..4096, or 0 for the default");
-        c->bopt.chunk = value;
-    } else if (!std::strcmp(key, "group")) {
-        if (value < 0 || value > kBrickMaxDirs) return fail(c, FTTE_ERR_ARG, "group (directions sharing a brick pass) must be 1..8, or 0 for the default");
-        c->bopt.group = value;
-    } else if (!std::strcmp(key, "hybrid")) {
-        if (value != 0 && value != 1) return fail(c, FTTE_ERR_ARG, "hybrid must be 0 (a refined cell array goes through the forest path as a whole) or 1 (bricks outside a box around the refined cells)");
-        c->hopt.hybrid = value;
-    } else if (!std::strcmp(key, "hybrid_slots")) {
-        if (value < 0 || value > 2) return fail(c, FTTE_ERR_ARG, "hybrid_slots must be 0 (phases), 1 (slots where there are several passes) or 2 (slots always)");
-        c->hopt.slots = value;
-    } else if (!std::strcmp(key, "graph")) {
-        if (value != 0 && value != 1) return fail(c, FTTE_ERR_ARG, "graph must be 0 (every launch of the hybrid sweep issued every time) or 1 (captured once, replayed)");
-        c->hopt.graph = value;
-    } else if (!std::strcmp(key, "box_lanes")) {
-        if (value < 1 || value > 64 || 64 % value) return fail(c, FTTE_ERR_ARG, "box_lanes (the boxes of the hybrid sweep end on multiples of it along a brick's 64 lanes) must divide 64");
-        c->hopt.lanes = value;
-    } else if (!std::strcmp(key, "forest_batch")) {
-        if (value < 0 || value > 65535) return fail(c, FTTE_ERR_ARG, "forest_batch (directions per launch of the segment forests) must be 1..65535, or 0 for the default");
-        c->hopt.forest_batch = value;
-    } else if (!std::strcmp(key, "pipelines")) {
-        if (value < 1 || value > kMaxPipes) return fail(c, FTTE_ERR_ARG, "pipelines (independent bricks-forests-bricks sequences of the hybrid sweep, each on a stream of its own) must be 1..4");
-        c->hopt.pipelines = value;
-    } else if (!std::strcmp(key, "fine_bricks")) {
-        if (value < 0 || value > 1) return fail(c, FTTE_ERR_ARG, "fine_bricks must be 0 (a fully refined block stays in the segment forest) or 1 (bricks of its own on the fine level where the block allows it)");
-        c->hopt.fine_bricks = value;
-    } else if (!std::strcmp(key, "fine_chunk")) {
-        if (value < 0 || value > 4096) return fail(c, FTTE_ERR_ARG, "fine_chunk (layers per brick on the fine level of a refined block) must be 1..4096, or 0 for the base bricks' chunk");
-        c->hopt.fine_chunk = value;
-    } else if (!std::strcmp(key, "atomic_acc")) {
-        if (value < 0 || value > 1) return fail(c, FTTE_ERR_ARG, "atomic_acc must be 0 or 1");
-        c->atomic_acc = value;
-    } else if (!std::strcmp(key, "nu_deal")) {
-        if (value < 0 || value > 4096) return fail(c, FTTE_ERR_ARG, "nu_deal (tasks of one frequency group that follow each other on an XCD) must be 1..4096, or 0 for workgroup b -> group b mod nnu");
-        c->nu_deal = value;
-        return FTTE_OK; // (a launch-time choice: no plan depends on it; a captured hybrid sweep, option "graph", keeps the placement it was captured with -- same J)
-    } else if (!std::strcmp(key, "ablate")) {
-        if (value < 0 || value > 63) return fail(c, FTTE_ERR_ARG, "ablate is a mask of 6 bits");
-        c->ablate = value;
-    } else if (!std::strcmp(key, "forest_fuse")) {
-        if (value < 0 || value > (1 << 24)) return fail(c, FTTE_ERR_ARG, "forest_fuse must be 0 (a launch per level) .. 16777216");
-        c->forest_fuse = value;
-    } else if (!std::strcmp(key, "queue_mix")) {
-        if (value < 0 || value > 2) return fail(c, FTTE_ERR_ARG, "queue_mix must be 0, 1 or 2");
-        c->bopt.queue_mix = value;
-    } else if (!std::strcmp(key, "dataflow")) {
-        if (value < 0 || value > 3) return fail(c, FTTE_ERR_ARG, "dataflow must be 0 (a launch per stage), 1 (one launch, bricks wait for each other), 2 (the same with write-through stores) or 3 (persistent workgroups, a task queue per XCD)");
-        c->bopt.dataflow = value;
-    } else if (!std::strcmp(key, "merge_overlap")) {
-        if (value != 0 && value != 1) return fail(c, FTTE_ERR_ARG, "merge_overlap must be 0 (the brick sweep merges J after its last stage) or 1 (block by block as the stages finish them)");
-        c->merge_overlap = value;
-    } else if (!std::strcmp(key, "lanes")) {
-        if (value < 1 || value > 16) return fail(c, FTTE_ERR_ARG, "lanes (streams the brick sweep spreads its frequency groups over) must be 1..16");
-        c->bopt.lanes = value;
-    } else if (!std::strcmp(key, "team")) {
-        if (value < -1 || value > 2 || value == 1) return fail(c, FTTE_ERR_ARG, "team must be -1 (by the number of frequency groups: 2 up to four, else 0), 0 (one wavefront sweeps a group's directions in turn) or 2 (two wavefronts per brick, four rows each); 1 (a wavefront per direction) lost everywhere and is gone");
-        c->bopt.team = value;
-    } else if (!std::strcmp(key, "tiled")) {
-        if (value < 0 || value > 2) return fail(c, FTTE_ERR_ARG, "tiled must be 0 (default), 1 (bricks: opacities and accumulators stored brick by brick where the grid is made of whole bricks: a brick's layer in one piece) or 2 (the whole brick in one piece)");
-        c->tiled_opt = value;
-    } else if (!std::strcmp(key, "pair_waves")) {
-        if (value < 2 || value > 4) return fail(c, FTTE_ERR_ARG, "pair_waves (workgroups of two wavefronts per SIMD the pair kernel is built for) must be 2..4");
-        c->pair_waves = value;
-    } else if (!std::strcmp(key, "share")) {
-        if (value < 0 || value > 2) return fail(c, FTTE_ERR_ARG, "share (groups sharing a J accumulator) must be 0 (none), 1 (passes of one izone) or 2 (and izone pairs)");
-        c->bopt.share = value;
-    } else if (!std::strcmp(key, "brick_waves")) {
-        if (value < 2 || value > 4) return fail(c, FTTE_ERR_ARG, "brick_waves must be 2..4");
-        c->brick_waves = value;
-    } else if (!std::strcmp(key, "stack")) {
-        if (value != 1 && value != 2 && value != 4 && value != 8) return fail(c, FTTE_ERR_ARG, "stack must be 1, 2, 4 or 8");
-        c->stack = value;
-    } else return fail(c, FTTE_ERR_ARG, std::string("unknown option: ") + key);
-    c->plan.valid = false;
-    c->bplan.valid = false;
-    c->hplan.invalidate();
+    std::string why;
+    const OptionSet how = set(c->opt, key, value, &why); // ranges, refusals and where the value goes: the table of ftte_options.h
+    if (how == OptionSet::refused) return fail(c, FTTE_ERR_ARG, why);
+    if (how == OptionSet::stored_invalidate) { // (also where the value did not change)
+        c->plan.valid = c->bplan.valid = false;
+        c->hplan.invalidate();
+    }
     return FTTE_OK;
 }
 
@@ -336,14 +246,14 @@ int ftte_diffuse_sweep_device(ftte_ctx *c, int ndir, const double *phi, const do
     FTTE_HIP(c, hipSetDevice(c->device));
     hipStream_t stream = stream_v ? (hipStream_t)stream_v : c->stream;
 
-    if (c->use_forest) {
-        if (c->hopt.hybrid && c->tree.refined() && !c->force_forest && ndir > 0) {
+    if (c->use_forest()) {
+        if (c->opt.hybrid.hybrid && c->tree.refined() && !c->opt.route.forest && ndir > 0) {
             bool done = false;
             if ((rc = hybrid_sweep(c, ndir, phi, theta, w, uvb, J_dev, stream, &done)) || done) return rc;
         }
         return forest_sweep(c, ndir, phi, theta, w, uvb, J_dev, stream);
     }
-    if (c->engine != 1) return brick_sweep(c, ndir, phi, theta, w, uvb, J_dev, stream);
+    if (c->opt.route.engine != 1) return brick_sweep(c, ndir, phi, theta, w, uvb, J_dev, stream);
     return tile_sweep(c, ndir, phi, theta, w, uvb, J_dev, stream);
 }
 
@@ -373,8 +283,9 @@ int ftte_diffuse_iteration(ftte_ctx *c, int nnu, const double *kappa, int ndir, 
     if (rc) return rc;
     if (nnu < 1 || !kappa || !J || ndir < 0 || (ndir > 0 && (!phi || !theta || !w)) || !uvb)
         return fail(c, FTTE_ERR_ARG, "ftte_diffuse_iteration: bad argument");
-    const bool lanes_apply = !c->use_forest && c->engine != 1 && !c->emit_mode && c->bopt.brick_form(nnu, c->emit_mode) != 1 && !c->bopt.dataflow && ndir > 0 &&
-                             c->bopt.lanes >= 2 && nnu >= c->bopt.lanes;
+    const BrickOptions &B = c->opt.brick;
+    const bool lanes_apply = !c->use_forest() && c->opt.route.engine != 1 && !c->emit_mode && B.brick_form(nnu, c->emit_mode) != 1 && !B.dataflow && ndir > 0 &&
+                             B.lanes >= 2 && nnu >= B.lanes;
     if (!lanes_apply) {
         if ((rc = ftte_set_opacity(c, nnu, kappa))) return rc;
         return ftte_diffuse_sweep(c, ndir, phi, theta, w, uvb, J);
@@ -435,7 +346,7 @@ long long ftte_counter(const ftte_ctx *c, const char *name)
     if (!std::strcmp(name, "brick_form")) return c->last_brick_form;
     if (!std::strcmp(name, "brick_dataflow")) return c->last_brick_dataflow;
     if (!std::strcmp(name, "brick_whole")) return c->last_brick_whole; // 1: the last sweep's stage launches took the whole-brick form
-    if (!std::strcmp(name, "nu_deal")) return c->nu_deal; // the option as it stands (its default before anybody set it)
+    if (!std::strcmp(name, "nu_deal")) return c->opt.launch.nu_deal; // the option as it stands (its default before anybody set it)
     if (!std::strcmp(name, "brick_chunk")) return c->bplan.valid ? c->bplan.chunk : 0;
     if (!std::strcmp(name, "brick_queue_mix")) return (c->bplan.valid && c->bplan.persistent) ? c->bplan.key.queue_mix : -1;
     if (!std::strcmp(name, "brick_groups")) return c->bplan.valid ? (long long)c->bplan.groups.size() : 0;

@@ -313,7 +313,7 @@ __global__ void __launch_bounds__(64, WAVES) brick_kernel(const BrickLaunch L)
     }
     // dataflow with write-through stores (sc1: the line goes to memory and leaves this XCD's L2) instead of an L2 write-back
     // before the flag
-    const bool through = FLOW == 1 && L.pad_ != 0;
+    const bool through = FLOW == 1 && L.through != 0;
     // (the one-launch forms keep slot = work % nnu: their queues and flags are indexed by it)
     const BrickWork W = brick_deal(work, (unsigned)nnu, FLOW ? 0u : (unsigned)L.deal);
     const int nu = L.nu0 + (int)W.slot;
@@ -333,8 +333,8 @@ __global__ void __launch_bounds__(64, WAVES) brick_kernel(const BrickLaunch L)
     const int tv = MASKED ? tv_field & kBrickTvMask : tv_field, box = MASKED ? (tv_field >> kBrickBoxShift) & kBrickBoxMask : 0;
     const int ti = uniform((int)T.ti) & (kBrickAccumulate - 1);
     static_assert(!WHOLE || (EMIT == 0 && FLOW == 0 && !MASKED), "the whole-brick form is the plain stage launch");
-    // (pad2_: diagnostic option "ablate", below)
-    const bool accumulate = (uniform((int)T.ti) & kBrickAccumulate) != 0 && (WHOLE || !(L.pad2_ & 4));
+    // (ablate: diagnostic option "ablate", below)
+    const bool accumulate = (uniform((int)T.ti) & kBrickAccumulate) != 0 && (WHOLE || !(L.ablate & 4));
     const bool atomic_acc = !WHOLE && L.atomic_acc != 0 && !through;
     cgroup *G = (cgroup *)(L.groups + (MASKED ? group_field & kBrickGroupMask : group_field));
     const int n = L.n, chunk = L.chunk, up = L.up, vp = L.vp;
@@ -361,10 +361,10 @@ __global__ void __launch_bounds__(64, WAVES) brick_kernel(const BrickLaunch L)
     const int i0 = ti * chunk + 1;
     const int i1 = (i0 + chunk - 1 < n) ? i0 + chunk - 1 : n;
 
-    // (pad2_: diagnostic option "ablate" -- WRONG RESULTS, timing only: bit 0 no rays taken from the left and from below, bit 1 none
+    // (ablate: diagnostic option "ablate" -- WRONG RESULTS, timing only: bit 0 no rays taken from the left and from below, bit 1 none
     // handed to the right and above, bit 2 no earlier J read, bit 3 no rays taken from or left for the chunks before and after,
     // bit 4 the opacities of a brick's first layer for all its layers, bit 5 no J stored)
-    const int ablate = WHOLE ? 0 : L.pad2_;
+    const int ablate = WHOLE ? 0 : L.ablate;
     const bool sub = !MASKED && L.sub != 0; // a sub-grid with neighbours all round (BrickLaunch::sub): rings at its faces too
     const bool has_u_in = (tu > 0 || lane_lo > 0 || sub) && !(ablate & 1), has_u_out = (64 * (tu + 1) < n || lane_hi < 63 || sub) && !(ablate & 2);
     const bool has_v_in = (tv > 0 || sub) && !(ablate & 1), has_v_out = (R * (tv + 1) < n || sub) && !(ablate & 2);
@@ -839,12 +839,12 @@ int launch_xcc_census(unsigned *mask_dev, hipStream_t stream)
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-int launch_brick_pair(const BrickLaunch &L, int max_dirs, int waves, hipStream_t stream)
+int launch_brick_pair(const BrickLaunch &L, int max_dirs, int waves, int lds_pad, hipStream_t stream)
 {
     if (L.ntasks <= 0) return 0;
     if (max_dirs < 1 || max_dirs > kBrickMaxDirs || L.ticket != nullptr) return -1;
     const dim3 grid((unsigned)L.ntasks * (unsigned)L.nnu);
-    const size_t lds = ((size_t)(max_dirs - 1) * kBrickRows * 64 + 2 * max_dirs * 64) * sizeof(double) + (size_t)lds_pad();
+    const size_t lds = ((size_t)(max_dirs - 1) * kBrickRows * 64 + 2 * max_dirs * 64) * sizeof(double) + (size_t)lds_pad;
     // emission: the log-mean's own division and polynomials (ftte_segment_emit) need the registers of three workgroups per SIMD
     if (L.emit == 1) hipLaunchKernelGGL((brick_pair_kernel<3, 1>), grid, dim3(128), lds, stream, L, max_dirs);
     else if (L.emit == 2) hipLaunchKernelGGL((brick_pair_kernel<4, 2>), grid, dim3(128), lds, stream, L, max_dirs);
@@ -861,16 +861,16 @@ int launch_brick_pair(const BrickLaunch &L, int max_dirs, int waves, hipStream_t
 // whole bricks, no emission, no dataflow, no diagnostic option: the form whose layer loop has only counted waits (brick_kernel's WHOLE)
 bool brick_whole_form(const BrickLaunch &L, int waves, bool masked)
 {
-    return !masked && !L.emit && !L.ticket && !L.queue && waves == 4 && L.n % 64 == 0 && L.n % kBrickRows == 0 && !L.atomic_acc && !L.pad2_;
+    return !masked && !L.emit && !L.ticket && !L.queue && waves == 4 && L.n % 64 == 0 && L.n % kBrickRows == 0 && !L.atomic_acc && !L.ablate;
 }
 
-int launch_brick(const BrickLaunch &L, int max_dirs, int waves, hipStream_t stream, bool masked, int persistent)
+int launch_brick(const BrickLaunch &L, int max_dirs, int waves, int lds_pad, hipStream_t stream, bool masked, int persistent)
 {
     if (L.ntasks <= 0) return 0;
     if (max_dirs < 1 || max_dirs > kBrickMaxDirs) return -1;
     if (L.tiled && (L.emit || masked)) return -1; // brick-ordered storage: the emission rows and the cut bricks are addressed in frame order only
     const dim3 grid((unsigned)L.ntasks * (unsigned)L.nnu);
-    const size_t lds = (size_t)(max_dirs - 1) * kBrickRows * 64 * sizeof(double) + (size_t)lds_pad(); // pad: diagnostic knob "ldspad"
+    const size_t lds = (size_t)(max_dirs - 1) * kBrickRows * 64 * sizeof(double) + (size_t)lds_pad; // pad: diagnostic knob "ldspad"
     const bool flow = L.ticket != nullptr;
     if (L.queue) { // persistent form: `persistent` workgroups, what the GPU holds at once (more are harmless: they find the queues empty)
         if (masked || L.emit || !flow || persistent < 1) return -1;

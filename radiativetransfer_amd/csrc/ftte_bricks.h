@@ -48,7 +48,8 @@ struct BrickKey {
 };
 
 // The options a brick plan depends on (ftte_set_option; 0 or -1: by the parallelism there is), and the rules that turn them into
-// a plan's parameters.  The launch-time options (brick_waves, pair_waves, atomic_acc, ablate, merge_overlap) are the context's.
+// a plan's parameters.  What the sweep reads when it launches (brick_waves, pair_waves, atomic_acc, nu_deal, ablate, tiled,
+// merge_overlap, the LDS pad) is LaunchOptions; both are members of the context's Options, with every option's range (ftte_options.h).
 struct BrickOptions {
     int chunk = 0, group = 0; // layers per brick, most directions per group
     int share = 2, team = -1, lanes = 2;
@@ -225,7 +226,7 @@ private:
 };
 
 // The launch record of tasks [task0, task1) of plan P for the frequency groups [nu0, nu1): everything that comes from the plan, its
-// tables and the context.  What belongs to one caller -- the dataflow and persistent fields, tiled, pad2_, atomic_acc, sub -- stays
+// tables and the context.  What belongs to one caller -- the dataflow and persistent fields, through, tiled, ablate, atomic_acc, sub -- stays
 // zero.  (uqface_off: only masked bricks read it.)
 inline BrickLaunch brick_launch(const BrickPlan &P, const BrickTables &T, size_t task0, size_t task1, int nu0, int nu1, int64_t group_stride,
                                 int64_t face_stride, const double *uvb, int emit)

@@ -6,8 +6,9 @@
 //
 // Every device buffer, pinned buffer, stream, event and graph of the context is a member that owns it (ftte_device.h): a buffer's
 // capacity travels with its pointer, `delete c` releases everything, and a new buffer is added by declaring it.  What a buffer
-// holds has an owner as well: the medium's fields (ftte_medium.h), the gas (ftte_gas.h), for the brick sweeps the options a plan
-// depends on with the rules that resolve them, the plan, its tables, the buffers that remember what they were sent and the state of
+// holds has an owner as well: the medium's fields (ftte_medium.h), the gas (ftte_gas.h), every option of ftte_set_option with its
+// range, its refusal and whether the plans depend on it (ftte_options.h: ftte_ctx::opt, this context's alone), for the brick sweeps
+// the rules that resolve their options, the plan, its tables, the buffers that remember what they were sent and the state of
 // the one-launch forms (ftte_bricks.h), for the ray-following tiles their plan (ftte_tiles.h), and for the sweeps of
 // a refined cell array the forests, their scratch and their cache (ftte_forests.h) and the hybrid sweep's options, plan and device
 // state (ftte_hybrid.h), for host arrays the staging blocks and the registered ranges (ftte_host.h), for the tree its copy on the
@@ -40,6 +41,7 @@
 #include "ftte_kernels.h"
 #include "ftte_lambda.h"
 #include "ftte_medium.h"
+#include "ftte_options.h"
 #include "ftte_point.h"
 #include "ftte_tiles.h"
 
@@ -77,9 +79,10 @@ struct ftte_ctx {
     int64_t ncell = 0;
     double box = 0;
 
+    Options opt; // every option of ftte_set_option (ftte_options.h)
+
     int nnu = 0;
     MediumField kappa; // the opacities, and their copies in the other layouts, in brick order and cell-major (ftte_medium.h)
-    int tiled_opt = 0; // option "tiled" (measured: no gain)
 
     // emissivity (mode 1: the reference's eta) or source function (mode 2): sized as the opacities, the same copies
     int emit_mode = 0;
@@ -87,19 +90,11 @@ struct ftte_ctx {
 
     DeviceBuffer<double> acc[3][kMaxAcc]; // one size for all of them (accumulator_size)
 
-    int rows = 8, slots = 8, waves = 4, stack = 1;
-
-    // which organisation sweeps a uniform grid: 0 = the default = 2 = cell-fixed bricks (brick_kernel), 1 = ray-following tiles
-    // (sweep_kernel)
-    int engine = 0, brick_waves = 4, pair_waves = 4, last_brick_form = -1, last_brick_dataflow = -1, last_brick_whole = 0;
-    BrickOptions bopt;                      // the options a brick plan depends on: chunk, group, share, team, lanes, dataflow, queue_mix
+    int last_brick_form = -1, last_brick_dataflow = -1, last_brick_whole = 0; // of the last uniform-grid sweep of the brick engine (ftte_counter)
     std::vector<Stream> lane_stream;        // extra streams of the brick sweep (frequency groups are independent)
     std::vector<Event> pipe_up;             // ftte_diffuse_iteration: lane k's opacities have arrived
     std::vector<Event> lane_done;
     Event ev_fork;
-    int atomic_acc = 0;               // option "atomic_acc": later visitors of an accumulator add with fp64 atomics instead of read-add-store
-    int nu_deal = 16;                 // option "nu_deal": run length of the deal of a stage launch's frequency groups over the XCDs (brick_deal); 0: work % nnu
-    int ablate = 0;                   // diagnostic option "ablate": parts of the brick kernel's memory traffic left out (wrong J; timing only)
     BrickDataflow bflow;              // flags, tickets and error word of the one-launch forms: brick_sweep prepares, wait_sweep checks
     int xcc_count = -1;               // XCC ids this device reports (census, ftte_brick.hip); -1: not taken yet
     int8_t xcc_queue[16] = {};        // XCC id -> 0 .. xcc_count - 1, or -1
@@ -120,8 +115,7 @@ struct ftte_ctx {
     // refined cell arrays: the tree, and the per-direction segment forests resident on the device
     AmrTree tree;
     DeviceTree dtree;         // its nodes on the device, for the point-source tracer and the maps (ftte_device_tree.h)
-    bool use_forest = false;  // refined grid (or option "forest" = 1 on a uniform one, for cross-checks)
-    int force_forest = 0;
+    bool use_forest() const { return (grid_set && tree.refined()) || opt.route.forest; } // refined grid (or option "forest" = 1 on a uniform one, for cross-checks)
     ForestCache forests;      // the whole tree's, per direction (forest_sweep)
     ForestScratch fscratch;   // segment scratch, batch records and per-depth tables of both paths
 
@@ -130,7 +124,6 @@ struct ftte_ctx {
     Event ev_layout_done, ev_merge_done, ev_layouts_ready;
     // brick sweep, option "merge_overlap" (1 = default): J merged block by block on merge_stream as the stages finish the blocks
     // (BrickPlan::merge_blocks), behind ev_merge_point[lane * points + m] of each lane; 0 = one merge after the last stage
-    int merge_overlap = 1;
     std::vector<Event> ev_merge_point;
     // end of the last sweep on whatever stream the caller gave it: the setters and the next sweep wait for it before they
     // overwrite what that sweep reads
@@ -138,11 +131,9 @@ struct ftte_ctx {
     bool sweep_pending = false;
 
     // Hybrid sweep of a refined cell array: bricks outside a box around the refined cells, the segment forest inside it
-    HybridOptions hopt;
     HybridPlan hplan;
     HybridDevice hdev;                // what hplan and the tree put on the device
     long long leaf_lists = 0;         // leaf lists built so far (HybridDevice::cells_id counts from 1)
-    int forest_fuse = 4096;           // option "forest_fuse": levels of a forest with at most this many (segment, group) pairs in one launch (0: a launch per level)
 
     // The species medium (ftte_gas.h): ftte_set_medium fills it; the tracer, the chemistry, the census, ftte_compute_opacities and
     // the thin limit read it; the chemistry's updates write its species and say so

@@ -32,14 +32,14 @@ static int gather_layouts(ftte_ctx *c, const MediumField &f, const int32_t *leaf
 static int build_hybrid_plan(ftte_ctx *c, int ndir, const double *phi, const double *theta, const double *w)
 {
     HybridPlan &H = c->hplan;
-    const BrickKey K = c->bopt.resolve_hybrid(c->n, c->nnu);
-    std::vector<double> key = c->hopt.plan_key(c->box, K.chunk, K.gmax, K.share, ndir, phi, theta, w);
+    const BrickKey K = c->opt.brick.resolve_hybrid(c->n, c->nnu);
+    std::vector<double> key = c->opt.hybrid.plan_key(c->box, K.chunk, K.gmax, K.share, ndir, phi, theta, w);
     if (H.valid && H.key == key) return FTTE_OK;
     c->hdev.drop_plan();
     H = HybridPlan();
     H.key = std::move(key);
     std::string why;
-    const int rc = plan_hybrid(HybridInputs{c->n, c->box, &c->tree, c->hopt, K.chunk, K.gmax, K.share, ndir, phi, theta, w}, H, &why);
+    const int rc = plan_hybrid(HybridInputs{c->n, c->box, &c->tree, c->opt.hybrid, K.chunk, K.gmax, K.share, ndir, phi, theta, w}, H, &why);
     c->n_plan_builds += H.brick_plans_made;
     H.bricks.id = ++c->brick_plans; // (new plans: no BrickTables holds them)
     if (H.brick_plans_made > 1) H.fine.plan.id = ++c->brick_plans;
@@ -108,7 +108,7 @@ static int reserve_hybrid_buffers(ftte_ctx *c, int ndir, const double *uvb, int6
     // forest scratch: as forest_sweep, per_dir elements a direction
     // (numbered by the list, a direction's scratch is small: every direction at once, where the memory is there)
     hipError_t no_scratch;
-    *batch = c->fscratch.reserve_batch(per_dir, ndir, c->hopt.forest_batch > 0 ? c->hopt.forest_batch : 1024, 0.6, false, &no_scratch);
+    *batch = c->fscratch.reserve_batch(per_dir, ndir, c->opt.hybrid.forest_batch > 0 ? c->opt.hybrid.forest_batch : 1024, 0.6, false, &no_scratch);
     if (!*batch) return fail(c, FTTE_ERR_NO_DEVICE, std::string("hybrid sweep: no room for the segment scratch: ") + hipGetErrorString(no_scratch));
     return FTTE_OK;
 }
@@ -119,11 +119,11 @@ template <typename Issue> static int issue_or_replay(ftte_ctx *c, hipStream_t st
 {
     HybridDevice &V = c->hdev;
     bool replayed = false;
-    if (c->hopt.graph && V.graph_exec && V.graph_sig == sig) {
+    if (c->opt.hybrid.graph && V.graph_exec && V.graph_sig == sig) {
         if (hipGraphLaunch(V.graph_exec, stream) == hipSuccess) replayed = true;
         else { (void)hipGetLastError(); V.drop_graph(); }
     }
-    if (!replayed && c->hopt.graph) {
+    if (!replayed && c->opt.hybrid.graph) {
         V.drop_graph();
         if (hipStreamBeginCapture(stream, hipStreamCaptureModeRelaxed) == hipSuccess) {
             const int irc = issue();
@@ -139,9 +139,9 @@ template <typename Issue> static int issue_or_replay(ftte_ctx *c, hipStream_t st
             } else {
                 (void)hipGetLastError();
                 V.drop_graph();
-                c->hopt.graph = 0; // this runtime or this sequence does not capture: launches one by one from now on
+                c->opt.hybrid.graph = 0; // this runtime or this sequence does not capture: launches one by one from now on
             }
-        } else { (void)hipGetLastError(); c->hopt.graph = 0; }
+        } else { (void)hipGetLastError(); c->opt.hybrid.graph = 0; }
     }
     return replayed ? FTTE_OK : issue();
 }
@@ -186,14 +186,15 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     Tm.updates = (int64_t)ndir * ncell * nnu; Tm.lanes = 0;
     c->timing_used = 0;
     const size_t masked_lists = (size_t)H.nhalves * H.nlist;
+    const LaunchOptions &launch = c->opt.launch;
     auto brick_stages = [&](int half, size_t from, size_t to, hipStream_t q) -> int {
       for (size_t l = from; l < to; ++l)
         for (int masked = 0; masked < 2; ++masked) { // the stage's whole bricks, then those a box cuts through
             const size_t *off = &H.stage_off[(masked ? masked_lists : 0) + (size_t)half * H.nlist];
             if (off[l + 1] == off[l]) continue;
             BrickLaunch L = brick_launch(P, c->btables, off[l], off[l + 1], 0, nnu, nbase, face_elems, c->d_uvb, emit);
-            L.deal = c->nu_deal;
-            const int lrc = launch_brick(L, P.max_dirs, c->brick_waves, q, masked != 0);
+            L.deal = launch.nu_deal;
+            const int lrc = launch_brick(L, P.max_dirs, launch.brick_waves, launch.lds_pad, q, masked != 0);
             if (lrc) return fail(c, lrc == -1 ? FTTE_ERR_ARG : FTTE_ERR_NO_DEVICE, "brick kernel launch failed");
         }
       return FTTE_OK;
@@ -212,8 +213,8 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
             const size_t l = (size_t)half * (size_t)FN.nstages + (size_t)st;
             if (FN.stage_off[l + 1] == FN.stage_off[l]) continue;
             BrickLaunch L = brick_launch(Q, V.fine_tables, FN.stage_off[l], FN.stage_off[l + 1], 0, nnu, (int64_t)FN.n * FN.n * FN.n, face_elems, c->d_uvb, emit);
-            L.sub = 1; L.deal = c->nu_deal;
-            const int lrc = launch_brick(L, Q.max_dirs, c->brick_waves, q, false);
+            L.sub = 1; L.deal = launch.nu_deal;
+            const int lrc = launch_brick(L, Q.max_dirs, launch.brick_waves, launch.lds_pad, q, false);
             if (lrc) return fail(c, lrc == -1 ? FTTE_ERR_ARG : FTTE_ERR_NO_DEVICE, "brick kernel launch failed");
         }
         return FTTE_OK;
@@ -344,8 +345,10 @@ int hybrid_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     // once into a hipGraph -- the streams' forks and joins become dependencies of the graph -- and replays it while the plan, J and
     // every buffer and table the launches name stay the same.  Measured on ROCm 7.2 / MI355X the replay is SLOWER than issuing the
     // launches (configs[3]: 15.8 against 12.2 ms; 8 clusters in 5 passes: 23.9 against 15.1 ms), so it is off by default.
-    // What the captured launches name: every owner appends the addresses and parameters it holds, the sweep its own.
-    std::vector<uintptr_t> sig = {(uintptr_t)J_dev, (uintptr_t)stream, (uintptr_t)nnu, (uintptr_t)nh, (uintptr_t)c->brick_waves, (uintptr_t)emit, (uintptr_t)c->forest_fuse,
+    // What the captured launches name: every owner appends the addresses and parameters it holds, the sweep its own.  (No entry
+    // for the LDS pad or the other options: every accepted option but "nu_deal" invalidates the plan, and a rebuilt plan drops the
+    // captured graph.)
+    std::vector<uintptr_t> sig = {(uintptr_t)J_dev, (uintptr_t)stream, (uintptr_t)nnu, (uintptr_t)nh, (uintptr_t)launch.brick_waves, (uintptr_t)emit, (uintptr_t)launch.forest_fuse,
                                   (uintptr_t)c->d_faces.get(), (uintptr_t)c->d_uvb.get()};
     V.sign(sig, FN.active, FN.plan.nacc);
     c->fscratch.sign(sig);

@@ -139,12 +139,12 @@ struct BrickLaunch {
     uint32_t *ticket, *done, *error;
     const int32_t *deps;
     uint32_t epoch;
-    int32_t pad_;
+    int32_t through;          // one launch with flags, option "dataflow" = 2: hand-overs by write-through stores instead of an L2 write-back per brick
     // kappa and the accumulators stored brick by brick: the eight rows of a brick's layer in one piece of 4 KB, the pieces of a
     // layer in brick order (v, then u), layers as in the frame.  Whole bricks only (n a multiple of 64 and of kBrickRows).  The
     // group's org, sv, bu, bv are then those of this order (tiled_index, ftte_kernels.hip); si is the same in both.  tiled == 2: the
     // `chunk` layers of a brick follow each other as well (the whole brick in one piece of chunk x 4 KB; n a multiple of the chunk).
-    int32_t tiled, pad2_;
+    int32_t tiled, ablate;    // ablate: diagnostic option "ablate", parts of the memory traffic left out (ftte_brick.hip)
     // Persistent form (queue != nullptr, ftte_brick.hip): as many workgroups as the GPU holds at once, each bound to the XCD it runs
     // on (read from HW_REG_XCC_ID); a workgroup draws (task, frequency group) pairs from ITS XCD's queue only, in queue order, until
     // the queue is empty.  A queue holds whole chains of dependent bricks (everything a brick waits for lies earlier in the same

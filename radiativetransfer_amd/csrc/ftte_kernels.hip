@@ -352,43 +352,39 @@ __global__ void __launch_bounds__(64 * STACK, WAVES) sweep_kernel(const LaunchRe
 }
 
 // WAVES = waves per SIMD the register allocation is held to (512 / WAVES VGPRs per lane)
-static int g_lds_pad = 0; // bytes of dynamic LDS per workgroup (diagnostic knob "ldspad")
-void set_lds_pad(int bytes) { g_lds_pad = bytes; }
-int lds_pad() { return g_lds_pad; }
-
 template <int ROWS, int STACK>
-static int launch_variant(const LaunchRec &L, int waves, dim3 grid, hipStream_t stream)
+static int launch_variant(const LaunchRec &L, int waves, int lds_pad, dim3 grid, hipStream_t stream)
 {
     const dim3 block(64 * STACK);
     switch (waves) {
-    case 2: hipLaunchKernelGGL((sweep_kernel<ROWS, 2, STACK, 0>), grid, block, g_lds_pad, stream, L); break;
-    case 3: hipLaunchKernelGGL((sweep_kernel<ROWS, 3, STACK, 0>), grid, block, g_lds_pad, stream, L); break;
-    case 4: hipLaunchKernelGGL((sweep_kernel<ROWS, 4, STACK, 0>), grid, block, g_lds_pad, stream, L); break;
-    case 5: hipLaunchKernelGGL((sweep_kernel<ROWS, 5, STACK, 0>), grid, block, g_lds_pad, stream, L); break;
-    case 6: hipLaunchKernelGGL((sweep_kernel<ROWS, 6, STACK, 0>), grid, block, g_lds_pad, stream, L); break;
+    case 2: hipLaunchKernelGGL((sweep_kernel<ROWS, 2, STACK, 0>), grid, block, lds_pad, stream, L); break;
+    case 3: hipLaunchKernelGGL((sweep_kernel<ROWS, 3, STACK, 0>), grid, block, lds_pad, stream, L); break;
+    case 4: hipLaunchKernelGGL((sweep_kernel<ROWS, 4, STACK, 0>), grid, block, lds_pad, stream, L); break;
+    case 5: hipLaunchKernelGGL((sweep_kernel<ROWS, 5, STACK, 0>), grid, block, lds_pad, stream, L); break;
+    case 6: hipLaunchKernelGGL((sweep_kernel<ROWS, 6, STACK, 0>), grid, block, lds_pad, stream, L); break;
     default: return -1;
     }
     return 0;
 }
 
-int launch_sweep(const LaunchRec &L, int rows, int waves, int stack, int nnu, hipStream_t stream)
+int launch_sweep(const LaunchRec &L, int rows, int waves, int stack, int nnu, int lds_pad, hipStream_t stream)
 {
     if (L.nitems <= 0 || nnu != L.nnu) return L.nitems <= 0 ? 0 : -1;
     const dim3 grid((unsigned)L.nitems * (unsigned)nnu);
     int rc = -1;
     if (L.emit) { // emission: one built shape (8 rows, single wavefront, 3 waves per SIMD)
         if (rows != 8 || stack != 1) return -1;
-        if (L.emit == 1) hipLaunchKernelGGL((sweep_kernel<8, 3, 1, 1>), grid, dim3(64), g_lds_pad, stream, L);
-        else hipLaunchKernelGGL((sweep_kernel<8, 3, 1, 2>), grid, dim3(64), g_lds_pad, stream, L);
+        if (L.emit == 1) hipLaunchKernelGGL((sweep_kernel<8, 3, 1, 1>), grid, dim3(64), lds_pad, stream, L);
+        else hipLaunchKernelGGL((sweep_kernel<8, 3, 1, 2>), grid, dim3(64), lds_pad, stream, L);
         return hipGetLastError() == hipSuccess ? 0 : -2;
     }
-    if (rows == 4 && stack == 1) rc = launch_variant<4, 1>(L, waves, grid, stream);
-    else if (rows == 4 && stack == 4) rc = launch_variant<4, 4>(L, waves, grid, stream);
-    else if (rows == 4 && stack == 8) rc = launch_variant<4, 8>(L, waves, grid, stream);
-    else if (rows == 8 && stack == 1) rc = launch_variant<8, 1>(L, waves, grid, stream);
-    else if (rows == 8 && stack == 2) rc = launch_variant<8, 2>(L, waves, grid, stream);
-    else if (rows == 8 && stack == 4) rc = launch_variant<8, 4>(L, waves, grid, stream);
-    else if (rows == 16 && stack == 1) rc = launch_variant<16, 1>(L, waves, grid, stream);
+    if (rows == 4 && stack == 1) rc = launch_variant<4, 1>(L, waves, lds_pad, grid, stream);
+    else if (rows == 4 && stack == 4) rc = launch_variant<4, 4>(L, waves, lds_pad, grid, stream);
+    else if (rows == 4 && stack == 8) rc = launch_variant<4, 8>(L, waves, lds_pad, grid, stream);
+    else if (rows == 8 && stack == 1) rc = launch_variant<8, 1>(L, waves, lds_pad, grid, stream);
+    else if (rows == 8 && stack == 2) rc = launch_variant<8, 2>(L, waves, lds_pad, grid, stream);
+    else if (rows == 8 && stack == 4) rc = launch_variant<8, 4>(L, waves, lds_pad, grid, stream);
+    else if (rows == 16 && stack == 1) rc = launch_variant<16, 1>(L, waves, lds_pad, grid, stream);
     if (rc) return rc;
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }

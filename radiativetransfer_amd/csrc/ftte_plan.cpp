@@ -9,25 +9,25 @@ namespace ftte {
 int build_plan(ftte_ctx *c, int rows, int stack, int ndir, const double *phi, const double *theta, const double *w)
 {
     Plan &P = c->plan;
-    if (P.valid && P.n == c->n && P.rows == rows && P.slots == c->slots && P.stack == stack && P.box == c->box && same_list(P.phi, phi, ndir) &&
+    if (P.valid && P.n == c->n && P.rows == rows && P.slots == c->opt.tile.slots && P.stack == stack && P.box == c->box && same_list(P.phi, phi, ndir) &&
         same_list(P.theta, theta, ndir) && same_list(P.w, w, ndir))
         return FTTE_OK;
     ++c->n_plan_builds;
     c->plan_uploaded = false;
     std::string why;
-    const int rc = plan_tiles(TileInputs{c->n, c->box, rows, stack, c->slots, ndir, phi, theta, w}, P, &why);
+    const int rc = plan_tiles(TileInputs{c->n, c->box, rows, stack, c->opt.tile.slots, ndir, phi, theta, w}, P, &why);
     return rc ? fail(c, rc, why) : FTTE_OK;
 }
 
 int build_brick_plan(ftte_ctx *c, int ndir, const double *phi, const double *theta, const double *w)
 {
     BrickPlan &P = c->bplan;
-    BrickKey key = c->bopt.resolve(c->n, c->nnu, c->emit_mode);
+    BrickKey key = c->opt.brick.resolve(c->n, c->nnu, c->emit_mode);
     key.box = c->box;
-    if (key.want_dataflow && c->bopt.dataflow == 3) { // persistent workgroups, a queue per XCD: needs to know the XCDs
+    if (key.want_dataflow && c->opt.brick.dataflow == 3) { // persistent workgroups, a queue per XCD: needs to know the XCDs
         const int rc = xcc_census(c);
         if (rc) return rc;
-        c->bopt.persistent(key, c->nnu, c->xcc_count);
+        c->opt.brick.persistent(key, c->nnu, c->xcc_count);
     }
     if (P.valid && P.key == key && same_list(P.phi, phi, ndir) && same_list(P.theta, theta, ndir) && same_list(P.w, w, ndir)) return FTTE_OK;
     ++c->n_plan_builds;

@@ -228,7 +228,7 @@ int launch_forest_pass(ftte_ctx *c, hipStream_t stream, const ForestRun &R, size
     A.ndir = B.nb;
     // Runs of thin levels (option "forest_fuse": at most that many (segment, frequency group) pairs in the fullest direction) go in
     // one launch, a workgroup per direction and a barrier per level; a thick level gets a launch of its own, a thread per pair.
-    const int64_t thin = (int64_t)c->forest_fuse;
+    const int64_t thin = (int64_t)c->opt.launch.forest_fuse;
     for (size_t depth = 0; depth < P.maxdepth;) {
         size_t end = depth;
         while (end < P.maxdepth && R.most_of[P.most_at + end] * (int64_t)c->nnu <= thin) ++end;
@@ -366,7 +366,7 @@ int forest_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, 
     // direction list, kAmrBatch and the free memory allow (two arrays of 3 ncell nnu doubles per direction: 38 GB for 48
     // directions of a 128^3 x 8 tree), and shrinks once more if the allocation still fails.
     const size_t per_dir = (size_t)nseg * nnu;
-    const int most = c->hopt.forest_batch > 0 ? c->hopt.forest_batch : kAmrBatch;
+    const int most = c->opt.hybrid.forest_batch > 0 ? c->opt.hybrid.forest_batch : kAmrBatch;
     if (!c->fscratch.fits(per_dir, ndir, most)) FTTE_HIP(c, hipStreamSynchronize(stream));
     hipError_t why;
     const int batch = c->fscratch.reserve_batch(per_dir, ndir, most, 0.9, true, &why);
@@ -410,6 +410,7 @@ namespace {
 struct BrickSweep {
     ftte_ctx *c; const BrickPlan &P; double *J_dev; hipStream_t stream; const HostPipe *pipe; // (what brick_sweep was called with)
     const int n = c->n, nnu = c->nnu;
+    const LaunchOptions &O = c->opt.launch;
     // Host arrays (ftte_diffuse_iteration): lanes of frequency groups do their own layouts before their first stage and their own
     // merge after their last.  (With device-resident opacities, layouts up front and one merge at the end are faster: 37.4-38.0
     // against 38.6 ms per 256^3 x 8 x 96 step.  With host arrays in flight the lanes are staggered by the transfers and their ends
@@ -432,7 +433,7 @@ struct BrickSweep {
     BrickLaunch launch(size_t task0, size_t task1, int nu0, int nu1) const
     {
         BrickLaunch L = brick_launch(P, c->btables, task0, task1, nu0, nu1, c->ncell, P.face_elems, c->d_uvb, c->emit_mode);
-        L.tiled = tiled ? 1 : 0; L.pad2_ = c->ablate; L.atomic_acc = c->atomic_acc; L.deal = c->nu_deal;
+        L.tiled = tiled ? 1 : 0; L.ablate = O.ablate; L.atomic_acc = O.atomic_acc; L.deal = O.nu_deal;
         return L;
     }
     int prepare(int ndir, const double *uvb), one_launch(), lane_stages(int lane, LaunchTiming &T), merge();
@@ -471,8 +472,8 @@ int BrickSweep::prepare(int ndir, const double *uvb)
     FTTE_HIP(c, c->ev_merge_done.create(hipEventDisableTiming));
     FTTE_HIP(c, c->ev_layouts_ready.create(hipEventDisableTiming));
     lane_ends = pipe != nullptr;
-    tiled = c->tiled_opt && !pipe && !c->emit_mode && n % 64 == 0 && n % kBrickRows == 0 && (c->tiled_opt == 1 || n % P.chunk == 0);
-    tchunk = tiled && c->tiled_opt == 2 ? P.chunk : 0;
+    tiled = O.tiled && !pipe && !c->emit_mode && n % 64 == 0 && n % kBrickRows == 0 && (O.tiled == 1 || n % P.chunk == 0);
+    tchunk = tiled && O.tiled == 2 ? P.chunk : 0;
     frame[1] = tiled ? 1 : 0;
     for (int l = 0; l < 3; ++l) {
         for (int s = 0; s < P.nacc[l]; ++s)
@@ -507,12 +508,12 @@ int BrickSweep::prepare(int ndir, const double *uvb)
     FTTE_HIP(c, c->btables.groups.send(G.data(), G.size()));
     FTTE_HIP(c, c->d_uvb.send(uvb, (size_t)nnu));
 
-    nulanes = P.glanes > 1 ? 1 : std::max(1, std::min(c->bopt.lanes, nnu)); // streams over frequency groups ...
+    nulanes = P.glanes > 1 ? 1 : std::max(1, std::min(c->opt.brick.lanes, nnu)); // streams over frequency groups ...
     nlanes = nulanes * P.glanes;                                        // ... or over the groups of directions
     FTTE_HIP(c, ensure_lanes(c->lane_stream, c->lane_done, (size_t)nlanes - 1));
     FTTE_HIP(c, c->ev_fork.create(hipEventDisableTiming));
     // (the plan has merge blocks only for stages on one lane of groups; with host arrays every lane merges its own after its stages)
-    overlap = c->merge_overlap && !lane_ends && !P.dataflow && P.glanes == 1 && !P.groups.empty() && !P.merge_stage.empty();
+    overlap = O.merge_overlap && !lane_ends && !P.dataflow && P.glanes == 1 && !P.groups.empty() && !P.merge_stage.empty();
     npoints = overlap ? P.merge_stage.size() : 0;
     FTTE_HIP(c, ensure_events(c->ev_merge_point, (size_t)nlanes * npoints, hipEventDisableTiming));
     if ((rc = ensure_timing(c, 1))) return rc;
@@ -525,7 +526,7 @@ int BrickSweep::one_launch()
 {
     BrickLaunch L = launch(0, P.tasks.size(), 0, nnu);
     FTTE_HIP(c, c->bflow.prepare(L, c->btables, P.tasks.size() * (size_t)nnu, stream));
-    L.pad_ = c->bopt.dataflow == 2 ? 1 : 0;
+    L.through = c->opt.brick.dataflow == 2 ? 1 : 0;
     int persistent = 0;
     if (P.persistent) {
         L.queue = c->btables.queue;
@@ -536,8 +537,8 @@ int BrickSweep::one_launch()
         FTTE_HIP(c, hipGetDeviceProperties(&prop, c->device));
         persistent = (int)std::min<size_t>((size_t)prop.multiProcessorCount * 16, P.queue.size());
     }
-    c->last_brick_form = 0; c->last_brick_dataflow = P.persistent ? 3 : c->bopt.dataflow == 2 ? 2 : 1; c->last_brick_whole = 0;
-    const int lrc = launch_brick(L, P.max_dirs, c->brick_waves, stream, false, persistent);
+    c->last_brick_form = 0; c->last_brick_dataflow = P.persistent ? 3 : c->opt.brick.dataflow == 2 ? 2 : 1; c->last_brick_whole = 0;
+    const int lrc = launch_brick(L, P.max_dirs, O.brick_waves, O.lds_pad, stream, false, persistent);
     if (lrc) return fail(c, lrc == -1 ? FTTE_ERR_ARG : FTTE_ERR_NO_DEVICE, "brick kernel launch failed");
     FTTE_HIP(c, c->bflow.read_back(P, stream));
     return FTTE_OK;
@@ -569,9 +570,9 @@ int BrickSweep::lane_stages(int lane, LaunchTiming &T)
     for (size_t st = 0, mp = 0; st < nstages; ++st) {
         if (off[st + 1] != off[st]) {
             const BrickLaunch L = launch(off[st], off[st + 1], S.nu0, S.nu1);
-            const int form = c->bopt.brick_form(nnu, c->emit_mode);
-            c->last_brick_form = form; c->last_brick_dataflow = 0; c->last_brick_whole = form != 2 && brick_whole_form(L, c->brick_waves);
-            const int lrc = form == 2 ? launch_brick_pair(L, P.max_dirs, c->pair_waves, q) : launch_brick(L, P.max_dirs, c->brick_waves, q);
+            const int form = c->opt.brick.brick_form(nnu, c->emit_mode);
+            c->last_brick_form = form; c->last_brick_dataflow = 0; c->last_brick_whole = form != 2 && brick_whole_form(L, O.brick_waves);
+            const int lrc = form == 2 ? launch_brick_pair(L, P.max_dirs, O.pair_waves, O.lds_pad, q) : launch_brick(L, P.max_dirs, O.brick_waves, O.lds_pad, q);
             if (lrc) return fail(c, lrc == -1 ? FTTE_ERR_ARG : FTTE_ERR_NO_DEVICE, "brick kernel launch failed");
         }
         // (after the stage: this lane's part of the blocks merge point mp waits for, recorded even behind an empty stage)
@@ -680,7 +681,7 @@ int tile_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, co
     const int n = c->n, nnu = c->nnu;
     const size_t per_acc = (size_t)nnu * c->ncell;
     // the emission variants of the tiled kernel are built for one shape
-    const int rows = c->emit_mode ? 8 : c->rows, stack = c->emit_mode ? 1 : c->stack;
+    const int rows = c->emit_mode ? 8 : c->opt.tile.rows, stack = c->emit_mode ? 1 : c->opt.tile.stack;
     if ((rc = build_plan(c, rows, stack, ndir, phi, theta, w))) return rc;
     Plan &P = c->plan;
 
@@ -758,7 +759,7 @@ int tile_sweep(ftte_ctx *c, int ndir, const double *phi, const double *theta, co
             layouts_awaited = true;
         }
         FTTE_HIP(c, hipEventRecord(T.start, stream));
-        const int lrc = launch_sweep(L, rows, c->waves, stack, nnu, stream);
+        const int lrc = launch_sweep(L, rows, c->opt.tile.waves, stack, nnu, c->opt.launch.lds_pad, stream);
         if (lrc == -1)
             return fail(c, FTTE_ERR_ARG, "no sweep kernel variant for this rows/stack/waves combination (rows x stack: 4x{1,4,8}, "
                                          "8x{1,2,4}, 16x1; waves 2, 3, 4, 6)");

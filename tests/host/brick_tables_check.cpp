@@ -159,7 +159,7 @@ static void check_launch()
     BrickLaunch L = brick_launch(P, T, 3, 7, 2, 5, 373248, 5000, uvb, 2);
     BrickLaunch E = expected(T.groups, T.tasks.get() + 3, uvb, 373248, 5000, 72, 4, 3, 2, 8, 2);
     CHECK(!std::memcmp(&L, &E, sizeof L));
-    CHECK(L.tiled == 0 && L.pad2_ == 0 && L.atomic_acc == 0 && L.sub == 0 && L.ticket == nullptr && L.queue == nullptr && L.epoch == 0);
+    CHECK(L.tiled == 0 && L.ablate == 0 && L.atomic_acc == 0 && L.sub == 0 && L.ticket == nullptr && L.queue == nullptr && L.epoch == 0);
     // the whole task list, every group (the one-launch forms)
     L = brick_launch(P, T, 0, 10, 0, 8, 373248, 5000, uvb, 0);
     E = expected(T.groups, T.tasks, uvb, 373248, 5000, 72, 10, 8, 0, 8, 0);
