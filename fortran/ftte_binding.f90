@@ -257,6 +257,50 @@ module ftte_binding
        integer(c_int64_t), intent(out) :: cell         ! 0-based cell-array index
      end function ftte_locate_cell
 
+     ! ---- the star catalogue: equiSources.f90:746-769 and :1169-1212 on the device, :1282-1293 on the host.  Stars are merged by
+     ! host leaf (include/ftte.h).  xyz(3,nstars) in the units of lo, hi; weight(nstars) >= 0 or c_null_ptr (1 each); star_cell(nstars)
+     ! 0-based host leaf, -1 outside the box, or c_null_ptr
+     integer(c_int) function ftte_star_catalogue(ctx, nstars, xyz, lo, hi, weight, star_cell, nsrc, outside) &
+          bind(C, name='ftte_star_catalogue')
+       import :: c_ptr, c_int, c_int64_t, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: nstars
+       real(c_double), intent(in) :: xyz(*), lo(3), hi(3)
+       type(c_ptr), value :: weight, star_cell
+       integer(c_int64_t), intent(out) :: nsrc, outside
+     end function ftte_star_catalogue
+
+     ! the sources of the last ftte_star_catalogue, ascending src_cell; every array may be c_null_ptr: src_cell (int64),
+     ! src_weight (int32), src_ndot (real64), src_first_star (int64, 0-based), src_abun2 (real64; needs a medium with abun2)
+     integer(c_int) function ftte_star_sources(ctx, nsrc, src_cell, src_weight, src_ndot, src_first_star, src_abun2) &
+          bind(C, name='ftte_star_sources')
+       import :: c_ptr, c_int, c_int64_t
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: nsrc
+       type(c_ptr), value :: src_cell, src_weight, src_ndot, src_first_star, src_abun2
+     end function ftte_star_sources
+
+     ! host only: (iMetal, coefMetal) per source and one population slot (0-based) per distinct pair; pop_first(npop) 0-based
+     integer(c_int) function ftte_star_populations(nmetal, metallicity, nsrc, abun2, iMetal, coefMetal, src_slot, npop, pop_first) &
+          bind(C, name='ftte_star_populations')
+       import :: c_int, c_int32_t, c_int64_t, c_double
+       integer(c_int), value :: nmetal
+       real(c_double), intent(in) :: metallicity(*), abun2(*)
+       integer(c_int64_t), value :: nsrc
+       integer(c_int32_t), intent(out) :: iMetal(*), src_slot(*)
+       real(c_double), intent(out) :: coefMetal(*)
+       integer(c_int64_t), intent(out) :: npop, pop_first(*)
+     end function ftte_star_populations
+
+     ! host only: the inverse of ftte_locate_cell; position needs 3*(level+1) entries, 183 always suffice
+     integer(c_int) function ftte_cell_position(ctx, cell, level, position) bind(C, name='ftte_cell_position')
+       import :: c_ptr, c_int, c_int32_t, c_int64_t
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: cell
+       integer(c_int), intent(out) :: level
+       integer(c_int32_t), intent(out) :: position(*)
+     end function ftte_cell_position
+
      integer(c_int) function ftte_point_sources(ctx, nsrc, src_cell, src_ndot, highest_pixel_level) &
           bind(C, name='ftte_point_sources')
        import :: c_ptr, c_int, c_int64_t, c_double

@@ -14,6 +14,9 @@
 ! cosmicSpectrum before (:1258) and divides by nStarsSpecificAge after (:1366), as the reference does around its loop.
 ! localDefinitions is a module of the reference's main file: compile this file after it (INTEGRATION.md).
 !
+! In front of it, where the stars come as coordinates: call ftteStarCatalogue(nx, nStars, xyz, lo, hi, star) replaces :750-757 of
+! the ingest loop and the whole of :1169-1212 (host leaves, call sequences, stars of one leaf merged); see there.
+!
 ! ftteStarBatch (default 1: the reference's sequence, one table build and one trace per star).  Set it larger and that many stars
 ! are traced together: each star's (iMetal, coefMetal) as before, stars with identical pairs share a population slot, one
 ! ftte_stellar_beta_tables and one ftte_point_sources_populations per batch; the per-star results follow in star order.
@@ -201,6 +204,70 @@ contains
     end subroutine traceBatch
 
   end subroutine ftteRunStellarTransfer
+
+  ! What replaces equiSources.f90:750-757 for every star and the whole of :1169-1212: the stars' coordinates xyz(3,nStars) in the
+  ! units of the box corners lo, hi (the reference's xa..zb); on entry star(:)%weight holds what the age filter (:773-783) gave.
+  ! On return star(:)%level and %position are the host leaf's (allocated here), and %weight is the sum over the stars of the
+  ! leaf on the leaf's first star with weight > 0 and 0 on the others, so that the rest of the driver and ftteRunStellarTransfer
+  ! run on the result.  Stars are merged by host leaf, not by the reference's location key (include/ftte.h).  A star outside the
+  ! box gets weight 0, level 0 and position (0,0,0); nOutside (optional) counts them.
+  subroutine ftteStarCatalogue(nx, nStars, xyz, lo, hi, star, nOutside)
+    integer, intent(in) :: nx, nStars
+    real(kind=RealKind), intent(in) :: xyz(3,nStars), lo(3), hi(3)
+    type(starType), intent(inout) :: star(:)
+    integer, intent(out), optional :: nOutside
+    integer(c_int64_t) :: ncell, nsrc, outside
+    integer(c_int32_t), allocatable, target :: lev(:), w(:), srcWeight(:)
+    integer(c_int64_t), allocatable, target :: cells(:), firstStar(:)
+    real(c_double), allocatable :: med(:,:)
+    integer(c_int32_t) :: pos(183)
+    integer(c_int) :: level
+    integer :: i, j, k, iStar
+
+    if (.not. c_associated(ctx)) call ftteCheck(c_null_ptr, ftte_create(ctx, 1, c_null_ptr), 'ftte_create')
+    ncell = 0
+    do i = 1, nx
+       do j = 1, nx
+          do k = 1, nx
+             call countCells(baseGrid%cell(i,j,k), ncell)
+          enddo
+       enddo
+    enddo
+    allocate(lev(ncell), med(ncell,5), w(nStars), cells(nStars))
+    cursor = 0
+    do i = 1, nx
+       do j = 1, nx
+          do k = 1, nx
+             call gatherMedium(baseGrid%cell(i,j,k), 0, lev, med)
+          enddo
+       enddo
+    enddo
+    call ftteCheck(ctx, ftte_set_grid(ctx, nx, nx, nx, ncell, lev, physicalBoxSize), 'ftte_set_grid')
+    do iStar = 1, nStars
+       w(iStar) = star(iStar)%weight
+    enddo
+    call ftteCheck(ctx, ftte_star_catalogue(ctx, int(nStars, c_int64_t), xyz, lo, hi, c_loc(w), c_loc(cells), nsrc, outside), &
+         'ftte_star_catalogue')
+    allocate(srcWeight(max(nsrc,1_c_int64_t)), firstStar(max(nsrc,1_c_int64_t)))
+    call ftteCheck(ctx, ftte_star_sources(ctx, nsrc, c_null_ptr, c_loc(srcWeight), c_null_ptr, c_loc(firstStar), c_null_ptr), &
+         'ftte_star_sources')
+    do iStar = 1, nStars
+       star(iStar)%weight = 0
+       if (cells(iStar) .ge. 0) then
+          call ftteCheck(ctx, ftte_cell_position(ctx, cells(iStar), level, pos), 'ftte_cell_position')
+       else
+          level = 0
+          pos(1:3) = 0
+       endif
+       star(iStar)%level = level
+       allocate(star(iStar)%position(3*level+3))
+       star(iStar)%position = pos(1:3*level+3)
+    enddo
+    do i = 1, int(nsrc)
+       star(firstStar(i)+1)%weight = srcWeight(i)
+    enddo
+    if (present(nOutside)) nOutside = int(outside)
+  end subroutine ftteStarCatalogue
 
   recursive subroutine countCells(c, total)
     type(zoneType) :: c

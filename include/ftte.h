@@ -187,7 +187,10 @@ int ftte_source_update_device(ftte_ctx *ctx, int nnu, double epsilon, const doub
  *   ftte_stellar_beta_tables(all populations of the batch) (or ftte_set_population_tables);
  *   ftte_point_sources_populations(stars, the slot each reads); ftte_point_escape;
  *   ftte_get_point_rates.
- * Rates accumulate on the device between ftte_set_zero_rates and ftte_get_point_rates. */
+ * Rates accumulate on the device between ftte_set_zero_rates and ftte_get_point_rates.
+ * In front of either, from a star list (equiSources.f90:746-769, :1169-1212, :1282-1293):
+ *   ftte_star_catalogue(coordinates, weights); ftte_star_sources -> src_cell, src_ndot, src_abun2;
+ *   ftte_star_populations(src_abun2) -> iMetal, coefMetal of each population and the slot each source reads. */
 
 #define FTTE_TABLE_SIZE 14641 /* (ndepth+1)^4 = 11^4, definitionsModule.f90:72-77 */
 #define FTTE_MAX_PIXEL_LEVEL 6 /* maxPixelLevel, equiSources.f90:9 */
@@ -240,6 +243,33 @@ int ftte_set_zero_rates(ftte_ctx *ctx);
 /* localizeCellFromStar, equiSources.f90:2597-2620: the star's call sequence position(1:3*(level+1)) (base
  * indices 1..n, then child indices 1..2 per level) -> 0-based cell-array index of its host cell. */
 int ftte_locate_cell(ftte_ctx *ctx, int level, const int32_t *position, int64_t *cell);
+/* The star catalogue on the device.  Stars are merged by HOST LEAF.  The reference merges by a key that two leaves of different
+ * depth can share (base cell 10 b + d, unrefined, and child d of base cell b), and then lets an unstable sort choose the survivor:
+ * that is not reproduced.
+ *
+ * :746-769 and :1169-1212 for nstars stars. xyz[nstars][3] in the units of lo/hi (the reference's xa..zb);
+ * weight[nstars] >= 0 or NULL (= 1 each: the age filter :773-783 stays with the caller).
+ * star_cell[nstars] (may be NULL): host leaf, -1 outside the box.
+ * *nsrc: leaves holding weight > 0; *outside: stars outside.
+ * Results stay on the device for ftte_star_sources.
+ * A star is inside where 0 <= int(x * n) < n along every axis of the unit cube, int() truncating as the reference's: -0.0 and
+ * nextafter(1, 0) are inside, 1.0, NaN and +-inf outside.  FTTE_ERR_ARG: hi <= lo or either not finite, a negative weight,
+ * weights beyond 2^31 - 1 in sum, nstars > 2^31 - 1 (ftte_last_error names the first offender); the last catalogue stays. */
+int ftte_star_catalogue(ftte_ctx *ctx, int64_t nstars, const double *xyz, const double lo[3], const double hi[3],
+                        const int32_t *weight, int64_t *star_cell, int64_t *nsrc, int64_t *outside);
+/* The sources of the LAST ftte_star_catalogue, ascending src_cell; any pointer may be NULL.
+ * src_ndot = (double)(float)weight (:1306); src_first_star = lowest star index with weight > 0 in the leaf;
+ * src_abun2 needs a medium with abun2 (else FTTE_ERR_STATE). */
+int ftte_star_sources(ftte_ctx *ctx, int64_t nsrc, int64_t *src_cell, int32_t *src_weight, double *src_ndot,
+                      int64_t *src_first_star, double *src_abun2);
+/* host only, no context: :1282-1293 per source, then one slot per distinct (iMetal, coefMetal) bit pattern in order
+ * of first appearance: src_slot[nsrc], *npop, pop_first[npop] = a source that carries slot p's parameters (room for nsrc entries
+ * always suffices).  metallicity[nmetal] ascending, nmetal >= 2; iMetal is 1-based and at most nmetal - 1.  Outputs may be NULL. */
+int ftte_star_populations(int nmetal, const double *metallicity, int64_t nsrc, const double *abun2,
+                          int32_t *iMetal, double *coefMetal, int32_t *src_slot, int64_t *npop, int64_t *pop_first);
+/* host only: inverse of ftte_locate_cell -- leaf -> level and call sequence position(1:3*(level+1)); position (may be NULL)
+ * needs room for the leaf's level, 183 entries always suffice */
+int ftte_cell_position(ftte_ctx *ctx, int64_t cell, int *level, int32_t *position);
 /* The per-star loop body, equiSources.f90:1268-1329, for nsrc stars that share the current tables:
  * src_cell[nsrc] host cells (0-based cell-array index), src_ndot[nsrc] = float(weight).  Adds into the device
  * rates.  highest_pixel_level (may be NULL): the largest value of the reference's highestPixelLevel over
@@ -498,7 +528,10 @@ int ftte_host_unregister(ftte_ctx *ctx, void *ptr);
  * the J accumulators they share (0 without a plan), "brick_chunk" (layers per brick of that plan) and "brick_queue_mix" (the
  * option "queue_mix" the persistent form's queues were laid out by; -1 when the plan has no queues); "brick_stages" (stages of that
  * plan), "merge_points" and "merge_blocks" (its block-wise merge: points and 32^3-cell blocks), "merge_stage_K" and "merge_final_K"
- * (the stage after which point K runs, the blocks final by then); "expansion_exact_tests" (ftte_expand_hii_regions); "devices"; of a multi-device context also "frequency_slices",
+ * (the stage after which point K runs, the blocks final by then); "expansion_exact_tests" (ftte_expand_hii_regions);
+ * "catalogue_stars" and "catalogue_sources" (the stars and the sources of the last ftte_star_catalogue; -1 sources: there is none),
+ * "catalogue_ns_locate", "_count", "_scan", "_emit" (device time of that call's four launches in nanoseconds, from events recorded
+ * around them; -1 where the launch did not run), "medium_abun2" (1: the medium of ftte_set_medium came with an abun2); "devices"; of a multi-device context also "frequency_slices",
  * "direction_slices" and "multi_rccl" (1: the last direction-split sweep was summed over RCCL), "rccl_loadable", "rccl_selftest" (runs the
  * direction sum's RCCL calls on a clique of one rank, the first device: 1 = the piece came back unchanged; negative = it could not
  * run), the rest from its first device.

@@ -64,6 +64,12 @@ SIGNATURES = {
     "ftte_set_medium_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.c_int]),
     "ftte_set_zero_rates": (C.c_int, [_vp]),
     "ftte_locate_cell": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
+    "ftte_star_catalogue": (C.c_int, [_vp, C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                      C.POINTER(C.c_int64)]),
+    "ftte_star_sources": (C.c_int, [_vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), _dp, C.POINTER(C.c_int64), _dp]),
+    "ftte_star_populations": (C.c_int, [C.c_int, _dp, C.c_int64, _dp, C.POINTER(C.c_int32), _dp, C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "ftte_cell_position": (C.c_int, [_vp, C.c_int64, _ip, C.POINTER(C.c_int32)]),
     "ftte_point_sources": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int64), _dp, _ip]),
     "ftte_point_sources_populations": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int64), _dp, C.POINTER(C.c_int32), _ip]),
     "ftte_point_escape": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, _dp, _dp]),

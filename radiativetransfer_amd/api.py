@@ -17,7 +17,7 @@ from . import _lib
 from ._lib import FtteError, Pattern
 
 __all__ = ["DiffuseTransfer", "StellarTransfer", "rmax", "dust_cross_section", "uvb_beta_table", "uniform_table", "coll_rates", "rate_coefficient_tables", "FtteError", "Pattern", "pix2ang_nest", "healpix_directions", "fold_direction",
-           "rotate_indices", "set_pattern", "layer_patterns", "compute_cell_intensity", "expansion_parameters", "map_axis", "slice_axis", "map_depth"]
+           "rotate_indices", "set_pattern", "layer_patterns", "compute_cell_intensity", "expansion_parameters", "map_axis", "slice_axis", "map_depth", "star_populations"]
 
 
 def _f64(a) -> np.ndarray:
@@ -365,6 +365,23 @@ def dust_cross_section(lambda_micron: float, a_smc) -> float:
     return float(_lib.load().ftte_dust_cross_section(float(lambda_micron), a.ctypes.data_as(C.POINTER(C.c_double))))
 
 
+def star_populations(metallicity, abun2) -> dict:
+    """The metallicity bracket of every source (equiSources.f90:1282-1293) from its host cell's abun2 and the library's
+    metallicity[nmetal] nodes, then one population slot per distinct (iMetal, coefMetal): dict of iMetal[nsrc] (1-based),
+    coefMetal[nsrc], slot[nsrc], pop_first[npop] (a source that carries slot p's parameters), pop_iMetal[npop], pop_coefMetal[npop].
+    Host only."""
+    met, abun2 = _f64(metallicity).reshape(-1), _f64(abun2).reshape(-1)
+    ns = abun2.size
+    i_metal, slot = np.empty(ns, dtype=np.int32), np.empty(ns, dtype=np.int32)
+    coef, first, npop = np.empty(ns), np.empty(max(ns, 1), dtype=np.int64), C.c_int64()
+    i32 = C.POINTER(C.c_int32)
+    _check(_lib.load().ftte_star_populations(met.size, _dp(met), ns, _dp(abun2), i_metal.ctypes.data_as(i32), _dp(coef),
+                                             slot.ctypes.data_as(i32), C.byref(npop), first.ctypes.data_as(C.POINTER(C.c_int64))),
+           "ftte_star_populations")
+    first = first[:npop.value].copy()
+    return dict(iMetal=i_metal, coefMetal=coef, slot=slot, pop_first=first, pop_iMetal=i_metal[first], pop_coefMetal=coef[first])
+
+
 class StellarTransfer(DiffuseTransfer):
     """The `if (runStellarTransfer)` block of the reference driver (equiSources.f90:1256-1370) on one GPU.
 
@@ -476,6 +493,41 @@ class StellarTransfer(DiffuseTransfer):
         cell = C.c_int64()
         self._ok(self._lib.ftte_locate_cell(self._ctx, pos.size // 3 - 1, pos.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(cell)))
         return cell.value
+
+    def star_catalogue(self, xyz, lo=(0.0, 0.0, 0.0), hi=(1.0, 1.0, 1.0), weight=None) -> dict:
+        """Stars -> host leaves -> one source per leaf (equiSources.f90:746-769, :1169-1212) on the device.  xyz[nstars][3] in
+        the units of the box corners lo, hi; weight[nstars] >= 0 (None: 1 each).  Returns star_cell[nstars] (-1 outside the box),
+        outside, and per source in ascending cell: cell, weight, ndot = float32(weight), first_star (lowest star index with
+        weight > 0 in the leaf), and abun2 where the medium has it.  Stars are merged by host leaf, not by the reference's key."""
+        xyz = _f64(xyz).reshape(-1, 3)
+        lo, hi = _f64(lo).reshape(3), _f64(hi).reshape(3)
+        i32, i64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        if weight is not None:
+            weight = np.ascontiguousarray(weight, dtype=np.int32).reshape(-1)
+            if weight.size != xyz.shape[0]:
+                raise ValueError("weight must have one entry per star")
+        star_cell = np.empty(xyz.shape[0], dtype=np.int64)
+        nsrc, outside = C.c_int64(), C.c_int64()
+        self._ok(self._lib.ftte_star_catalogue(self._ctx, xyz.shape[0], _dp(xyz), _dp(lo), _dp(hi),
+                                               None if weight is None else weight.ctypes.data_as(i32), star_cell.ctypes.data_as(i64),
+                                               C.byref(nsrc), C.byref(outside)))
+        ns = nsrc.value
+        out = dict(star_cell=star_cell, outside=outside.value, cell=np.empty(ns, dtype=np.int64), weight=np.empty(ns, dtype=np.int32),
+                   ndot=np.empty(ns), first_star=np.empty(ns, dtype=np.int64))
+        args = (self._ctx, ns, out["cell"].ctypes.data_as(i64), out["weight"].ctypes.data_as(i32), _dp(out["ndot"]),
+                out["first_star"].ctypes.data_as(i64))
+        if self.counter("medium_abun2") == 1:
+            out["abun2"] = np.empty(ns)
+        self._ok(self._lib.ftte_star_sources(*args, _dp(out["abun2"]) if "abun2" in out else None))
+        return out
+
+    def cell_position(self, cell: int) -> np.ndarray:
+        """The call sequence (1-based: base indices, then child indices per level) of a leaf: the inverse of locate_cell."""
+        level = C.c_int()
+        self._ok(self._lib.ftte_cell_position(self._ctx, int(cell), C.byref(level), None))
+        pos = np.empty(3 * (level.value + 1), dtype=np.int32)
+        self._ok(self._lib.ftte_cell_position(self._ctx, int(cell), C.byref(level), pos.ctypes.data_as(C.POINTER(C.c_int32))))
+        return pos
 
     def point_sources(self, cells, ndot) -> int:
         """Trace the stars in `cells` (0-based cell-array indices) with photon rates `ndot` through the medium, adding

@@ -118,6 +118,7 @@ int ftte_set_grid(ftte_ctx *c, int nx, int ny, int nz, int64_t ncell, const int3
     c->hdev.drop_grid();
     c->gas.drop();
     c->point.drop_grid();
+    c->catalogue.drop_grid();
     c->dtree.drop();
     c->chem.drop_grid();
     c->analysis.drop_grid();
@@ -340,6 +341,15 @@ long long ftte_counter(const ftte_ctx *c, const char *name)
     if (!std::strcmp(name, "device_objects")) return g_device_objects.load();
     if (!std::strcmp(name, "population_slots")) return c->point.tables.slot_count();
     if (!std::strcmp(name, "expansion_exact_tests")) return c->chem.expansion_tests;
+    if (!std::strcmp(name, "medium_abun2")) return c->gas.ready_with_abundance(c->ncell) ? 1 : 0; // the medium came with an abun2
+    if (!std::strcmp(name, "catalogue_stars")) return c->catalogue.stars();      // of the last ftte_star_catalogue
+    if (!std::strcmp(name, "catalogue_sources")) return c->catalogue.sources();  // -1: there is none
+    if (!std::strncmp(name, "catalogue_ns_", 13)) { // device time of the last catalogue's launches: locate, count, scan, emit
+        static const char *const phase[4] = {"locate", "count", "scan", "emit"};
+        for (int p = 0; p < 4; ++p)
+            if (!std::strcmp(name + 13, phase[p])) return catalogue_phase_ns(c->catalogue, p);
+        return -1;
+    }
     if (!std::strcmp(name, "hybrid_boxes")) return c->hplan.boxes();
     if (!std::strcmp(name, "hybrid_passes")) return c->hplan.passes();
     if (!std::strcmp(name, "fine_block")) return c->hplan.fine_block();

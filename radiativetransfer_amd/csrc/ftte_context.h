@@ -13,8 +13,8 @@
 // a refined cell array the forests, their scratch and their cache (ftte_forests.h) and the hybrid sweep's options, plan and device
 // state (ftte_hybrid.h), for host arrays the staging blocks and the registered ranges (ftte_host.h), for the tree its copy on the
 // device (ftte_device_tree.h), and for point sources the rate tables with their output cross-sections, the accumulated rates, the
-// tracer's scratch and the escape record of the last trace (ftte_point.h).  The reference's table mathematics reads no context and
-// no HIP (ftte_tables.cpp).
+// tracer's scratch and the escape record of the last trace (ftte_point.h), and for the star catalogue its scratch and the sources of
+// the last catalogue (ftte_star_catalogue.h).  The reference's table mathematics reads no context and no HIP (ftte_tables.cpp).
 //
 // There is no CPU fallback behind any of this: every entry point that computes on the grid needs a HIP device and fails with
 // FTTE_ERR_NO_DEVICE otherwise.
@@ -43,6 +43,7 @@
 #include "ftte_medium.h"
 #include "ftte_options.h"
 #include "ftte_point.h"
+#include "ftte_star_catalogue.h"
 #include "ftte_tiles.h"
 
 
@@ -159,6 +160,8 @@ struct ftte_ctx {
     DeviceBuffer<double> d_lambda_host; // ftte_lambda_diagonal: the diagonal on its way to the caller's host array
     DeviceBuffer<unsigned long long> d_update_stats;
     PinnedBuffer<unsigned long long> h_update_stats;
+
+    StarCatalogue catalogue; // stars -> host leaves -> merged sources (ftte_star_catalogue.h)
 };
 
 namespace ftte {

@@ -21,6 +21,7 @@ public:
     int dust() const { return dust_; } // dustApproximation of the last fill
     bool ready(int64_t ncell) const { return cells_ > 0 && cells_ == ncell; }
     bool ready_with_density(int64_t ncell) const { return ready(ncell) && density_; } // (the chemistry and the census need rho)
+    bool ready_with_abundance(int64_t ncell) const { return ready(ncell) && abundance_; } // (the star catalogue's abun2)
 
     // Room for a fill of ncell cells, which starts here: the packed copy is stale.  For another cell count everything is released
     // first and the gas is not ready until filled(); for the same one the buffers, the packed copy's among them, stay.  On failure
@@ -35,9 +36,9 @@ public:
         }
         return hipSuccess;
     }
-    void filled(int64_t ncell, int dust, bool density)
+    void filled(int64_t ncell, int dust, bool density, bool abundance = false)
     {
-        cells_ = ncell; dust_ = dust; density_ = density;
+        cells_ = ncell; dust_ = dust; density_ = density; abundance_ = abundance;
     }
     void species_changed() { ++version_; } // the packed copy is stale
     void drop()                            // another grid: nothing of the old one is kept
@@ -46,7 +47,7 @@ public:
         packed_.reset();
         packed_from_ = kNever;
         cells_ = 0;
-        density_ = false;
+        density_ = abundance_ = false;
     }
 
     // the tracer's copy, [cells][cell_rec]: room (a new buffer holds nothing), then the launch, then packed_made()
@@ -67,6 +68,7 @@ private:
     int64_t cells_ = 0; // of the last fill; 0: none
     int dust_ = 0;
     bool density_ = false; // that fill brought a density
+    bool abundance_ = false; // ... and an abun2
     long long version_ = 0, packed_from_ = kNever;
 };
 

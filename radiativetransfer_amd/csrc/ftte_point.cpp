@@ -192,7 +192,7 @@ int point_set_medium(GasState &G, hipStream_t stream, int64_t ncell, const doubl
             POINT_HIP(hipMemsetAsync(G.field(f), 0, sizeof(double) * ncell, stream)); // rho, abun2 are only read with dust
     }
     POINT_HIP(hipStreamSynchronize(stream));
-    G.filled(ncell, dust, field[GasState::kRho] != nullptr);
+    G.filled(ncell, dust, field[GasState::kRho] != nullptr, field[GasState::kAbun2] != nullptr);
     return 0;
 }
 
