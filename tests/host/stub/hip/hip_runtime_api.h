@@ -2,7 +2,9 @@
 // live objects, a count of releases, and a switch that makes the next allocation or creation fail; the copies and fills that
 // ftte_bricks.h issues, as memcpy / memset with a count of the copies; the free memory that ftte_forests.h asks for; the pinning of
 // host ranges and the waits that ftte_host.h calls.  The streams run everything at once unless stub().lazy asks for the laziest
-// legal schedule: an asynchronous copy waits on its stream until the host waits for it.  tests/host/ only.
+// legal schedule: an asynchronous copy waits on its stream until the host waits for it.  For the sweeps of a refined cell array
+// (ftte_sweeps.cpp, ftte_hybrid.cpp): a blocking fill, the device's properties, event times, and stream capture that reports failure.
+// tests/host/ only.
 #pragma once
 
 #include <cstddef>
@@ -12,7 +14,7 @@
 #include <set>
 #include <vector>
 
-typedef enum { hipSuccess = 0, hipErrorOutOfMemory = 2, hipErrorHostMemoryNotRegistered = 713 } hipError_t;
+typedef enum { hipSuccess = 0, hipErrorOutOfMemory = 2, hipErrorHostMemoryNotRegistered = 713, hipErrorStreamCaptureUnsupported = 900 } hipError_t;
 typedef struct stub_event *hipEvent_t;
 typedef struct stub_stream *hipStream_t;
 typedef struct stub_graph *hipGraph_t;
@@ -123,5 +125,18 @@ inline hipError_t hipHostRegister(void *p, size_t, unsigned)
     return hipSuccess;
 }
 inline hipError_t hipHostUnregister(void *p) { return stub().pinned.erase(p) ? hipSuccess : hipErrorHostMemoryNotRegistered; }
+// what the sweeps of ftte_sweeps.cpp and ftte_hybrid.cpp call beside the above: a blocking fill, the device's properties, the
+// time between two events (none passes here), and stream capture, which this runtime refuses: the hybrid sweep then issues its
+// launches one by one
+inline hipError_t hipMemset(void *dst, int value, size_t bytes) { std::memset(dst, value, bytes); return hipSuccess; }
+struct hipDeviceProp_t { char gcnArchName[256]; int multiProcessorCount; };
+inline hipError_t hipGetDeviceProperties(hipDeviceProp_t *prop, int) { std::memset(prop, 0, sizeof *prop); std::strcpy(prop->gcnArchName, "gfx950"); prop->multiProcessorCount = 256; return hipSuccess; }
+inline hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) { *ms = 0.f; return hipSuccess; }
+typedef enum { hipStreamCaptureModeGlobal = 0, hipStreamCaptureModeThreadLocal = 1, hipStreamCaptureModeRelaxed = 2 } hipStreamCaptureMode;
+typedef struct stub_graph_node *hipGraphNode_t;
+inline hipError_t hipStreamBeginCapture(hipStream_t, hipStreamCaptureMode) { return hipErrorStreamCaptureUnsupported; }
+inline hipError_t hipStreamEndCapture(hipStream_t, hipGraph_t *graph) { *graph = nullptr; return hipErrorStreamCaptureUnsupported; }
+inline hipError_t hipGraphInstantiate(hipGraphExec_t *exec, hipGraph_t, hipGraphNode_t *, char *, size_t) { *exec = nullptr; return hipErrorStreamCaptureUnsupported; }
+inline hipError_t hipGraphLaunch(hipGraphExec_t, hipStream_t) { return hipErrorStreamCaptureUnsupported; }
 inline hipError_t hipGetLastError() { return hipSuccess; }
 inline const char *hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : e == hipErrorOutOfMemory ? "out of memory" : "error"; }
