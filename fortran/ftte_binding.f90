@@ -619,6 +619,87 @@ module ftte_binding
        real(c_double), intent(out) :: logtem0, logtem9, dlogtem
      end function ftte_rate_coefficient_tables
 
+     ! the thirteen cooling coefficients of calc_rates and compa; case B reads the caller's copies of the two data files (c_null_ptr
+     ! for case A): mellema(2,81) = columns 1, 3 of HII-ktbetas.tab, gnedin(3,201) = columns 1, 3, 5 of cratesHe.res
+     integer(c_int) function ftte_cooling_coefficient_tables(nratec, temstart, temend, recombination_type, mellema, gnedin, c, compa) &
+          bind(C, name='ftte_cooling_coefficient_tables')
+       import :: c_ptr, c_int, c_double
+       integer(c_int), value :: nratec, recombination_type
+       real(c_double), value :: temstart, temend
+       type(c_ptr), value :: mellema, gnedin
+       real(c_double), intent(out) :: c(*)         ! (nratec, 13): ceHIa .. lineHIa in the order of equiSources.f90:3975-3987
+       real(c_double), intent(out) :: compa
+     end function ftte_cooling_coefficient_tables
+
+     ! ---- thermal balance: thermalEquilibrium (equiSources.f90:3870-4042) and the temperature advanced over a time step
+     integer(c_int) function ftte_get_temperature(ctx, tgas) bind(C, name='ftte_get_temperature')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       real(c_double), intent(out) :: tgas(*)
+     end function ftte_get_temperature
+
+     integer(c_int) function ftte_set_cooling_coefficients(ctx, nratec, c, compa, redshift) bind(C, name='ftte_set_cooling_coefficients')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: nratec
+       real(c_double), intent(in) :: c(*)          ! (nratec, 13)
+       real(c_double), value :: compa, redshift
+     end function ftte_set_cooling_coefficients
+
+     ! heating, cooling, hydro_heating: c_loc of an array of ncell, or c_null_ptr
+     integer(c_int) function ftte_thermal_equilibrium(ctx, run_uvb_transfer, J, gamma, uniform_gamma, self_shielding_threshold, &
+          use_point_rates, heating, cooling, hydro_heating) bind(C, name='ftte_thermal_equilibrium')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: run_uvb_transfer, use_point_rates
+       real(c_double), intent(in) :: J(*)          ! (ncell, 3): Jmean1..3
+       real(c_double), intent(in) :: gamma(3,3)    ! (gammaHI, gammaHeI, gammaHeII) x (group1, group2, group3)
+       real(c_double), intent(in) :: uniform_gamma(3) ! the uniform background's gammas of HI, HeII, HeI
+       real(c_double), value :: self_shielding_threshold
+       type(c_ptr), value :: heating, cooling, hydro_heating
+     end function ftte_thermal_equilibrium
+
+     integer(c_int) function ftte_thermal_equilibrium_device(ctx, run_uvb_transfer, J_dev, gamma, uniform_gamma, &
+          self_shielding_threshold, use_point_rates, heating, cooling, hydro_heating) bind(C, name='ftte_thermal_equilibrium_device')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: run_uvb_transfer, use_point_rates
+       type(c_ptr), value :: J_dev
+       real(c_double), intent(in) :: gamma(3,3)
+       real(c_double), intent(in) :: uniform_gamma(3)
+       real(c_double), value :: self_shielding_threshold
+       type(c_ptr), value :: heating, cooling, hydro_heating
+     end function ftte_thermal_equilibrium_device
+
+     ! the temperature advanced over dt_s seconds in `substeps` implicit steps at fixed species, clipped to [tmin, tmax];
+     ! use_hydro_heating adds the hydroHeating of the last ftte_thermal_equilibrium; the rate arguments as there
+     integer(c_int) function ftte_advance_temperature(ctx, dt_s, substeps, tmin, tmax, use_hydro_heating, run_uvb_transfer, J, gamma, &
+          uniform_gamma, self_shielding_threshold, use_point_rates, max_change) bind(C, name='ftte_advance_temperature')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       real(c_double), value :: dt_s, tmin, tmax
+       integer(c_int), value :: substeps, use_hydro_heating, run_uvb_transfer, use_point_rates
+       real(c_double), intent(in) :: J(*)
+       real(c_double), intent(in) :: gamma(3,3)
+       real(c_double), intent(in) :: uniform_gamma(3)
+       real(c_double), value :: self_shielding_threshold
+       real(c_double), intent(out) :: max_change
+     end function ftte_advance_temperature
+
+     integer(c_int) function ftte_advance_temperature_device(ctx, dt_s, substeps, tmin, tmax, use_hydro_heating, run_uvb_transfer, &
+          J_dev, gamma, uniform_gamma, self_shielding_threshold, use_point_rates, max_change) &
+          bind(C, name='ftte_advance_temperature_device')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       real(c_double), value :: dt_s, tmin, tmax
+       integer(c_int), value :: substeps, use_hydro_heating, run_uvb_transfer, use_point_rates
+       type(c_ptr), value :: J_dev
+       real(c_double), intent(in) :: gamma(3,3)
+       real(c_double), intent(in) :: uniform_gamma(3)
+       real(c_double), value :: self_shielding_threshold
+       real(c_double), intent(out) :: max_change
+     end function ftte_advance_temperature_device
+
   end interface
 
 contains

@@ -5,6 +5,7 @@
 ! against oracle/_ref/definitions.mod (fortran/Makefile: target `dropin-check`).
 !
 !   call ftteInitialIonizationEquilibrium(nx)        ! replaces :1008-1022 (both passes, computeMass, the printed fraction)
+!   call ftteThermalEquilibrium(nx)                  ! replaces :1025-1033 (thermalEquilibrium for every leaf; sets hydroHeating)
 !   call ftteExpandHIIRegions(nx, nStars, star)      ! replaces :1035-1069, inside `if (expansionFlag)` (off in the shipped source)
 !   call ftteSolveRateEquations(nx, runUVBTransfer)  ! replaces the solveRateEquations calls of :1824-1831
 !   call ftteComputeMass(nx)                         ! replaces the computeMass calls of :1824-1831
@@ -235,6 +236,56 @@ contains
     endif
     call ftteCheck(ctx, ftte_hydrogen_mass(ctx, neutralHydrogenMass, totalHydrogenMass), 'ftte_hydrogen_mass')
   end subroutine ftteComputeMass
+
+  ! equiSources.f90:1025-1033: thermalEquilibrium for every leaf, from the module's own cooling tables as calc_rates filled them.
+  ! hydroHeating goes back into the tree and stays on the device, where ftte_advance_temperature adds it behind its flag.
+  subroutine ftteThermalEquilibrium(nx)
+    integer, intent(in) :: nx
+    real(c_double), allocatable :: f(:,:), cool(:,:)
+    real(c_double), allocatable, target :: hydro(:)
+    real(c_double) :: gamma(3,3), uniformGamma(3)
+    integer :: i, j, k
+
+    call loadTree(nx, f)
+    resident = .true.
+    allocate(cool(nratec,13), hydro(size(f,1)))
+    cool(:,1) = ceHIa;   cool(:,2) = ceHeIa;   cool(:,3) = ceHeIIa;   cool(:,4) = ciHIa;     cool(:,5) = ciHeIa
+    cool(:,6) = ciHeISa; cool(:,7) = ciHeIIa;  cool(:,8) = reHIIa;    cool(:,9) = reHeII1a;  cool(:,10) = reHeII2a
+    cool(:,11) = reHeIIIa; cool(:,12) = brema; cool(:,13) = lineHIa
+    call ftteCheck(ctx, ftte_set_cooling_coefficients(ctx, nratec, cool, compa, currentRedshift), 'ftte_set_cooling_coefficients')
+    gamma = 0.d0
+    uniformGamma = (/ uniformQuasar*quasar%gammaHI + uniformStellar*stellar%gammaHI, &
+                      uniformQuasar*quasar%gammaHeII + uniformStellar*stellar%gammaHeII, &
+                      uniformQuasar*quasar%gammaHeI + uniformStellar*stellar%gammaHeI /)
+    call ftteCheck(ctx, ftte_thermal_equilibrium(ctx, 0, f(:,9:11), gamma, uniformGamma, selfShieldingThreshold, 0, c_null_ptr, &
+         c_null_ptr, c_loc(hydro)), 'ftte_thermal_equilibrium')
+    cursor = 0
+    do i = 1, nx
+       do j = 1, nx
+          do k = 1, nx
+             call scatterHydroHeating(baseGrid%cell(i,j,k), hydro)
+          enddo
+       enddo
+    enddo
+  end subroutine ftteThermalEquilibrium
+
+  recursive subroutine scatterHydroHeating(c, hydro)
+    type(zoneType) :: c
+    real(c_double), intent(in) :: hydro(:)
+    integer :: a, b, d
+    if (c%refined) then
+       do a = 1, 2
+          do b = 1, 2
+             do d = 1, 2
+                call scatterHydroHeating(c%cell(a,b,d), hydro)
+             enddo
+          enddo
+       enddo
+    else
+       cursor = cursor + 1
+       c%hydroHeating = hydro(cursor)
+    endif
+  end subroutine scatterHydroHeating
 
   recursive subroutine countChemCells(c, total)
     type(zoneType) :: c

@@ -318,6 +318,14 @@ int ftte_coll_rates(double T, int recombination_type, double *k);
  * what ftte_set_rate_coefficients takes (the reference: nratec = 5000, temstart = 1., temend = 1.e8) */
 int ftte_rate_coefficient_tables(int nratec, double temstart, double temend, int recombination_type, double *k, double *logtem0,
                                  double *logtem9, double *dlogtem);
+/* The thirteen cooling coefficients as calc_rates.f:414-544 fills them with the flags as compiled (:155), and compa (:619), on the
+ * temperature grid of ftte_rate_coefficient_tables (host, no context): c[13][nratec] in the order of equiSources.f90:3975-3987 --
+ * ceHI, ceHeI, ceHeII, ciHI, ciHeI, ciHeIS, ciHeII, reHII, reHeII1, reHeII2, reHeIII, brem, lineHI -- what
+ * ftte_set_cooling_coefficients takes.  Case B (recombination_type 2) interpolates the reference's two data files, which the
+ * caller hands over as the files hold them: mellema[81][2] = columns 1 and 3 of HII-ktbetas.tab, gnedin[201][3] = columns 1, 3, 5
+ * of cratesHe.res; FTTE_ERR_ARG without them.  Case A needs neither (NULL). */
+int ftte_cooling_coefficient_tables(int nratec, double temstart, double temend, int recombination_type, const double *mellema,
+                                    const double *gnedin, double *c, double *compa);
 /* uniformTable(nfreq, freqdel, alphaQuasar, alphaStellar), uniformTable.f90:1-200 (host): the two power-law components of the
  * uniform background.  ksi[2][3] = [quasar, stellar][ksi24, ksi25, ksi26], gamma[2][3] = [quasar, stellar][gammaHI, gammaHeI,
  * gammaHeII]; uniformQuasar*ksi[0][x] + uniformStellar*ksi[1][x] is the `uniform` argument of ftte_solve_rate_equations. */
@@ -337,7 +345,7 @@ double ftte_dust_cross_section(double lambda_micron, const double *a_smc);
  * dlogtem (equiSources.f90:174-176) */
 int ftte_set_rate_coefficients(ftte_ctx *ctx, int nratec, double logtem0, double logtem9, double dlogtem, const double *k1a,
                                const double *k2a, const double *k3a, const double *k4a, const double *k5a, const double *k6a);
-/* zoneType%tgas per leaf [K] */
+/* zoneType%tgas per leaf [K]: its logarithm, taken on the host, for the chemistry, and the temperature itself for the thermal balance */
 int ftte_set_temperature(ftte_ctx *ctx, const double *tgas);
 /* run_uvb_transfer != 0 (:3545-3553): J[3][ncell] (Jmean1..3) and ksi[3][3] = (ksi24, ksi25, ksi26) of group1..3
  * (normCrossSectionType, definitionsModule.f90:94-103); uniform may be NULL.
@@ -369,6 +377,52 @@ int ftte_advance_rate_equations(ftte_ctx *ctx, double dt_s, int substeps, int ru
 int ftte_advance_rate_equations_device(ftte_ctx *ctx, double dt_s, int substeps, int run_uvb_transfer, const double *J_dev,
                                        const double *ksi, const double *uniform, double self_shielding_threshold,
                                        int use_point_rates, double *max_change);
+/* ---- thermal balance: thermalEquilibrium (equiSources.f90:3870-4042) and the temperature over a time step -----------------
+ * Per cell one statement shared by host and device (csrc/ftte_thermal_math.h).  The reference's: the locals HI .. de (:3907-3925),
+ * the heating of the uniform background behind the self-shielding test (:3929-3940), the interpolation of the thirteen cooling
+ * coefficients (:3946-3987), edot (:3991-4029, without the two terms it multiplies by literal zeros) and hydroHeating
+ * (:4030-4038); its write-back of the clipped helium into the cell (:3914-3918) is not made: no thermal call changes a species.
+ * The build's own: the heating by the transfer's J and by the point sources, formed as solveRateEquations forms the ionisation
+ * rates, and the temperature step.  The rate arguments are those of ftte_solve_rate_equations with the heating integrals in place
+ * of ksi: gamma[3][3] = [group][gammaHI, gammaHeI, gammaHeII] of ftte_uvb_beta_table (crate24 += t1 g[0][0] + t2 g[1][0] +
+ * t3 g[2][0], crate26 += t2 g[1][1] + t3 g[2][1], crate25 += t3 g[2][2], t = 4 pi J), uniform_gamma[3] = uniformQuasar*quasar%gamma +
+ * uniformStellar*stellar%gamma of HI, HeII, HeI (ftte_uniform_table), use_point_rates: crate24..26 of the device-resident rates.
+ * Preconditions those of ftte_solve_rate_equations plus ftte_set_cooling_coefficients. */
+
+/* The temperature per leaf [K] as it stands on the device: what ftte_set_temperature gave, or the last ftte_advance_temperature's */
+int ftte_get_temperature(ftte_ctx *ctx, double *tgas);
+/* c[13][nratec] of ftte_cooling_coefficient_tables, compa, and currentRedshift: comp1 = compa (1+z)^4, comp2 = 2.73 (1+z).
+ * FTTE_ERR_STATE before ftte_set_rate_coefficients, FTTE_ERR_ARG unless nratec is that call's: the two share one temperature grid
+ * (another nratec there drops these coefficients). */
+int ftte_set_cooling_coefficients(ftte_ctx *ctx, int nratec, const double *c, double compa, double redshift);
+/* thermalEquilibrium for every leaf, at ftte_log of its temperature: heating = crate (:3940), cooling = minus the cooling sum,
+ * hydro_heating = max(cooling - heating, 0) [erg/(s cm^3)], ncell each, each may be NULL; hydroHeating stays on the device.  With
+ * run_uvb_transfer == 0 and use_point_rates == 0 it is the reference's start-up pass (:1025-1033).  FTTE_ERR_RATES (first
+ * failing cell named, nothing stored) where a temperature is not positive and finite or a result is not finite. */
+int ftte_thermal_equilibrium(ftte_ctx *ctx, int run_uvb_transfer, const double *J, const double *gamma, const double *uniform_gamma,
+                             double self_shielding_threshold, int use_point_rates, double *heating, double *cooling,
+                             double *hydro_heating);
+int ftte_thermal_equilibrium_device(ftte_ctx *ctx, int run_uvb_transfer, const double *J_dev, const double *gamma,
+                                    const double *uniform_gamma, double self_shielding_threshold, int use_point_rates, double *heating,
+                                    double *cooling, double *hydro_heating);
+/* The temperature of every leaf advanced over dt_s seconds, isochoric, the species held fixed (the chemistry is advanced by its
+ * own calls: operator-split, explicit).  Heat capacity per volume c = kB (nH + nHe + de)/(gamma - 1); the rates per absorber are
+ * formed once per call; use_hydro_heating != 0 adds the leaf's stored hydroHeating to the net rate.  The incoming T is clipped to
+ * [tmin, tmax]; each of `substeps` backward-Euler steps of h = dt_s/substeps solves F(T) = (T - T0) - (h/c) (edot(T) + hydro) = 0:
+ * F(T0) == 0 leaves T0; net heating brackets [T0, tmax] (T1 = tmax if F(tmax) <= 0), net cooling [tmin, T0] (T1 = tmin if
+ * F(tmin) > 0); else bisection in T until the midpoint is an end of the bracket, so that F(T1) <= 0 < F(nextafter(T1)).  The
+ * cooling curve is not monotonic: of several roots the step returns the one its bracket, on the gas's own side of T0, closes on.
+ * Afterwards the leaf's temperature and its logarithm (ftte_log) are the device's: the next chemistry call reads them.
+ * max_change (may be NULL): largest |T1 - T0|/T0, T0 the clipped incoming temperature; ftte_rate_equation_steps counts the bisection
+ * steps.  FTTE_ERR_ARG unless dt_s is finite and > 0, 1 <= substeps <= 4096 and 0 < tmin < tmax are finite; FTTE_ERR_STATE when
+ * use_hydro_heating is set and no ftte_thermal_equilibrium has run on this grid; FTTE_ERR_RATES, the first failing cell named and
+ * nothing changed, where a temperature, a heat capacity or an F is not finite or a bisection does not settle in 4096 steps. */
+int ftte_advance_temperature(ftte_ctx *ctx, double dt_s, int substeps, double tmin, double tmax, int use_hydro_heating,
+                             int run_uvb_transfer, const double *J, const double *gamma, const double *uniform_gamma,
+                             double self_shielding_threshold, int use_point_rates, double *max_change);
+int ftte_advance_temperature_device(ftte_ctx *ctx, double dt_s, int substeps, double tmin, double tmax, int use_hydro_heating,
+                                    int run_uvb_transfer, const double *J_dev, const double *gamma, const double *uniform_gamma,
+                                    double self_shielding_threshold, int use_point_rates, double *max_change);
 /* HI, HeI, HeII of the device-resident medium, ncell each */
 int ftte_get_medium(ftte_ctx *ctx, double *HI, double *HeI, double *HeII);
 /* computeOpacities (equiSources.f90:4956-4983) on the device-resident medium: kappa[g] = HI beta[0][g] + HeI beta[1][g] +
@@ -379,7 +433,7 @@ int ftte_compute_opacities(ftte_ctx *ctx, int nnu, const double *beta);
  * HeII 1.58e-18) of the device-resident medium is at least the threshold, else 0.  J[nnu][ncell]. */
 int ftte_assign_uvb_radiation(ftte_ctx *ctx, int nnu, const double *uvb, double self_shielding_threshold, double *J);
 int ftte_assign_uvb_radiation_device(ftte_ctx *ctx, int nnu, const double *uvb, double self_shielding_threshold, double *J_dev);
-/* bisection steps of the last ftte_solve_rate_equations*, ftte_advance_rate_equations* or ftte_initial_ionization_equilibrium, summed over the cells (and
+/* bisection steps of the last ftte_solve_rate_equations*, ftte_advance_rate_equations*, ftte_advance_temperature* or ftte_initial_ionization_equilibrium, summed over the cells (and
  * over the passes of the latter) */
 long long ftte_rate_equation_steps(const ftte_ctx *ctx);
 /* The start-up ionisation equilibrium, equiSources.f90:1008-1022: initialIonizationEquilibrium (:3679-3868) `passes` times

@@ -87,6 +87,15 @@ SIGNATURES = {
     "ftte_assign_uvb_radiation_device": (C.c_int, [_vp, C.c_int, _dp, C.c_double, _vp]),
     "ftte_advance_rate_equations": (C.c_int, [_vp, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, _dp]),
     "ftte_advance_rate_equations_device": (C.c_int, [_vp, C.c_double, C.c_int, C.c_int, _vp, _dp, _dp, C.c_double, C.c_int, _dp]),
+    "ftte_get_temperature": (C.c_int, [_vp, _dp]),
+    "ftte_set_cooling_coefficients": (C.c_int, [_vp, C.c_int, _dp, C.c_double, C.c_double]),
+    "ftte_thermal_equilibrium": (C.c_int, [_vp, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, _dp, _dp, _dp]),
+    "ftte_thermal_equilibrium_device": (C.c_int, [_vp, C.c_int, _vp, _dp, _dp, C.c_double, C.c_int, _dp, _dp, _dp]),
+    "ftte_advance_temperature": (C.c_int, [_vp, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double,
+                                           C.c_int, _dp]),
+    "ftte_advance_temperature_device": (C.c_int, [_vp, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _dp, _dp,
+                                                  C.c_double, C.c_int, _dp]),
+    "ftte_cooling_coefficient_tables": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, _dp]),
     "ftte_rate_equation_steps": (C.c_longlong, [_vp]),
     "ftte_initial_ionization_equilibrium": (C.c_int, [_vp, _dp, C.c_double, C.c_int, _dp]),
     "ftte_hydrogen_mass": (C.c_int, [_vp, _dp, _dp]),

@@ -16,7 +16,7 @@ import numpy as np
 from . import _lib
 from ._lib import FtteError, Pattern
 
-__all__ = ["DiffuseTransfer", "StellarTransfer", "rmax", "dust_cross_section", "uvb_beta_table", "uniform_table", "coll_rates", "rate_coefficient_tables", "FtteError", "Pattern", "pix2ang_nest", "healpix_directions", "fold_direction",
+__all__ = ["DiffuseTransfer", "StellarTransfer", "rmax", "dust_cross_section", "uvb_beta_table", "uniform_table", "coll_rates", "rate_coefficient_tables", "cooling_coefficient_tables", "FtteError", "Pattern", "pix2ang_nest", "healpix_directions", "fold_direction",
            "rotate_indices", "set_pattern", "layer_patterns", "compute_cell_intensity", "expansion_parameters", "map_axis", "slice_axis", "map_depth", "star_populations"]
 
 
@@ -351,6 +351,28 @@ def rate_coefficient_tables(nratec: int = 5000, temstart: float = 1.0, temend: O
     return k, a.value, b.value, c.value
 
 
+def cooling_coefficient_tables(nratec: int = 5000, temstart: float = 1.0, temend: Optional[float] = None, recombination_type: int = 2,
+                               mellema=None, gnedin=None):
+    """The thirteen cooling coefficients as the reference's driver tabulates them (calc_rates.f:414-544) on the temperature grid of
+    rate_coefficient_tables, and compa (:619): returns (c[13][nratec], compa), the arguments of
+    StellarTransfer.set_cooling_coefficients.  Case B interpolates the reference's two data files, handed over as the files hold
+    them: mellema[81][2] = columns 1, 3 of HII-ktbetas.tab, gnedin[201][3] = columns 1, 3, 5 of cratesHe.res; case A (1) needs neither."""
+    temend = float(np.float32(1.0e8)) if temend is None else float(temend)
+    c, compa = np.empty((13, nratec)), C.c_double()
+    if mellema is not None:
+        mellema = _f64(mellema)
+        if mellema.shape != (81, 2):
+            raise ValueError("mellema must have shape [81][2]")
+    if gnedin is not None:
+        gnedin = _f64(gnedin)
+        if gnedin.shape != (201, 3):
+            raise ValueError("gnedin must have shape [201][3]")
+    _check(_lib.load().ftte_cooling_coefficient_tables(int(nratec), float(temstart), temend, int(recombination_type),
+                                                       None if mellema is None else _dp(mellema), None if gnedin is None else _dp(gnedin),
+                                                       _dp(c), C.byref(compa)), "ftte_cooling_coefficient_tables")
+    return c, compa.value
+
+
 def uniform_table(alpha_quasar: float, alpha_stellar: float, nfreq: int = 400, freqdel: Optional[float] = None):
     """uniformTable (uniformTable.f90): (ksi[2][3], gamma[2][3]) of the quasar and the stellar power-law component."""
     ksi, gamma = np.empty((2, 3)), np.empty((2, 3))
@@ -646,6 +668,68 @@ class StellarTransfer(DiffuseTransfer):
         fn = self._lib.ftte_advance_rate_equations_device
         return self._solve(lambda ctx, *rest: fn(ctx, float(dt), int(substeps), *rest), C.c_void_p(j_device_ptr), True, ksi, None, 0.0,
                            use_point_rates)
+
+    # -- thermal balance: thermalEquilibrium (equiSources.f90:3870-4042) and the temperature advanced over dt
+    def set_cooling_coefficients(self, c, compa: float, redshift: float):
+        """c[13][nratec] and compa of cooling_coefficient_tables, on the temperature grid of set_rate_coefficients (call that
+        first); redshift: currentRedshift of the Compton term."""
+        c = _f64(c)
+        if c.ndim != 2 or c.shape[0] != 13:
+            raise ValueError("c must have shape [13][nratec]")
+        self._ok(self._lib.ftte_set_cooling_coefficients(self._ctx, c.shape[1], _dp(c), float(compa), float(redshift)))
+
+    def temperature(self) -> np.ndarray:
+        """tgas per leaf as it stands on the device."""
+        out = np.empty(max(self.ncell, 1))
+        self._ok(self._lib.ftte_get_temperature(self._ctx, _dp(out)))
+        return out
+
+    def _thermal_rates(self, J, run_uvb, gamma, uniform_gamma, threshold, use_point_rates):
+        gamma = None if gamma is None else _f64(gamma).reshape(3, 3)
+        uniform_gamma = None if uniform_gamma is None else _f64(uniform_gamma).reshape(3)
+        return (int(bool(run_uvb)), J, None if gamma is None else _dp(gamma), None if uniform_gamma is None else _dp(uniform_gamma),
+                float(threshold), int(bool(use_point_rates))), (gamma, uniform_gamma)
+
+    def _host_J(self, J):
+        J = None if J is None else _f64(J)
+        if J is not None and J.shape != (3, self.ncell):
+            raise ValueError("J must have shape [3][ncell]")
+        return J
+
+    def thermal_equilibrium(self, run_uvb: bool = False, J=None, gamma=None, uniform_gamma=None, threshold: float = 0.0,
+                            use_point_rates: bool = False, j_device_ptr: Optional[int] = None):
+        """thermalEquilibrium for every leaf: returns (heating, cooling, hydroHeating) [erg/(s cm^3)]; hydroHeating stays on the
+        device for advance_temperature(hydro_heating=True).  J[3][ncell] (or j_device_ptr) with gamma[3][3] of uvb_beta_table, or
+        uniform_gamma[3] = the gammas of HI, HeII, HeI of the uniform background behind the self-shielding threshold."""
+        J = self._host_J(J)
+        out = [np.empty(max(self.ncell, 1)) for _ in range(3)]
+        fn = self._lib.ftte_thermal_equilibrium if j_device_ptr is None else self._lib.ftte_thermal_equilibrium_device
+        Jarg = (None if J is None else _dp(J)) if j_device_ptr is None else C.c_void_p(j_device_ptr)
+        args, keep = self._thermal_rates(Jarg, run_uvb, gamma, uniform_gamma, threshold, use_point_rates)
+        self._ok(fn(self._ctx, *args, *[_dp(a) for a in out]))
+        return tuple(out)
+
+    def advance_temperature(self, dt: float, run_uvb: bool = False, J=None, gamma=None, uniform_gamma=None, threshold: float = 0.0,
+                            use_point_rates: bool = False, substeps: int = 1, tmin: float = 1.0, tmax: float = 1.0e9,
+                            hydro_heating: bool = False) -> float:
+        """The temperature of every leaf advanced over dt seconds in `substeps` implicit steps at fixed species and at the rates of
+        the state on entry (arguments as thermal_equilibrium), clipped to [tmin, tmax]; hydro_heating adds the hydroHeating of the
+        last thermal_equilibrium.  Returns the largest |T1 - T0| / T0."""
+        J = self._host_J(J)
+        args, keep = self._thermal_rates(None if J is None else _dp(J), run_uvb, gamma, uniform_gamma, threshold, use_point_rates)
+        change = C.c_double()
+        self._ok(self._lib.ftte_advance_temperature(self._ctx, float(dt), int(substeps), float(tmin), float(tmax), int(bool(hydro_heating)), *args,
+                                                    C.byref(change)))
+        return change.value
+
+    def advance_temperature_device(self, dt: float, j_device_ptr: int, gamma, use_point_rates: bool = False, substeps: int = 1,
+                                   tmin: float = 1.0, tmax: float = 1.0e9, hydro_heating: bool = False) -> float:
+        """Same with J[3][ncell] in device memory (e.g. what transport_device wrote)."""
+        args, keep = self._thermal_rates(C.c_void_p(j_device_ptr), True, gamma, None, 0.0, use_point_rates)
+        change = C.c_double()
+        self._ok(self._lib.ftte_advance_temperature_device(self._ctx, float(dt), int(substeps), float(tmin), float(tmax), int(bool(hydro_heating)),
+                                                           *args, C.byref(change)))
+        return change.value
 
     def medium(self):
         out = [np.empty(max(self.ncell, 1)) for _ in range(3)]

@@ -695,6 +695,16 @@ int ftte_rate_coefficient_tables(int nratec, double temstart, double temend, int
     return FTTE_OK;
 }
 
+int ftte_cooling_coefficient_tables(int nratec, double temstart, double temend, int recombination_type, const double *mellema,
+                                    const double *gnedin, double *c, double *compa)
+{
+    if (nratec < 2 || !(temstart > 0.0) || !(temend > temstart) || (recombination_type != 1 && recombination_type != 2) || !c || !compa)
+        return FTTE_ERR_ARG;
+    if (recombination_type == 2 && (!mellema || !gnedin)) return FTTE_ERR_ARG; // case B interpolates the caller's two arrays
+    cooling_coefficient_tables(nratec, temstart, temend, recombination_type, mellema, gnedin, c, compa);
+    return FTTE_OK;
+}
+
 int ftte_uniform_table(int nfreq, double freqdel, double alpha_quasar, double alpha_stellar, double *ksi, double *gamma)
 {
     if (nfreq < 2 || !(freqdel > 0.0) || !ksi || !gamma) return FTTE_ERR_ARG;

@@ -2,8 +2,12 @@
 // ionisation chemistry (rate coefficients, temperature, the equilibrium update, the advance over a time step, the start-up equilibrium, the hydrogen census), the
 // species' way out, the opacities and the thin-limit radiation made from them, and the start-up expansion of HII regions (kernel:
 // ftte_expansion.hip).  The chemistry's own state is ftte_ctx::chem.
+#include <cstdlib>
+
 #include "ftte_chem_math.h"
 #include "ftte_context.h"
+#include "ftte_thermal.h"
+#include "ftte_thermal_math.h"
 
 using namespace ftte;
 
@@ -78,10 +82,10 @@ template <typename Own> int chem_update(ftte_ctx *c, const ChemUpdate &U, Own ow
 // The fields of the record that name the rates of the moment -- the transfer's J or the uniform background, with or without the
 // point sources' rates -- from the arguments solveRateEquations and the advance over dt share; J goes to the device if it is not there
 int rate_arguments(ftte_ctx *c, ChemRec &R, const char *who, int run_uvb, const double *J, bool J_on_device, const double *ksi,
-                   const double *uniform, double threshold, int use_point_rates)
+                   const double *uniform, double threshold, int use_point_rates, const char *table = "ksi")
 {
     const PointRates &P = c->point.rates;
-    if (run_uvb && (!J || !ksi)) return fail(c, FTTE_ERR_ARG, std::string(who) + ": the transfer-driven update needs J and ksi");
+    if (run_uvb && (!J || !ksi)) return fail(c, FTTE_ERR_ARG, std::string(who) + ": the transfer-driven update needs J and " + table);
     if (!run_uvb && !uniform) return fail(c, FTTE_ERR_ARG, std::string(who) + ": the uniform-background update needs the background rates");
     if (use_point_rates && !P.ready(c->ncell))
         return fail(c, FTTE_ERR_STATE, std::string(who) + ": no point-source rates (ftte_set_zero_rates / ftte_point_sources)");
@@ -122,6 +126,115 @@ int advance_rates(ftte_ctx *c, double dt, int substeps, int run_uvb, const doubl
         R.dt = dt; R.substeps = substeps;
         return rate_arguments(c, R, who, run_uvb, J, J_on_device, ksi, uniform, threshold, use_point_rates);
     }, max_change);
+}
+
+// ---- thermal balance (ftte_thermal_math.h; kernels: ftte_thermal.hip) -------------------------------------------------------
+
+// the rate arguments the thermal entry points share: those of solveRateEquations with the heating integrals gamma in place of ksi
+struct ThermalRates { int run_uvb; const double *J; bool J_on_device; const double *gamma, *uniform; double threshold; int use_point_rates; };
+
+// One thermal pass over all leaves, as chem_update is one update of the species: the preconditions, then own(R) (the entry point's
+// arguments), the record, the launch, and either the refusal -- the state as it was -- or done(R), which copies the results in.
+template <typename Own, typename Done>
+int thermal_pass(ftte_ctx *c, const char *who_, const char *stops, int (*launch)(const ThermalRec &, hipStream_t), const ThermalRates &A, Own own,
+                 Done done, double *max_change)
+{
+    int rc = check_ready(c, false);
+    if (rc) return rc;
+    ChemState &K = c->chem;
+    GasState &G = c->gas;
+    const std::string who = std::string(who_) + ": ";
+    if (!K.k) return fail(c, FTTE_ERR_STATE, who + "no rate coefficients (ftte_set_rate_coefficients)");
+    if (!K.cool) return fail(c, FTTE_ERR_STATE, who + "no cooling coefficients (ftte_set_cooling_coefficients)");
+    if (!K.temperature_set) return fail(c, FTTE_ERR_STATE, who + "no temperature (ftte_set_temperature)");
+    if (!G.ready_with_density(c->ncell)) return fail(c, FTTE_ERR_STATE, who + "no medium with density (ftte_set_medium with rho)");
+    FTTE_HIP(c, hipSetDevice(c->device));
+    ThermalRec R;
+    std::memset(&R, 0, sizeof R);
+    if ((rc = own(R))) return rc;
+    ChemRec rates;
+    std::memset(&rates, 0, sizeof rates);
+    if ((rc = rate_arguments(c, rates, who_, A.run_uvb, A.J, A.J_on_device, A.gamma, A.uniform, A.threshold, A.use_point_rates, "gamma"))) return rc;
+    R.J = rates.J; R.crate = rates.krate; R.run_uvb = rates.run_uvb; R.threshold = rates.threshold;
+    std::memcpy(R.gamma, rates.ksi, sizeof R.gamma);
+    std::memcpy(R.uniform, rates.uniform, sizeof R.uniform);
+    const size_t nc = (size_t)c->ncell;
+    if ((rc = ensure_level(c))) return rc;
+    FTTE_HIP(c, K.out.reserve(3 * nc));
+    FTTE_HIP(c, K.counters.reserve(4));
+    const unsigned long long init[4] = {~0ull, 0ull, 0ull, 0ull};
+    FTTE_HIP(c, hipMemcpyAsync(K.counters, init, sizeof init, hipMemcpyHostToDevice, c->stream));
+
+    R.level = K.level;
+    R.rho = G.field(GasState::kRho); R.tgas = K.tgas;
+    R.HI = G.field(GasState::kHI); R.HeI = G.field(GasState::kHeI); R.HeII = G.field(GasState::kHeII);
+    R.out0 = K.out; R.out1 = K.out + nc; R.out2 = K.out + 2 * nc;
+    R.cool = K.cool;
+    R.coef_stride = K.cool_node_major ? 1 : K.nratec;
+    R.node_stride = K.cool_node_major ? kCoolNode : 1;
+    R.ncell = c->ncell; R.n = c->n; R.nratec = K.nratec;
+    R.box = c->box; R.logtem0 = K.logtem0; R.logtem9 = K.logtem9; R.dlogtem = K.dlogtem;
+    R.comp1 = K.comp1; R.comp2 = K.comp2;
+    R.first_bad = K.counters; R.max_change = K.counters + 1; R.steps = K.counters + 2;
+    R.K = kMath;
+    if (launch(R, c->stream)) return fail(c, FTTE_ERR_NO_DEVICE, who + "kernel launch failed");
+    unsigned long long out[4];
+    FTTE_HIP(c, hipMemcpyAsync(out, K.counters, sizeof out, hipMemcpyDeviceToHost, c->stream));
+    FTTE_HIP(c, hipStreamSynchronize(c->stream));
+    if (out[0] != ~0ull) return fail(c, FTTE_ERR_RATES, who + stops + " in cell " + std::to_string(out[0]) + " (0-based cell-array index)");
+    if ((rc = done(R))) return rc;
+    FTTE_HIP(c, hipStreamSynchronize(c->stream));
+    if (max_change) std::memcpy(max_change, &out[1], sizeof *max_change);
+    K.steps = (long long)out[2];
+    return FTTE_OK;
+}
+
+// thermalEquilibrium (equiSources.f90:3870-4042): hydroHeating per leaf stays on the device
+int thermal_equilibrium(ftte_ctx *c, const ThermalRates &A, double *heating, double *cooling, double *hydro_heating, const char *who)
+{
+    return thermal_pass(
+        c, who, "temperature not positive and finite, or heating or cooling not finite,", launch_thermal_equilibrium, A,
+        [&](ThermalRec &) -> int { return FTTE_OK; },
+        [&](ThermalRec &R) -> int {
+            ChemState &K = c->chem;
+            const size_t bytes = sizeof(double) * (size_t)c->ncell;
+            FTTE_HIP(c, K.hydro.reserve((size_t)c->ncell));
+            FTTE_HIP(c, hipMemcpyAsync(K.hydro, R.out2, bytes, hipMemcpyDeviceToDevice, c->stream));
+            K.hydro_set = true;
+            double *dst[3] = {heating, cooling, hydro_heating};
+            const double *src[3] = {R.out0, R.out1, R.out2};
+            for (int f = 0; f < 3; ++f)
+                if (dst[f]) FTTE_HIP(c, hipMemcpyAsync(dst[f], src[f], bytes, hipMemcpyDeviceToHost, c->stream));
+            return FTTE_OK;
+        },
+        nullptr);
+}
+
+// The temperature advanced over dt in `substeps` implicit steps (thermal_advance_cell; the build's own, the reference has no time step)
+int advance_temperature(ftte_ctx *c, double dt, int substeps, double tmin, double tmax, int use_hydro, const ThermalRates &A, double *max_change,
+                        const char *who_)
+{
+    const std::string who = std::string(who_) + ": ";
+    return thermal_pass(
+        c, who_, "temperature or heat capacity not finite and positive, rates not finite, or no convergence,", launch_thermal_advance, A,
+        [&](ThermalRec &R) -> int {
+            if (!std::isfinite(dt) || !(dt > 0.)) return fail(c, FTTE_ERR_ARG, who + "dt_s must be finite and positive");
+            if (substeps < 1 || substeps > 4096) return fail(c, FTTE_ERR_ARG, who + "substeps must lie in 1 .. 4096");
+            if (!std::isfinite(tmin) || !std::isfinite(tmax) || !(tmin > 0.) || !(tmax > tmin))
+                return fail(c, FTTE_ERR_ARG, who + "0 < tmin < tmax must be finite");
+            if (use_hydro && !c->chem.hydro_set) return fail(c, FTTE_ERR_STATE, who + "no hydroHeating on this grid (ftte_thermal_equilibrium)");
+            R.dt = dt; R.substeps = substeps; R.tmin = tmin; R.tmax = tmax;
+            R.hydro = use_hydro ? c->chem.hydro.get() : nullptr;
+            return FTTE_OK;
+        },
+        [&](ThermalRec &R) -> int {
+            ChemState &K = c->chem;
+            const size_t bytes = sizeof(double) * (size_t)c->ncell;
+            FTTE_HIP(c, hipMemcpyAsync(K.tgas, R.out0, bytes, hipMemcpyDeviceToDevice, c->stream));
+            FTTE_HIP(c, hipMemcpyAsync(K.logtem, R.out1, bytes, hipMemcpyDeviceToDevice, c->stream));
+            return FTTE_OK;
+        },
+        max_change);
 }
 
 // computeMass over the leaves of HI (the medium's or a candidate's): the two totals [msun], deterministic
@@ -263,7 +376,7 @@ int ftte_set_rate_coefficients(ftte_ctx *c, int nratec, double logtem0, double l
     ChemState &K = c->chem;
     FTTE_HIP(c, hipSetDevice(c->device));
     FTTE_HIP(c, hipStreamSynchronize(c->stream));
-    if (K.nratec != nratec) K.k.reset();
+    if (K.nratec != nratec) { K.k.reset(); K.cool.reset(); } // (the cooling coefficients share the temperature grid)
     FTTE_HIP(c, K.k.reserve(6 * (size_t)nratec));
     const double *src[6] = {k1a, k2a, k3a, k4a, k5a, k6a};
     for (int r = 0; r < 6; ++r)
@@ -295,9 +408,89 @@ int ftte_set_temperature(ftte_ctx *c, const double *tgas)
     }
     FTTE_HIP(c, c->chem.logtem.reserve((size_t)c->ncell));
     FTTE_HIP(c, hipMemcpyAsync(c->chem.logtem, logtem.data(), sizeof(double) * (size_t)c->ncell, hipMemcpyHostToDevice, c->stream));
+    // the temperature itself, for the thermal balance
+    FTTE_HIP(c, c->chem.tgas.reserve((size_t)c->ncell));
+    FTTE_HIP(c, hipMemcpyAsync(c->chem.tgas, tgas, sizeof(double) * (size_t)c->ncell, hipMemcpyHostToDevice, c->stream));
     FTTE_HIP(c, hipStreamSynchronize(c->stream));
     c->chem.temperature_set = true;
     return FTTE_OK;
+}
+
+int ftte_get_temperature(ftte_ctx *c, double *tgas)
+{
+    int rc = check_ready(c, false);
+    if (rc) return rc;
+    if (!tgas) return fail(c, FTTE_ERR_ARG, "ftte_get_temperature: bad argument");
+    if (!c->chem.temperature_set) return fail(c, FTTE_ERR_STATE, "ftte_get_temperature: no temperature (ftte_set_temperature)");
+    FTTE_HIP(c, hipSetDevice(c->device));
+    FTTE_HIP(c, hipMemcpyAsync(tgas, c->chem.tgas, sizeof(double) * (size_t)c->ncell, hipMemcpyDeviceToHost, c->stream));
+    FTTE_HIP(c, hipStreamSynchronize(c->stream));
+    return FTTE_OK;
+}
+
+int ftte_set_cooling_coefficients(ftte_ctx *c, int nratec, const double *coef, double compa, double redshift)
+{
+    const std::string who = "ftte_set_cooling_coefficients: ";
+    int rc = check_single(c);
+    if (rc) return rc;
+    if (nratec < 2 || !coef || !std::isfinite(compa) || !std::isfinite(redshift)) return fail(c, FTTE_ERR_ARG, who + "bad argument");
+    ChemState &K = c->chem;
+    if (!K.k) return fail(c, FTTE_ERR_STATE, who + "no rate coefficients (ftte_set_rate_coefficients): the two share one temperature grid");
+    if (nratec != K.nratec) return fail(c, FTTE_ERR_ARG, who + "nratec must be that of ftte_set_rate_coefficients, " + std::to_string(K.nratec));
+    // The device copy: the caller's [13][nratec] as it stands.  FTTE_THERMAL_TABLE=nodes in the environment makes it node-major
+    // instead -- the thirteen coefficients of a temperature node side by side, padded to 128 bytes, so that the two nodes of a
+    // look-up are two adjacent cache lines and not 26 scattered words -- for measurements only: it measured 2.4 times slower
+    // (the section on the thermal balance).
+    const char *env = std::getenv("FTTE_THERMAL_TABLE");
+    K.cool_node_major = env && !std::strcmp(env, "nodes");
+    std::vector<double> table;
+    if (K.cool_node_major) {
+        table.assign((size_t)kCoolNode * nratec, 0.);
+        for (int r = 0; r < THERMAL_NCOEF; ++r)
+            for (int i = 0; i < nratec; ++i) table[(size_t)i * kCoolNode + r] = coef[(size_t)r * nratec + i];
+    } else table.assign(coef, coef + (size_t)THERMAL_NCOEF * nratec);
+    FTTE_HIP(c, hipSetDevice(c->device));
+    FTTE_HIP(c, hipStreamSynchronize(c->stream));
+    K.cool.reset();
+    FTTE_HIP(c, K.cool.reserve(table.size()));
+    hipError_t e = hipMemcpyAsync(K.cool, table.data(), sizeof(double) * table.size(), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream); // (table is a local)
+    if (e != hipSuccess) { K.cool.reset(); return fail(c, FTTE_ERR_NO_DEVICE, who + hipGetErrorString(e)); }
+    const double a = 1. + redshift;
+    K.comp1 = compa * ((a * a) * (a * a)); // compa * (1. + currentRedshift)**4, equiSources.f90:3970
+    K.comp2 = FTTE_T_CMB * a;              // :3971
+    return FTTE_OK;
+}
+
+int ftte_thermal_equilibrium(ftte_ctx *c, int run_uvb_transfer, const double *J, const double *gamma, const double *uniform_gamma,
+                             double self_shielding_threshold, int use_point_rates, double *heating, double *cooling, double *hydro_heating)
+{
+    const ThermalRates A{run_uvb_transfer, J, false, gamma, uniform_gamma, self_shielding_threshold, use_point_rates};
+    return thermal_equilibrium(c, A, heating, cooling, hydro_heating, "ftte_thermal_equilibrium");
+}
+
+int ftte_thermal_equilibrium_device(ftte_ctx *c, int run_uvb_transfer, const double *J_dev, const double *gamma, const double *uniform_gamma,
+                                    double self_shielding_threshold, int use_point_rates, double *heating, double *cooling,
+                                    double *hydro_heating)
+{
+    const ThermalRates A{run_uvb_transfer, J_dev, true, gamma, uniform_gamma, self_shielding_threshold, use_point_rates};
+    return thermal_equilibrium(c, A, heating, cooling, hydro_heating, "ftte_thermal_equilibrium_device");
+}
+
+int ftte_advance_temperature(ftte_ctx *c, double dt_s, int substeps, double tmin, double tmax, int use_hydro_heating, int run_uvb_transfer,
+                             const double *J, const double *gamma, const double *uniform_gamma, double self_shielding_threshold,
+                             int use_point_rates, double *max_change)
+{
+    const ThermalRates A{run_uvb_transfer, J, false, gamma, uniform_gamma, self_shielding_threshold, use_point_rates};
+    return advance_temperature(c, dt_s, substeps, tmin, tmax, use_hydro_heating, A, max_change, "ftte_advance_temperature");
+}
+
+int ftte_advance_temperature_device(ftte_ctx *c, double dt_s, int substeps, double tmin, double tmax, int use_hydro_heating,
+                                    int run_uvb_transfer, const double *J_dev, const double *gamma, const double *uniform_gamma,
+                                    double self_shielding_threshold, int use_point_rates, double *max_change)
+{
+    const ThermalRates A{run_uvb_transfer, J_dev, true, gamma, uniform_gamma, self_shielding_threshold, use_point_rates};
+    return advance_temperature(c, dt_s, substeps, tmin, tmax, use_hydro_heating, A, max_change, "ftte_advance_temperature_device");
 }
 
 int ftte_solve_rate_equations(ftte_ctx *c, int run_uvb_transfer, const double *J, const double *ksi, const double *uniform,

@@ -1,44 +1,17 @@
 // ftte_chem.hip -- the kernels behind ftte_chem.cpp: the ionisation equilibrium of every leaf (solveRateEquations,
 // initialIonizationEquilibrium), its advance over a time step, the optically thin radiation field, the hydrogen census and the opacities.  The chemistry of a
 // cell is ftte_chem_math.h, compiled here for the device and by the tests' host library for the host; an equilibrium kernel is the
-// grid-stride loop, the cell's loads, one call into that header and the cell's stores, and then the fold of its statistics.
+// grid-stride loop, the cell's loads, one call into that header and the cell's stores, and then the fold of its statistics
+// (ftte_chem_fold.h).
 #include <hip/hip_runtime.h>
 
+#include "ftte_chem_fold.h"
 #include "ftte_chem_math.h"
 #include "ftte_internal.h"
 #include "ftte_kernels.h"
 #include "ftte_tree_sum.h"
 
 namespace ftte {
-
-// The statistics of an update -- the largest change (kChange), the bisection steps, the first cell the reference would stop at --
-// are combined per wavefront, then per workgroup, before they go to their single words in memory with one atomic each: a
-// quarter of a million atomics on ONE address each cost more than all the arithmetic of the kernel.
-template <bool kChange>
-__device__ __forceinline__ void fold_statistics(const ChemRec &R, unsigned long long my_change, unsigned long long my_steps,
-                                                unsigned long long my_bad)
-{
-    __shared__ unsigned long long blk_change[4], blk_steps[4], blk_bad[4];
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long oc = kChange ? __shfl_xor(my_change, off) : 0ull, os = __shfl_xor(my_steps, off), ob = __shfl_xor(my_bad, off);
-        my_change = oc > my_change ? oc : my_change;
-        my_steps += os;
-        my_bad = ob < my_bad ? ob : my_bad;
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { if (kChange) blk_change[wave] = my_change; blk_steps[wave] = my_steps; blk_bad[wave] = my_bad; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int k = 1; k < 4; ++k) {
-            if (kChange) my_change = blk_change[k] > my_change ? blk_change[k] : my_change;
-            my_steps += blk_steps[k];
-            my_bad = blk_bad[k] < my_bad ? blk_bad[k] : my_bad;
-        }
-        if (my_bad != ~0ull) atomicMin(R.first_bad, my_bad);
-        if (kChange && my_change) atomicMax(R.max_change, my_change);
-        if (my_steps) atomicAdd(R.steps, my_steps);
-    }
-}
 
 // solveRateEquations, equiSources.f90:3459-3677, per leaf (chem_solve_cell)
 __global__ void __launch_bounds__(256) rate_equations_kernel(const ChemRec R)
@@ -60,7 +33,7 @@ __global__ void __launch_bounds__(256) rate_equations_kernel(const ChemRec R)
             R.HI_out[c] = HI; R.HeI_out[c] = HeI; R.HeII_out[c] = HeII;
         }
     }
-    fold_statistics<true>(R, my_change, my_steps, my_bad);
+    fold_statistics<true>(R.first_bad, R.max_change, R.steps, my_change, my_steps, my_bad);
 }
 
 // The start-up ionisation equilibrium, initialIonizationEquilibrium (equiSources.f90:3679-3868), R.passes times per leaf
@@ -78,7 +51,7 @@ __global__ void __launch_bounds__(256) initial_equilibrium_kernel(const ChemRec 
         if (!ok) my_bad = (unsigned long long)c < my_bad ? (unsigned long long)c : my_bad;
         else { R.HI_out[c] = HI; R.HeI_out[c] = HeI; R.HeII_out[c] = HeII; }
     }
-    fold_statistics<false>(R, 0ull, my_steps, my_bad);
+    fold_statistics<false>(R.first_bad, R.max_change, R.steps, 0ull, my_steps, my_bad);
 }
 
 // HI, HeI, HeII of every leaf advanced over R.dt in R.substeps implicit steps at the rates of the state on entry (chem_advance_cell)
@@ -101,7 +74,7 @@ __global__ void __launch_bounds__(256) advance_equations_kernel(const ChemRec R)
             R.HI_out[c] = HI; R.HeI_out[c] = HeI; R.HeII_out[c] = HeII;
         }
     }
-    fold_statistics<true>(R, my_change, my_steps, my_bad);
+    fold_statistics<true>(R.first_bad, R.max_change, R.steps, my_change, my_steps, my_bad);
 }
 
 // (enough workgroups to fill the GPU several times over, few enough that their atomics are nothing)

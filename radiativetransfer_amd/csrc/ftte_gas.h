@@ -72,7 +72,7 @@ private:
     long long version_ = 0, packed_from_ = kNever;
 };
 
-// ionisation equilibrium (solveRateEquations, initialIonizationEquilibrium, computeMass)
+// ionisation equilibrium (solveRateEquations, initialIonizationEquilibrium, computeMass) and thermal balance
 struct ChemState {
     DeviceBuffer<int8_t> level;   // per leaf, uploaded on first use after ftte_set_grid
     DeviceBuffer<double> k;       // [6][nratec]
@@ -92,12 +92,18 @@ struct ChemState {
     DeviceBuffer<ExpStarTest> exp_test;
     DeviceBuffer<int64_t> exp_cells;
     long long expansion_tests = 0;
+    // thermal balance (thermalEquilibrium and the temperature step, ftte_thermal_math.h): the temperature itself beside its
+    // logarithm, the cooling coefficients on the rate coefficients' temperature grid ([13][nratec], or node-major [nratec][16]:
+    // cool_node_major, for measurements), Compton's two numbers, and hydroHeating per leaf once a thermal-equilibrium pass has run on this grid
+    DeviceBuffer<double> tgas, cool, hydro;
+    bool cool_node_major = false, hydro_set = false;
+    double comp1 = 0, comp2 = 0;
 
-    void drop_grid() // after ftte_set_grid: what is sized by the old grid; the rate coefficients stay
+    void drop_grid() // after ftte_set_grid: what is sized by the old grid; the rate and cooling coefficients stay
     {
-        level.reset(); logtem.reset(); out.reset(); J.reset(); leaf_pos.reset();
+        level.reset(); logtem.reset(); out.reset(); J.reset(); leaf_pos.reset(); tgas.reset(); hydro.reset();
         leaf_node.clear();
-        temperature_set = false;
+        temperature_set = hydro_set = false;
     }
 };
 

@@ -205,6 +205,71 @@ void rate_coefficient_tables(int nratec, double temstart, double temend, int rec
     }
 }
 
+namespace {
+
+// one case-B entry: 0 outside the file's temperatures, else 10.** the linear interpolation in log10 T (calc_rates.f:471-483,
+// :492-508); n nodes t[] (log10 T) and v[] (log10 of the coefficient).  At log10ttt == t(1) the reference's search stops at j = 1 and
+// reads t(0); here that point takes the first interval, whose weight there is 0.
+double case_b_entry(double log10ttt, const double *t, const double *v, int n)
+{
+    if (log10ttt < t[0] || log10ttt > t[n - 1]) return 0.;
+    int j = 1; // 1-based, as the reference counts
+    while (log10ttt > t[j - 1]) ++j;
+    if (j < 2) j = 2;
+    return std::pow(10., (log10ttt - t[j - 2]) / (t[j - 1] - t[j - 2]) * (v[j - 1] - v[j - 2]) + v[j - 2]);
+}
+
+} // namespace
+
+void cooling_coefficient_tables(int nratec, double temstart, double temend, int recombination_type, const double *mellema,
+                                const double *gnedin, double *c, double *compa)
+{
+    const double dlogtem = (std::log(temend) - std::log(temstart)) / (double)(float)(nratec - 1);
+    const double lhuge = std::log(1.0e30); // dlog(dhuge), calc_rates.f:160
+    std::vector<double> tM, cM, tG, c2G, c3G;
+    if (recombination_type != 1) { // :397-411: Mellema's file holds log10 values, Gnedin's the values themselves
+        for (int i = 0; i < 81; ++i) { tM.push_back(mellema[2 * i]); cM.push_back(mellema[2 * i + 1]); }
+        for (int i = 0; i < 201; ++i) {
+            tG.push_back(std::log10(gnedin[3 * i])); c2G.push_back(std::log10(gnedin[3 * i + 1])); c3G.push_back(std::log10(gnedin[3 * i + 2]));
+        }
+    }
+    for (int i = 1; i <= nratec; ++i) { // :414-544
+        const double ttt = std::exp(std::log(temstart) + (double)(float)(i - 1) * dlogtem), log10ttt = std::log10(ttt);
+        double six[6], *at = c + (i - 1);
+        const size_t row = (size_t)nratec;
+        coll_rates(ttt, recombination_type, six);
+        const double soft = 1. + std::sqrt(ttt / 1.0e5);
+        // a) collisional excitations, :423-428
+        at[0 * row] = 7.5e-19 * std::exp(-std::fmin(lhuge, W(118348.) / ttt)) / soft;
+        at[1 * row] = 9.1e-27 * std::exp(-std::fmin(lhuge, W(13179.) / ttt)) * std::pow(ttt, W(-0.1687)) / soft;
+        at[2 * row] = 5.54e-17 * std::exp(-std::fmin(lhuge, W(473638.) / ttt)) * std::pow(ttt, W(-0.397)) / soft;
+        // b) collisional ionisations, :446-453
+        at[3 * row] = 2.18e-11 * six[0];
+        at[4 * row] = 3.94e-11 * six[2];
+        at[5 * row] = 5.01e-27 * std::pow(ttt, W(-0.1687)) / soft * std::exp(-std::fmin(lhuge, W(55338.) / ttt));
+        at[6 * row] = 8.72e-11 * six[4];
+        // c) recombinations, :467-515
+        if (recombination_type == 1) {
+            at[7 * row] = 8.70e-27 * std::sqrt(ttt) * std::pow(ttt / W(1000.0), W(-0.2)) / (W(1.0) + std::pow(ttt / 1.0e6, W(0.7)));
+            at[8 * row] = 1.55e-26 * std::pow(ttt, W(0.3647));
+            at[10 * row] = 3.48e-26 * std::sqrt(ttt) * std::pow(ttt / W(1000.0), W(-0.2)) / (W(1.0) + std::pow(ttt / 1.0e6, W(0.7)));
+        } else {
+            at[7 * row] = case_b_entry(log10ttt, tM.data(), cM.data(), 81);
+            at[8 * row] = case_b_entry(log10ttt, tG.data(), c2G.data(), 201);
+            at[10 * row] = case_b_entry(log10ttt, tG.data(), c3G.data(), 201);
+        }
+        at[9 * row] = 1.24e-13 * std::pow(ttt, W(-1.5)) * std::exp(-std::fmin(lhuge, W(470000.) / ttt)) *
+                      (W(1.) + W(0.3) * std::exp(-std::fmin(lhuge, W(94000.) / ttt)));
+        // d) bremsstrahlung, :527-528
+        const double off = W(5.5) - log10ttt;
+        at[11 * row] = 1.43e-27 * std::sqrt(ttt) * (W(1.1) + W(0.34) * std::exp(-(off * off) / W(3.0)));
+        // HI line excitation, :543-544
+        const double tmp = (double)(2.f * 13.598f) * 1.60217646e-12 / (1.3806503e-16 * ttt);
+        at[12 * row] = W(7.5e-19) * std::exp(W(-0.75) * tmp / W(2.)) / (W(1.) + std::sqrt(ttt / W(1.e5)));
+    }
+    *compa = 5.65e-36; // :619
+}
+
 void rmax_table(double *rmax30)
 {
     for (int ir = 1; ir <= 30; ++ir) {

@@ -35,6 +35,12 @@ void coll_rates(double T, int recombination_type, double *k);
 // k1a..k6a(nratec) as calc_rates.f:324-337 fills them, with the table bounds of equiSources.f90:174-176; k[6][nratec]
 void rate_coefficient_tables(int nratec, double temstart, double temend, int recombination_type, double *k, double *logtem0,
                              double *logtem9, double *dlogtem);
+// The thirteen cooling coefficients as calc_rates.f:414-544 fills them (flags as compiled, :155), c[13][nratec] in the order of
+// equiSources.f90:3975-3987 on the temperature grid of rate_coefficient_tables, and compa (:619).  Case B reads the caller's
+// copies of the reference's two data files: mellema[81][2] = columns 1, 3 of HII-ktbetas.tab, gnedin[201][3] = columns 1, 3, 5 of
+// cratesHe.res, as the files hold them; case A reads neither.
+void cooling_coefficient_tables(int nratec, double temstart, double temend, int recombination_type, const double *mellema,
+                                const double *gnedin, double *c, double *compa);
 // rmax(1:30), equiSources.f90:296-309
 void rmax_table(double *rmax30);
 

@@ -4,6 +4,9 @@ A step is what an iteration of the reference's loop is (equiSources.f90:1811-181
 the opacities from the medium, sweep the diffuse field into J -- followed by StellarTransfer.advance_rate_equations_device in
 place of solveRateEquations.  Everything stays on the device; per step only the two masses of hydrogen_mass() come back.
 
+With thermal=..., the temperature is advanced over the same dt after the species (StellarTransfer.advance_temperature_device),
+operator-split: the species of the thermal step are the new ones, its J and point rates the step's.
+
 The coupling is explicit: the rates and J of a step are those of the state at its start, held fixed over dt.  The chemistry
 itself is implicit and stable for any dt; the ionisation front is not resolved in time unless dt is short against the time the
 front takes to cross a cell."""
@@ -15,7 +18,7 @@ import numpy as np
 
 
 def evolve(st, dt: float, nsteps: int, sources: Optional[Tuple[Sequence[int], Sequence[float]]] = None, directions=None, beta=None, uvb=None,
-           ksi=None, substeps: int = 1, on_step: Optional[Callable] = None):
+           ksi=None, substeps: int = 1, on_step: Optional[Callable] = None, thermal: Optional[dict] = None):
     """Advance the medium of the StellarTransfer `st` over nsteps steps of dt seconds each.
 
     st          a StellarTransfer with grid, medium (with rho), rate coefficients, temperature and, for sources, rate tables set
@@ -25,6 +28,11 @@ def evolve(st, dt: float, nsteps: int, sources: Optional[Tuple[Sequence[int], Se
     uvb         [nnu] the background's intensity entering the box
     ksi         [3][3] = [group][ksi24, ksi25, ksi26]
     substeps    implicit steps per dt, at the rates of the step's start
+    thermal     None: the temperature stays what set_temperature gave, and the sequence of library calls is as without it.
+                dict(gamma=[3][3], tmin=, tmax=, hydro_heating=bool): each step ends, after the ionisation advance, with
+                advance_temperature_device over the same dt and substeps, with the same J and point rates (gamma[group][gammaHI,
+                gammaHeI, gammaHeII] of uvb_beta_table; needs set_cooling_coefficients, and thermal_equilibrium for hydro_heating);
+                the next step's chemistry reads the new temperature
     on_step     called as on_step(step, st, J) after each step, J the step's [3][ncell] device tensor (for inspection; the rates of
                 the step are still on the device)
 
@@ -55,6 +63,10 @@ def evolve(st, dt: float, nsteps: int, sources: Optional[Tuple[Sequence[int], Se
         st.transport_device(phi, theta, weight, uvb, J.data_ptr(), stream.cuda_stream)
         stream.synchronize()
         st.advance_rate_equations_device(dt, J.data_ptr(), ksi, use_point_rates=True, substeps=substeps)
+        if thermal is not None:
+            st.advance_temperature_device(dt, J.data_ptr(), thermal["gamma"], use_point_rates=True, substeps=substeps,
+                                          tmin=thermal.get("tmin", 1.0), tmax=thermal.get("tmax", 1.0e9),
+                                          hydro_heating=bool(thermal.get("hydro_heating", False)))
         if on_step is not None:
             on_step(step, st, J)
         times.append((step + 1) * float(dt))

@@ -1,0 +1,277 @@
+"""The thermal balance (radiativetransfer_amd/csrc/ftte_thermal_math.h) for the tests, twice:
+
+  * log(), equilibrium(), advance(): the header itself, compiled by g++ from tests/host/thermal_check.cpp into a small shared
+    library (no sanitizers) and looped over the cells -- the host evaluation the GPU tests compare with bit for bit;
+  * equilibrium_numpy(): an independent restatement of thermalEquilibrium in numpy, vectorised over the cells, written from the
+    reference's lines (equiSources.f90:3907-4038) and not from the header: its own constants, species, heating, interpolation and sum.
+
+Parity with the compiled reference is not established for this feature: calc_rates cannot run without its two data files."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+import os
+import shutil
+import subprocess
+import tempfile
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+CSRC = os.path.join(ROOT, "radiativetransfer_amd", "csrc")
+SOURCE = os.path.join(HERE, "host", "thermal_check.cpp")
+LIB = os.path.join(HERE, "host", "libthermal.so")
+
+# -ffp-contract=off: every product is rounded before the sum, as in the library's build
+FLAGS = ["-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-Wall", "-Werror"]
+SANITIZE = ["-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+
+EPS = np.finfo(float).eps
+TMIN, TMAX = 1.0, 1.0e9
+STEPS = [(1e9, 1), (1e13, 3), (1e40, 1)]
+REDSHIFT = 9.0
+
+_lib = None
+
+
+def build():
+    """the shared library, rebuilt when the source or a header is newer; in a temporary directory where the tree is read-only"""
+    global LIB
+    deps = [SOURCE] + [os.path.join(CSRC, h) for h in ("ftte_thermal_math.h", "ftte_chem_math.h", "ftte_math.h")]
+    if os.path.exists(LIB) and all(os.path.getmtime(d) <= os.path.getmtime(LIB) for d in deps):
+        return LIB
+    gxx = shutil.which("g++")
+    if not gxx:
+        raise RuntimeError("no g++: the host evaluation of the thermal balance cannot be built")
+    if not os.access(os.path.dirname(LIB), os.W_OK):
+        LIB = os.path.join(tempfile.mkdtemp(prefix="thermal_"), "libthermal.so")
+    tmp = LIB + f".{os.getpid()}.tmp"
+    subprocess.check_call([gxx, *FLAGS, "-shared", "-I" + CSRC, SOURCE, "-o", tmp])
+    os.replace(tmp, LIB)
+    return LIB
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        L = C.CDLL(build())
+        dp, ip, lp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_longlong)
+        L.th_log.argtypes = [C.c_longlong, dp, dp]
+        L.th_log.restype = None
+        tail = [dp, C.c_int, dp, dp, dp, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, dp, C.c_double, C.c_double]
+        L.th_equilibrium.argtypes = [C.c_longlong, C.c_int, ip, C.c_double, dp, dp, dp, dp, dp, dp] + tail + [dp, dp, dp]
+        L.th_advance.argtypes = [C.c_longlong, C.c_int, ip, C.c_double, dp, dp, dp, dp, dp] + tail + [dp, C.c_double, C.c_int, C.c_double, C.c_double, dp,
+                                                                                                    dp, lp, dp]
+        L.th_solve.argtypes = [C.c_longlong, C.c_int, ip, C.c_double, dp, dp, dp, dp, dp, dp, dp, C.c_int, C.c_double, C.c_double, C.c_double, dp, dp, dp,
+                               dp]
+        L.th_equilibrium.restype = L.th_advance.restype = L.th_solve.restype = C.c_longlong
+        _lib = L
+    return _lib
+
+
+def _f64(a):
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _dp(a):
+    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def log(x):
+    """ftte_log over an array"""
+    x = _f64(x)
+    out = np.empty_like(x)
+    lib().th_log(x.size, _dp(x), _dp(out))
+    return out
+
+
+def comp(compa, redshift=REDSHIFT):
+    """comp1, comp2 as ftte_set_cooling_coefficients forms them (equiSources.f90:3970-3971)"""
+    a = 1.0 + redshift
+    return compa * ((a * a) * (a * a)), float(np.float32(2.73)) * a
+
+
+def _tail(nc, crate, run_uvb, J, gamma, uniform, threshold, logtem0, logtem9, dlogtem, cool, comp1, comp2):
+    opt = [None if a is None else _f64(a) for a in (crate, J, gamma, uniform)]
+    if opt[0] is not None:
+        assert opt[0].shape == (3, nc)
+    if run_uvb:
+        assert opt[1].shape == (3, nc) and opt[2].size == 9
+    else:
+        assert opt[3].size == 3
+    cool = _f64(cool)
+    assert cool.ndim == 2 and cool.shape[0] == 13
+    args = [_dp(opt[0]), int(bool(run_uvb)), _dp(opt[1]), _dp(opt[2]), _dp(opt[3]), float(threshold), cool.shape[1], float(logtem0), float(logtem9),
+            float(dlogtem), _dp(cool), float(comp1), float(comp2)]
+    return args, opt + [cool]
+
+
+def equilibrium(n, level, box, rho, tgas, HI, HeI, HeII, crate, run_uvb, J, gamma, uniform, threshold, logtem0, logtem9, dlogtem, cool, comp1, comp2,
+                logtem=None):
+    """-> heating, cooling, hydroHeating, status (0, or 1 + the first failing cell); at logtem, or at ftte_log(tgas)"""
+    level = np.ascontiguousarray(level, dtype=np.int32)
+    f = [_f64(a) for a in (rho, tgas, HI, HeI, HeII)]
+    lt = None if logtem is None else _f64(logtem)
+    nc = f[0].size
+    tail, keep = _tail(nc, crate, run_uvb, J, gamma, uniform, threshold, logtem0, logtem9, dlogtem, cool, comp1, comp2)
+    out = [np.empty(nc) for _ in range(3)]
+    status = lib().th_equilibrium(nc, int(n), level.ctypes.data_as(C.POINTER(C.c_int32)), float(box), _dp(f[0]), _dp(f[1]), _dp(lt), *[_dp(a) for a in f[2:]],
+                                  *tail, *[_dp(a) for a in out])
+    return out[0], out[1], out[2], int(status)
+
+
+def advance(n, level, box, rho, tgas, HI, HeI, HeII, crate, run_uvb, J, gamma, uniform, threshold, logtem0, logtem9, dlogtem, cool, comp1, comp2, dt,
+            substeps=1, tmin=TMIN, tmax=TMAX, hydro=None):
+    """-> T1, ftte_log(T1), status (0, or 1 + the first failing cell), steps[ncell], change[ncell]"""
+    level = np.ascontiguousarray(level, dtype=np.int32)
+    f = [_f64(a) for a in (rho, tgas, HI, HeI, HeII)]
+    nc = f[0].size
+    tail, keep = _tail(nc, crate, run_uvb, J, gamma, uniform, threshold, logtem0, logtem9, dlogtem, cool, comp1, comp2)
+    hydro = None if hydro is None else _f64(hydro)
+    T1, lt, change, steps = np.empty(nc), np.empty(nc), np.empty(nc), np.zeros(nc, dtype=np.int64)
+    status = lib().th_advance(nc, int(n), level.ctypes.data_as(C.POINTER(C.c_int32)), float(box), *[_dp(a) for a in f], *tail, _dp(hydro), float(dt),
+                              int(substeps), float(tmin), float(tmax), _dp(T1), _dp(lt), steps.ctypes.data_as(C.POINTER(C.c_longlong)), _dp(change))
+    return T1, lt, int(status), steps, change
+
+
+def solve_at(n, level, box, rho, logtem, HI, HeI, HeII, J, ksi, logtem0, logtem9, dlogtem, k):
+    """the equilibrium update (chem_solve_cell) at a given logtem, with J and no point rates -> HI, HeI, HeII, status"""
+    level = np.ascontiguousarray(level, dtype=np.int32)
+    f = [_f64(a) for a in (rho, logtem, HI, HeI, HeII, J, ksi, k)]
+    nc = f[0].size
+    out = [np.empty(nc) for _ in range(3)]
+    status = lib().th_solve(nc, int(n), level.ctypes.data_as(C.POINTER(C.c_int32)), float(box), *[_dp(a) for a in f[:7]], f[7].shape[1], float(logtem0),
+                            float(logtem9), float(dlogtem), _dp(f[7]), *[_dp(a) for a in out])
+    return out[0], out[1], out[2], int(status)
+
+
+# ---- the inputs the CPU and the GPU tests share ----------------------------------------------------------------------------
+
+_tables = None
+
+
+def tables():
+    """the case-A cooling coefficients on the goldens' temperature grid, compa, and the heating integrals of the reference's slopes:
+    dict of cool[13][5000], compa, comp1, comp2 (z = 9), gamma[3][3], uniform_gamma[3] (HI, HeII, HeI).  Host code of libftte.so."""
+    global _tables
+    if _tables is None:
+        import radiativetransfer_amd as rt
+        cool, compa = rt.cooling_coefficient_tables(recombination_type=1)
+        _, _, gamma = rt.uvb_beta_table([1.8, 1.5, 1.2])
+        _, ug = rt.uniform_table(1.8, 1.5)                   # [quasar, stellar][gammaHI, gammaHeI, gammaHeII]
+        mix = 1.0e-22 * ug[0] + 3.0e-22 * ug[1]              # uniformQuasar, uniformStellar of the size of the goldens' uniform[]
+        c1, c2 = comp(compa)
+        _tables = dict(cool=cool, compa=compa, comp1=c1, comp2=c2, gamma=gamma, uniform_gamma=np.array([mix[0], mix[2], mix[1]]))
+    return _tables
+
+
+def wide_medium(grid, n=32, seed=17, uniform=False):
+    """a random medium, as a case of golden_case: densities over five decades, temperatures over the table's whole span and beyond both
+    ends, mean intensities over three decades (or, uniform: the uniform background behind a threshold that shields the denser half),
+    point-source heating (crate rows 3..5 of the rates) in three cells of ten, HeI + HeII > nHe in some cells"""
+    box = 2.5e23
+    nc = n ** 3
+    vol = (box / n) ** 3
+    rng = np.random.default_rng(seed)
+    rho = 10 ** rng.uniform(-27.5, -22.5, nc)
+    nh, nhe = PSI * rho / MH, (1 - PSI) * rho / MHE
+    tgas = 10 ** rng.uniform(-0.5, 8.5, nc)
+    J = 10 ** rng.uniform(-24.0, -21.0, (3, nc))
+    HI, HeI, HeII = nh * 10 ** rng.uniform(-8, 0.0, nc), nhe * rng.uniform(0, 1.1, nc), nhe * rng.uniform(0, 1.1, nc)
+    rates = np.zeros((6, nc))
+    lit = rng.random(nc) < 0.3
+    for r in range(3):
+        rates[3 + r] = np.where(lit, 10 ** rng.uniform(-27, -22, nc) * vol * nh, 0.0)
+    head = (n, np.zeros(nc, np.int32), box, rho, tgas, HI, HeI, HeII)
+    if uniform:
+        mfp = 1.0 / (HI * SIGMA[0] + HeI * SIGMA[1] + HeII * SIGMA[2])
+        return dict(head=head, rates=rates, run_uvb=False, J=None, threshold=float(np.median(mfp)), grid=grid)
+    return dict(head=head, rates=rates, run_uvb=True, J=J, threshold=0.0, grid=grid)
+
+
+def golden_case(g, name, grid):
+    """A golden medium as the thermal tests run it -> dict of head (n, level, box, rho, tgas, HI, HeI, HeII), rates [6][ncell] or None,
+    run_uvb, J, threshold, grid (logtem0, logtem9, dlogtem of chem_uvb_refined).  initial_refined and chem_uniform_background take
+    the uniform branch; chem_uvb_refined takes its J and synthetic point-source heating (crate, rows 3..5) in three cells of ten."""
+    n, level, box = int(g["n"]), g["level"], float(g["box"])
+    head = (n, level, box, g["rho"], g["tgas"], g["HI"], g["HeI"], g["HeII"])
+    if name != "chem_uvb_refined":
+        return dict(head=head, rates=None, run_uvb=False, J=None, threshold=float(g["threshold"]), grid=grid)
+    nc = level.size
+    rng = np.random.default_rng(5)
+    vol = (box / (2.0 ** level * n)) ** 3
+    lit = rng.random(nc) < 0.3
+    rates = np.zeros((6, nc))
+    for r in range(3):
+        rates[3 + r] = np.where(lit, 10 ** rng.uniform(-27, -22, nc) * vol * PSI * g["rho"] / MH, 0.0)
+    return dict(head=head, rates=rates, run_uvb=True, J=g["J"], threshold=0.0, grid=grid)
+
+
+def rate_args(case, T):
+    """the arguments between the species and the grid of equilibrium() / advance() for a case of golden_case or wide_medium"""
+    return (None if case["rates"] is None else case["rates"][3:], case["run_uvb"], case["J"], T["gamma"], T["uniform_gamma"], case["threshold"],
+            *case["grid"], T["cool"], T["comp1"], T["comp2"])
+
+
+# ---- the restatement ------------------------------------------------------------------------------------------------------
+
+f32 = np.float32
+PI = float(f32(3.141592654))
+MP, MN = float(f32(1.6726231e-24)), float(f32(1.67492728e-24))
+PSI = float(f32(0.76))
+MH, MHE = MP, 2.0 * (MP + MN)
+SIGMA = (float(f32(6.3e-18)), float(f32(7.42e-18)), float(f32(1.58e-18)))
+
+
+def equilibrium_numpy(n, level, box, rho, tgas, logtem, HI, HeI, HeII, crate, run_uvb, J, gamma, uniform, threshold, logtem0, logtem9, dlogtem, cool,
+                      comp1, comp2):
+    """thermalEquilibrium over the cells -> heating, cooling, hydroHeating, and the sum of the absolute values of the terms and the
+    heating (what the comparison's bound is made of).  The sum runs in the opposite order to the reference's."""
+    rho, tgas, logtem, HI, HeI, HeII, cool = (np.asarray(x, dtype=np.float64) for x in (rho, tgas, logtem, HI, HeI, HeII, cool))
+    nc = rho.size
+    with np.errstate(all="ignore"):
+        nh, nhe = PSI * rho / MH, (1.0 - PSI) * rho / MHE
+        hi, hii, hei, heii = np.minimum(HI, nh), nh - HI, HeI.copy(), HeII.copy()          # :3907-3910
+        heiii = nhe - HeI - HeII                                                           # :3911
+        over = heiii < 0.0                                                                 # :3913-3922
+        heii[over & (nhe - HeI < 0.0)] = 0.0
+        heiii[over] = 0.0
+        de = hii + heii + 2.0 * heiii                                                      # :3925
+        g = [np.zeros(nc) for _ in range(3)]                                               # crate24 (HI), crate25 (HeII), crate26 (HeI)
+        if crate is not None:
+            size = box / (f32(2) ** np.asarray(level).astype(f32) * f32(n)).astype(np.float64)
+            vol = size * size * size
+            for r, absorber in enumerate((hi, heii, hei)):
+                g[r] = np.maximum(np.where(absorber > 0.0, crate[r] / (vol * absorber), 0.0), 0.0)
+        if run_uvb:
+            gm = np.asarray(gamma, dtype=np.float64).reshape(3, 3)
+            t1, t2, t3 = 4.0 * PI * J[0], 4.0 * PI * J[1], 4.0 * PI * J[2]
+            g[0] = g[0] + t1 * gm[0, 0] + t2 * gm[1, 0] + t3 * gm[2, 0]
+            g[2] = g[2] + t2 * gm[1, 1] + t3 * gm[2, 1]
+            g[1] = g[1] + t3 * gm[2, 2]
+        else:
+            lit = 1.0 / (hi * SIGMA[0] + hei * SIGMA[1] + heii * SIGMA[2]) >= threshold     # :3929-3938
+            for r in range(3):
+                g[r] = np.where(lit, g[r] + 4.0 * PI * uniform[r], g[r])
+        heat = g[0] * hi + g[1] * heii + g[2] * hei                                        # :3940
+        lt = np.minimum(np.maximum(logtem, logtem0), logtem9)                              # :3947-3955
+        nr = cool.shape[1]
+        ix = np.clip(((lt - logtem0) / dlogtem).astype(np.int64) + 1, 1, nr - 1)
+        t1, t2 = logtem0 + (ix - 1).astype(np.float64) * dlogtem, logtem0 + ix.astype(np.float64) * dlogtem
+        ceHI, ceHeI, ceHeII, ciHI, ciHeI, ciHeIS, ciHeII, reHII, reHeII1, reHeII2, reHeIII, brem, lineHI = (
+            cool[r][ix - 1] + (lt - t1) * (cool[r][ix] - cool[r][ix - 1]) / (t2 - t1) for r in range(13))      # :3975-3987
+        terms = [ceHI * hi * de, ceHeI * hei * de ** 2, ceHeII * heii * de, ciHI * hi * de, ciHeI * hei * de, ciHeII * heii * de,
+                 ciHeIS * heii * de ** 2, reHII * hii * de, reHeII1 * heii * de, reHeII2 * heii * de, reHeIII * heiii * de,
+                 comp1 * (tgas - comp2) * de, brem * (hii + heii + 4.0 * heiii) * de]      # :3995-4023; :4019 and :4027 are zero
+        cooling = np.zeros(nc)
+        for t in reversed(terms):
+            cooling = cooling + t
+        scale = np.abs(heat) + sum(np.abs(t) for t in terms)
+        hydro = np.maximum(cooling - heat, 0.0)                                            # :4029-4038
+    return heat, cooling, hydro, scale
+
+
+def libm_log(x):
+    """(math.log is the C library's; numpy's own may differ in the last bit)"""
+    return np.array([math.log(v) for v in np.asarray(x, dtype=np.float64).ravel()])
