@@ -700,6 +700,51 @@ module ftte_binding
        real(c_double), intent(out) :: max_change
      end function ftte_advance_temperature_device
 
+     ! species and temperature of every leaf advanced together over dt_s seconds, each leaf in at most max_subcycles subcycles of
+     ! h = min(remaining, max(eta tau, remaining/(max_subcycles - s))), tau its own time scale; ksi, uniform as
+     ! ftte_advance_rate_equations takes them, gamma, uniform_gamma as ftte_advance_temperature does.  max_change: the largest change
+     ! of a species fraction and of T; subcycles: their sum, the largest count of a leaf, the leaves the cap bounded
+     integer(c_int) function ftte_advance_thermochemistry(ctx, dt_s, eta, max_subcycles, tmin, tmax, use_hydro_heating, &
+          run_uvb_transfer, J, ksi, gamma, uniform, uniform_gamma, self_shielding_threshold, use_point_rates, max_change, subcycles) &
+          bind(C, name='ftte_advance_thermochemistry')
+       import :: c_ptr, c_int, c_double, c_int64_t
+       type(c_ptr), value :: ctx
+       real(c_double), value :: dt_s, eta, tmin, tmax
+       integer(c_int), value :: max_subcycles, use_hydro_heating, run_uvb_transfer, use_point_rates
+       real(c_double), intent(in) :: J(*)          ! (ncell, 3): Jmean1..3
+       real(c_double), intent(in) :: ksi(3,3)      ! (ksi24, ksi25, ksi26) x (group1, group2, group3)
+       real(c_double), intent(in) :: gamma(3,3)    ! (gammaHI, gammaHeI, gammaHeII) x (group1, group2, group3)
+       real(c_double), intent(in) :: uniform(3)
+       real(c_double), intent(in) :: uniform_gamma(3)
+       real(c_double), value :: self_shielding_threshold
+       real(c_double), intent(out) :: max_change(2)
+       integer(c_int64_t), intent(out) :: subcycles(3)
+     end function ftte_advance_thermochemistry
+
+     integer(c_int) function ftte_advance_thermochemistry_device(ctx, dt_s, eta, max_subcycles, tmin, tmax, use_hydro_heating, &
+          run_uvb_transfer, J_dev, ksi, gamma, uniform, uniform_gamma, self_shielding_threshold, use_point_rates, max_change, &
+          subcycles) bind(C, name='ftte_advance_thermochemistry_device')
+       import :: c_ptr, c_int, c_double, c_int64_t
+       type(c_ptr), value :: ctx
+       real(c_double), value :: dt_s, eta, tmin, tmax
+       integer(c_int), value :: max_subcycles, use_hydro_heating, run_uvb_transfer, use_point_rates
+       type(c_ptr), value :: J_dev
+       real(c_double), intent(in) :: ksi(3,3)
+       real(c_double), intent(in) :: gamma(3,3)
+       real(c_double), intent(in) :: uniform(3)
+       real(c_double), intent(in) :: uniform_gamma(3)
+       real(c_double), value :: self_shielding_threshold
+       real(c_double), intent(out) :: max_change(2)
+       integer(c_int64_t), intent(out) :: subcycles(3)
+     end function ftte_advance_thermochemistry_device
+
+     ! the subcycles each leaf took in the last such call
+     integer(c_int) function ftte_get_subcycles(ctx, per_leaf) bind(C, name='ftte_get_subcycles')
+       import :: c_ptr, c_int, c_int32_t
+       type(c_ptr), value :: ctx
+       integer(c_int32_t), intent(out) :: per_leaf(*) ! (ncell)
+     end function ftte_get_subcycles
+
   end interface
 
 contains

@@ -423,6 +423,38 @@ int ftte_advance_temperature(ftte_ctx *ctx, double dt_s, int substeps, double tm
 int ftte_advance_temperature_device(ftte_ctx *ctx, double dt_s, int substeps, double tmin, double tmax, int use_hydro_heating,
                                     int run_uvb_transfer, const double *J_dev, const double *gamma, const double *uniform_gamma,
                                     double self_shielding_threshold, int use_point_rates, double *max_change);
+/* Species and temperature of every leaf advanced TOGETHER over dt_s seconds (csrc/ftte_thermochem_math.h; the build's own -- the
+ * reference has no time step, and its commented-out coupled solver is not restated).  Where the pair ftte_advance_rate_equations,
+ * ftte_advance_temperature runs the chemistry of the whole step at the temperature of its start and the thermal step at the
+ * species of its end, this call takes the two implicit steps in turn over subcycles that each leaf chooses for itself.  Per leaf,
+ * once: the state clipped to the elements' budgets, the ionisation rates per absorber as ftte_advance_rate_equations forms
+ * them, the heating rates per absorber as ftte_advance_temperature forms them from the incoming state, T clipped to [tmin,
+ * tmax]; all six rates stay fixed for the call (the radiation is explicit: J and the point rates are the caller's).  Subcycle s,
+ * while time remains: the coefficients at the stored logarithm (s = 0) or at ftte_log(T); the time scale tau = min over HI, HeI,
+ * HeII of max(species, 0.2 element)/|d species/dt| and T/|dT/dt|; h = min(remaining, max(eta tau, remaining/(max_subcycles - s)))
+ * -- eta = 0 is max_subcycles equal subcycles, and no leaf takes more than max_subcycles; the chemistry's step over h, then the
+ * temperature's over h with the new species.  First order in h.  With max_subcycles = 1 the species are those of
+ * ftte_advance_rate_equations(dt_s, 1) bit for bit, and T that of ftte_advance_temperature(dt_s, 1) after it where the heating per
+ * absorber does not depend on the state (J without point rates).
+ * Arguments: those of the two calls -- ksi and uniform as ftte_solve_rate_equations takes them, gamma and uniform_gamma as
+ * ftte_thermal_equilibrium does; preconditions those of both.  max_change (may be NULL): [0] the largest change of a species
+ * fraction, [1] the largest |T1 - T0|/T0.  subcycles (may be NULL): [0] the sum over the leaves, [1] the largest count of a leaf,
+ * [2] the leaves in which the even split of the remaining time (the cap) decided a subcycle.  ftte_rate_equation_steps counts the
+ * bisection steps of both kinds.  Afterwards the species are the medium's and T and its logarithm the device's.
+ * FTTE_ERR_ARG unless dt_s is finite and > 0, eta finite and >= 0, 1 <= max_subcycles <= 4096 and 0 < tmin < tmax finite;
+ * FTTE_ERR_STATE as ftte_advance_temperature; FTTE_ERR_RATES, the first failing leaf named and medium, temperature and logarithm
+ * untouched, where either step fails in any subcycle. */
+int ftte_advance_thermochemistry(ftte_ctx *ctx, double dt_s, double eta, int max_subcycles, double tmin, double tmax,
+                                 int use_hydro_heating, int run_uvb_transfer, const double *J, const double *ksi, const double *gamma,
+                                 const double *uniform, const double *uniform_gamma, double self_shielding_threshold, int use_point_rates,
+                                 double *max_change, int64_t *subcycles);
+int ftte_advance_thermochemistry_device(ftte_ctx *ctx, double dt_s, double eta, int max_subcycles, double tmin, double tmax,
+                                        int use_hydro_heating, int run_uvb_transfer, const double *J_dev, const double *ksi,
+                                        const double *gamma, const double *uniform, const double *uniform_gamma,
+                                        double self_shielding_threshold, int use_point_rates, double *max_change, int64_t *subcycles);
+/* per_leaf[ncell]: the subcycles each leaf took in the last ftte_advance_thermochemistry* that got through on this grid;
+ * FTTE_ERR_STATE before any */
+int ftte_get_subcycles(ftte_ctx *ctx, int32_t *per_leaf);
 /* HI, HeI, HeII of the device-resident medium, ncell each */
 int ftte_get_medium(ftte_ctx *ctx, double *HI, double *HeI, double *HeII);
 /* computeOpacities (equiSources.f90:4956-4983) on the device-resident medium: kappa[g] = HI beta[0][g] + HeI beta[1][g] +
@@ -433,7 +465,7 @@ int ftte_compute_opacities(ftte_ctx *ctx, int nnu, const double *beta);
  * HeII 1.58e-18) of the device-resident medium is at least the threshold, else 0.  J[nnu][ncell]. */
 int ftte_assign_uvb_radiation(ftte_ctx *ctx, int nnu, const double *uvb, double self_shielding_threshold, double *J);
 int ftte_assign_uvb_radiation_device(ftte_ctx *ctx, int nnu, const double *uvb, double self_shielding_threshold, double *J_dev);
-/* bisection steps of the last ftte_solve_rate_equations*, ftte_advance_rate_equations*, ftte_advance_temperature* or ftte_initial_ionization_equilibrium, summed over the cells (and
+/* bisection steps of the last ftte_solve_rate_equations*, ftte_advance_rate_equations*, ftte_advance_temperature*, ftte_advance_thermochemistry* or ftte_initial_ionization_equilibrium, summed over the cells (and
  * over the passes of the latter) */
 long long ftte_rate_equation_steps(const ftte_ctx *ctx);
 /* The start-up ionisation equilibrium, equiSources.f90:1008-1022: initialIonizationEquilibrium (:3679-3868) `passes` times

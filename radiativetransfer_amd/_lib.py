@@ -95,6 +95,11 @@ SIGNATURES = {
                                            C.c_int, _dp]),
     "ftte_advance_temperature_device": (C.c_int, [_vp, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _dp, _dp,
                                                   C.c_double, C.c_int, _dp]),
+    "ftte_advance_thermochemistry": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _dp, _dp, _dp,
+                                               _dp, _dp, C.c_double, C.c_int, _dp, C.POINTER(C.c_int64)]),
+    "ftte_advance_thermochemistry_device": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _dp,
+                                                      _dp, _dp, _dp, C.c_double, C.c_int, _dp, C.POINTER(C.c_int64)]),
+    "ftte_get_subcycles": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
     "ftte_cooling_coefficient_tables": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, _dp]),
     "ftte_rate_equation_steps": (C.c_longlong, [_vp]),
     "ftte_initial_ionization_equilibrium": (C.c_int, [_vp, _dp, C.c_double, C.c_int, _dp]),

@@ -731,6 +731,41 @@ class StellarTransfer(DiffuseTransfer):
                                                            *args, C.byref(change)))
         return change.value
 
+    # -- species and temperature together over dt, each leaf in subcycles of its own (csrc/ftte_thermochem_math.h)
+    def _thermochemistry(self, fn, dt, eta, max_subcycles, tmin, tmax, hydro_heating, Jarg, run_uvb, ksi, gamma, uniform, uniform_gamma, threshold,
+                         use_point_rates):
+        tables = [None if a is None else _f64(a).reshape(shape) for a, shape in ((ksi, (3, 3)), (gamma, (3, 3)), (uniform, 3), (uniform_gamma, 3))]
+        ptr = [None if a is None else _dp(a) for a in tables]
+        change = (C.c_double * 2)()
+        sub = (C.c_int64 * 3)()
+        self._ok(fn(self._ctx, float(dt), float(eta), int(max_subcycles), float(tmin), float(tmax), int(bool(hydro_heating)), int(bool(run_uvb)), Jarg,
+                    *ptr, float(threshold), int(bool(use_point_rates)), change, sub))
+        return dict(species_change=change[0], temperature_change=change[1], subcycles=int(sub[0]), largest=int(sub[1]), capped=int(sub[2]))
+
+    def advance_thermochemistry(self, dt: float, run_uvb: bool = False, J=None, ksi=None, gamma=None, uniform=None, uniform_gamma=None,
+                                threshold: float = 0.0, use_point_rates: bool = False, eta: float = 0.1, max_subcycles: int = 64,
+                                tmin: float = 1.0, tmax: float = 1.0e9, hydro_heating: bool = False) -> dict:
+        """HI, HeI, HeII and T of every leaf advanced together over dt seconds: per leaf, the chemistry's and the temperature's implicit
+        steps in turn over subcycles of h = min(remaining, max(eta tau, remaining / (max_subcycles - s))), tau the leaf's own time scale
+        (eta = 0: max_subcycles equal subcycles).  Rates as advance_rate_equations (ksi, uniform) and advance_temperature (gamma,
+        uniform_gamma) take them, held fixed over the call.  Returns dict(species_change, temperature_change -- the largest of each --,
+        subcycles -- summed over the leaves --, largest -- of a leaf --, capped -- leaves the cap bounded)."""
+        J = self._host_J(J)
+        return self._thermochemistry(self._lib.ftte_advance_thermochemistry, dt, eta, max_subcycles, tmin, tmax, hydro_heating,
+                                     None if J is None else _dp(J), run_uvb, ksi, gamma, uniform, uniform_gamma, threshold, use_point_rates)
+
+    def advance_thermochemistry_device(self, dt: float, j_device_ptr: int, ksi, gamma, use_point_rates: bool = False, eta: float = 0.1,
+                                       max_subcycles: int = 64, tmin: float = 1.0, tmax: float = 1.0e9, hydro_heating: bool = False) -> dict:
+        """Same with J[3][ncell] in device memory (e.g. what transport_device wrote)."""
+        return self._thermochemistry(self._lib.ftte_advance_thermochemistry_device, dt, eta, max_subcycles, tmin, tmax, hydro_heating,
+                                     C.c_void_p(j_device_ptr), True, ksi, gamma, None, None, 0.0, use_point_rates)
+
+    def subcycles(self) -> np.ndarray:
+        """int32 per leaf: the subcycles it took in the last advance_thermochemistry that got through."""
+        out = np.empty(max(self.ncell, 1), dtype=np.int32)
+        self._ok(self._lib.ftte_get_subcycles(self._ctx, out.ctypes.data_as(C.POINTER(C.c_int32))))
+        return out
+
     def medium(self):
         out = [np.empty(max(self.ncell, 1)) for _ in range(3)]
         self._ok(self._lib.ftte_get_medium(self._ctx, *[_dp(a) for a in out]))

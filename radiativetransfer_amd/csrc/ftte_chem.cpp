@@ -8,6 +8,7 @@
 #include "ftte_context.h"
 #include "ftte_thermal.h"
 #include "ftte_thermal_math.h"
+#include "ftte_thermochem.h"
 
 using namespace ftte;
 
@@ -135,9 +136,9 @@ struct ThermalRates { int run_uvb; const double *J; bool J_on_device; const doub
 
 // One thermal pass over all leaves, as chem_update is one update of the species: the preconditions, then own(R) (the entry point's
 // arguments), the record, the launch, and either the refusal -- the state as it was -- or done(R), which copies the results in.
-template <typename Own, typename Done>
-int thermal_pass(ftte_ctx *c, const char *who_, const char *stops, int (*launch)(const ThermalRec &, hipStream_t), const ThermalRates &A, Own own,
-                 Done done, double *max_change)
+// launch(R, stream) is a launch wrapper of ftte_thermal.h, or one that puts the record into a wider one (the coupled step).
+template <typename Launch, typename Own, typename Done>
+int thermal_pass(ftte_ctx *c, const char *who_, const char *stops, Launch launch, const ThermalRates &A, Own own, Done done, double *max_change)
 {
     int rc = check_ready(c, false);
     if (rc) return rc;
@@ -232,6 +233,74 @@ int advance_temperature(ftte_ctx *c, double dt, int substeps, double tmin, doubl
             const size_t bytes = sizeof(double) * (size_t)c->ncell;
             FTTE_HIP(c, hipMemcpyAsync(K.tgas, R.out0, bytes, hipMemcpyDeviceToDevice, c->stream));
             FTTE_HIP(c, hipMemcpyAsync(K.logtem, R.out1, bytes, hipMemcpyDeviceToDevice, c->stream));
+            return FTTE_OK;
+        },
+        max_change);
+}
+
+// Species and temperature advanced together over dt, each leaf in subcycles of its own (thermochem_advance_cell; the build's own).
+// A thermal pass whose record rides in a wider one: thermal_pass and its rate_arguments check and place J, the point rates and
+// the heating's half of the tables; the chemistry's half (ksi, uniform) is copied beside them, and its outputs and counters lie
+// behind the thermal ones in the same two buffers.
+int advance_thermochemistry(ftte_ctx *c, double dt, double eta, int max_subcycles, double tmin, double tmax, int use_hydro, const ThermalRates &A,
+                            const double *ksi, const double *uniform, double *max_change, int64_t *subcycles, const char *who_)
+{
+    const std::string who = std::string(who_) + ": ";
+    ThermochemRec W;
+    std::memset(&W, 0, sizeof W);
+    return thermal_pass(
+        c, who_, "species, temperature or heat capacity not finite or out of range, rates not finite, or no convergence,",
+        [&](const ThermalRec &R, hipStream_t stream) -> int {
+            ChemState &K = c->chem;
+            const size_t nc = (size_t)c->ncell;
+            W.T = R;
+            W.logtem = K.logtem; W.k = K.k;
+            W.HI_out = K.out + 2 * nc; W.HeI_out = K.out + 3 * nc; W.HeII_out = K.out + 4 * nc;
+            W.subcycles = K.subcycles_out;
+            W.eta = eta; W.max_subcycles = max_subcycles;
+            W.max_tchange = K.counters + 4; W.sub_sum = K.counters + 5; W.sub_max = K.counters + 6; W.capped = K.counters + 7;
+            return launch_thermochem_advance(W, stream);
+        },
+        A,
+        [&](ThermalRec &R) -> int {
+            ChemState &K = c->chem;
+            const size_t nc = (size_t)c->ncell;
+            if (!std::isfinite(dt) || !(dt > 0.)) return fail(c, FTTE_ERR_ARG, who + "dt_s must be finite and positive");
+            if (!std::isfinite(eta) || !(eta >= 0.)) return fail(c, FTTE_ERR_ARG, who + "eta must be finite and not negative");
+            if (max_subcycles < 1 || max_subcycles > 4096) return fail(c, FTTE_ERR_ARG, who + "max_subcycles must lie in 1 .. 4096");
+            if (!std::isfinite(tmin) || !std::isfinite(tmax) || !(tmin > 0.) || !(tmax > tmin))
+                return fail(c, FTTE_ERR_ARG, who + "0 < tmin < tmax must be finite");
+            if (A.run_uvb ? !ksi : !uniform) return fail(c, FTTE_ERR_ARG, who + (A.run_uvb ? "the transfer-driven update needs ksi" : "the uniform-background update needs the background rates"));
+            if (use_hydro && !K.hydro_set) return fail(c, FTTE_ERR_STATE, who + "no hydroHeating on this grid (ftte_thermal_equilibrium)");
+            R.dt = dt; R.tmin = tmin; R.tmax = tmax; R.substeps = 1;
+            R.hydro = use_hydro ? K.hydro.get() : nullptr;
+            // room for five outputs and eight counters where a thermal pass asks for three and four
+            FTTE_HIP(c, K.out.reserve(5 * nc));
+            FTTE_HIP(c, K.counters.reserve(8));
+            FTTE_HIP(c, K.subcycles_out.reserve(nc));
+            static const unsigned long long zero[4] = {0ull, 0ull, 0ull, 0ull};
+            FTTE_HIP(c, hipMemcpyAsync(K.counters + 4, zero, sizeof zero, hipMemcpyHostToDevice, c->stream));
+            if (ksi) std::memcpy(W.ksi, ksi, sizeof W.ksi);
+            if (uniform) std::memcpy(W.uniform, uniform, sizeof W.uniform);
+            return FTTE_OK;
+        },
+        [&](ThermalRec &R) -> int {
+            ChemState &K = c->chem;
+            GasState &G = c->gas;
+            const size_t nc = (size_t)c->ncell, bytes = sizeof(double) * nc;
+            unsigned long long more[4];
+            FTTE_HIP(c, hipMemcpyAsync(more, K.counters + 4, sizeof more, hipMemcpyDeviceToHost, c->stream));
+            FTTE_HIP(c, K.subcycles.reserve(nc));
+            const double *species[3] = {W.HI_out, W.HeI_out, W.HeII_out};
+            for (int f = 0; f < 3; ++f) FTTE_HIP(c, hipMemcpyAsync(G.field(f), species[f], bytes, hipMemcpyDeviceToDevice, c->stream));
+            G.species_changed();
+            FTTE_HIP(c, hipMemcpyAsync(K.tgas, R.out0, bytes, hipMemcpyDeviceToDevice, c->stream));
+            FTTE_HIP(c, hipMemcpyAsync(K.logtem, R.out1, bytes, hipMemcpyDeviceToDevice, c->stream));
+            FTTE_HIP(c, hipMemcpyAsync(K.subcycles, K.subcycles_out, sizeof(int32_t) * nc, hipMemcpyDeviceToDevice, c->stream));
+            FTTE_HIP(c, hipStreamSynchronize(c->stream));
+            K.subcycles_set = true;
+            if (max_change) std::memcpy(&max_change[1], &more[0], sizeof(double));
+            if (subcycles) for (int i = 0; i < 3; ++i) subcycles[i] = (int64_t)more[1 + i];
             return FTTE_OK;
         },
         max_change);
@@ -491,6 +560,38 @@ int ftte_advance_temperature_device(ftte_ctx *c, double dt_s, int substeps, doub
 {
     const ThermalRates A{run_uvb_transfer, J_dev, true, gamma, uniform_gamma, self_shielding_threshold, use_point_rates};
     return advance_temperature(c, dt_s, substeps, tmin, tmax, use_hydro_heating, A, max_change, "ftte_advance_temperature_device");
+}
+
+int ftte_advance_thermochemistry(ftte_ctx *c, double dt_s, double eta, int max_subcycles, double tmin, double tmax, int use_hydro_heating,
+                                 int run_uvb_transfer, const double *J, const double *ksi, const double *gamma, const double *uniform,
+                                 const double *uniform_gamma, double self_shielding_threshold, int use_point_rates, double *max_change,
+                                 int64_t *subcycles)
+{
+    const ThermalRates A{run_uvb_transfer, J, false, gamma, uniform_gamma, self_shielding_threshold, use_point_rates};
+    return advance_thermochemistry(c, dt_s, eta, max_subcycles, tmin, tmax, use_hydro_heating, A, ksi, uniform, max_change, subcycles,
+                                   "ftte_advance_thermochemistry");
+}
+
+int ftte_advance_thermochemistry_device(ftte_ctx *c, double dt_s, double eta, int max_subcycles, double tmin, double tmax, int use_hydro_heating,
+                                        int run_uvb_transfer, const double *J_dev, const double *ksi, const double *gamma, const double *uniform,
+                                        const double *uniform_gamma, double self_shielding_threshold, int use_point_rates, double *max_change,
+                                        int64_t *subcycles)
+{
+    const ThermalRates A{run_uvb_transfer, J_dev, true, gamma, uniform_gamma, self_shielding_threshold, use_point_rates};
+    return advance_thermochemistry(c, dt_s, eta, max_subcycles, tmin, tmax, use_hydro_heating, A, ksi, uniform, max_change, subcycles,
+                                   "ftte_advance_thermochemistry_device");
+}
+
+int ftte_get_subcycles(ftte_ctx *c, int32_t *per_leaf)
+{
+    int rc = check_ready(c, false);
+    if (rc) return rc;
+    if (!per_leaf) return fail(c, FTTE_ERR_ARG, "ftte_get_subcycles: bad argument");
+    if (!c->chem.subcycles_set) return fail(c, FTTE_ERR_STATE, "ftte_get_subcycles: no coupled step on this grid yet (ftte_advance_thermochemistry)");
+    FTTE_HIP(c, hipSetDevice(c->device));
+    FTTE_HIP(c, hipMemcpyAsync(per_leaf, c->chem.subcycles, sizeof(int32_t) * (size_t)c->ncell, hipMemcpyDeviceToHost, c->stream));
+    FTTE_HIP(c, hipStreamSynchronize(c->stream));
+    return FTTE_OK;
 }
 
 int ftte_solve_rate_equations(ftte_ctx *c, int run_uvb_transfer, const double *J, const double *ksi, const double *uniform,

@@ -80,8 +80,8 @@ struct ChemState {
     double logtem0 = 0, logtem9 = 0, dlogtem = 0;
     DeviceBuffer<double> logtem;  // [ncell] log of the gas temperature
     bool temperature_set = false;
-    DeviceBuffer<double> out, J;  // [3][ncell] each
-    DeviceBuffer<unsigned long long> counters; // first bad cell, bits of the largest change, bisection steps
+    DeviceBuffer<double> out, J;  // [3][ncell] each ([5][ncell] out for the coupled step)
+    DeviceBuffer<unsigned long long> counters; // first bad cell, bits of the largest change, bisection steps (+4..+7: the coupled step's)
     long long steps = 0;          // of the last update
     DeviceBuffer<double> mass;    // computeMass: per-workgroup partial sums, then the two totals (kMassParts)
     // expansion of HII regions (ftte_expansion.h): where each leaf of a refined cell array lies, uploaded on first use after
@@ -98,12 +98,17 @@ struct ChemState {
     DeviceBuffer<double> tgas, cool, hydro;
     bool cool_node_major = false, hydro_set = false;
     double comp1 = 0, comp2 = 0;
+    // the coupled step (ftte_thermochem_math.h): the subcycles each leaf took in the last call that got through on this grid, and
+    // the buffer the kernel writes them into (copied in, like `out`, once no leaf has failed)
+    DeviceBuffer<int32_t> subcycles, subcycles_out;
+    bool subcycles_set = false;
 
     void drop_grid() // after ftte_set_grid: what is sized by the old grid; the rate and cooling coefficients stay
     {
         level.reset(); logtem.reset(); out.reset(); J.reset(); leaf_pos.reset(); tgas.reset(); hydro.reset();
+        subcycles.reset(); subcycles_out.reset();
         leaf_node.clear();
-        temperature_set = hydro_set = false;
+        temperature_set = hydro_set = subcycles_set = false;
     }
 };
 

@@ -217,6 +217,9 @@ FTTE_HD unsigned thermal_advance_close(const ftte_consts *K, const ChemTable *T,
     return steps;
 }
 
+/* the heat capacity per volume at constant volume, kB (nh + nhe + de) / (gamma - 1) [erg/(K cm^3)] */
+FTTE_HD double thermal_heat_capacity(double rho, double de) { return FTTE_KB * (chem_nh(rho) + chem_nhe(rho) + de) / (FTTE_GAMMA_GAS - 1.); }
+
 /* what a call fixes for a cell before its first substep (all of ThermalCell but T0); returns whether the cell can be stepped */
 FTTE_HD int thermal_advance_setup(ThermalCell *q, double rho, double tgas, double HI0, double HeI0, double HeII0, double vol, int point, double p24,
                                   double p25, double p26, const double *J, long J_stride, const double *gamma, const double *uniform_gamma,
@@ -227,7 +230,7 @@ FTTE_HD int thermal_advance_setup(ThermalCell *q, double rho, double tgas, doubl
     thermal_heating(&q->s, vol, point, p24, p25, p26, J, J_stride, gamma, uniform_gamma, threshold, &c24, &c25, &c26);
     q->crate = c24 * q->s.HI + c25 * q->s.HeII + c26 * q->s.HeI;
     q->comp1 = comp1; q->comp2 = comp2; q->extra = extra;
-    const double heat_capacity = FTTE_KB * (chem_nh(rho) + chem_nhe(rho) + q->s.de) / (FTTE_GAMMA_GAS - 1.);
+    const double heat_capacity = thermal_heat_capacity(rho, q->s.de);
     q->hc = (dt / (double)substeps) / heat_capacity;
     q->T0 = tgas;
     return thermal_finite(tgas) && heat_capacity > 0. && thermal_finite(heat_capacity) && thermal_finite(q->crate) && thermal_finite(extra);

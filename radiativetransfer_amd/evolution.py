@@ -5,7 +5,9 @@ the opacities from the medium, sweep the diffuse field into J -- followed by Ste
 place of solveRateEquations.  Everything stays on the device; per step only the two masses of hydrogen_mass() come back.
 
 With thermal=..., the temperature is advanced over the same dt after the species (StellarTransfer.advance_temperature_device),
-operator-split: the species of the thermal step are the new ones, its J and point rates the step's.
+operator-split: the species of the thermal step are the new ones, its J and point rates the step's.  With
+thermal=dict(..., coupled=dict(eta=..., max_subcycles=...)) the two are one call, StellarTransfer.advance_thermochemistry_device:
+each leaf is subcycled on the device as finely as its own time scales ask.
 
 The coupling is explicit: the rates and J of a step are those of the state at its start, held fixed over dt.  The chemistry
 itself is implicit and stable for any dt; the ionisation front is not resolved in time unless dt is short against the time the
@@ -32,7 +34,9 @@ def evolve(st, dt: float, nsteps: int, sources: Optional[Tuple[Sequence[int], Se
                 dict(gamma=[3][3], tmin=, tmax=, hydro_heating=bool): each step ends, after the ionisation advance, with
                 advance_temperature_device over the same dt and substeps, with the same J and point rates (gamma[group][gammaHI,
                 gammaHeI, gammaHeII] of uvb_beta_table; needs set_cooling_coefficients, and thermal_equilibrium for hydro_heating);
-                the next step's chemistry reads the new temperature
+                the next step's chemistry reads the new temperature.  With coupled=dict(eta=, max_subcycles=) in it, ONE call,
+                advance_thermochemistry_device, takes the place of the two: species and temperature of a leaf advance together over
+                subcycles of the leaf's own (`substeps` is then not used); without `coupled` the calls are exactly the two above
     on_step     called as on_step(step, st, J) after each step, J the step's [3][ncell] device tensor (for inspection; the rates of
                 the step are still on the device)
 
@@ -47,6 +51,7 @@ def evolve(st, dt: float, nsteps: int, sources: Optional[Tuple[Sequence[int], Se
     beta = np.ascontiguousarray(beta, dtype=np.float64)
     if beta.ndim != 2 or beta.shape != (3, 3):
         raise ValueError("beta must have shape [3][3]: the update takes J in three frequency groups")
+    coupled = None if thermal is None else thermal.get("coupled")
     J = torch.empty((3, st.ncell), dtype=torch.float64, device="cuda")  # (the current device, which is the context's by default)
     stream = torch.cuda.current_stream()
 
@@ -62,8 +67,13 @@ def evolve(st, dt: float, nsteps: int, sources: Optional[Tuple[Sequence[int], Se
         st.compute_opacities_from_medium(beta)
         st.transport_device(phi, theta, weight, uvb, J.data_ptr(), stream.cuda_stream)
         stream.synchronize()
-        st.advance_rate_equations_device(dt, J.data_ptr(), ksi, use_point_rates=True, substeps=substeps)
-        if thermal is not None:
+        if coupled is not None:
+            st.advance_thermochemistry_device(dt, J.data_ptr(), ksi, thermal["gamma"], use_point_rates=True, eta=coupled.get("eta", 0.1),
+                                              max_subcycles=coupled.get("max_subcycles", 64), tmin=thermal.get("tmin", 1.0),
+                                              tmax=thermal.get("tmax", 1.0e9), hydro_heating=bool(thermal.get("hydro_heating", False)))
+        else:
+            st.advance_rate_equations_device(dt, J.data_ptr(), ksi, use_point_rates=True, substeps=substeps)
+        if thermal is not None and coupled is None:
             st.advance_temperature_device(dt, J.data_ptr(), thermal["gamma"], use_point_rates=True, substeps=substeps,
                                           tmin=thermal.get("tmin", 1.0), tmax=thermal.get("tmax", 1.0e9),
                                           hydro_heating=bool(thermal.get("hydro_heating", False)))
