@@ -1,326 +1,17 @@
-// ftte_chem.cpp -- the entry points of include/ftte.h that read or write the species medium (ftte_ctx::gas) outside the tracer: the
-// ionisation chemistry (rate coefficients, temperature, the equilibrium update, the advance over a time step, the start-up equilibrium, the hydrogen census), the
-// species' way out, the opacities and the thin-limit radiation made from them, and the start-up expansion of HII regions (kernel:
+// ftte_chem.cpp -- the entry points of include/ftte.h that read or write the species medium (ftte_ctx::gas) outside the tracer and
+// outside the per-leaf updates (ftte_leaf_pass.cpp): the chemistry's tables and the temperature, the hydrogen census, the species' way
+// out, the opacities and the thin-limit radiation made from them, and the start-up expansion of HII regions (kernel:
 // ftte_expansion.hip).  The chemistry's own state is ftte_ctx::chem.
 #include <cstdlib>
 
 #include "ftte_chem_math.h"
 #include "ftte_context.h"
-#include "ftte_thermal.h"
+#include "ftte_leaf.h"
 #include "ftte_thermal_math.h"
-#include "ftte_thermochem.h"
 
 using namespace ftte;
 
-namespace ftte {
-
-// the leaves' levels on the device: uploaded on first use after ftte_set_grid
-int ensure_level(ftte_ctx *c)
-{
-    if (c->chem.level) return FTTE_OK;
-    FTTE_HIP(c, c->chem.level.reserve((size_t)c->ncell));
-    FTTE_HIP(c, hipMemcpyAsync(c->chem.level, c->leaf_level.data(), (size_t)c->ncell, hipMemcpyHostToDevice, c->stream));
-    return FTTE_OK;
-}
-
-} // namespace ftte
-
 namespace {
-
-// What an update of the species has of its own, beside its arguments
-struct ChemUpdate {
-    const char *who;   // the entry point, in front of every text
-    const char *stops; // where the reference prints the species of the cell and stops; the state is left as it was
-    int (*launch)(const ChemRec &, hipStream_t);
-};
-
-// One update of HI, HeI, HeII over all leaves: the preconditions, the outputs and counters, the record, the launch, and then
-// either the refusal or the new species in the gas.  own(R) checks the entry point's arguments and fills its fields of the record,
-// uploading what they name; it runs behind the preconditions and in front of everything else, so that a bad argument allocates nothing.
-template <typename Own> int chem_update(ftte_ctx *c, const ChemUpdate &U, Own own, double *max_change)
-{
-    int rc = check_ready(c, false);
-    if (rc) return rc;
-    ChemState &K = c->chem;
-    GasState &G = c->gas;
-    const std::string who = std::string(U.who) + ": ";
-    if (!K.k) return fail(c, FTTE_ERR_STATE, who + "no rate coefficients (ftte_set_rate_coefficients)");
-    if (!K.temperature_set) return fail(c, FTTE_ERR_STATE, who + "no temperature (ftte_set_temperature)");
-    if (!G.ready_with_density(c->ncell)) return fail(c, FTTE_ERR_STATE, who + "no medium with density (ftte_set_medium with rho)");
-    FTTE_HIP(c, hipSetDevice(c->device));
-    ChemRec R;
-    std::memset(&R, 0, sizeof R);
-    if ((rc = own(R))) return rc;
-    const size_t nc = (size_t)c->ncell;
-    if ((rc = ensure_level(c))) return rc;
-    FTTE_HIP(c, K.out.reserve(3 * nc));
-    FTTE_HIP(c, K.counters.reserve(4));
-    const unsigned long long init[4] = {~0ull, 0ull, 0ull, 0ull};
-    FTTE_HIP(c, hipMemcpyAsync(K.counters, init, sizeof init, hipMemcpyHostToDevice, c->stream));
-
-    R.level = K.level;
-    R.rho = G.field(GasState::kRho); R.logtem = K.logtem;
-    R.HI = G.field(GasState::kHI); R.HeI = G.field(GasState::kHeI); R.HeII = G.field(GasState::kHeII);
-    R.HI_out = K.out; R.HeI_out = K.out + nc; R.HeII_out = K.out + 2 * nc;
-    R.k = K.k;
-    R.ncell = c->ncell; R.n = c->n; R.nratec = K.nratec;
-    R.box = c->box; R.logtem0 = K.logtem0; R.logtem9 = K.logtem9; R.dlogtem = K.dlogtem;
-    R.first_bad = K.counters; R.max_change = K.counters + 1; R.steps = K.counters + 2;
-    if (U.launch(R, c->stream)) return fail(c, FTTE_ERR_NO_DEVICE, who + "kernel launch failed");
-    unsigned long long out[4];
-    FTTE_HIP(c, hipMemcpyAsync(out, K.counters, sizeof out, hipMemcpyDeviceToHost, c->stream));
-    FTTE_HIP(c, hipStreamSynchronize(c->stream));
-    if (out[0] != ~0ull) return fail(c, FTTE_ERR_RATES, who + U.stops + " in cell " + std::to_string(out[0]) + " (0-based cell-array index)");
-    for (int f = 0; f < 3; ++f)
-        FTTE_HIP(c, hipMemcpyAsync(G.field(f), K.out + f * nc, sizeof(double) * nc, hipMemcpyDeviceToDevice, c->stream));
-    G.species_changed();
-    FTTE_HIP(c, hipStreamSynchronize(c->stream));
-    if (max_change) std::memcpy(max_change, &out[1], sizeof *max_change);
-    K.steps = (long long)out[2];
-    return FTTE_OK;
-}
-
-// The fields of the record that name the rates of the moment -- the transfer's J or the uniform background, with or without the
-// point sources' rates -- from the arguments solveRateEquations and the advance over dt share; J goes to the device if it is not there
-int rate_arguments(ftte_ctx *c, ChemRec &R, const char *who, int run_uvb, const double *J, bool J_on_device, const double *ksi,
-                   const double *uniform, double threshold, int use_point_rates, const char *table = "ksi")
-{
-    const PointRates &P = c->point.rates;
-    if (run_uvb && (!J || !ksi)) return fail(c, FTTE_ERR_ARG, std::string(who) + ": the transfer-driven update needs J and " + table);
-    if (!run_uvb && !uniform) return fail(c, FTTE_ERR_ARG, std::string(who) + ": the uniform-background update needs the background rates");
-    if (use_point_rates && !P.ready(c->ncell))
-        return fail(c, FTTE_ERR_STATE, std::string(who) + ": no point-source rates (ftte_set_zero_rates / ftte_point_sources)");
-    if (run_uvb && !J_on_device) {
-        const size_t nc = (size_t)c->ncell;
-        FTTE_HIP(c, c->chem.J.reserve(3 * nc));
-        FTTE_HIP(c, hipMemcpyAsync(c->chem.J, J, sizeof(double) * 3 * nc, hipMemcpyHostToDevice, c->stream));
-        J = c->chem.J;
-    }
-    R.J = run_uvb ? J : nullptr;
-    R.krate = use_point_rates ? P.packed() : nullptr;
-    R.run_uvb = run_uvb ? 1 : 0;
-    if (ksi) std::memcpy(R.ksi, ksi, sizeof R.ksi);
-    if (uniform) std::memcpy(R.uniform, uniform, sizeof R.uniform);
-    R.threshold = threshold;
-    return FTTE_OK;
-}
-
-// solveRateEquations (equiSources.f90:3459-3677; it stops at :3637-3654)
-int solve_rates(ftte_ctx *c, int run_uvb, const double *J, bool J_on_device, const double *ksi, const double *uniform, double threshold,
-                int use_point_rates, double *max_change, const char *who)
-{
-    const ChemUpdate U{who, "species fraction outside [0, 1]", launch_rate_equations};
-    return chem_update(c, U, [&](ChemRec &R) -> int {
-        return rate_arguments(c, R, who, run_uvb, J, J_on_device, ksi, uniform, threshold, use_point_rates);
-    }, max_change);
-}
-
-// The species advanced over dt in `substeps` implicit steps at the same rates (chem_advance_cell; the build's own, the reference
-// has no time step)
-int advance_rates(ftte_ctx *c, double dt, int substeps, int run_uvb, const double *J, bool J_on_device, const double *ksi, const double *uniform,
-                  double threshold, int use_point_rates, double *max_change, const char *who)
-{
-    const ChemUpdate U{who, "species not finite or outside their element's budget, or no convergence,", launch_advance_equations};
-    return chem_update(c, U, [&](ChemRec &R) -> int {
-        if (!std::isfinite(dt) || !(dt > 0.)) return fail(c, FTTE_ERR_ARG, std::string(who) + ": dt_s must be finite and positive");
-        if (substeps < 1 || substeps > 4096) return fail(c, FTTE_ERR_ARG, std::string(who) + ": substeps must lie in 1 .. 4096");
-        R.dt = dt; R.substeps = substeps;
-        return rate_arguments(c, R, who, run_uvb, J, J_on_device, ksi, uniform, threshold, use_point_rates);
-    }, max_change);
-}
-
-// ---- thermal balance (ftte_thermal_math.h; kernels: ftte_thermal.hip) -------------------------------------------------------
-
-// the rate arguments the thermal entry points share: those of solveRateEquations with the heating integrals gamma in place of ksi
-struct ThermalRates { int run_uvb; const double *J; bool J_on_device; const double *gamma, *uniform; double threshold; int use_point_rates; };
-
-// One thermal pass over all leaves, as chem_update is one update of the species: the preconditions, then own(R) (the entry point's
-// arguments), the record, the launch, and either the refusal -- the state as it was -- or done(R), which copies the results in.
-// launch(R, stream) is a launch wrapper of ftte_thermal.h, or one that puts the record into a wider one (the coupled step).
-template <typename Launch, typename Own, typename Done>
-int thermal_pass(ftte_ctx *c, const char *who_, const char *stops, Launch launch, const ThermalRates &A, Own own, Done done, double *max_change)
-{
-    int rc = check_ready(c, false);
-    if (rc) return rc;
-    ChemState &K = c->chem;
-    GasState &G = c->gas;
-    const std::string who = std::string(who_) + ": ";
-    if (!K.k) return fail(c, FTTE_ERR_STATE, who + "no rate coefficients (ftte_set_rate_coefficients)");
-    if (!K.cool) return fail(c, FTTE_ERR_STATE, who + "no cooling coefficients (ftte_set_cooling_coefficients)");
-    if (!K.temperature_set) return fail(c, FTTE_ERR_STATE, who + "no temperature (ftte_set_temperature)");
-    if (!G.ready_with_density(c->ncell)) return fail(c, FTTE_ERR_STATE, who + "no medium with density (ftte_set_medium with rho)");
-    FTTE_HIP(c, hipSetDevice(c->device));
-    ThermalRec R;
-    std::memset(&R, 0, sizeof R);
-    if ((rc = own(R))) return rc;
-    ChemRec rates;
-    std::memset(&rates, 0, sizeof rates);
-    if ((rc = rate_arguments(c, rates, who_, A.run_uvb, A.J, A.J_on_device, A.gamma, A.uniform, A.threshold, A.use_point_rates, "gamma"))) return rc;
-    R.J = rates.J; R.crate = rates.krate; R.run_uvb = rates.run_uvb; R.threshold = rates.threshold;
-    std::memcpy(R.gamma, rates.ksi, sizeof R.gamma);
-    std::memcpy(R.uniform, rates.uniform, sizeof R.uniform);
-    const size_t nc = (size_t)c->ncell;
-    if ((rc = ensure_level(c))) return rc;
-    FTTE_HIP(c, K.out.reserve(3 * nc));
-    FTTE_HIP(c, K.counters.reserve(4));
-    const unsigned long long init[4] = {~0ull, 0ull, 0ull, 0ull};
-    FTTE_HIP(c, hipMemcpyAsync(K.counters, init, sizeof init, hipMemcpyHostToDevice, c->stream));
-
-    R.level = K.level;
-    R.rho = G.field(GasState::kRho); R.tgas = K.tgas;
-    R.HI = G.field(GasState::kHI); R.HeI = G.field(GasState::kHeI); R.HeII = G.field(GasState::kHeII);
-    R.out0 = K.out; R.out1 = K.out + nc; R.out2 = K.out + 2 * nc;
-    R.cool = K.cool;
-    R.coef_stride = K.cool_node_major ? 1 : K.nratec;
-    R.node_stride = K.cool_node_major ? kCoolNode : 1;
-    R.ncell = c->ncell; R.n = c->n; R.nratec = K.nratec;
-    R.box = c->box; R.logtem0 = K.logtem0; R.logtem9 = K.logtem9; R.dlogtem = K.dlogtem;
-    R.comp1 = K.comp1; R.comp2 = K.comp2;
-    R.first_bad = K.counters; R.max_change = K.counters + 1; R.steps = K.counters + 2;
-    R.K = kMath;
-    if (launch(R, c->stream)) return fail(c, FTTE_ERR_NO_DEVICE, who + "kernel launch failed");
-    unsigned long long out[4];
-    FTTE_HIP(c, hipMemcpyAsync(out, K.counters, sizeof out, hipMemcpyDeviceToHost, c->stream));
-    FTTE_HIP(c, hipStreamSynchronize(c->stream));
-    if (out[0] != ~0ull) return fail(c, FTTE_ERR_RATES, who + stops + " in cell " + std::to_string(out[0]) + " (0-based cell-array index)");
-    if ((rc = done(R))) return rc;
-    FTTE_HIP(c, hipStreamSynchronize(c->stream));
-    if (max_change) std::memcpy(max_change, &out[1], sizeof *max_change);
-    K.steps = (long long)out[2];
-    return FTTE_OK;
-}
-
-// thermalEquilibrium (equiSources.f90:3870-4042): hydroHeating per leaf stays on the device
-int thermal_equilibrium(ftte_ctx *c, const ThermalRates &A, double *heating, double *cooling, double *hydro_heating, const char *who)
-{
-    return thermal_pass(
-        c, who, "temperature not positive and finite, or heating or cooling not finite,", launch_thermal_equilibrium, A,
-        [&](ThermalRec &) -> int { return FTTE_OK; },
-        [&](ThermalRec &R) -> int {
-            ChemState &K = c->chem;
-            const size_t bytes = sizeof(double) * (size_t)c->ncell;
-            FTTE_HIP(c, K.hydro.reserve((size_t)c->ncell));
-            FTTE_HIP(c, hipMemcpyAsync(K.hydro, R.out2, bytes, hipMemcpyDeviceToDevice, c->stream));
-            K.hydro_set = true;
-            double *dst[3] = {heating, cooling, hydro_heating};
-            const double *src[3] = {R.out0, R.out1, R.out2};
-            for (int f = 0; f < 3; ++f)
-                if (dst[f]) FTTE_HIP(c, hipMemcpyAsync(dst[f], src[f], bytes, hipMemcpyDeviceToHost, c->stream));
-            return FTTE_OK;
-        },
-        nullptr);
-}
-
-// The temperature advanced over dt in `substeps` implicit steps (thermal_advance_cell; the build's own, the reference has no time step)
-int advance_temperature(ftte_ctx *c, double dt, int substeps, double tmin, double tmax, int use_hydro, const ThermalRates &A, double *max_change,
-                        const char *who_)
-{
-    const std::string who = std::string(who_) + ": ";
-    return thermal_pass(
-        c, who_, "temperature or heat capacity not finite and positive, rates not finite, or no convergence,", launch_thermal_advance, A,
-        [&](ThermalRec &R) -> int {
-            if (!std::isfinite(dt) || !(dt > 0.)) return fail(c, FTTE_ERR_ARG, who + "dt_s must be finite and positive");
-            if (substeps < 1 || substeps > 4096) return fail(c, FTTE_ERR_ARG, who + "substeps must lie in 1 .. 4096");
-            if (!std::isfinite(tmin) || !std::isfinite(tmax) || !(tmin > 0.) || !(tmax > tmin))
-                return fail(c, FTTE_ERR_ARG, who + "0 < tmin < tmax must be finite");
-            if (use_hydro && !c->chem.hydro_set) return fail(c, FTTE_ERR_STATE, who + "no hydroHeating on this grid (ftte_thermal_equilibrium)");
-            R.dt = dt; R.substeps = substeps; R.tmin = tmin; R.tmax = tmax;
-            R.hydro = use_hydro ? c->chem.hydro.get() : nullptr;
-            return FTTE_OK;
-        },
-        [&](ThermalRec &R) -> int {
-            ChemState &K = c->chem;
-            const size_t bytes = sizeof(double) * (size_t)c->ncell;
-            FTTE_HIP(c, hipMemcpyAsync(K.tgas, R.out0, bytes, hipMemcpyDeviceToDevice, c->stream));
-            FTTE_HIP(c, hipMemcpyAsync(K.logtem, R.out1, bytes, hipMemcpyDeviceToDevice, c->stream));
-            return FTTE_OK;
-        },
-        max_change);
-}
-
-// Species and temperature advanced together over dt, each leaf in subcycles of its own (thermochem_advance_cell; the build's own).
-// A thermal pass whose record rides in a wider one: thermal_pass and its rate_arguments check and place J, the point rates and
-// the heating's half of the tables; the chemistry's half (ksi, uniform) is copied beside them, and its outputs and counters lie
-// behind the thermal ones in the same two buffers.
-int advance_thermochemistry(ftte_ctx *c, double dt, double eta, int max_subcycles, double tmin, double tmax, int use_hydro, const ThermalRates &A,
-                            const double *ksi, const double *uniform, double *max_change, int64_t *subcycles, const char *who_)
-{
-    const std::string who = std::string(who_) + ": ";
-    ThermochemRec W;
-    std::memset(&W, 0, sizeof W);
-    return thermal_pass(
-        c, who_, "species, temperature or heat capacity not finite or out of range, rates not finite, or no convergence,",
-        [&](const ThermalRec &R, hipStream_t stream) -> int {
-            ChemState &K = c->chem;
-            const size_t nc = (size_t)c->ncell;
-            W.T = R;
-            W.logtem = K.logtem; W.k = K.k;
-            W.HI_out = K.out + 2 * nc; W.HeI_out = K.out + 3 * nc; W.HeII_out = K.out + 4 * nc;
-            W.subcycles = K.subcycles_out;
-            W.eta = eta; W.max_subcycles = max_subcycles;
-            W.max_tchange = K.counters + 4; W.sub_sum = K.counters + 5; W.sub_max = K.counters + 6; W.capped = K.counters + 7;
-            return launch_thermochem_advance(W, stream);
-        },
-        A,
-        [&](ThermalRec &R) -> int {
-            ChemState &K = c->chem;
-            const size_t nc = (size_t)c->ncell;
-            if (!std::isfinite(dt) || !(dt > 0.)) return fail(c, FTTE_ERR_ARG, who + "dt_s must be finite and positive");
-            if (!std::isfinite(eta) || !(eta >= 0.)) return fail(c, FTTE_ERR_ARG, who + "eta must be finite and not negative");
-            if (max_subcycles < 1 || max_subcycles > 4096) return fail(c, FTTE_ERR_ARG, who + "max_subcycles must lie in 1 .. 4096");
-            if (!std::isfinite(tmin) || !std::isfinite(tmax) || !(tmin > 0.) || !(tmax > tmin))
-                return fail(c, FTTE_ERR_ARG, who + "0 < tmin < tmax must be finite");
-            if (A.run_uvb ? !ksi : !uniform) return fail(c, FTTE_ERR_ARG, who + (A.run_uvb ? "the transfer-driven update needs ksi" : "the uniform-background update needs the background rates"));
-            if (use_hydro && !K.hydro_set) return fail(c, FTTE_ERR_STATE, who + "no hydroHeating on this grid (ftte_thermal_equilibrium)");
-            R.dt = dt; R.tmin = tmin; R.tmax = tmax; R.substeps = 1;
-            R.hydro = use_hydro ? K.hydro.get() : nullptr;
-            // room for five outputs and eight counters where a thermal pass asks for three and four
-            FTTE_HIP(c, K.out.reserve(5 * nc));
-            FTTE_HIP(c, K.counters.reserve(8));
-            FTTE_HIP(c, K.subcycles_out.reserve(nc));
-            static const unsigned long long zero[4] = {0ull, 0ull, 0ull, 0ull};
-            FTTE_HIP(c, hipMemcpyAsync(K.counters + 4, zero, sizeof zero, hipMemcpyHostToDevice, c->stream));
-            if (ksi) std::memcpy(W.ksi, ksi, sizeof W.ksi);
-            if (uniform) std::memcpy(W.uniform, uniform, sizeof W.uniform);
-            return FTTE_OK;
-        },
-        [&](ThermalRec &R) -> int {
-            ChemState &K = c->chem;
-            GasState &G = c->gas;
-            const size_t nc = (size_t)c->ncell, bytes = sizeof(double) * nc;
-            unsigned long long more[4];
-            FTTE_HIP(c, hipMemcpyAsync(more, K.counters + 4, sizeof more, hipMemcpyDeviceToHost, c->stream));
-            FTTE_HIP(c, K.subcycles.reserve(nc));
-            const double *species[3] = {W.HI_out, W.HeI_out, W.HeII_out};
-            for (int f = 0; f < 3; ++f) FTTE_HIP(c, hipMemcpyAsync(G.field(f), species[f], bytes, hipMemcpyDeviceToDevice, c->stream));
-            G.species_changed();
-            FTTE_HIP(c, hipMemcpyAsync(K.tgas, R.out0, bytes, hipMemcpyDeviceToDevice, c->stream));
-            FTTE_HIP(c, hipMemcpyAsync(K.logtem, R.out1, bytes, hipMemcpyDeviceToDevice, c->stream));
-            FTTE_HIP(c, hipMemcpyAsync(K.subcycles, K.subcycles_out, sizeof(int32_t) * nc, hipMemcpyDeviceToDevice, c->stream));
-            FTTE_HIP(c, hipStreamSynchronize(c->stream));
-            K.subcycles_set = true;
-            if (max_change) std::memcpy(&max_change[1], &more[0], sizeof(double));
-            if (subcycles) for (int i = 0; i < 3; ++i) subcycles[i] = (int64_t)more[1 + i];
-            return FTTE_OK;
-        },
-        max_change);
-}
-
-// computeMass over the leaves of HI (the medium's or a candidate's): the two totals [msun], deterministic
-int hydrogen_mass(ftte_ctx *c, const double *HI_dev, double *neutral, double *total, const char *who)
-{
-    int rc = ensure_level(c);
-    if (rc) return rc;
-    FTTE_HIP(c, c->chem.mass.reserve(kMassParts));
-    if (launch_hydrogen_mass(c->chem.level, HI_dev, c->gas.field(GasState::kRho), (long)c->ncell, c->n, c->box, c->chem.mass, c->stream))
-        return fail(c, FTTE_ERR_NO_DEVICE, std::string(who) + ": kernel launch failed");
-    double out[2];
-    FTTE_HIP(c, hipMemcpyAsync(out, c->chem.mass + 2 * kMassBlocks, sizeof out, hipMemcpyDeviceToHost, c->stream));
-    FTTE_HIP(c, hipStreamSynchronize(c->stream));
-    *neutral = out[0];
-    *total = out[1];
-    return FTTE_OK;
-}
 
 int assign_uvb(ftte_ctx *c, int nnu, const double *uvb, double threshold, double *J, bool J_on_device, const char *who)
 {
@@ -531,57 +222,6 @@ int ftte_set_cooling_coefficients(ftte_ctx *c, int nratec, const double *coef, d
     return FTTE_OK;
 }
 
-int ftte_thermal_equilibrium(ftte_ctx *c, int run_uvb_transfer, const double *J, const double *gamma, const double *uniform_gamma,
-                             double self_shielding_threshold, int use_point_rates, double *heating, double *cooling, double *hydro_heating)
-{
-    const ThermalRates A{run_uvb_transfer, J, false, gamma, uniform_gamma, self_shielding_threshold, use_point_rates};
-    return thermal_equilibrium(c, A, heating, cooling, hydro_heating, "ftte_thermal_equilibrium");
-}
-
-int ftte_thermal_equilibrium_device(ftte_ctx *c, int run_uvb_transfer, const double *J_dev, const double *gamma, const double *uniform_gamma,
-                                    double self_shielding_threshold, int use_point_rates, double *heating, double *cooling,
-                                    double *hydro_heating)
-{
-    const ThermalRates A{run_uvb_transfer, J_dev, true, gamma, uniform_gamma, self_shielding_threshold, use_point_rates};
-    return thermal_equilibrium(c, A, heating, cooling, hydro_heating, "ftte_thermal_equilibrium_device");
-}
-
-int ftte_advance_temperature(ftte_ctx *c, double dt_s, int substeps, double tmin, double tmax, int use_hydro_heating, int run_uvb_transfer,
-                             const double *J, const double *gamma, const double *uniform_gamma, double self_shielding_threshold,
-                             int use_point_rates, double *max_change)
-{
-    const ThermalRates A{run_uvb_transfer, J, false, gamma, uniform_gamma, self_shielding_threshold, use_point_rates};
-    return advance_temperature(c, dt_s, substeps, tmin, tmax, use_hydro_heating, A, max_change, "ftte_advance_temperature");
-}
-
-int ftte_advance_temperature_device(ftte_ctx *c, double dt_s, int substeps, double tmin, double tmax, int use_hydro_heating,
-                                    int run_uvb_transfer, const double *J_dev, const double *gamma, const double *uniform_gamma,
-                                    double self_shielding_threshold, int use_point_rates, double *max_change)
-{
-    const ThermalRates A{run_uvb_transfer, J_dev, true, gamma, uniform_gamma, self_shielding_threshold, use_point_rates};
-    return advance_temperature(c, dt_s, substeps, tmin, tmax, use_hydro_heating, A, max_change, "ftte_advance_temperature_device");
-}
-
-int ftte_advance_thermochemistry(ftte_ctx *c, double dt_s, double eta, int max_subcycles, double tmin, double tmax, int use_hydro_heating,
-                                 int run_uvb_transfer, const double *J, const double *ksi, const double *gamma, const double *uniform,
-                                 const double *uniform_gamma, double self_shielding_threshold, int use_point_rates, double *max_change,
-                                 int64_t *subcycles)
-{
-    const ThermalRates A{run_uvb_transfer, J, false, gamma, uniform_gamma, self_shielding_threshold, use_point_rates};
-    return advance_thermochemistry(c, dt_s, eta, max_subcycles, tmin, tmax, use_hydro_heating, A, ksi, uniform, max_change, subcycles,
-                                   "ftte_advance_thermochemistry");
-}
-
-int ftte_advance_thermochemistry_device(ftte_ctx *c, double dt_s, double eta, int max_subcycles, double tmin, double tmax, int use_hydro_heating,
-                                        int run_uvb_transfer, const double *J_dev, const double *ksi, const double *gamma, const double *uniform,
-                                        const double *uniform_gamma, double self_shielding_threshold, int use_point_rates, double *max_change,
-                                        int64_t *subcycles)
-{
-    const ThermalRates A{run_uvb_transfer, J_dev, true, gamma, uniform_gamma, self_shielding_threshold, use_point_rates};
-    return advance_thermochemistry(c, dt_s, eta, max_subcycles, tmin, tmax, use_hydro_heating, A, ksi, uniform, max_change, subcycles,
-                                   "ftte_advance_thermochemistry_device");
-}
-
 int ftte_get_subcycles(ftte_ctx *c, int32_t *per_leaf)
 {
     int rc = check_ready(c, false);
@@ -591,55 +231,6 @@ int ftte_get_subcycles(ftte_ctx *c, int32_t *per_leaf)
     FTTE_HIP(c, hipSetDevice(c->device));
     FTTE_HIP(c, hipMemcpyAsync(per_leaf, c->chem.subcycles, sizeof(int32_t) * (size_t)c->ncell, hipMemcpyDeviceToHost, c->stream));
     FTTE_HIP(c, hipStreamSynchronize(c->stream));
-    return FTTE_OK;
-}
-
-int ftte_solve_rate_equations(ftte_ctx *c, int run_uvb_transfer, const double *J, const double *ksi, const double *uniform,
-                              double self_shielding_threshold, int use_point_rates, double *max_change)
-{
-    return solve_rates(c, run_uvb_transfer, J, false, ksi, uniform, self_shielding_threshold, use_point_rates, max_change,
-                       "ftte_solve_rate_equations");
-}
-
-int ftte_solve_rate_equations_device(ftte_ctx *c, int run_uvb_transfer, const double *J_dev, const double *ksi, const double *uniform,
-                                     double self_shielding_threshold, int use_point_rates, double *max_change)
-{
-    return solve_rates(c, run_uvb_transfer, J_dev, true, ksi, uniform, self_shielding_threshold, use_point_rates, max_change,
-                       "ftte_solve_rate_equations_device");
-}
-
-int ftte_advance_rate_equations(ftte_ctx *c, double dt_s, int substeps, int run_uvb_transfer, const double *J, const double *ksi,
-                                const double *uniform, double self_shielding_threshold, int use_point_rates, double *max_change)
-{
-    return advance_rates(c, dt_s, substeps, run_uvb_transfer, J, false, ksi, uniform, self_shielding_threshold, use_point_rates, max_change,
-                         "ftte_advance_rate_equations");
-}
-
-int ftte_advance_rate_equations_device(ftte_ctx *c, double dt_s, int substeps, int run_uvb_transfer, const double *J_dev, const double *ksi,
-                                       const double *uniform, double self_shielding_threshold, int use_point_rates, double *max_change)
-{
-    return advance_rates(c, dt_s, substeps, run_uvb_transfer, J_dev, true, ksi, uniform, self_shielding_threshold, use_point_rates, max_change,
-                         "ftte_advance_rate_equations_device");
-}
-
-// initialIonizationEquilibrium (it stops at equiSources.f90:3809-3818, :3832-3843)
-int ftte_initial_ionization_equilibrium(ftte_ctx *c, const double *uniform, double threshold, int passes, double *neutral_fraction)
-{
-    const char *who = "ftte_initial_ionization_equilibrium";
-    const ChemUpdate U{who, "species fraction outside [0, 1] or no convergence", launch_initial_equilibrium};
-    int rc = chem_update(c, U, [&](ChemRec &R) -> int {
-        if (!uniform) return fail(c, FTTE_ERR_ARG, std::string(who) + ": the uniform-background update needs the background rates");
-        if (passes < 1) return fail(c, FTTE_ERR_ARG, std::string(who) + ": passes must be at least 1");
-        R.passes = passes;
-        std::memcpy(R.uniform, uniform, sizeof R.uniform);
-        R.threshold = threshold;
-        return FTTE_OK;
-    }, nullptr);
-    if (rc || !neutral_fraction) return rc;
-    // equiSources.f90:1020-1022
-    double neutral = 0., total = 0.;
-    if ((rc = hydrogen_mass(c, c->gas.field(GasState::kHI), &neutral, &total, who))) return rc;
-    *neutral_fraction = neutral / total;
     return FTTE_OK;
 }
 
@@ -811,7 +402,5 @@ int ftte_assign_uvb_radiation_device(ftte_ctx *c, int nnu, const double *uvb, do
 {
     return assign_uvb(c, nnu, uvb, self_shielding_threshold, J_dev, true, "ftte_assign_uvb_radiation_device");
 }
-
-long long ftte_rate_equation_steps(const ftte_ctx *c) { return c ? c->chem.steps : 0; }
 
 } // extern "C"

@@ -1,14 +1,13 @@
-// ftte_chem.hip -- the kernels behind ftte_chem.cpp: the ionisation equilibrium of every leaf (solveRateEquations,
-// initialIonizationEquilibrium), its advance over a time step, the optically thin radiation field, the hydrogen census and the opacities.  The chemistry of a
-// cell is ftte_chem_math.h, compiled here for the device and by the tests' host library for the host; an equilibrium kernel is the
-// grid-stride loop, the cell's loads, one call into that header and the cell's stores, and then the fold of its statistics
-// (ftte_chem_fold.h).
+// ftte_chem.hip -- the kernels behind the chemistry's per-leaf updates (ftte_leaf_pass.cpp) and ftte_chem.cpp: the ionisation equilibrium
+// of every leaf (solveRateEquations, initialIonizationEquilibrium), its advance over a time step, the optically thin radiation field,
+// the hydrogen census and the opacities.  The chemistry of a cell is ftte_chem_math.h, compiled here for the device and by the tests'
+// host library for the host; a per-leaf kernel is the loop over the leaves, the leaf's loads, one call into that header and the
+// leaf's stores, and then the fold of its statistics (all of ftte_leaf.h).
 #include <hip/hip_runtime.h>
 
-#include "ftte_chem_fold.h"
 #include "ftte_chem_math.h"
-#include "ftte_internal.h"
 #include "ftte_kernels.h"
+#include "ftte_leaf.h"
 #include "ftte_tree_sum.h"
 
 namespace ftte {
@@ -16,86 +15,78 @@ namespace ftte {
 // solveRateEquations, equiSources.f90:3459-3677, per leaf (chem_solve_cell)
 __global__ void __launch_bounds__(256) rate_equations_kernel(const ChemRec R)
 {
-    unsigned long long my_change = 0ull, my_steps = 0ull, my_bad = ~0ull;
-    const ChemTable T = {R.k, R.nratec, R.logtem0, R.logtem9, R.dlogtem};
-    for (long c = (long)blockIdx.x * blockDim.x + threadIdx.x; c < R.ncell; c += (long)gridDim.x * blockDim.x) { // (a few cells per thread)
-        double p24 = 0., p25 = 0., p26 = 0., HI, HeI, HeII, change;
-        if (R.krate) { p24 = R.krate[c * kCellRec]; p25 = R.krate[c * kCellRec + 1]; p26 = R.krate[c * kCellRec + 2]; }
+    const LeafRec &L = R.L;
+    LeafWords<1, 1> w;
+    const ChemTable T = {R.k, L.nratec, L.logtem0, L.logtem9, L.dlogtem};
+    FTTE_FOR_LEAVES(c, L.ncell) {
+        double p24, p25, p26, HI, HeI, HeII, change;
+        load_point_rates(L.rates, c, 0, p24, p25, p26);
         unsigned steps; int tame;
-        const int ok = chem_solve_cell(&T, R.rho[c], R.logtem[c], R.HI[c], R.HeI[c], R.HeII[c], chem_cell_volume(R.box, R.level[c], R.n),
-                                       R.krate != nullptr, p24, p25, p26, R.run_uvb ? R.J + c : nullptr, R.ncell, R.ksi, R.uniform, R.threshold,
+        const int ok = chem_solve_cell(&T, L.rho[c], R.logtem[c], L.HI[c], L.HeI[c], L.HeII[c], chem_cell_volume(L.box, L.level[c], L.n),
+                                       L.rates != nullptr, p24, p25, p26, L.run_uvb ? L.J + c : nullptr, L.ncell, L.table, L.uniform, L.threshold,
                                        &HI, &HeI, &HeII, &steps, &change, &tame);
-        if (!ok) my_bad = (unsigned long long)c < my_bad ? (unsigned long long)c : my_bad;
+        if (!ok) note_bad(w.bad, c);
         else {
-            const unsigned long long bits = (unsigned long long)__double_as_longlong(change); // non-negative doubles order like their bits
-            my_change = bits > my_change ? bits : my_change;
-            my_steps += (unsigned long long)steps;
+            note_change(w.mx[0], change);
+            w.sm[0] += (unsigned long long)steps;
             R.HI_out[c] = HI; R.HeI_out[c] = HeI; R.HeII_out[c] = HeII;
         }
     }
-    fold_statistics<true>(R.first_bad, R.max_change, R.steps, my_change, my_steps, my_bad);
+    fold_head_words(w, L.first_bad, L.max_change, L.steps);
 }
 
 // The start-up ionisation equilibrium, initialIonizationEquilibrium (equiSources.f90:3679-3868), R.passes times per leaf
-// (chem_initial_cell).  R.krate, R.J, R.run_uvb, R.ksi are not used.
+// (chem_initial_cell).  L.rates, L.J, L.run_uvb, L.table are not used.
 __global__ void __launch_bounds__(256) initial_equilibrium_kernel(const ChemRec R)
 {
-    unsigned long long my_steps = 0ull, my_bad = ~0ull;
-    const ChemTable T = {R.k, R.nratec, R.logtem0, R.logtem9, R.dlogtem};
-    for (long c = (long)blockIdx.x * blockDim.x + threadIdx.x; c < R.ncell; c += (long)gridDim.x * blockDim.x) {
+    const LeafRec &L = R.L;
+    LeafWords<0, 1> w;
+    const ChemTable T = {R.k, L.nratec, L.logtem0, L.logtem9, L.dlogtem};
+    FTTE_FOR_LEAVES(c, L.ncell) {
         double HI, HeI, HeII;
         unsigned long long steps;
-        const int ok = chem_initial_cell(&T, R.rho[c], R.logtem[c], R.HI[c], R.HeI[c], R.HeII[c], R.uniform, R.threshold, R.passes, &HI, &HeI,
+        const int ok = chem_initial_cell(&T, L.rho[c], R.logtem[c], L.HI[c], L.HeI[c], L.HeII[c], L.uniform, L.threshold, R.passes, &HI, &HeI,
                                          &HeII, &steps);
-        my_steps += steps;
-        if (!ok) my_bad = (unsigned long long)c < my_bad ? (unsigned long long)c : my_bad;
+        w.sm[0] += steps;
+        if (!ok) note_bad(w.bad, c);
         else { R.HI_out[c] = HI; R.HeI_out[c] = HeI; R.HeII_out[c] = HeII; }
     }
-    fold_statistics<false>(R.first_bad, R.max_change, R.steps, 0ull, my_steps, my_bad);
+    fold_head_words(w, L.first_bad, L.max_change, L.steps);
 }
 
 // HI, HeI, HeII of every leaf advanced over R.dt in R.substeps implicit steps at the rates of the state on entry (chem_advance_cell)
 __global__ void __launch_bounds__(256) advance_equations_kernel(const ChemRec R)
 {
-    unsigned long long my_change = 0ull, my_steps = 0ull, my_bad = ~0ull;
-    const ChemTable T = {R.k, R.nratec, R.logtem0, R.logtem9, R.dlogtem};
-    for (long c = (long)blockIdx.x * blockDim.x + threadIdx.x; c < R.ncell; c += (long)gridDim.x * blockDim.x) {
-        double p24 = 0., p25 = 0., p26 = 0., HI, HeI, HeII, change;
-        if (R.krate) { p24 = R.krate[c * kCellRec]; p25 = R.krate[c * kCellRec + 1]; p26 = R.krate[c * kCellRec + 2]; }
+    const LeafRec &L = R.L;
+    LeafWords<1, 1> w;
+    const ChemTable T = {R.k, L.nratec, L.logtem0, L.logtem9, L.dlogtem};
+    FTTE_FOR_LEAVES(c, L.ncell) {
+        double p24, p25, p26, HI, HeI, HeII, change;
+        load_point_rates(L.rates, c, 0, p24, p25, p26);
         unsigned long long steps;
-        const int ok = chem_advance_cell(&T, R.rho[c], R.logtem[c], R.HI[c], R.HeI[c], R.HeII[c], chem_cell_volume(R.box, R.level[c], R.n),
-                                         R.krate != nullptr, p24, p25, p26, R.run_uvb ? R.J + c : nullptr, R.ncell, R.ksi, R.uniform, R.threshold,
+        const int ok = chem_advance_cell(&T, L.rho[c], R.logtem[c], L.HI[c], L.HeI[c], L.HeII[c], chem_cell_volume(L.box, L.level[c], L.n),
+                                         L.rates != nullptr, p24, p25, p26, L.run_uvb ? L.J + c : nullptr, L.ncell, L.table, L.uniform, L.threshold,
                                          R.dt, R.substeps, &HI, &HeI, &HeII, &steps, &change);
-        my_steps += steps;
-        if (!ok) my_bad = (unsigned long long)c < my_bad ? (unsigned long long)c : my_bad;
+        w.sm[0] += steps;
+        if (!ok) note_bad(w.bad, c);
         else {
-            const unsigned long long bits = (unsigned long long)__double_as_longlong(change);
-            my_change = bits > my_change ? bits : my_change;
+            note_change(w.mx[0], change);
             R.HI_out[c] = HI; R.HeI_out[c] = HeI; R.HeII_out[c] = HeII;
         }
     }
-    fold_statistics<true>(R.first_bad, R.max_change, R.steps, my_change, my_steps, my_bad);
+    fold_head_words(w, L.first_bad, L.max_change, L.steps);
 }
 
-// (enough workgroups to fill the GPU several times over, few enough that their atomics are nothing)
-static int launch_equilibrium(void (*kernel)(const ChemRec), const ChemRec &R, hipStream_t stream)
-{
-    if (R.ncell <= 0) return 0;
-    const long blocks = (R.ncell + 255) / 256;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, stream, R);
-    return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-int launch_rate_equations(const ChemRec &R, hipStream_t stream) { return launch_equilibrium(rate_equations_kernel, R, stream); }
+int launch_rate_equations(const ChemRec &R, hipStream_t stream) { return launch_over_leaves(rate_equations_kernel, R, R.L.ncell, stream); }
 
 int launch_initial_equilibrium(const ChemRec &R, hipStream_t stream)
 {
-    return R.ncell > 0 && R.passes < 1 ? -1 : launch_equilibrium(initial_equilibrium_kernel, R, stream);
+    return R.L.ncell > 0 && R.passes < 1 ? -1 : launch_over_leaves(initial_equilibrium_kernel, R, R.L.ncell, stream);
 }
 
 int launch_advance_equations(const ChemRec &R, hipStream_t stream)
 {
-    return R.ncell > 0 && (R.substeps < 1 || !(R.dt > 0.)) ? -1 : launch_equilibrium(advance_equations_kernel, R, stream);
+    return R.L.ncell > 0 && (R.substeps < 1 || !(R.dt > 0.)) ? -1 : launch_over_leaves(advance_equations_kernel, R, R.L.ncell, stream);
 }
 
 // assignUvbRadiation, transportRoutinesModule.f90:1056-1093: the optically thin alternative to the sweep.  J_g = uvb_g where the

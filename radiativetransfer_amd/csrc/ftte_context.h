@@ -2,7 +2,7 @@
 // planners' cached callers (ftte_plan.cpp; the planners themselves read no context: ftte_planner.cpp), the sweeps
 // (ftte_sweeps.cpp: segment forests, cell-fixed bricks), the hybrid sweep of refined cell arrays (ftte_hybrid.cpp) and the
 // host-array transfers (ftte_host_arrays.cpp).  ftte_api.cpp is the C ABI itself, ftte_chem.cpp its part that reads or writes the
-// species medium.
+// species medium, ftte_leaf_pass.cpp the per-leaf updates of the species and the temperature.
 //
 // Every device buffer, pinned buffer, stream, event and graph of the context is a member that owns it (ftte_device.h): a buffer's
 // capacity travels with its pointer, `delete c` releases everything, and a new buffer is added by declaring it.  What a buffer
@@ -252,8 +252,9 @@ const char *multi_how(const ftte_ctx *c);
 ftte_ctx *multi_first(const ftte_ctx *c);
 int multi_host_register(ftte_ctx *c, void *ptr, size_t bytes, bool on);
 
-// ---- ftte_chem.cpp
+// ---- ftte_leaf_pass.cpp
 int ensure_level(ftte_ctx *c); // the leaves' levels in ChemState::level (uploaded on first use after ftte_set_grid)
+int hydrogen_mass(ftte_ctx *c, const double *HI_dev, double *neutral, double *total, const char *who); // computeMass over the leaves of HI [msun]
 
 // ---- ftte_host_arrays.cpp
 bool is_registered(const ftte_ctx *c, const void *p, size_t bytes);

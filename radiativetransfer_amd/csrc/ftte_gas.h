@@ -2,7 +2,7 @@
 // HeI, HeII, rho, abun2 in cell-array order), with the packed copy the tracer reads.  The species have a version and the packed copy
 // remembers the version it was made from, as a MediumField's copies do (ftte_medium.h): whoever writes the species says
 // species_changed(), and the tracer asks packed_current().  Launches nothing and copies nothing: point_set_medium fills it.
-// ChemState: what the ionisation chemistry and the expansion of HII regions keep beside the gas (ftte_chem.cpp).
+// ChemState: what the per-leaf updates (ftte_leaf_pass.cpp) and the expansion of HII regions (ftte_chem.cpp) keep beside the gas.
 #pragma once
 
 #include <cstdint>
@@ -80,8 +80,8 @@ struct ChemState {
     double logtem0 = 0, logtem9 = 0, dlogtem = 0;
     DeviceBuffer<double> logtem;  // [ncell] log of the gas temperature
     bool temperature_set = false;
-    DeviceBuffer<double> out, J;  // [3][ncell] each ([5][ncell] out for the coupled step)
-    DeviceBuffer<unsigned long long> counters; // first bad cell, bits of the largest change, bisection steps (+4..+7: the coupled step's)
+    DeviceBuffer<double> out, J;  // out: as many planes [ncell] as the update declares (leaf_pass); J: [3][ncell]
+    DeviceBuffer<unsigned long long> counters; // first bad cell, bits of the largest change, bisection steps, then the update's own words
     long long steps = 0;          // of the last update
     DeviceBuffer<double> mass;    // computeMass: per-workgroup partial sums, then the two totals (kMassParts)
     // expansion of HII regions (ftte_expansion.h): where each leaf of a refined cell array lies, uploaded on first use after

@@ -1,5 +1,5 @@
-// ftte_kernels.h -- launch wrappers of ftte_kernels.hip, ftte_brick.hip and, from launch_opacity and launch_rate_equations on,
-// ftte_chem.hip (all asynchronous on `stream`; return 0, -1 bad argument, -2 launch failure)
+// ftte_kernels.h -- launch wrappers of ftte_kernels.hip, ftte_brick.hip and, for launch_opacity and from launch_hydrogen_mass on,
+// ftte_chem.hip; those of the per-leaf updates are in ftte_leaf.h (all asynchronous on `stream`; return 0, -1 bad argument, -2 launch failure)
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -53,12 +53,6 @@ int launch_point_trace(const TraceRec &T, hipStream_t stream);
 int launch_pack_medium(const double *const field[5], double *packed, long ncell, hipStream_t stream);
 int launch_repack_rates(double *planes, double *packed, long ncell, bool to_packed, hipStream_t stream);
 
-// ionisation equilibrium of every leaf (solveRateEquations)
-int launch_rate_equations(const ChemRec &R, hipStream_t stream);
-// the start-up equilibrium (initialIonizationEquilibrium), R.passes times per leaf; R.krate, R.J, R.run_uvb, R.ksi unused
-int launch_initial_equilibrium(const ChemRec &R, hipStream_t stream);
-// HI, HeI, HeII of every leaf advanced over R.dt in R.substeps implicit steps; R.passes unused
-int launch_advance_equations(const ChemRec &R, hipStream_t stream);
 // computeMass over the leaves: part[kMassParts]; the neutral and the total hydrogen mass [msun] land in part[2 kMassBlocks], [+1]
 constexpr int kMassBlocks = 1024;
 constexpr int kMassParts = 2 * kMassBlocks + 2;

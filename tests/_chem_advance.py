@@ -10,21 +10,10 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "radiativetransfer_amd", "csrc")
-SOURCE = os.path.join(HERE, "host", "chem_advance_check.cpp")
-LIB = os.path.join(HERE, "host", "libchem_advance.so")
-
-# -ffp-contract=off: every product is rounded before the sum, as in the library's build
-FLAGS = ["-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-Wall", "-Werror"]
+from _hostlib import HostLib, dp as _dp, f64 as _f64
 
 # The equilibrium limit (test_chem_advance_host.py (a), (b); test_chem_advance_gpu.py): the worst difference measured when the step
 # was written, in units of the element's density; a test's bound is 16 times that and never above CEILING
@@ -32,46 +21,17 @@ WORST_A = 2.96e-15      # a step of 1e40 s, twice, against the reference's HI_ou
 WORST_B = 1.05e-14      # once, against chem_bisect + chem_close at the same rates over chem_uvb_refined.npz (worst: HeII, no point rates)
 CEILING = 1e-12
 
-_lib = None
+
+def _declare(L):
+    dp, ip, lp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_longlong)
+    head = [C.c_longlong, C.c_int, ip, C.c_double, dp, dp, dp, dp, dp, dp, C.c_int, dp, dp, dp, C.c_double, C.c_int, C.c_double, C.c_double,
+            C.c_double, dp]
+    L.ca_advance.argtypes = head + [C.c_double, C.c_int, dp, dp, dp, lp, dp]
+    L.ca_equilibrium.argtypes = head + [dp, dp, dp]
+    L.ca_advance.restype = L.ca_equilibrium.restype = C.c_longlong
 
 
-def build():
-    """the shared library, rebuilt when the source or a header is newer; in a temporary directory where the tree is read-only"""
-    global LIB
-    deps = [SOURCE, os.path.join(CSRC, "ftte_chem_math.h"), os.path.join(CSRC, "ftte_math.h")]
-    if os.path.exists(LIB) and all(os.path.getmtime(d) <= os.path.getmtime(LIB) for d in deps):
-        return LIB
-    gxx = shutil.which("g++")
-    if not gxx:
-        raise RuntimeError("no g++: the host evaluation of the chemistry step cannot be built")
-    if not os.access(os.path.dirname(LIB), os.W_OK):
-        LIB = os.path.join(tempfile.mkdtemp(prefix="chem_advance_"), "libchem_advance.so")
-    tmp = LIB + f".{os.getpid()}.tmp"
-    subprocess.check_call([gxx, *FLAGS, "-shared", "-I" + CSRC, SOURCE, "-o", tmp])
-    os.replace(tmp, LIB)
-    return LIB
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        L = C.CDLL(build())
-        dp, ip, lp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_longlong)
-        head = [C.c_longlong, C.c_int, ip, C.c_double, dp, dp, dp, dp, dp, dp, C.c_int, dp, dp, dp, C.c_double, C.c_int, C.c_double, C.c_double,
-                C.c_double, dp]
-        L.ca_advance.argtypes = head + [C.c_double, C.c_int, dp, dp, dp, lp, dp]
-        L.ca_equilibrium.argtypes = head + [dp, dp, dp]
-        L.ca_advance.restype = L.ca_equilibrium.restype = C.c_longlong
-        _lib = L
-    return _lib
-
-
-def _f64(a):
-    return np.ascontiguousarray(a, dtype=np.float64)
-
-
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+lib = HostLib("chem_advance", "chem_advance_check.cpp", ("ftte_chem_math.h", "ftte_math.h"), "the chemistry step", _declare)
 
 
 def _head(n, level, box, rho, tgas, HI, HeI, HeII, krate, run_uvb, J, ksi, uniform, threshold, logtem0, logtem9, dlogtem, k):

@@ -10,72 +10,32 @@ from __future__ import annotations
 
 import ctypes as C
 import math
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-CSRC = os.path.join(ROOT, "radiativetransfer_amd", "csrc")
-SOURCE = os.path.join(HERE, "host", "thermal_check.cpp")
-LIB = os.path.join(HERE, "host", "libthermal.so")
-
-# -ffp-contract=off: every product is rounded before the sum, as in the library's build
-FLAGS = ["-std=c++17", "-O2", "-fPIC", "-ffp-contract=off", "-Wall", "-Werror"]
-SANITIZE = ["-std=c++17", "-O1", "-g", "-ffp-contract=off", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
+from _hostlib import CSRC, FLAGS, ROOT, SANITIZE, HostLib, dp as _dp, f64 as _f64
 
 EPS = np.finfo(float).eps
 TMIN, TMAX = 1.0, 1.0e9
 STEPS = [(1e9, 1), (1e13, 3), (1e40, 1)]
 REDSHIFT = 9.0
 
-_lib = None
+
+def _declare(L):
+    dp, ip, lp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_longlong)
+    L.th_log.argtypes = [C.c_longlong, dp, dp]
+    L.th_log.restype = None
+    tail = [dp, C.c_int, dp, dp, dp, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, dp, C.c_double, C.c_double]
+    L.th_equilibrium.argtypes = [C.c_longlong, C.c_int, ip, C.c_double, dp, dp, dp, dp, dp, dp] + tail + [dp, dp, dp]
+    L.th_advance.argtypes = [C.c_longlong, C.c_int, ip, C.c_double, dp, dp, dp, dp, dp] + tail + [dp, C.c_double, C.c_int, C.c_double, C.c_double, dp,
+                                                                                                dp, lp, dp]
+    L.th_solve.argtypes = [C.c_longlong, C.c_int, ip, C.c_double, dp, dp, dp, dp, dp, dp, dp, C.c_int, C.c_double, C.c_double, C.c_double, dp, dp, dp,
+                           dp]
+    L.th_equilibrium.restype = L.th_advance.restype = L.th_solve.restype = C.c_longlong
 
 
-def build():
-    """the shared library, rebuilt when the source or a header is newer; in a temporary directory where the tree is read-only"""
-    global LIB
-    deps = [SOURCE] + [os.path.join(CSRC, h) for h in ("ftte_thermal_math.h", "ftte_chem_math.h", "ftte_math.h")]
-    if os.path.exists(LIB) and all(os.path.getmtime(d) <= os.path.getmtime(LIB) for d in deps):
-        return LIB
-    gxx = shutil.which("g++")
-    if not gxx:
-        raise RuntimeError("no g++: the host evaluation of the thermal balance cannot be built")
-    if not os.access(os.path.dirname(LIB), os.W_OK):
-        LIB = os.path.join(tempfile.mkdtemp(prefix="thermal_"), "libthermal.so")
-    tmp = LIB + f".{os.getpid()}.tmp"
-    subprocess.check_call([gxx, *FLAGS, "-shared", "-I" + CSRC, SOURCE, "-o", tmp])
-    os.replace(tmp, LIB)
-    return LIB
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        L = C.CDLL(build())
-        dp, ip, lp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_longlong)
-        L.th_log.argtypes = [C.c_longlong, dp, dp]
-        L.th_log.restype = None
-        tail = [dp, C.c_int, dp, dp, dp, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, dp, C.c_double, C.c_double]
-        L.th_equilibrium.argtypes = [C.c_longlong, C.c_int, ip, C.c_double, dp, dp, dp, dp, dp, dp] + tail + [dp, dp, dp]
-        L.th_advance.argtypes = [C.c_longlong, C.c_int, ip, C.c_double, dp, dp, dp, dp, dp] + tail + [dp, C.c_double, C.c_int, C.c_double, C.c_double, dp,
-                                                                                                    dp, lp, dp]
-        L.th_solve.argtypes = [C.c_longlong, C.c_int, ip, C.c_double, dp, dp, dp, dp, dp, dp, dp, C.c_int, C.c_double, C.c_double, C.c_double, dp, dp, dp,
-                               dp]
-        L.th_equilibrium.restype = L.th_advance.restype = L.th_solve.restype = C.c_longlong
-        _lib = L
-    return _lib
-
-
-def _f64(a):
-    return np.ascontiguousarray(a, dtype=np.float64)
-
-
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+lib = HostLib("thermal", "thermal_check.cpp", ("ftte_thermal_math.h", "ftte_chem_math.h", "ftte_math.h"), "the thermal balance", _declare)
+SOURCE = lib.source
 
 
 def log(x):

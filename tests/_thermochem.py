@@ -6,65 +6,31 @@ is the yardstick, as for the thermal step."""
 from __future__ import annotations
 
 import ctypes as C
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
 import _thermal as T
+from _hostlib import HostLib, dp as _dp, f64 as _f64
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-CSRC = T.CSRC
-SOURCE = os.path.join(HERE, "host", "thermochem_check.cpp")
-LIB = os.path.join(HERE, "host", "libthermochem.so")
-FLAGS, SANITIZE = T.FLAGS, T.SANITIZE
+CSRC, FLAGS, SANITIZE = T.CSRC, T.FLAGS, T.SANITIZE
 TMIN, TMAX = T.TMIN, T.TMAX
 
 # (dt, eta, max_subcycles) of the bitwise GPU tests
 RUNS = [(1e9, 0.1, 64), (1e13, 0.1, 64), (1e13, 0.0, 3), (1e40, 0.5, 8)]
 
-_lib = None
+
+def _declare(L):
+    dp, ip, lp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_longlong)
+    head = [C.c_longlong, C.c_int, ip, C.c_double, dp, dp, dp, dp, dp, dp, dp, C.c_int, dp, dp, dp, dp, dp, C.c_double, C.c_int, C.c_double,
+            C.c_double, C.c_double, dp, dp, C.c_double, C.c_double]
+    L.tc_advance.argtypes = head + [dp, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, dp, dp, dp, dp, dp, lp, ip, ip, dp, dp]
+    L.tc_pair.argtypes = head + [C.c_double, C.c_double, C.c_double, dp, dp, dp, dp, dp]
+    L.tc_advance.restype = L.tc_pair.restype = C.c_longlong
 
 
-def build():
-    """the shared library, rebuilt when the source or a header is newer; in a temporary directory where the tree is read-only"""
-    global LIB
-    deps = [SOURCE] + [os.path.join(CSRC, h) for h in ("ftte_thermochem_math.h", "ftte_thermal_math.h", "ftte_chem_math.h", "ftte_math.h")]
-    if os.path.exists(LIB) and all(os.path.getmtime(d) <= os.path.getmtime(LIB) for d in deps):
-        return LIB
-    gxx = shutil.which("g++")
-    if not gxx:
-        raise RuntimeError("no g++: the host evaluation of the coupled step cannot be built")
-    if not os.access(os.path.dirname(LIB), os.W_OK):
-        LIB = os.path.join(tempfile.mkdtemp(prefix="thermochem_"), "libthermochem.so")
-    tmp = LIB + f".{os.getpid()}.tmp"
-    subprocess.check_call([gxx, *FLAGS, "-shared", "-I" + CSRC, SOURCE, "-o", tmp])
-    os.replace(tmp, LIB)
-    return LIB
-
-
-def lib():
-    global _lib
-    if _lib is None:
-        L = C.CDLL(build())
-        dp, ip, lp = C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_longlong)
-        head = [C.c_longlong, C.c_int, ip, C.c_double, dp, dp, dp, dp, dp, dp, dp, C.c_int, dp, dp, dp, dp, dp, C.c_double, C.c_int, C.c_double,
-                C.c_double, C.c_double, dp, dp, C.c_double, C.c_double]
-        L.tc_advance.argtypes = head + [dp, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, dp, dp, dp, dp, dp, lp, ip, ip, dp, dp]
-        L.tc_pair.argtypes = head + [C.c_double, C.c_double, C.c_double, dp, dp, dp, dp, dp]
-        L.tc_advance.restype = L.tc_pair.restype = C.c_longlong
-        _lib = L
-    return _lib
-
-
-def _f64(a):
-    return np.ascontiguousarray(a, dtype=np.float64)
-
-
-def _dp(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+lib = HostLib("thermochem", "thermochem_check.cpp", ("ftte_thermochem_math.h", "ftte_thermal_math.h", "ftte_chem_math.h", "ftte_math.h"),
+              "the coupled step", _declare, local=("fit_tables.h",))
+SOURCE = lib.source
 
 
 def _head(case, tab, chem, logtem=None, state=None):

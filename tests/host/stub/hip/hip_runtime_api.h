@@ -139,4 +139,5 @@ inline hipError_t hipStreamEndCapture(hipStream_t, hipGraph_t *graph) { *graph =
 inline hipError_t hipGraphInstantiate(hipGraphExec_t *exec, hipGraph_t, hipGraphNode_t *, char *, size_t) { *exec = nullptr; return hipErrorStreamCaptureUnsupported; }
 inline hipError_t hipGraphLaunch(hipGraphExec_t, hipStream_t) { return hipErrorStreamCaptureUnsupported; }
 inline hipError_t hipGetLastError() { return hipSuccess; }
+inline hipError_t hipSetDevice(int) { return hipSuccess; } // (one device: the per-leaf updates of ftte_leaf_pass.cpp select theirs)
 inline const char *hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : e == hipErrorOutOfMemory ? "out of memory" : "error"; }

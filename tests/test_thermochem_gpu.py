@@ -254,6 +254,40 @@ def test_refusals(golden, chem, grid):
         assert st.subcycles().shape == (8,) and out["subcycles"] == int(st.subcycles().sum())
 
 
+def test_two_bad_leaves_the_lower_one_is_named(golden, chem, grid):
+    """The fold's minimum across wavefronts and workgroups, for each of the six per-leaf kernels through its entry point: on the 405
+    leaves of chem_uvb_refined (two workgroups, the last wavefront partly filled) leaf 300, in the second workgroup, and leaf 130, in
+    the third wavefront of the first, are bad at once -- a NaN temperature for the thermal kernels and the coupled one; for the
+    chemistry's an empty leaf, as in their own refusal tests: their statements clip a NaN species into range and do not refuse it.
+    The refusal names leaf 130, and medium, temperature and subcycle map are left as they were."""
+    import radiativetransfer_amd as rt
+    tab, case = T.tables(), TC.case(golden, "chem_uvb_refined", grid)
+    n, level, box, rho, tgas, HI, HeI, HeII = case["head"]
+    assert level.size == 405
+    r = _rates(case, tab)
+    both = [300, 130]
+    nan_t, empty = tgas.copy(), rho.copy()
+    nan_t[both], empty[both] = np.nan, 0.0
+    chemistry = (r["run_uvb"], r["J"], r["ksi"], None, r["threshold"], True)
+    heating = (r["run_uvb"], r["J"], r["gamma"], None, r["threshold"], True)
+    calls = [("rate_equations_kernel", empty, tgas, lambda st: st.solve_rate_equations(*chemistry)),
+             ("advance_equations_kernel", empty, tgas, lambda st: st.advance_rate_equations(1e12, *chemistry)),
+             ("initial_equilibrium_kernel", empty, tgas, lambda st: st.initial_ionization_equilibrium(golden("initial_refined")["uniform"], 0.0)),
+             ("thermal_equilibrium_kernel", rho, nan_t, lambda st: st.thermal_equilibrium(*heating)),
+             ("thermal_advance_kernel", rho, nan_t, lambda st: st.advance_temperature(1e12, *heating)),
+             ("thermochem_advance_kernel", rho, nan_t, lambda st: st.advance_thermochemistry(1e12, **r))]
+    with rt.StellarTransfer() as st:
+        _load(st, case, chem)
+        st.advance_thermochemistry(1e12, eta=0.0, max_subcycles=2, **r)      # a subcycle map to leave alone
+        for kernel, rho_, tgas_, call in calls:
+            st.set_medium(HI, HeI, HeII, rho_, None, 0)
+            st.set_temperature(tgas_)
+            text = _expect("FTTE_ERR_RATES", call, st)
+            assert "cell 130 " in text, (kernel, text)
+            assert all(np.array_equal(a, b) for a, b in zip(st.medium(), (HI, HeI, HeII))), kernel
+            assert np.array_equal(st.temperature(), tgas_, equal_nan=True) and np.all(st.subcycles() == 2), kernel
+
+
 def test_device_objects_come_back(stellar, golden, chem, grid):
     import radiativetransfer_amd as rt
     tab, case = T.tables(), TC.case(golden, "chem_uvb_refined", grid)
