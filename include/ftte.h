@@ -609,7 +609,8 @@ int ftte_host_unregister(ftte_ctx *ctx, void *ptr);
  * stage, 1 one launch with flags, 2 the same with write-through stores, 3 persistent workgroups with a queue per XCD; the form
  * option "dataflow" asks for falls back to 1 or 0 where the XCD census or the grid size does not allow it; -1 before the first);
  * "brick_whole": 1 when that sweep's stage launches took the whole-brick form of the brick kernel (every brick whole, four waves, no
- * emission, no diagnostic option), else 0; "nu_deal": option "nu_deal" as it stands (the library's default until it is set);
+ * emission, no diagnostic option), else 0; "brick_duo": the workgroups per stage sweep of that sweep's plan in which two passes of one
+ * izone cross a brick together and share its opacities and its J (0: every pass on its own); "nu_deal": option "nu_deal" as it stands (the library's default until it is set);
  * "brick_groups" and "brick_accumulators" (also "_0", "_1", "_2" per memory layout): direction groups of the current brick plan and
  * the J accumulators they share (0 without a plan), "brick_chunk" (layers per brick of that plan) and "brick_queue_mix" (the
  * option "queue_mix" the persistent form's queues were laid out by; -1 when the plan has no queues); "brick_stages" (stages of that

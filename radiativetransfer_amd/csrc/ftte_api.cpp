@@ -356,6 +356,7 @@ long long ftte_counter(const ftte_ctx *c, const char *name)
     if (!std::strcmp(name, "brick_form")) return c->last_brick_form;
     if (!std::strcmp(name, "brick_dataflow")) return c->last_brick_dataflow;
     if (!std::strcmp(name, "brick_whole")) return c->last_brick_whole; // 1: the last sweep's stage launches took the whole-brick form
+    if (!std::strcmp(name, "brick_duo")) return c->last_brick_duo;     // seats of the last sweep's plan where two passes share a visit (0: single passes)
     if (!std::strcmp(name, "nu_deal")) return c->opt.launch.nu_deal; // the option as it stands (its default before anybody set it)
     if (!std::strcmp(name, "brick_chunk")) return c->bplan.valid ? c->bplan.chunk : 0;
     if (!std::strcmp(name, "brick_queue_mix")) return (c->bplan.valid && c->bplan.persistent) ? c->bplan.key.queue_mix : -1;

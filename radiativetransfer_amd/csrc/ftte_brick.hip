@@ -825,6 +825,200 @@ __global__ void __launch_bounds__(128, WAVES) brick_pair_kernel(const BrickLaunc
     }
 }
 
+// Two passes of an izone per visit (BrickPlan::duo, BrickSeat): a workgroup of two wavefronts per seat, each wavefront a whole brick
+// of its own pass as in brick_kernel<4, 0, 0, false, true> -- the same shape steps, double-buffered opacities and counted waits,
+// its own rays, parked rays and faces.  In a linked seat both cross the SAME brick: the helper (wavefront 1) starts every layer's
+// sums from zero and hands its eight rows to the owner through 4 KB of LDS, the owner adds them to its own and is the only one to
+// read or write the cells' J, so the pair costs the J traffic of one pass; the helper's opacity loads follow the owner's to the
+// same lines.  A cell's J is (J before + the owner's directions) + (0 + the helper's directions): a fixed order.
+// Two barriers close a layer of a linked seat, for both wavefronts and on every path, (i1 - i0 + 1) times: behind the first the
+// owner has read the rows of the layer before and the helper writes this layer's, behind the second the owner reads them.  They
+// are bare barriers behind a wait for the LDS alone: the next layer's opacities and the J stores stay in flight.
+// Seats that are not linked hold no barrier; the wavefront of an empty place leaves at once.
+// grid: seats * nnu workgroups of 128 threads; dynamic LDS: brick_duo_lds(max_dirs, pad)
+__global__ void __launch_bounds__(128, 4) brick_duo_kernel(const BrickLaunch L, int max_dirs)
+{
+    extern __shared__ double duo_lds[];
+    constexpr int R = kBrickRows;
+    using cgroup = const __attribute__((address_space(4))) BrickGroup;
+    using clayer = const __attribute__((address_space(4))) LayerRec;
+    const int lane = threadIdx.x & 63;
+    const int wv = uniform((int)(threadIdx.x >> 6));
+    const int nnu = L.nnu;
+    const BrickWork W = brick_deal(blockIdx.x, (unsigned)nnu, (unsigned)L.deal);
+    const int nu = L.nu0 + (int)W.slot;
+    // the seat: both places' records in every wavefront.  Whether the seat is linked and, if it is, the brick are read from place 0
+    // by both, so that the two agree on the barriers whatever the table holds.
+    const __attribute__((address_space(4))) unsigned long *seat = (const __attribute__((address_space(4))) unsigned long *)(unsigned long)L.seats + 2ul * W.task;
+    const unsigned long raw0 = seat[0], raw1 = seat[1];
+    // (flags as scalar integers, by scalar arithmetic alone: a scalar compare and branch each where they are tested, no lane mask)
+    const int linked = (uniform((int)(raw0 >> 48)) / kBrickLinked) & 1;
+    const int helper = linked & wv;
+    const unsigned long raw = wv ? raw1 : raw0, where = linked ? raw0 : raw;
+    const int group = uniform((int)(int16_t)(raw & 0xffffu));
+    if (group < 0) return; // an empty place (never in a linked seat)
+    const int tu = uniform((int)(int16_t)((where >> 16) & 0xffffu)), tv = uniform((int)(int16_t)((where >> 32) & 0xffffu));
+    const int ti_field = uniform((int)(int16_t)(where >> 48));
+    const int ti = ti_field & (kBrickLinked - 1);
+    const int accumulate = (ti_field / kBrickAccumulate) & 1 & (helper ^ 1);
+    // LDS, in doubles: [row][lane] the helper's sums of a layer, then each wavefront's parked rays [slot][row][lane], `shift` apart.
+    // In the layer loop a wavefront's lanes go by lx = lane + shift: as an index into the parked rays it is the wavefront's own
+    // place, and the pointers to the v-faces, the only other thing a lane indexes there, are moved back by as much, so that one
+    // register serves both, as in brick_kernel.  (The lane that hands rays to the right is then 63 + shift.)
+    const int shift = wv * (max_dirs - 1) * R * 64;
+    const int lx = lane + shift;
+    double *state = duo_lds + R * 64;
+    cgroup *G = (cgroup *)(L.groups + group);
+    const int n = L.n, chunk = L.chunk, up = L.up, vp = L.vp;
+    const int ndir = G->ndir;
+    const double uvb = ((const __attribute__((address_space(4))) double *)(unsigned long)L.uvb)[nu];
+    double lead = L.math.c[9];
+    asm volatile("" : "+v"(lead));
+
+    const int sv = G->sv, si = G->si;
+    const bool mirror_u = G->su < 0;
+    const long org = G->org;
+    gcbyte *kbase = (gcbyte *)(G->kappa + (long)nu * L.group_stride + org);
+    gbyte *jbase = (gbyte *)(G->J + (long)nu * L.group_stride + org);
+
+    const int cu = 64 * tu + lane + 1;
+    const int cv0 = R * tv + 1;
+    const unsigned off0 = 8u * (unsigned)(mirror_u ? n + 1 - cu : cu);
+    const long row_bytes = 8l * sv;
+    const int i0 = ti * chunk + 1, i1 = i0 + chunk - 1; // (n is a multiple of the chunk)
+    const bool has_u_in = tu > 0, has_u_out = 64 * (tu + 1) < n;
+    const bool has_v_in = tv > 0, has_v_out = R * (tv + 1) < n;
+    const bool has_i_in = ti > 0, has_i_out = i1 < n;
+    const long fnu = (long)nu * L.face_stride;
+    const int uw = L.uw, ut = L.ut;
+    const int ns = L.nslot, sl = ti % ns;
+    const long u_out = ((long)(tu * ns + sl) * chunk) * uw + ut * tv;
+    const long u_in = ((long)((tu > 0 ? tu - 1 : 0) * ns + sl) * chunk) * uw + ut * tv;
+    const long v_out = L.vface_off + ((long)(tv * ns + sl) * chunk) * up + 64 * tu;
+    const long v_in = L.vface_off + ((long)((tv > 0 ? tv - 1 : 0) * ns + sl) * chunk) * up + 64 * tu;
+    const long i_in = L.iface_off + ((long)sl * vp + R * tv) * up + 64 * tu + lane;
+
+    // directions, slots and the order of a layer's sums: brick_kernel
+    int p0 = (ndir - (i0 - 1) % ndir) % ndir;
+    double kap_next[R], kap_odd[R], cur[R];
+    const long row0 = cv0 * row_bytes;
+    load_rows<R, false>(kap_next, kbase + 8l * i0 * si + row0, off0, row_bytes, R);
+    gcdouble *uvb_at = (gcdouble *)L.uvb + nu; // (where the inflow lies in memory: every ray a brick takes in is a load)
+    asm volatile("" : "+s"(uvb_at));
+    const long ist = has_i_in ? (long)up : 0l;
+    {
+        gcdouble *f = has_i_in ? (gcdouble *)(G->dir[p0].faces + fnu) + i_in : uvb_at;
+#pragma unroll
+        for (int r = 0; r < R; ++r) cur[r] = f[r * ist];
+    }
+    for (int k = 0; k + 1 < ndir; ++k) {
+        int d = p0 + 1 + k;
+        d = d >= ndir ? d - ndir : d;
+        gcdouble *f = has_i_in ? (gcdouble *)(G->dir[d].faces + fnu) + i_in : uvb_at;
+        double parked[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) parked[r] = f[r * ist];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int r = 0; r < R; ++r) state[(k * R + r) * 64 + lx] = parked[r];
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) asm volatile("" ::"v"(kap_next[r]), "v"(cur[r])); // the one drain before the loop
+    auto layer = [&](const int i, const double(&kap)[R], double(&kn)[R]) __attribute__((always_inline)) {
+        const int il = i - i0;
+        const double xs[1] = {0.0};
+        double Jacc[R];
+        gbyte *jplane = jbase + 8l * i * si;
+        const long rstep = here(row_bytes);
+        // (the seat's flags pass through an empty asm where they are tested: a scalar compare each, no lane mask kept and inverted
+        // in a vector register, which the loop header would have to wait for)
+        int adds = accumulate, pair = linked, helps = helper;
+        asm volatile("" : "+s"(adds), "+s"(pair), "+s"(helps));
+        if (adds) load_rows<R, true>(Jacc, (gcbyte *)jplane + row0, off0, rstep, R);
+        else {
+#pragma unroll
+            for (int r = 0; r < R; ++r) Jacc[r] = 0.0;
+        }
+        load_rows<R, false>(kn, kbase + 8l * (i < i1 ? i + 1 : i) * si + row0, off0, rstep, R);
+        for (int j = 0; j < ndir; ++j) {
+            int d = p0 + j;
+            d = d >= ndir ? d - ndir : d;
+            if (j) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const double parked = state[((j - 1) * R + r) * 64 + lx];
+                    state[((j - 1) * R + r) * 64 + lx] = cur[r];
+                    cur[r] = parked;
+                }
+            }
+            clayer *rp = (clayer *)(G->dir[d].layers) + (i - 1);
+            const double d0 = rp->dpath[0], d1 = rp->dpath[1], d2 = rp->dpath[2];
+            const int rc = rp->info & 7;
+            const double w = G->dir[d].w;
+            gbyte *f = (gbyte *)(G->dir[d].faces + fnu);
+            gcbyte *uin = has_u_in ? (gcbyte *)f + 8 * (u_in + (long)il * uw) : nullptr;
+            gbyte *uout = has_u_out ? f + 8 * (u_out + (long)il * uw) : nullptr;
+            gcbyte *vin = has_v_in ? (gcbyte *)f + 8 * (v_in + (long)il * up - shift) : nullptr;
+            gbyte *vout = has_v_out ? f + 8 * (v_out + (long)il * up - shift) : nullptr;
+            gcbyte *vb = (gcbyte *)uvb_at;
+            const bool third_first = rc == RC_THREE_U_SWAP || rc == RC_THREE_V_SWAP;
+            switch (rc) {
+            case RC_ONE: brick_step<RC_ONE, 0, R, true>(L.math, lead, cur, kap, xs, Jacc, false, d0, d1, d2, w, uvb, uin, uout, vin, vout, lx, false, false, 0, 63 + shift, true, nullptr, nullptr, vb); break;
+            case RC_TWO_U: brick_step<RC_TWO_U, 0, R, true>(L.math, lead, cur, kap, xs, Jacc, false, d0, d1, d2, w, uvb, uin, uout, vin, vout, lx, false, false, 0, 63 + shift, true, nullptr, nullptr, vb); break;
+            case RC_TWO_V: brick_step<RC_TWO_V, 0, R, true>(L.math, lead, cur, kap, xs, Jacc, false, d0, d1, d2, w, uvb, uin, uout, vin, vout, lx, false, false, 0, 63 + shift, true, nullptr, nullptr, vb); break;
+            case RC_THREE_U:
+            case RC_THREE_U_SWAP:
+                brick_step<RC_THREE_U, 0, R, true>(L.math, lead, cur, kap, xs, Jacc, third_first, d0, d1, d2, w, uvb, uin, uout, vin, vout, lx, false, false, 0, 63 + shift, true, nullptr, nullptr, vb);
+                break;
+            default:
+                brick_step<RC_THREE_V, 0, R, true>(L.math, lead, cur, kap, xs, Jacc, third_first, d0, d1, d2, w, uvb, uin, uout, vin, vout, lx, false, false, 0, 63 + shift, true, nullptr, nullptr, vb);
+                break;
+            }
+        }
+        p0 = p0 ? p0 - 1 : ndir - 1;
+        if (pair) {
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); // the owner is done with the rows of the layer before
+            double *rows = duo_lds + ((int)here((unsigned)lx) - shift); // (made where it is used: no register kept for it)
+            if (helps) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) rows[r * 64] = Jacc[r];
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); // the helper's rows of this layer are in LDS
+            if (!helps) {
+#pragma unroll
+                for (int r = 0; r < R; ++r) Jacc[r] += rows[r * 64];
+            }
+        }
+        if (!helps) {
+            gbyte *jrow = jplane + row0;
+            const unsigned off = here(off0);
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                __builtin_nontemporal_store(Jacc[r], (gdouble *)lane_address(jrow, off));
+                jrow += rstep;
+            }
+        }
+    };
+    for (int i = i0;; i += 2) {
+        layer(i, kap_next, kap_odd);
+        if (i == i1) break;
+        layer(i + 1, kap_odd, kap_next);
+        if (i + 1 == i1) break;
+    }
+
+    if (has_i_out) { // p0 is in registers, p0 + 1 + k in slot k
+        // (the lane from lx again: the lane itself is then not kept through the loop)
+        const long i_out = L.iface_off + ((long)((ti + 1) % ns) * vp + R * tv) * up + 64 * tu + ((int)here((unsigned)lx) - shift);
+        for (int j = 0; j < ndir; ++j) {
+            int d = p0 + j;
+            d = d >= ndir ? d - ndir : d;
+            gdouble *f = (gdouble *)(G->dir[d].faces + fnu);
+#pragma unroll
+            for (int r = 0; r < R; ++r) f[i_out + (long)r * up] = j ? state[((j - 1) * R + r) * 64 + lx] : cur[r];
+        }
+    }
+}
+
 // Which XCC ids does this device have?  Every workgroup of a grid large enough to reach every XCD reports the id it reads.
 __global__ void xcc_census_kernel(unsigned *mask)
 {
@@ -858,6 +1052,17 @@ int launch_brick_pair(const BrickLaunch &L, int max_dirs, int waves, int lds_pad
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
+// a stage of seats (L.seats, L.ntasks of them): whole bricks, no emission, a launch per stage, no diagnostic option (BrickOptions::visits)
+int launch_brick_duo(const BrickLaunch &L, int max_dirs, int lds_pad, hipStream_t stream)
+{
+    if (L.ntasks <= 0) return 0;
+    if (max_dirs < 1 || max_dirs > kBrickMaxDirs || !L.seats || lds_pad < 0) return -1;
+    if (L.emit || L.ticket || L.queue || L.tiled || L.atomic_acc || L.ablate || L.sub || L.n % 64 || L.n % kBrickRows || L.n % L.chunk) return -1;
+    const dim3 grid((unsigned)L.ntasks * (unsigned)L.nnu);
+    hipLaunchKernelGGL(brick_duo_kernel, grid, dim3(128), brick_duo_lds(max_dirs, lds_pad), stream, L, max_dirs);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
 // whole bricks, no emission, no dataflow, no diagnostic option: the form whose layer loop has only counted waits (brick_kernel's WHOLE)
 bool brick_whole_form(const BrickLaunch &L, int waves, bool masked)
 {
@@ -867,6 +1072,7 @@ bool brick_whole_form(const BrickLaunch &L, int waves, bool masked)
 int launch_brick(const BrickLaunch &L, int max_dirs, int waves, int lds_pad, hipStream_t stream, bool masked, int persistent)
 {
     if (L.ntasks <= 0) return 0;
+    if (L.seats) return masked || persistent || waves != 4 ? -1 : launch_brick_duo(L, max_dirs, lds_pad, stream); // two passes per visit
     if (max_dirs < 1 || max_dirs > kBrickMaxDirs) return -1;
     if (L.tiled && (L.emit || masked)) return -1; // brick-ordered storage: the emission rows and the cut bricks are addressed in frame order only
     const dim3 grid((unsigned)L.ntasks * (unsigned)L.nnu);

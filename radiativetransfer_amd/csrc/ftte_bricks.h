@@ -40,10 +40,11 @@ struct BrickKey {
     int chunk = 0, gmax = 0, share = 0;        // layers per brick, most directions per group, who shares an accumulator
     int want_dataflow = 0, want_glanes = 0;    // 0 a launch per stage, 1 one launch, 3 persistent workgroups; streams the groups are dealt to
     int nnu = 0, xcc_count = 0, queue_mix = 0; // what the persistent form's queues are cut for (want_dataflow == 3), else 0
+    int duo = 0;                               // 1: two passes of an izone cross a brick in one visit where an izone has two (BrickOptions::visits)
     bool operator==(const BrickKey &o) const
     {
         return n == o.n && box == o.box && chunk == o.chunk && gmax == o.gmax && share == o.share && want_dataflow == o.want_dataflow &&
-               want_glanes == o.want_glanes && nnu == o.nnu && xcc_count == o.xcc_count && queue_mix == o.queue_mix;
+               want_glanes == o.want_glanes && nnu == o.nnu && xcc_count == o.xcc_count && queue_mix == o.queue_mix && duo == o.duo;
     }
 };
 
@@ -91,6 +92,15 @@ struct BrickOptions {
         if (!k.want_dataflow || dataflow != 3 || xcc_count < 1 || xcc_count > kBrickQueues) return;
         k.want_dataflow = 3; k.nnu = nnu; k.xcc_count = xcc_count; k.queue_mix = queue_mix;
     }
+    // Two passes of an izone per visit (brick_duo_kernel), a step of its own like persistent(): only the whole-brick form of the
+    // stage launches has it -- one wavefront per brick, no emission, a launch per stage, passes that share accumulators, a grid
+    // of whole bricks, and a launch with none of the options that form lacks (`plain_launch`: LaunchOptions::plain()).
+    void visits(BrickKey &k, int nnu, int emit_mode, bool plain_launch) const
+    {
+        if (brick_form(nnu, emit_mode) != 0 || emit_mode || k.want_dataflow || k.share < 1 || !plain_launch) return;
+        if (k.n % 64 || k.n % kBrickRows || k.n % k.chunk || k.n / k.chunk >= kBrickLinked) return;
+        k.duo = 1;
+    }
     // The hybrid sweep's base plan: short bricks (the box is widened by one brick on every side, and what lies inside it costs
     // several times a brick's bytes), the group size by the frequency groups alone (the pair form does not sweep it), a launch
     // per stage: its chunk, gmax and share enter HybridOptions::plan_key
@@ -115,9 +125,16 @@ struct BrickPlan {
     int n = 0, chunk = 0;              // cells a side, layers per brick
     std::vector<DirPlan> dirs;
     std::vector<LayerRec> layers;
-    struct Group { int izone = 0, layout = 0, acc = 0, offset = 0, lane = 0; std::vector<int> dirs; };
+    // (partner, helper -- two passes per visit: the pass this one crosses every brick with, or -1; the one of the two that never touches J)
+    struct Group { int izone = 0, layout = 0, acc = 0, offset = 0, lane = 0; std::vector<int> dirs; int partner = -1; bool helper = false; };
     std::vector<Group> groups;
     std::vector<BrickTask> tasks;      // stage after stage
+    // Two passes per visit (key.duo, and an izone with two passes): the passes of an izone linked two by two into visits, a visit where
+    // a pass stands today (one accumulator, one stage offset, one store-or-accumulate bit per brick); each stage's tasks dealt to seats
+    bool duo = false;
+    std::vector<BrickSeat> seats;      // stage after stage, the seats with the most directions first
+    std::vector<size_t> seat_off;      // [glanes][nstages + 1] into seats
+    int nvisits = 0, nlinked = 0;      // visits (passes where nobody is linked); seats that hold a linked visit
     bool dataflow = false;             // one launch, bricks wait for each other through flags (needs whole bricks: n % 64 == 0)
     std::vector<int32_t> deps;         // [tasks][kBrickDeps]
     // persistent form (option "dataflow" = 3): one queue of (task, frequency slot) pairs per XCD, whole dependency chains each
@@ -208,6 +225,7 @@ private:
 struct BrickTables {
     DeviceBuffer<LayerRec> layers; DeviceBuffer<BrickTask> tasks; Sent<BrickGroup> groups;
     DeviceBuffer<int32_t> deps, merge_blocks; DeviceBuffer<uint32_t> queue; // the uniform grid's plan only
+    DeviceBuffer<BrickSeat> seats;                                          // ... with two passes per visit
     bool holds(const BrickPlan &P) const { return held_ != 0 && held_ == P.id; }
     hipError_t upload(const BrickPlan &P)
     {
@@ -218,6 +236,7 @@ struct BrickTables {
         if (P.dataflow && !P.deps.empty() && (e = to_device(deps, P.deps)) != hipSuccess) return e;
         if (!P.merge_blocks.empty() && (e = to_device(merge_blocks, P.merge_blocks)) != hipSuccess) return e;
         if (P.persistent && !P.queue.empty() && (e = to_device(queue, P.queue)) != hipSuccess) return e;
+        if (P.duo && (e = to_device(seats, P.seats)) != hipSuccess) return e;
         held_ = P.id;
         return hipSuccess;
     }

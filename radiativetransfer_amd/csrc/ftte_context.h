@@ -91,7 +91,7 @@ struct ftte_ctx {
 
     DeviceBuffer<double> acc[3][kMaxAcc]; // one size for all of them (accumulator_size)
 
-    int last_brick_form = -1, last_brick_dataflow = -1, last_brick_whole = 0; // of the last uniform-grid sweep of the brick engine (ftte_counter)
+    int last_brick_form = -1, last_brick_dataflow = -1, last_brick_whole = 0, last_brick_duo = 0; // of the last uniform-grid sweep of the brick engine (ftte_counter)
     std::vector<Stream> lane_stream;        // extra streams of the brick sweep (frequency groups are independent)
     std::vector<Event> pipe_up;             // ftte_diffuse_iteration: lane k's opacities have arrived
     std::vector<Event> lane_done;

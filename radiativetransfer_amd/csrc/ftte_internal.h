@@ -1,6 +1,7 @@
 // ftte_internal.h -- records shared by the host planner (ftte_plan.cpp) and the kernels
 // (ftte_kernels.hip).  Plain structs, no HIP types.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 #include "ftte_math.h"
@@ -115,6 +116,15 @@ constexpr int kBrickAccumulate = 0x4000;
 constexpr int kBrickTuMask = 0x3ff, kBrickLaneLoShift = 10, kBrickGroupMask = 0xff, kBrickLaneHiShift = 8;
 constexpr int kBrickTvMask = 0x3ff, kBrickBoxShift = 10, kBrickBoxMask = 31;
 static_assert(sizeof(BrickTask) == 8, "BrickTask must be 8 bytes");
+// A seat of the two-wavefront stage launch (brick_duo_kernel): wavefront w of the workgroup sweeps place[w].  Linked (bit 13 of both
+// places' ti, kBrickLinked): two passes of one izone cross the same brick together, place 0 the owner of the cells' J, place 1 the
+// helper, whose sums reach J through the owner.  Not linked: two tasks that merely share a workgroup, or one and an empty place
+// (group -1).
+struct BrickSeat { BrickTask place[2]; };
+constexpr int kBrickLinked = 0x2000;
+static_assert(sizeof(BrickSeat) == 16, "BrickSeat must be 16 bytes");
+// dynamic LDS of a seat: the pad, each wavefront's parked rays (4 KB per direction but one), the 4 KB a helper's sums cross in
+constexpr size_t brick_duo_lds(int max_dirs, int lds_pad) { return (size_t)lds_pad + 2 * (size_t)(max_dirs - 1) * kBrickRows * 64 * 8 + (size_t)kBrickRows * 64 * 8; }
 
 struct BrickLaunch {
     const BrickGroup *groups;
@@ -166,6 +176,7 @@ struct BrickLaunch {
     // Stage launches (no ticket, no queue): how the launch's workgroups are dealt to (task, frequency slot) pairs, brick_deal below
     // (option "nu_deal"; 0: workgroup b sweeps slot b % nnu of task b / nnu)
     int32_t deal;
+    const BrickSeat *seats;   // two passes per visit (brick_duo_kernel): the stage's seats, `ntasks` of them; `tasks` is then not read
     ftte_consts math;
 };
 

@@ -13,6 +13,9 @@ int launch_sweep(const LaunchRec &L, int rows, int waves, int stack, int nnu, in
 // one stage of the cell-fixed brick sweep; max_dirs: directions of the launch's largest group (sizes the LDS); waves 2..4
 // persistent > 0 (BrickLaunch::queue set): the whole sweep in one launch of that many workgroups, a task queue per XCD
 int launch_brick(const BrickLaunch &L, int max_dirs, int waves, int lds_pad, hipStream_t stream, bool masked = false, int persistent = 0);
+// a stage of a plan with two passes per visit (BrickLaunch::seats): a workgroup of two wavefronts per seat, whole bricks only;
+// launch_brick hands such a launch on to it
+int launch_brick_duo(const BrickLaunch &L, int max_dirs, int lds_pad, hipStream_t stream);
 bool brick_whole_form(const BrickLaunch &L, int waves, bool masked = false); // does launch_brick take brick_kernel's WHOLE form for this launch?
 int launch_xcc_census(unsigned *mask_dev, hipStream_t stream); // bit x of *mask_dev set: some workgroup ran on the XCD whose HW_REG_XCC_ID is x
 int launch_brick_pair(const BrickLaunch &L, int max_dirs, int waves, int lds_pad, hipStream_t stream); // two wavefronts per brick, four rows each

@@ -26,6 +26,8 @@ struct LaunchOptions {
     int merge_overlap = 1;               // brick sweep: J merged block by block as the stages finish the blocks; 0 = one merge after the last stage
     int forest_fuse = 4096;              // levels of a forest with at most this many (segment, group) pairs in one launch (0: a launch per level)
     int lds_pad = 0;                     // diagnostic "ldspad": extra bytes of dynamic LDS per workgroup, to cap residency
+    // nothing set that the whole-brick form of the stage launches lacks (launch_brick; BrickOptions::visits)
+    bool plain() const { return brick_waves == 4 && !atomic_acc && !ablate && !tiled; }
 };
 
 // who sweeps: 0 = the default = 2 = cell-fixed bricks (brick_kernel), 1 = ray-following tiles (sweep_kernel); forest = 1: the

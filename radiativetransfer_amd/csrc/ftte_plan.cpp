@@ -29,6 +29,8 @@ int build_brick_plan(ftte_ctx *c, int ndir, const double *phi, const double *the
         if (rc) return rc;
         c->opt.brick.persistent(key, c->nnu, c->xcc_count);
     }
+    c->opt.brick.visits(key, c->nnu, c->emit_mode, c->opt.launch.plain()); // two passes per visit, where the sweep has the form for it
+
     if (P.valid && P.key == key && same_list(P.phi, phi, ndir) && same_list(P.theta, theta, ndir) && same_list(P.w, w, ndir)) return FTTE_OK;
     ++c->n_plan_builds;
     const long long id = ++c->brick_plans; // (a new plan: no BrickTables holds it)

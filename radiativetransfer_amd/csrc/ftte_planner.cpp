@@ -297,6 +297,75 @@ void deal_group_lanes(BrickPlan &P, int want_glanes)
     }
 }
 
+// Two passes per visit (BrickKey::duo).  The passes of an izone follow each other in P.groups, pass p at stage offset p * step
+// (step 2 where the izone is paired with one of opposite parity).  They are linked two by two, (0, 1), (2, 3), ..., an odd last one
+// stays alone; visit v = p / 2 takes the place pass v has in a plan of single passes: offset v * step, the izone's accumulator.
+// The even pass of a linked visit owns the cells' J, the odd one is its helper.  No izone with two passes: nothing changes.
+void link_visits(BrickPlan &P)
+{
+    const size_t ng = P.groups.size();
+    for (size_t g0 = 0, g1; g0 < ng; g0 = g1) {
+        for (g1 = g0 + 1; g1 < ng && P.groups[g1].izone == P.groups[g0].izone && P.groups[g1].layout == P.groups[g0].layout; ++g1) {}
+        if (g1 - g0 >= 2) P.duo = true;
+    }
+    P.nvisits = (int)ng;
+    if (!P.duo) return;
+    P.nvisits = 0;
+    for (size_t g0 = 0, g1; g0 < ng; g0 = g1) {
+        for (g1 = g0 + 1; g1 < ng && P.groups[g1].izone == P.groups[g0].izone && P.groups[g1].layout == P.groups[g0].layout; ++g1) {}
+        const int step = g1 - g0 >= 2 ? P.groups[g0 + 1].offset - P.groups[g0].offset : 1;
+        for (size_t g = g0; g < g1; ++g) {
+            BrickPlan::Group &G = P.groups[g];
+            const size_t p = g - g0;
+            G.offset = (int)(p / 2) * step;
+            G.helper = p % 2 == 1;
+            G.partner = G.helper ? (int)g - 1 : g + 1 < g1 ? (int)g + 1 : -1;
+            if (!G.helper) ++P.nvisits;
+        }
+    }
+}
+
+// The seats of every stage list of a plan with two passes per visit: a linked visit's two tasks of a brick in one seat, the owner's
+// first; the stage's other tasks two by two in list order (the most directions first), an odd last one with an empty place; then
+// the seats with the most directions first.  A helper's task carries no accumulate bit: it neither stores nor reads J.
+void seat_stage_lists(BrickPlan &P)
+{
+    const size_t nb = (size_t)P.ntu * P.ntv * P.nti;
+    const size_t none = ~(size_t)0;
+    std::vector<size_t> helper_at(P.groups.size() * nb, none); // the helper's task that crosses a brick with its owner's
+    for (size_t q = 0; q < P.tasks.size(); ++q) {
+        BrickTask &T = P.tasks[q];
+        if (!P.groups[(size_t)T.group].helper) continue;
+        T.ti = (int16_t)(T.ti & ~kBrickAccumulate);
+        helper_at[(size_t)T.group * nb + brick_index(P, T.tu, T.tv, T.ti)] = q;
+    }
+    auto ndirs = [&](const BrickTask &T) { return T.group < 0 ? (size_t)0 : P.groups[(size_t)T.group].dirs.size(); };
+    const BrickTask empty{-1, 0, 0, 0};
+    P.seat_off.assign((size_t)P.glanes * ((size_t)P.nstages + 1), 0);
+    for (size_t l = 0; l < (size_t)P.glanes; ++l) {
+        for (size_t st = 0; st < (size_t)P.nstages; ++st) {
+            const size_t q0 = P.stage_off[l * ((size_t)P.nstages + 1) + st], q1 = P.stage_off[l * ((size_t)P.nstages + 1) + st + 1];
+            std::vector<BrickSeat> seats;
+            std::vector<BrickTask> lone;
+            for (size_t q = q0; q < q1; ++q) {
+                const BrickTask &T = P.tasks[q];
+                const BrickPlan::Group &G = P.groups[(size_t)T.group];
+                if (G.helper) continue;
+                if (G.partner < 0) { lone.push_back(T); continue; }
+                BrickTask own = T, help = P.tasks[helper_at[(size_t)G.partner * nb + brick_index(P, T.tu, T.tv, T.ti & (kBrickAccumulate - 1))]];
+                own.ti = (int16_t)(own.ti | kBrickLinked); help.ti = (int16_t)(help.ti | kBrickLinked);
+                seats.push_back(BrickSeat{{own, help}});
+                ++P.nlinked;
+            }
+            for (size_t k = 0; k < lone.size(); k += 2) seats.push_back(BrickSeat{{lone[k], k + 1 < lone.size() ? lone[k + 1] : empty}});
+            std::stable_sort(seats.begin(), seats.end(), [&](const BrickSeat &x, const BrickSeat &y) { return ndirs(x.place[0]) + ndirs(x.place[1]) > ndirs(y.place[0]) + ndirs(y.place[1]); });
+            P.seats.insert(P.seats.end(), seats.begin(), seats.end());
+            P.seat_off[l * ((size_t)P.nstages + 1) + st + 1] = P.seats.size();
+        }
+        if (l + 1 < (size_t)P.glanes) P.seat_off[(l + 1) * ((size_t)P.nstages + 1)] = P.seats.size();
+    }
+}
+
 // Stages: brick (tu, tv, ti) of a group runs in stage tu + tv + ti + the group's offset of its lane.  Fills P.tasks, P.nstages,
 // P.stage_off ([glanes][nstages + 1], the lanes one after the other) and P.updates.
 void write_stage_lists(BrickPlan &P, int ndir)
@@ -471,8 +540,11 @@ int plan_bricks(const BrickInputs &in, BrickPlan &P, std::string *err)
     int rc;
     if ((rc = plan_brick_groups(P, K.n, K.box, in.ndir, in.phi, in.theta, in.w, K.chunk, K.gmax, K.share, K.want_dataflow, false, nullptr, err))) return rc;
     P.key = K;
+    P.nvisits = (int)P.groups.size();
+    if (K.duo) link_visits(P);
     deal_group_lanes(P, K.want_glanes);
     write_stage_lists(P, in.ndir);
+    if (P.duo) seat_stage_lists(P);
     if (P.dataflow && !P.tasks.empty() && (rc = link_dependencies(P, err))) return rc;
     if (!P.dataflow && P.glanes == 1 && !P.tasks.empty()) cut_merge_points(P); // (merge points: stages on one lane of groups)
     if (P.dataflow && K.want_dataflow == 3 && !P.tasks.empty()) deal_queues(P, K.nnu, K.xcc_count, K.queue_mix);

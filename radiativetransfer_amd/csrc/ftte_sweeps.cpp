@@ -537,7 +537,7 @@ int BrickSweep::one_launch()
         FTTE_HIP(c, hipGetDeviceProperties(&prop, c->device));
         persistent = (int)std::min<size_t>((size_t)prop.multiProcessorCount * 16, P.queue.size());
     }
-    c->last_brick_form = 0; c->last_brick_dataflow = P.persistent ? 3 : c->opt.brick.dataflow == 2 ? 2 : 1; c->last_brick_whole = 0;
+    c->last_brick_form = 0; c->last_brick_dataflow = P.persistent ? 3 : c->opt.brick.dataflow == 2 ? 2 : 1; c->last_brick_whole = 0; c->last_brick_duo = 0;
     const int lrc = launch_brick(L, P.max_dirs, O.brick_waves, O.lds_pad, stream, false, persistent);
     if (lrc) return fail(c, lrc == -1 ? FTTE_ERR_ARG : FTTE_ERR_NO_DEVICE, "brick kernel launch failed");
     FTTE_HIP(c, c->bflow.read_back(P, stream));
@@ -567,8 +567,16 @@ int BrickSweep::lane_stages(int lane, LaunchTiming &T)
                 return fail(c, FTTE_ERR_NO_DEVICE, "layout kernel launch failed");
         FTTE_HIP(c, hipEventRecord(T.first[(size_t)lane], q));
     }
+    const size_t *seat_off = P.duo ? &P.seat_off[(size_t)(P.glanes > 1 ? lane : 0) * (nstages + 1)] : nullptr;
     for (size_t st = 0, mp = 0; st < nstages; ++st) {
-        if (off[st + 1] != off[st]) {
+        if (P.duo && seat_off[st + 1] != seat_off[st]) { // two passes per visit: the stage's seats, two wavefronts each
+            BrickLaunch L = launch(off[st], off[st + 1], S.nu0, S.nu1);
+            L.seats = c->btables.seats + seat_off[st]; L.ntasks = (int)(seat_off[st + 1] - seat_off[st]);
+            c->last_brick_form = 0; c->last_brick_dataflow = 0; c->last_brick_whole = 1; c->last_brick_duo = P.nlinked;
+            const int lrc = launch_brick(L, P.max_dirs, O.brick_waves, O.lds_pad, q); // (seats: launch_brick_duo)
+            if (lrc) return fail(c, lrc == -1 ? FTTE_ERR_ARG : FTTE_ERR_NO_DEVICE, "brick kernel launch failed");
+        } else if (!P.duo && off[st + 1] != off[st]) {
+            c->last_brick_duo = 0;
             const BrickLaunch L = launch(off[st], off[st + 1], S.nu0, S.nu1);
             const int form = c->opt.brick.brick_form(nnu, c->emit_mode);
             c->last_brick_form = form; c->last_brick_dataflow = 0; c->last_brick_whole = form != 2 && brick_whole_form(L, O.brick_waves);
