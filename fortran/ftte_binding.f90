@@ -745,6 +745,36 @@ module ftte_binding
        integer(c_int32_t), intent(out) :: per_leaf(*) ! (ncell)
      end function ftte_get_subcycles
 
+     ! ---- diffuse recombination radiation (the build's own; include/ftte.h) -----------------------------------------------------
+     ! g(nratec, 3): the coefficients of recombination to the ground states of HI, HeI, HeII on the rate coefficients' temperature grid
+     integer(c_int) function ftte_set_ground_recombination(ctx, nratec, g) bind(C, name='ftte_set_ground_recombination')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: nratec
+       real(c_double), intent(in) :: g(*)          ! (nratec, 3)
+     end function ftte_set_ground_recombination
+
+     ! the source function of every leaf from the device-resident gas state, into the context's emission field: the next sweep
+     ! carries it.  S: c_loc of a host array (ncell, 3), or c_null_ptr; lost: c_loc of an integer(c_int64_t), or c_null_ptr
+     integer(c_int) function ftte_recombination_source(ctx, ksi, share, S, lost) bind(C, name='ftte_recombination_source')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       real(c_double), intent(in) :: ksi(3,3)      ! (ksi24, ksi25, ksi26) x (group1, group2, group3)
+       real(c_double), intent(in) :: share(3,3)    ! (group1, group2, group3) x (HII, HeII, HeIII recombining)
+       type(c_ptr), value :: S
+       type(c_ptr), value :: lost
+     end function ftte_recombination_source
+
+     integer(c_int) function ftte_recombination_source_device(ctx, ksi, share, S_dev, lost) &
+          bind(C, name='ftte_recombination_source_device')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       real(c_double), intent(in) :: ksi(3,3)
+       real(c_double), intent(in) :: share(3,3)
+       type(c_ptr), value :: S_dev
+       type(c_ptr), value :: lost
+     end function ftte_recombination_source_device
+
   end interface
 
 contains

@@ -455,6 +455,40 @@ int ftte_advance_thermochemistry_device(ftte_ctx *ctx, double dt_s, double eta, 
 /* per_leaf[ncell]: the subcycles each leaf took in the last ftte_advance_thermochemistry* that got through on this grid;
  * FTTE_ERR_STATE before any */
 int ftte_get_subcycles(ftte_ctx *ctx, int32_t *per_leaf);
+
+/* ---- diffuse recombination radiation: a source function from the gas state (csrc/ftte_recombination_math.h) -----------------
+ *
+ * The build's own (the reference's emissivity is hard-wired to zero, transportRoutinesModule.f90:673-675): recombinations to
+ * the ground states of HI, HeI, HeII emit ionising photons, and one pass over the leaves turns the device-resident gas state into
+ * the source function the sweep carries.  Per leaf, with the species clipped to the elements' budgets as ftte_advance_rate_equations
+ * clips them, HII = nh - HI, HeIII = nhe - HeI - HeII, de = HII + HeII + 2 HeIII and g[0..2] interpolated at the leaf's stored
+ * logarithm of the temperature as the rate coefficients are:
+ *   R = g de (HII, HeII, HeIII)                                        recombinations to ground per volume and second
+ *   E[j] = share[0][j] R[0] + share[1][j] R[1] + share[2][j] R[2]      photons emitted into group j
+ *   D[0] = HI ksi[0][0],  D[1] = HI ksi[1][0] + HeI ksi[1][2],  D[2] = HI ksi[2][0] + HeII ksi[2][1] + HeI ksi[2][2]
+ *   S[j] = E[j] / (4 pi D[j]),  0 where D[j] == 0
+ * D is the leaf's photon capture per unit 4 pi J as ftte_solve_rate_equations evaluates it, so a leaf bathed in J = S re-absorbs
+ * exactly E[j]: photon number is conserved against the chemistry, whatever the mix of absorbers.  A (leaf, group) with E > 0 and
+ * D == 0 is "lost": nothing there absorbs the group, so the sweep's S (1 - exp(-tau)) cannot emit it. */
+
+/* g[3][nratec]: the coefficients of recombination to the ground states of HI, HeI, HeII [cm^3/s] on the temperature grid of
+ * ftte_set_rate_coefficients.  FTTE_ERR_STATE before that call; FTTE_ERR_ARG unless nratec is that call's, or if an entry is
+ * negative or not finite.  Another nratec there drops this table, as it drops the cooling coefficients. */
+int ftte_set_ground_recombination(ftte_ctx *ctx, int nratec, const double *g);
+/* The source function of every leaf, written straight into the context's emission field in cell-array order; on success the next
+ * sweep runs with it, on uniform grids, refined grids and with every option, exactly as after ftte_set_source_function_device with
+ * the same values.  ksi[3][3] = [group][ksi24, ksi25, ksi26] of ftte_uvb_beta_table; share[3][3] = [ion][group], every entry in
+ * [0, 1] and every row sum <= 1 (else FTTE_ERR_ARG).  S[3][ncell] (host; S_dev: device) receives a copy and may be NULL; *lost
+ * the count of lost (leaf, group) pairs, may be NULL.
+ * FTTE_ERR_STATE, the text naming the missing call, before ftte_set_grid, ftte_set_medium with rho, ftte_set_temperature,
+ * ftte_set_rate_coefficients, ftte_set_ground_recombination, or opacities with nnu == 3 (they size the emission field).
+ * FTTE_ERR_RATES, the first such leaf named, where a density is not positive and finite or an electron density or an S is not
+ * finite; the emission state is then what it was.  How: while no emission is in force the pass writes the field's own buffer,
+ * which nothing reads, and emission is switched on only once no leaf has failed (a time loop that switches emission off after each
+ * step's sweep, ftte_set_source_function(ctx, NULL), always takes this way); while one is in force the pass writes a buffer of its
+ * own, which is copied into the field only once no leaf has failed. */
+int ftte_recombination_source(ftte_ctx *ctx, const double *ksi, const double *share, double *S, int64_t *lost);
+int ftte_recombination_source_device(ftte_ctx *ctx, const double *ksi, const double *share, double *S_dev, int64_t *lost);
 /* HI, HeI, HeII of the device-resident medium, ncell each */
 int ftte_get_medium(ftte_ctx *ctx, double *HI, double *HeI, double *HeII);
 /* computeOpacities (equiSources.f90:4956-4983) on the device-resident medium: kappa[g] = HI beta[0][g] + HeI beta[1][g] +

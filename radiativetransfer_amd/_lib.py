@@ -100,6 +100,9 @@ SIGNATURES = {
     "ftte_advance_thermochemistry_device": (C.c_int, [_vp, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, _vp, _dp,
                                                       _dp, _dp, _dp, C.c_double, C.c_int, _dp, C.POINTER(C.c_int64)]),
     "ftte_get_subcycles": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
+    "ftte_set_ground_recombination": (C.c_int, [_vp, C.c_int, _dp]),
+    "ftte_recombination_source": (C.c_int, [_vp, _dp, _dp, _dp, C.POINTER(C.c_int64)]),
+    "ftte_recombination_source_device": (C.c_int, [_vp, _dp, _dp, _vp, C.POINTER(C.c_int64)]),
     "ftte_cooling_coefficient_tables": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, _dp, _dp, _dp, _dp]),
     "ftte_rate_equation_steps": (C.c_longlong, [_vp]),
     "ftte_initial_ionization_equilibrium": (C.c_int, [_vp, _dp, C.c_double, C.c_int, _dp]),

@@ -373,6 +373,22 @@ def cooling_coefficient_tables(nratec: int = 5000, temstart: float = 1.0, temend
     return c, compa.value
 
 
+def ground_recombination_tables(nratec: int = 5000, temstart: float = 1.0, temend: Optional[float] = None) -> np.ndarray:
+    """g[3][nratec], the argument of StellarTransfer.set_ground_recombination: the coefficients of recombination to the ground
+    states of HI, HeI, HeII on the temperature grid of rate_coefficient_tables, as the difference of the case-A and the case-B fit,
+    max(k_A - k_B, 0).  Rows 0 and 2: of k2 and k6.  Row 1: of the RADIATIVE part of k4 alone, coll_rates' case-A
+    3.92e-13 / T_eV**0.6353 without the dielectronic term it adds above 0.8 eV -- dielectronic recombination passes through an
+    autoionising state and emits no ground-state continuum, and above 1e5 K it would make k4_A - k4_B 15 to 150 times k4_B.  This is
+    the build's own choice, not the reference's, which enables no emission and has no such table."""
+    temend = float(np.float32(1.0e8)) if temend is None else float(temend)
+    ka, logtem0, _, dlogtem = rate_coefficient_tables(nratec, temstart, temend, 1)
+    kb = rate_coefficient_tables(nratec, temstart, temend, 2)[0]
+    # the tables' temperature nodes (calc_rates.f:324-326) in eV as coll_rates takes them, its literals default-real
+    t_ev = np.exp(logtem0 + np.arange(nratec).astype(np.float32).astype(np.float64) * dlogtem) / float(np.float32(11605.0))
+    k4_radiative = float(np.float32(3.92e-13)) / t_ev ** float(np.float32(0.6353))
+    return np.maximum(np.stack([ka[1] - kb[1], k4_radiative - kb[3], ka[5] - kb[5]]), 0.0)
+
+
 def uniform_table(alpha_quasar: float, alpha_stellar: float, nfreq: int = 400, freqdel: Optional[float] = None):
     """uniformTable (uniformTable.f90): (ksi[2][3], gamma[2][3]) of the quasar and the stellar power-law component."""
     ksi, gamma = np.empty((2, 3)), np.empty((2, 3))
@@ -765,6 +781,35 @@ class StellarTransfer(DiffuseTransfer):
         out = np.empty(max(self.ncell, 1), dtype=np.int32)
         self._ok(self._lib.ftte_get_subcycles(self._ctx, out.ctypes.data_as(C.POINTER(C.c_int32))))
         return out
+
+    # -- diffuse recombination radiation: a source function from the gas state (csrc/ftte_recombination_math.h)
+    def set_ground_recombination(self, g):
+        """g[3][nratec] of ground_recombination_tables (or the caller's own): the coefficients of recombination to the ground states
+        of HI, HeI, HeII on the temperature grid of set_rate_coefficients (call that first)."""
+        g = _f64(g)
+        if g.ndim != 2 or g.shape[0] != 3:
+            raise ValueError("g must have shape [3][nratec]")
+        self._ok(self._lib.ftte_set_ground_recombination(self._ctx, g.shape[1], _dp(g)))
+
+    def _recombination(self, fn, ksi, share, S):
+        ksi, share = _f64(ksi).reshape(3, 3), _f64(share).reshape(3, 3)
+        lost = C.c_int64()
+        self._ok(fn(self._ctx, _dp(ksi), _dp(share), S, C.byref(lost)))
+        return int(lost.value)
+
+    def recombination_source(self, ksi, share, want_S: bool = True):
+        """The source function of the ground-state recombination photons from the device-resident gas state, written into the
+        context's emission field: the next transport carries it, exactly as after set_source_function with the same values.
+        ksi[3][3] = [group][ksi24, ksi25, ksi26]; share[3][3] = [ion HII, HeII, HeIII recombining][group], entries in [0, 1], row
+        sums <= 1.  Needs the medium with rho, the temperature, the rate coefficients, set_ground_recombination and opacities in
+        three groups.  Returns (S[3][ncell] or None, lost): lost counts the (leaf, group) pairs that emit where nothing absorbs."""
+        S = np.empty((3, max(self.ncell, 1))) if want_S else None
+        lost = self._recombination(self._lib.ftte_recombination_source, ksi, share, None if S is None else _dp(S))
+        return S, lost
+
+    def recombination_source_device(self, ksi, share, s_device_ptr: int = 0) -> int:
+        """Same; a copy of S[3][ncell] goes to device memory at s_device_ptr unless that is 0.  Returns lost."""
+        return self._recombination(self._lib.ftte_recombination_source_device, ksi, share, C.c_void_p(s_device_ptr) if s_device_ptr else None)
 
     def medium(self):
         out = [np.empty(max(self.ncell, 1)) for _ in range(3)]

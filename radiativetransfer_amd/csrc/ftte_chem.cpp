@@ -136,7 +136,7 @@ int ftte_set_rate_coefficients(ftte_ctx *c, int nratec, double logtem0, double l
     ChemState &K = c->chem;
     FTTE_HIP(c, hipSetDevice(c->device));
     FTTE_HIP(c, hipStreamSynchronize(c->stream));
-    if (K.nratec != nratec) { K.k.reset(); K.cool.reset(); } // (the cooling coefficients share the temperature grid)
+    if (K.nratec != nratec) { K.k.reset(); K.cool.reset(); K.ground.reset(); } // (the cooling and the ground-state coefficients share the temperature grid)
     FTTE_HIP(c, K.k.reserve(6 * (size_t)nratec));
     const double *src[6] = {k1a, k2a, k3a, k4a, k5a, k6a};
     for (int r = 0; r < 6; ++r)

@@ -102,11 +102,16 @@ struct ChemState {
     // the buffer the kernel writes them into (copied in, like `out`, once no leaf has failed)
     DeviceBuffer<int32_t> subcycles, subcycles_out;
     bool subcycles_set = false;
+    // the diffuse recombination source (ftte_recombination.cpp): the ground-state recombination coefficients [3][nratec] on the rate
+    // coefficients' temperature grid, the pass's two words (first bad leaf, lost (leaf, group) pairs), and S [3][ncell] on its way
+    // into an emission field whose contents are in force
+    DeviceBuffer<double> ground, ground_out;
+    DeviceBuffer<unsigned long long> ground_words;
 
     void drop_grid() // after ftte_set_grid: what is sized by the old grid; the rate and cooling coefficients stay
     {
         level.reset(); logtem.reset(); out.reset(); J.reset(); leaf_pos.reset(); tgas.reset(); hydro.reset();
-        subcycles.reset(); subcycles_out.reset();
+        subcycles.reset(); subcycles_out.reset(); ground_out.reset();
         leaf_node.clear();
         temperature_set = hydro_set = subcycles_set = false;
     }
