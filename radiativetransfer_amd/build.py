@@ -16,9 +16,9 @@ import sys
 PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libftte.so")
-SOURCES = ["ftte_kernels.hip", "ftte_chem.hip", "ftte_thermal.hip", "ftte_thermochem.hip", "ftte_recombination.hip", "ftte_recombination.cpp", "ftte_brick.hip", "ftte_lambda.hip", "ftte_expansion.hip", "ftte_catalogue.hip", "ftte_catalogue.cpp", "ftte_analysis.hip", "ftte_analysis.cpp", "ftte_lambda_host.cpp", "ftte_api.cpp", "ftte_chem.cpp", "ftte_leaf_pass.cpp", "ftte_plan.cpp", "ftte_planner.cpp", "ftte_sweeps.cpp", "ftte_hybrid.cpp", "ftte_multi.cpp", "ftte_host_arrays.cpp",
+# the two long compiles first: the pool starts them at once
+SOURCES = ["ftte_tile.hip", "ftte_brick.hip", "ftte_layout.hip", "ftte_forest.hip", "ftte_point.hip", "ftte_chem.hip", "ftte_thermal.hip", "ftte_thermochem.hip", "ftte_recombination.hip", "ftte_recombination.cpp", "ftte_lambda.hip", "ftte_expansion.hip", "ftte_catalogue.hip", "ftte_catalogue.cpp", "ftte_analysis.hip", "ftte_analysis.cpp", "ftte_lambda_host.cpp", "ftte_api.cpp", "ftte_chem.cpp", "ftte_leaf_pass.cpp", "ftte_plan.cpp", "ftte_planner.cpp", "ftte_sweeps.cpp", "ftte_hybrid.cpp", "ftte_multi.cpp", "ftte_host_arrays.cpp",
            "ftte_geometry.cpp", "ftte_amr.cpp", "ftte_point.cpp", "ftte_tables.cpp", "ftte_ingest.cpp"]
-HEADERS = ["ftte.map", "ftte_bricks.h", "ftte_context.h", "ftte_device.h", "ftte_forests.h", "ftte_host.h", "ftte_hybrid.h", "ftte_gas.h", "ftte_expansion.h", "ftte_catalogue.h", "ftte_star_catalogue.h", "ftte_analysis.h", "ftte_tree_sum.h", "ftte_medium.h", "ftte_options.h", "ftte_internal.h", "ftte_kernels.h", "ftte_lambda.h", "ftte_geometry.h", "ftte_math.h", "ftte_chem_math.h", "ftte_thermal_math.h", "ftte_leaf.h", "ftte_thermochem_math.h", "ftte_recombination.h", "ftte_recombination_math.h", "ftte_amr.h", "ftte_point.h", "ftte_tables.h", "ftte_device_tree.h", "ftte_tiles.h", os.path.join("..", "..", "include", "ftte.h")]
 # -ffp-contract=off: the sweep arithmetic spells out its fused multiply-adds (ftte_math.h); nothing else may be fused,
 # so that the device rounds exactly like the host evaluation the parity tests compare against.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-gpu-rdc", "-Wall"]
@@ -45,10 +45,14 @@ def includes(path: str, seen=None) -> set:
 
 
 def stale() -> bool:
+    """Is the library older than a source, a header one of them includes, the version script or this script?"""
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [os.path.abspath(__file__)]
+    deps = {os.path.join(CSRC, "ftte.map"), os.path.abspath(__file__)}
+    for s in SOURCES:
+        deps.add(os.path.join(CSRC, s))
+        includes(os.path.join(CSRC, s), deps)
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -83,7 +83,7 @@ int sub_layer_patterns(const ftte_pattern &pp, double phi, double theta, ftte_pa
 
 namespace {
 
-constexpr int kBrickRowsHost = 8; // kBrickRows of ftte_internal.h
+constexpr int kBrickRowsHost = 8; // kBrickRows of ftte_brick_rec.h
 
 struct PatNode {
     ftte_pattern p;

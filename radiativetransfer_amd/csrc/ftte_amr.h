@@ -7,7 +7,7 @@
 // coarser one that has no segment ending on that face, :612-634) from the mean of two segments of that leaf.
 // The planner walks the tree once per direction in the reference's sweep order, resolves those links with
 // the reference's rules, and orders the segments by their depth in the forest.  The device then processes one
-// depth after the other (ftte_kernels.hip: amr_level_kernel), every segment of a depth in parallel.
+// depth after the other (ftte_forest.hip: amr_level_kernel), every segment of a depth in parallel.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -35,7 +35,7 @@ struct AmrTree {
 };
 
 // A box of base cells in the sweep frame of one izone (1-based, inclusive; i = march axis, j, k) to which a forest can be
-// restricted, and where the rays that cross its surface live in the face buffers of the brick sweep (ftte_internal.h:
+// restricted, and where the rays that cross its surface live in the face buffers of the brick sweep (ftte_brick_rec.h:
 // BrickLaunch).  Hybrid sweep of a refined cell array: the bricks outside the box are swept by the brick kernel, the box --
 // every refined cell plus a rim of unrefined base cells, so that its surface separates unrefined base cells only -- by the forest.
 struct ForestRegion {

@@ -8,7 +8,7 @@
 #include <cstdint>
 
 #include "ftte_device.h"
-#include "ftte_internal.h"
+#include "ftte_node_rec.h"
 
 namespace ftte {
 

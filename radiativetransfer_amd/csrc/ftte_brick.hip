@@ -1,13 +1,13 @@
 // ftte_brick.hip -- the cell-fixed brick organisation of the uniform-grid diffuse sweep (CDNA4, gfx950).
 //
-// Same computation as ftte::sweep_kernel (ftte_kernels.hip): the reference's cell transfer,
+// Same computation as ftte::sweep_kernel (ftte_tile.hip): the reference's cell transfer,
 //   transportRoutinesModule.f90:587-961  /  equiSources.f90:1580-1788,
 // same segment arithmetic (ftte_math.h), organised so that the directions of one izone share every opacity load and
 // every J store, and no cell is computed twice.
 #include <hip/hip_runtime.h>
 
-#include "ftte_internal.h"
-#include "ftte_kernels.h"
+#include "ftte_brick_rec.h"
+#include "ftte_layer_rec.h"
 #include "ftte_math.h"
 
 namespace ftte {
@@ -53,7 +53,7 @@ __device__ __forceinline__ void load_rows(double (&dst)[ROWS], gcbyte *row, unsi
 }
 
 // ------------------------------------------------------------------------------------------------
-// Cell-fixed bricks (ftte_internal.h: BrickGroup, BrickTask, BrickLaunch).
+// Cell-fixed bricks (ftte_brick_rec.h: BrickGroup, BrickTask, BrickLaunch).
 //
 // The tile kernel above follows the rays: a wave's cells drift with its direction, so nothing can be shared between
 // directions and every update costs a kappa load and a J read-modify-write of its own (24 B), plus a recomputed halo.
@@ -370,7 +370,7 @@ __global__ void __launch_bounds__(64, WAVES) brick_kernel(const BrickLaunch L)
     const bool has_v_in = (tv > 0 || sub) && !(ablate & 1), has_v_out = (R * (tv + 1) < n || sub) && !(ablate & 2);
     const bool has_i_in = (ti > 0 || sub) && !(ablate & 8), has_i_out = (i1 < n || sub) && !(ablate & 8);
     const long fnu = (long)nu * L.face_stride;
-    // element offsets inside a direction's face block (ftte_internal.h)
+    // element offsets inside a direction's face block (ftte_brick_rec.h)
     const int uw = L.uw, ut = L.ut;
     const int ns = L.nslot, sl = ti % ns;
     // masked bricks: lanes that end inside the brick hand their rays to the near u-face of the box there (ring 2 * box at

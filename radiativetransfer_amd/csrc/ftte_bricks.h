@@ -15,8 +15,9 @@
 #include <vector>
 
 #include "../../include/ftte.h"
+#include "ftte_brick_rec.h"
 #include "ftte_device.h"
-#include "ftte_internal.h"
+#include "ftte_layout.h"
 
 namespace ftte {
 

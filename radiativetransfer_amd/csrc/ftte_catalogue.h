@@ -23,7 +23,7 @@ constexpr int kCatRounds = 4;            // leaves per thread of the compaction,
 constexpr int kCatTile = kCatGroup * kCatRounds; // leaves of a compaction workgroup
 constexpr int32_t kCatNoStar = 0x7fffffff;       // `first` of a leaf without a star of weight > 0
 
-// What star_locate_kernel reads and writes.  Node is NodeRec (ftte_internal.h): child0, leaf.
+// What star_locate_kernel reads and writes.  Node is NodeRec (ftte_node_rec.h): child0, leaf.
 template <class Node> struct LocateRecT {
     const double *xyz;        // [nstars][3], the units of lo / hi
     const int32_t *weight;    // [nstars] >= 0, or nullptr: 1 each

@@ -14,7 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ftte_catalogue.h"
-#include "ftte_internal.h"
+#include "ftte_node_rec.h"
 
 namespace ftte {
 

@@ -5,8 +5,8 @@
 // leaf's stores, and then the fold of its statistics (all of ftte_leaf.h).
 #include <hip/hip_runtime.h>
 
+#include "ftte_chem.h"
 #include "ftte_chem_math.h"
-#include "ftte_kernels.h"
 #include "ftte_leaf.h"
 #include "ftte_tree_sum.h"
 

@@ -33,17 +33,22 @@
 #include "../../include/ftte.h"
 #include "ftte_amr.h"
 #include "ftte_analysis.h"
+#include "ftte_brick_rec.h"
 #include "ftte_bricks.h"
+#include "ftte_chem.h"
+#include "ftte_forest_rec.h"
 #include "ftte_gas.h"
 #include "ftte_geometry.h"
 #include "ftte_host.h"
 #include "ftte_hybrid.h"
-#include "ftte_kernels.h"
 #include "ftte_lambda.h"
+#include "ftte_layout.h"
 #include "ftte_medium.h"
 #include "ftte_options.h"
 #include "ftte_point.h"
+#include "ftte_point_rec.h"
 #include "ftte_star_catalogue.h"
+#include "ftte_tile_rec.h"
 #include "ftte_tiles.h"
 
 

@@ -9,7 +9,7 @@
 
 #include "ftte_amr.h"
 #include "ftte_device.h"
-#include "ftte_internal.h"
+#include "ftte_forest_rec.h"
 
 namespace ftte {
 

@@ -7,8 +7,8 @@
 
 #include <cstdint>
 
-#include "ftte_internal.h"
 #include "ftte_math.h"
+#include "ftte_point_rec.h"
 
 namespace ftte {
 

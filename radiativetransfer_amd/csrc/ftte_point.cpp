@@ -5,7 +5,7 @@
 #include <cstring>
 
 #include "ftte_chem_math.h"
-#include "ftte_kernels.h"
+#include "ftte_point_rec.h"
 
 namespace ftte {
 

@@ -15,7 +15,7 @@
 #include "ftte_device.h"
 #include "ftte_device_tree.h"
 #include "ftte_gas.h"
-#include "ftte_internal.h"
+#include "ftte_point_rec.h"
 #include "ftte_tables.h"
 
 namespace ftte {

@@ -1,10 +1,9 @@
 // ftte_tables.h -- the reference's table mathematics on the host: the dust and photoionisation cross-sections, the stellar
 // spectra, the background's group tables, the collisional rate coefficients, the frequency grid and the bins of a population, the
-// output cross-sections, the pixel directions and rmax.  Plain C++: no HIP, nothing of the context.  Every expression keeps the
-// reference's operation order; the CPU tests pin the results bit for bit (tests/test_abi_and_host.py).
+// output cross-sections, the pixel directions and rmax, with the sizes of the tables and FreqBin.  Plain C++: no HIP, nothing of
+// the context.  Every expression keeps the reference's operation order; the CPU tests pin the results bit for bit
+// (tests/test_abi_and_host.py).
 #pragma once
-
-#include "ftte_internal.h"
 
 namespace ftte {
 
@@ -13,6 +12,24 @@ constexpr int kFrequencies = 400; // nfreq, stellarBetaTable.f90:14
 // precision (W() in ftte_tables.cpp).
 constexpr double kSigmaDustThreshold = (double)5.4116737e-22f;            // what the tabulated dust depth is counted in
 constexpr double kKpc = (double)1.e3f * (double)3.08568025e18f;           // definitionsModule.f90:21-22 [cm]
+
+// the rate tables of a population, the tracer's pixels, the escape record of a star
+constexpr int kTableDepths = 11;                    // ndepth + 1, definitionsModule.f90:72
+constexpr int kTableSize = 11 * 11 * 11 * 11;       // one rate table
+constexpr int kMaxPixelLevel = 6;                   // localDefinitions, equiSources.f90:9
+constexpr int kPixelCount = 12 * (4096 - 1) / 3;    // pixels of levels 1..6: 12 (4^6 - 1)/3 = 16380
+constexpr int kOutputRadii = 7;                     // nradius, equiSources.f90:9
+constexpr int kOutputEnergies = 300;                // nenergy, definitionsModule.f90:290
+// one star's escape bookkeeping (startNewLongRay, equiSources.f90:3198-3233, 3336-3345): ndotRemaining[7], ndotBoundary[7],
+// ndotDust, ndotSpectrum[300]
+constexpr int kEscapeRec = 2 * kOutputRadii + 1 + kOutputEnergies;
+
+// One frequency bin of stellarBetaTable as the table kernel needs it
+struct FreqBin {
+    double dtmp;                 // photons/s in the bin
+    double r24, r26, r25, rdust; // sigma(nu)/sigma(threshold) per absorber: multiplies the tabulated depth
+    double excess[3];            // (nu - nu_threshold) in erg, per reaction; < 0: below threshold, bin does not count
+};
 
 // The three photoionisation cross-sections at nu [eV], zero at and below each threshold: 24 the hydrogenic HI form, 25 the
 // hydrogenic HeII form (stellarBetaTable.f90:40-44, :52-56), 26 the HeI fit (:46-50)

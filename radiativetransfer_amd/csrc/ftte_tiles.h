@@ -4,6 +4,8 @@
 #pragma once
 
 #include "ftte_bricks.h"
+#include "ftte_layer_rec.h"
+#include "ftte_tile_rec.h"
 
 namespace ftte {
 

@@ -1,4 +1,4 @@
-// brick_deal (ftte_internal.h) on the CPU: which (task, frequency slot) pair each workgroup of a stage launch sweeps.
+// brick_deal (ftte_brick_rec.h) on the CPU: which (task, frequency slot) pair each workgroup of a stage launch sweeps.
 // For nnu = 1..16, run lengths 0, 1, 4, 16 and task counts from 1 to 1000:
 //   every (task, slot) pair is swept by exactly one workgroup;
 //   for a run length >= 1, among the workgroups of one class `work % kXcds` (one XCD under round-robin placement) the counts of
@@ -8,7 +8,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "ftte_internal.h"
+#include "ftte_brick_rec.h"
 
 using namespace ftte;
 

@@ -1,15 +1,15 @@
-// device_model.cpp -- host definitions of the launches of ftte_kernels.h that the sweeps of a refined cell array reach
+// device_model.cpp -- host definitions of the launches (ftte_*_rec.h, ftte_layout.h) that the sweeps of a refined cell array reach
 // (ftte_sweeps.cpp: forest_sweep; ftte_hybrid.cpp: hybrid_sweep), for programs that link those sources against the stub of the HIP
 // runtime (tests/host/stub): "device" memory is malloc there, so under the address sanitizer every index the host code hands to
 // the device becomes a checked access.
 //
 // The launches for the forests and the medium copies are serial loops over the (thread -> element) mapping of their kernels
-// (ftte_kernels.hip), with the arithmetic of ftte_math.h: they dereference the addresses the kernels dereference.
+// (ftte_forest.hip, ftte_layout.hip), with the arithmetic of ftte_math.h: they dereference the addresses the kernels dereference.
 //
 // launch_brick is NOT a transcription of the brick kernel.  It is an oracle brick: the program that drives the model has evaluated
 // the whole tree direction by direction (model::DirOracle), and for every task, direction and frequency group of a launch the
 // oracle brick
-//  * reads every face element the kernel takes rays from (u_in, v_in, i_in at the offsets of BrickLaunch, ftte_internal.h) and
+//  * reads every face element the kernel takes rays from (u_in, v_in, i_in at the offsets of BrickLaunch, ftte_brick_rec.h) and
 //    requires it to hold, bit for bit, the oracle's incoming intensity of the cell that receives it;
 //  * writes the oracle's value into every face element the kernel hands rays on through (u_out, v_out, i_out);
 //  * adds the oracle's cell means into the accumulator at the address the kernel forms from the group record.
@@ -380,7 +380,7 @@ int launch_brick(const BrickLaunch &L, int max_dirs, int, int, hipStream_t, bool
         const bool has_u_in = tu > 0 || lane_lo > 0 || sub, has_u_out = 64 * (tu + 1) < n || lane_hi < 63 || sub;
         const bool has_v_in = tv > 0 || sub, has_v_out = R * (tv + 1) < n || sub;
         const bool has_i_in = ti > 0 || sub, has_i_out = i1 < n || sub;
-        // element offsets inside a direction's face block (BrickLaunch, ftte_internal.h)
+        // element offsets inside a direction's face block (BrickLaunch, ftte_brick_rec.h)
         const int64_t u_out = lane_hi < 63 ? L.uqface_off + ((int64_t)((2 * box) * ns + sl) * chunk) * uw + ut * tv : ((int64_t)(tu * ns + sl) * chunk) * uw + ut * tv;
         const int64_t u_in = lane_lo > 0 ? L.uqface_off + ((int64_t)((2 * box + 1) * ns + sl) * chunk) * uw + ut * tv
                                          : ((int64_t)((tu > 0 ? tu - 1 : up / 64) * ns + sl) * chunk) * uw + ut * tv;

@@ -1,4 +1,4 @@
-// device_model.h -- what tests/host/device_model.cpp (host definitions of the launches of ftte_kernels.h that the refined-grid sweeps
+// device_model.h -- what tests/host/device_model.cpp (host definitions of the launches, ftte_*_rec.h and ftte_layout.h, that the refined-grid sweeps
 // reach) shares with the program that drives it: the oracle's per-direction values that the oracle brick reads and writes, the
 // patterns the face block and the scratch are poisoned with, and the record of what the model found.  tests/host/ only.
 #pragma once

@@ -8,7 +8,7 @@
 #include <string>
 #include <vector>
 
-#include "ftte_kernels.h"
+#include "ftte_point_rec.h"
 #include "ftte_point.h"
 
 using namespace ftte;

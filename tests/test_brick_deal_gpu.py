@@ -1,4 +1,4 @@
-"""Option "nu_deal" of the brick sweep (brick_deal, csrc/ftte_internal.h): which workgroup of a stage launch sweeps which (brick,
+"""Option "nu_deal" of the brick sweep (brick_deal, csrc/ftte_brick_rec.h): which workgroup of a stage launch sweeps which (brick,
 frequency group) pair.  It decides where work runs, never what is computed: every pair is still swept once, with the same inputs
 and the same store-or-accumulate bit, so J with run lengths 1 and 16 is BYTE FOR BYTE the J of run length 0 (the placement
 `work % nnu`), and for a single direction all three are the oracle's bits (device arithmetic), as in test_brick_gpu.py.

@@ -1,6 +1,10 @@
 """Where the brick sweep's layer loop waits: the gfx950 code of one brick_kernel instance, from the compiler.
 
     python tools/brick_isa.py [--source FILE] [--kernel NAME] [--json]
+    python tools/brick_isa.py [--source FILE] --compare OTHER.s
+
+--compare: is the device code of FILE (a .hip unit, or assembly kept as .s; several units' assembly may stand in one file) the
+same, kernel by kernel, as that of OTHER.s?  Exit status 1 if anything differs.
 
 Compiles csrc/ftte_brick.hip (or FILE) with the library's FLAGS (radiativetransfer_amd/build.py) to gfx950 assembly, finds the
 instance `bench.py` runs (launch_brick: brick_kernel<4, 0, 0, false, true>, or brick_kernel<4, 0, 0, false> in a tree that
@@ -36,6 +40,30 @@ def compile_asm(source: str) -> str:
         cmd = [build.hipcc(), *build.FLAGS, "-x", "hip", "--cuda-device-only", "-S", source, "-o", out]
         subprocess.run(cmd, check=True, capture_output=True, text=True)
         return open(out).read()
+
+
+def compare(asm: str, other: str) -> list[str]:
+    """What differs between two assemblies, kernel by kernel: the names, each body from its label to its .Lfunc_end without comment,
+    debug and .loc lines and without the function number in local labels (.LBB12_3 -> .LBB_3), and each metadata record.  Either
+    side may be several units' assembly one after the other.  Text only: no instruction is looked for."""
+    def kernels(text):
+        out = {}
+        for name in re.findall(r"\.symbol:\s+(\S+)\.kd", text):
+            start = text.index("\n" + name + ":")
+            body = text[start:text.index(".Lfunc_end", start)].split("\n")
+            body = [re.sub(r"\.L([A-Za-z]+)\d+_", r".L\1_", ln.split(";")[0].rstrip()) for ln in body
+                    if not re.match(r"^\s*(;|\.loc\s|\.file\s|\.Ltmp|\.cfi_|$)", ln)]
+            out[name] = ("\n".join(body), metadata(text, name))
+        return out
+    a, b = kernels(asm), kernels(other)
+    diffs = [f"only here: {n}" for n in sorted(set(a) - set(b))] + [f"only there: {n}" for n in sorted(set(b) - set(a))]
+    for n in sorted(set(a) & set(b)):
+        if a[n][0] != b[n][0]:
+            diffs.append(f"body differs: {n}")
+        if a[n][1] != b[n][1]:
+            diffs.append(f"metadata differs: {n}: {a[n][1]} / {b[n][1]}")
+    print(f"{len(a)} kernels here, {len(b)} there, {len(set(a) & set(b))} in both: {len(diffs)} differ")
+    return diffs
 
 
 def metadata(asm: str, name: str) -> dict:
@@ -110,8 +138,13 @@ def main() -> int:
     ap.add_argument("--source", default=os.path.join(build.CSRC, "ftte_brick.hip"))
     ap.add_argument("--kernel", default=None, help=f"mangled name (default: the bench instance; the pair kernel: {PAIR})")
     ap.add_argument("--json", action="store_true")
+    ap.add_argument("--compare", metavar="OTHER.s", default=None, help="compare every kernel's text and metadata with this assembly")
     a = ap.parse_args()
-    asm = compile_asm(os.path.abspath(a.source))
+    asm = open(a.source).read() if a.source.endswith(".s") else compile_asm(os.path.abspath(a.source))
+    if a.compare:
+        diffs = compare(asm, open(a.compare).read())
+        print("\n".join(diffs), end="\n" if diffs else "")
+        return 1 if diffs else 0
     rec = report(asm, find_kernel(asm, a.kernel))
     if a.json:
         print(json.dumps(rec, indent=1))
