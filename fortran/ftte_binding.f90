@@ -569,6 +569,48 @@ module ftte_binding
        real(c_double), intent(out) :: mean_host_HI
      end function ftte_star_pdf
 
+     ! ---- absorption spectra along the projected map's pixel columns (not in the reference; include/ftte.h, csrc/ftte_spectra_math.h)
+     ! velx, vely, velz: (ncell) each [cm/s] along storage i, j, k (c_loc of host arrays); three c_null_ptr drop the field
+     integer(c_int) function ftte_set_velocity(ctx, velx, vely, velz) bind(C, name='ftte_set_velocity')
+       import :: c_ptr, c_int
+       type(c_ptr), value :: ctx
+       type(c_ptr), value :: velx, vely, velz ! host arrays
+     end function ftte_set_velocity
+
+     integer(c_int) function ftte_set_velocity_device(ctx, velx, vely, velz) bind(C, name='ftte_set_velocity_device')
+       import :: c_ptr, c_int
+       type(c_ptr), value :: ctx
+       type(c_ptr), value :: velx, vely, velz ! device arrays
+     end function ftte_set_velocity_device
+
+     ! line = (/ sigma_line, damping, mass, b_turb /); value: c_null_ptr = HI of the medium; tau(nvel,nxmap,nymap) and
+     ! summary(3,nxmap,nymap) = N, W, dv90 as c_loc of host arrays, either one (not both) c_null_ptr
+     integer(c_int) function ftte_sightline_spectra(ctx, izone, nxmap, nymap, centre, zoom, nvel, v0, dv, hubble, period, line, &
+          value, tau, summary) bind(C, name='ftte_sightline_spectra')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: izone, nxmap, nymap
+       real(c_double), intent(in) :: centre(3)
+       real(c_double), value :: zoom
+       integer(c_int), value :: nvel
+       real(c_double), value :: v0, dv, hubble, period
+       real(c_double), intent(in) :: line(4)
+       type(c_ptr), value :: value, tau, summary ! host arrays
+     end function ftte_sightline_spectra
+
+     integer(c_int) function ftte_sightline_spectra_device(ctx, izone, nxmap, nymap, centre, zoom, nvel, v0, dv, hubble, period, &
+          line, value, tau, summary) bind(C, name='ftte_sightline_spectra_device')
+       import :: c_ptr, c_int, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int), value :: izone, nxmap, nymap
+       real(c_double), intent(in) :: centre(3)
+       real(c_double), value :: zoom
+       integer(c_int), value :: nvel
+       real(c_double), value :: v0, dv, hubble, period
+       real(c_double), intent(in) :: line(4)
+       type(c_ptr), value :: value, tau, summary ! device arrays
+     end function ftte_sightline_spectra_device
+
      integer(c_int) function ftte_compute_opacities(ctx, nnu, beta) bind(C, name='ftte_compute_opacities')
        import :: c_ptr, c_int, c_double
        type(c_ptr), value :: ctx

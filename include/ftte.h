@@ -623,6 +623,47 @@ int ftte_gas_pdf(ftte_ctx *ctx, double pdf[50], double *outside);
  * their host leaves (ftte_locate_cell), as they do for the tracer: a gather of nsrc leaves.  mean_host_HI may be NULL. */
 int ftte_star_pdf(ftte_ctx *ctx, int nsrc, const int64_t *src_cell, int32_t pdf[50], int32_t *outside, double *mean_host_HI);
 
+/* ---- absorption spectra along sightlines: the optical depth of a line in velocity space ------------
+ * Not in the reference (which carries the cell array's velocities and never reads them); this build's own definition, stated in
+ * full in csrc/ftte_spectra_math.h.  Single-device context, as the analysis above.
+ *
+ * The velocity field: [ncell] doubles in cm/s each, cell-array order; velx runs along storage-i, vely along storage-j, velz along
+ * storage-k, the tracer's frame (what ftte_cellarray_fields hands out).  Three NULLs drop the field; with no field the peculiar
+ * velocity is zero.  The field has an owner of its own in the context (it is no field of the medium), is dropped by
+ * ftte_set_grid with another grid and counts in ftte_counter("device_objects").  FTTE_ERR_STATE without a grid,
+ * FTTE_ERR_UNSUPPORTED on a multi-device context, FTTE_ERR_ARG for one or two NULLs. */
+int ftte_set_velocity(ftte_ctx *ctx, const double *velx, const double *vely, const double *velz);
+int ftte_set_velocity_device(ftte_ctx *ctx, const double *velx_dev, const double *vely_dev, const double *velz_dev);
+/* tau(v) of one line along every pixel column of ftte_project_map's map: the same axis tables (ftte_map_axis), the same depth
+ * (ftte_map_depth), the same leaves in the same order -- base cells kstart..kend, both depth children of a refined cell, k = 1
+ * before 2.  The line of sight is the sweep frame's depth axis: a leaf's velocity u is the component of the storage axis the depth
+ * feeds, negated where izone mirrors it.
+ *   line[4] = {sigma_line = (pi e^2 / m_e c) f lambda0 [cm^2 cm/s] (HI Lyman alpha: 1.3435e-7), damping = Gamma lambda0 / 4 pi
+ *   [cm/s] (0: a pure Doppler profile), mass of the absorber [g], b_turb [cm/s]}.
+ * Leaf l with path D_l (its size [cm]), density n_l = value (NULL: HI of the medium), temperature T_l (the context's:
+ * ftte_set_temperature or what the thermal steps left): N_l = n_l D_l, b_l = sqrt(2 k_B T_l / mass + b_turb^2), a_l = damping / b_l,
+ * v_l = hubble s_l + u_l with s_l [cm] the distance of the leaf's centre from the entry face of base cell kstart.  Pixel p at
+ * v_p = v0 + (p + 1/2) dv, d = v_p - v_l reduced by period rint(d / period) where period > 0, x = d / b_l:
+ *   tau_p = sum_l N_l sigma_line / (sqrt(pi) b_l) H(a_l, x),  leaves in sightline order, one running sum per pixel,
+ * H Tepper-Garcia's (2006) approximation of the Voigt function (exp(-x^2) exactly 0 for x^2 > 64; its error: DESIGN.md 8).
+ *   tau[(i + nxmap j) nvel + p];  summary[(i + nxmap j) 3 + {0, 1, 2}] = N = sum N_l (float32(N) is ftte_project_map's mode-1
+ *   pixel), W = sum_p (1 - exp(-tau_p)) dv, dv90 = (p_hi - p_lo) dv with p_lo, p_hi the first pixels whose running sum of tau
+ *   reaches 0.05 and 0.95 of the total (0 where the total is 0).
+ * Either output may be NULL (not both).  _device: value_dev, tau_dev and summary_dev are device pointers.  The same bits call
+ * after call (no floating-point atomics).  Working memory belongs to the context; sightlines go in batches so that it stays
+ * under 64 MiB (beyond that only where a single line needs more).
+ * Refusals: as the maps'; FTTE_ERR_ARG for nvel < 1, dv <= 0, mass <= 0, a negative damping, b_turb or period, anything not finite;
+ * FTTE_ERR_STATE without a temperature; FTTE_ERR_ARG where 2 k_B T / mass + b_turb^2 of any leaf on a sightline is not positive and
+ * finite, decided in a pass of its own before anything of the caller's is written: on a refusal the outputs are untouched.
+ * ftte_counter: "spectra_chunk_segments" (segments of a sightline held in LDS at a time), "spectra_pass_pixels" (pixels of a
+ * sightline a workgroup holds in registers in one pass), "spectra_velocity" (1: a field is set). */
+int ftte_sightline_spectra(ftte_ctx *ctx, int izone, int nxmap, int nymap, const double centre[3], double zoom, int nvel, double v0,
+                           double dv, double hubble, double period, const double line[4], const double *value, double *tau,
+                           double *summary);
+int ftte_sightline_spectra_device(ftte_ctx *ctx, int izone, int nxmap, int nymap, const double centre[3], double zoom, int nvel,
+                                  double v0, double dv, double hubble, double period, const double line[4], const double *value_dev,
+                                  double *tau_dev, double *summary_dev);
+
 /* ---- host arrays ------------------------------------------------------------------------------
  * The reference keeps its fields in host memory (the zoneType tree, definitionsModule.f90:163-180); the drop-ins
  * flatten them into cell-array order and hand them over.  Pageable arrays cross PCIe through pinned staging blocks

@@ -120,6 +120,12 @@ SIGNATURES = {
     "ftte_clumping": (C.c_int, [_vp, _dp, _dp, _dp]),
     "ftte_gas_pdf": (C.c_int, [_vp, _dp, _dp]),
     "ftte_star_pdf": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp]),
+    "ftte_set_velocity": (C.c_int, [_vp, _dp, _dp, _dp]),
+    "ftte_set_velocity_device": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "ftte_sightline_spectra": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double,
+                                         _dp, _dp, _dp, _dp]),
+    "ftte_sightline_spectra_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double,
+                                                C.c_double, _dp, _vp, _vp, _vp]),
     "ftte_point_ray_steps": (C.c_longlong, [_vp]),
     "ftte_rmax": (C.c_int, [_dp]),
     "ftte_uvb_beta_table": (C.c_int, [C.c_int, C.c_double, _dp, _dp, _dp, _dp]),

@@ -17,7 +17,7 @@ from . import _lib
 from ._lib import FtteError, Pattern
 
 __all__ = ["DiffuseTransfer", "StellarTransfer", "rmax", "dust_cross_section", "uvb_beta_table", "uniform_table", "coll_rates", "rate_coefficient_tables", "cooling_coefficient_tables", "FtteError", "Pattern", "pix2ang_nest", "healpix_directions", "fold_direction",
-           "rotate_indices", "set_pattern", "layer_patterns", "compute_cell_intensity", "expansion_parameters", "map_axis", "slice_axis", "map_depth", "star_populations"]
+           "rotate_indices", "set_pattern", "layer_patterns", "compute_cell_intensity", "expansion_parameters", "map_axis", "slice_axis", "map_depth", "star_populations", "LYMAN_ALPHA"]
 
 
 def _f64(a) -> np.ndarray:
@@ -26,6 +26,11 @@ def _f64(a) -> np.ndarray:
 
 def _dp(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+# A ready `line` of sightline_spectra for HI Lyman alpha at b_turb = 0: sigma_line = (pi e^2 / m_e c) f lambda0 [cm^2 cm/s] with f = 0.4164 and
+# lambda0 = 1215.67 A, damping = Gamma lambda0 / 4 pi [cm/s] with Gamma = 6.265e8 / s, the hydrogen atom's mass [g], b_turb [cm/s]
+LYMAN_ALPHA = (1.3435e-7, 606.08, 1.6735e-24, 0.0)
 
 
 def _check(code: int, what: str):
@@ -935,6 +940,59 @@ class StellarTransfer(DiffuseTransfer):
         self._ok(self._lib.ftte_star_pdf(self._ctx, cells.size, cells.ctypes.data_as(C.POINTER(C.c_int64)),
                                          pdf.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(outside), C.byref(mean)))
         return pdf, outside.value, mean.value
+
+    # -- absorption spectra along the projected map's pixel columns (the library's own: include/ftte.h, csrc/ftte_spectra_math.h)
+    def set_velocity(self, velx=None, vely=None, velz=None, device_ptrs=None):
+        """The velocity field [cm/s], per leaf in cell-array order: velx along storage-i, vely along storage-j, velz along storage-k
+        (what cellarray fields hand out).  Three None drop the field (zero peculiar velocity).  device_ptrs: three device addresses
+        in place of the host arrays."""
+        if device_ptrs is not None:
+            self._ok(self._lib.ftte_set_velocity_device(self._ctx, *[C.c_void_p(int(p)) for p in device_ptrs]))
+            return
+        v = [None if a is None else _f64(a).reshape(-1) for a in (velx, vely, velz)]
+        for a in v:
+            if a is not None and self.ncell and a.size != self.ncell:
+                raise ValueError("a velocity component must have ncell elements")
+        self._ok(self._lib.ftte_set_velocity(self._ctx, *[None if a is None else _dp(a) for a in v]))
+
+    def sightline_spectra(self, izone: int, shape, nvel: int, v0: float, dv: float, line, centre=(0.5, 0.5, 0.5), zoom: float = 1.0,
+                          hubble: float = 0.0, period: float = 0.0, value=None, value_device_ptr: int = 0, want_tau: bool = True,
+                          want_summary: bool = True, tau_device_ptr: int = 0, summary_device_ptr: int = 0) -> dict:
+        """tau(v) of one line along every pixel column of project_map's map: dict(tau [nxmap][nymap][nvel] (None unless want_tau), N,
+        W, dv90 [nxmap][nymap] (None unless want_summary), velocity [nvel] the pixels' centres).  line = (sigma_line, damping, mass, b_turb), e.g. LYMAN_ALPHA;
+        value[ncell] the absorber's density (or value_device_ptr), None = HI of the medium.  With tau_device_ptr or
+        summary_device_ptr the _device variant writes there ([nymap][nxmap][nvel] and [nymap][nxmap][3] doubles as they lie in
+        memory) and the dict holds None for what went to the device."""
+        if len(centre) != 3:
+            raise ValueError("centre must have three entries")
+        nxmap, nymap, nvel = int(shape[0]), int(shape[1]), int(nvel)
+        centre, line = _f64(centre).reshape(-1), _f64(line).reshape(-1)
+        if line.size != 4:
+            raise ValueError("line must have four entries: sigma_line, damping, mass, b_turb")
+        head = (self._ctx, int(izone), nxmap, nymap, _dp(centre), float(zoom), nvel, float(v0), float(dv), float(hubble), float(period), _dp(line))
+        tau = summary = None
+        if value_device_ptr or tau_device_ptr or summary_device_ptr:
+            if value is not None:
+                raise ValueError("the device variant takes value_device_ptr, not a host value array")
+            if not tau_device_ptr and not summary_device_ptr:
+                raise ValueError("the device variant writes to tau_device_ptr or summary_device_ptr")
+            self._ok(self._lib.ftte_sightline_spectra_device(*head, C.c_void_p(int(value_device_ptr) or None), C.c_void_p(int(tau_device_ptr) or None),
+                                                             C.c_void_p(int(summary_device_ptr) or None)))
+        else:
+            if value is not None:
+                value = _f64(value).reshape(-1)
+                if value.size != self.ncell:
+                    raise ValueError("value must have one entry per leaf")
+            shape3 = (max(nymap, 1), max(nxmap, 1))
+            tau = np.empty(shape3 + (max(nvel, 1),)) if want_tau else None
+            summary = np.empty(shape3 + (3,)) if want_summary else None
+            self._ok(self._lib.ftte_sightline_spectra(*head, None if value is None else _dp(value), None if tau is None else _dp(tau),
+                                                      None if summary is None else _dp(summary)))
+        out = dict(tau=None if tau is None else tau.transpose(1, 0, 2), N=None, W=None, dv90=None,
+                   velocity=float(v0) + (np.arange(max(nvel, 0)) + 0.5) * float(dv))
+        if summary is not None:
+            out.update(N=summary[:, :, 0].T, W=summary[:, :, 1].T, dv90=summary[:, :, 2].T)
+        return out
 
 
 expansion_parameters = StellarTransfer.expansion_parameters

@@ -46,10 +46,6 @@ int map_depth(int n, double centre, double zoom, int32_t *kstart, int32_t *kend)
     return 0;
 }
 
-} // namespace ftte
-
-namespace {
-
 bool map_zone(int izone, MapZone *Z, int *fast_is_j)
 {
     ZoneMap m;
@@ -67,6 +63,10 @@ bool map_zone(int izone, MapZone *Z, int *fast_is_j)
     *fast_is_j = feeds == 1;
     return true;
 }
+
+} // namespace ftte
+
+namespace {
 
 // what every analysis call asks first: a single-device context with a grid; the sweep that may still write what is read has ended
 int analysis_ready(ftte_ctx *c)

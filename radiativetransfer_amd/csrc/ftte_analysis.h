@@ -84,6 +84,9 @@ struct AnalysisState {
     }
 };
 
+// MapZone of an izone, and along which map axis neighbouring lanes should be neighbours: the one that feeds the contiguous storage
+// index where a map axis does, else the one that feeds the next.  false: izone outside 1..24.
+bool map_zone(int izone, MapZone *Z, int *fast_is_j);
 // i0 and xnew of the map's columns (or rows), context-free.  quotient_first: the reader's form, the single-precision quotient
 // (float(i)-0.5)/float(nmap) widened (readCellArray.f90:126), inside the window; else the driver's, left to right in double
 // (equiSources.f90:703).  0, or -1 where an argument is bad or a base index leaves 1..n (the reference indexes out of bounds there).

@@ -122,6 +122,7 @@ int ftte_set_grid(ftte_ctx *c, int nx, int ny, int nz, int64_t ncell, const int3
     c->dtree.drop();
     c->chem.drop_grid();
     c->analysis.drop_grid();
+    c->spectra.drop_grid();
     c->leaf_level.assign(level, level + ncell);
     c->n = nx; c->ncell = ncell; c->box = box_cm; c->grid_set = true;
     c->kappa.invalidate();
@@ -339,6 +340,9 @@ long long ftte_counter(const ftte_ctx *c, const char *name)
     if (!std::strcmp(name, "plan_builds")) return c->n_plan_builds;
     if (!std::strcmp(name, "forest_builds")) return c->n_forest_builds;
     if (!std::strcmp(name, "device_objects")) return g_device_objects.load();
+    if (!std::strcmp(name, "spectra_chunk_segments")) return kSpectraChunk;     // segments of a sightline in LDS at a time
+    if (!std::strcmp(name, "spectra_pass_pixels")) return kSpectraPassPixels;   // pixels of a sightline a workgroup holds in registers in one pass
+    if (!std::strcmp(name, "spectra_velocity")) return c->spectra.velocity_set ? 1 : 0;
     if (!std::strcmp(name, "population_slots")) return c->point.tables.slot_count();
     if (!std::strcmp(name, "expansion_exact_tests")) return c->chem.expansion_tests;
     if (!std::strcmp(name, "medium_abun2")) return c->gas.ready_with_abundance(c->ncell) ? 1 : 0; // the medium came with an abun2

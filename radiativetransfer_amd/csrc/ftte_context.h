@@ -14,7 +14,7 @@
 // state (ftte_hybrid.h), for host arrays the staging blocks and the registered ranges (ftte_host.h), for the tree its copy on the
 // device (ftte_device_tree.h), and for point sources the rate tables with their output cross-sections, the accumulated rates, the
 // tracer's scratch and the escape record of the last trace (ftte_point.h), and for the star catalogue its scratch and the sources of
-// the last catalogue (ftte_star_catalogue.h).  The reference's table mathematics reads no context and no HIP (ftte_tables.cpp).
+// the last catalogue (ftte_star_catalogue.h), and for the sightline spectra the velocity field and their working memory (ftte_spectra.h).  The reference's table mathematics reads no context and no HIP (ftte_tables.cpp).
 //
 // There is no CPU fallback behind any of this: every entry point that computes on the grid needs a HIP device and fails with
 // FTTE_ERR_NO_DEVICE otherwise.
@@ -47,6 +47,7 @@
 #include "ftte_options.h"
 #include "ftte_point.h"
 #include "ftte_point_rec.h"
+#include "ftte_spectra.h"
 #include "ftte_star_catalogue.h"
 #include "ftte_tile_rec.h"
 #include "ftte_tiles.h"
@@ -154,6 +155,7 @@ struct ftte_ctx {
     std::vector<int8_t> leaf_level;  // per leaf, as handed to ftte_set_grid
     ChemState chem;                  // ionisation equilibrium (ftte_chem.cpp)
     AnalysisState analysis;          // maps and censuses of the medium (ftte_analysis.cpp)
+    SpectraState spectra;            // the velocity field, and the working memory of the sightline spectra (ftte_spectra.cpp)
 
     // accelerated source iteration (ftte_lambda_host.cpp): the segment-length tables of the last direction list, the leaves' places on
     // their levels (made for the tree of grid build lambda_leaves_grid) with the sub-layers that hold a leaf, the update's statistics
