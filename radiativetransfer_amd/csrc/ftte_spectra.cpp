@@ -1,26 +1,12 @@
 // ftte_spectra.cpp -- the spectra entry points of include/ftte.h: the velocity field on the device and the absorption spectra
-// along the pixel columns of the projected map (kernels: ftte_spectra.hip; the statement: ftte_spectra_math.h), and the
-// context-free batch rule.  The kernels read GasState::field(f), ChemState::tgas, the velocity field and the tracer's NodeRec tree
+// along the pixel columns of the projected map (kernels: ftte_spectra.hip; the statement: ftte_spectra_math.h; the
+// context-free batch rule: ftte_spectra.h).  The kernels read GasState::field(f), ChemState::tgas, the velocity field and the tracer's NodeRec tree
 // where they lie.  What the spectra keep on the device is ftte_ctx::spectra.
 #include "ftte_spectra.h"
 
 #include "ftte_context.h"
 
 using namespace ftte;
-
-namespace ftte {
-
-int64_t spectra_batch_lines(int64_t nlines, int64_t nvel, bool stage_tau, int64_t most_segments)
-{
-    if (nlines < 1) return 1;
-    size_t per_line = 3 * sizeof(double);
-    if (stage_tau) per_line += sizeof(double) * (size_t)(nvel > 0 ? nvel : 0);
-    if (most_segments > kSpectraChunk) per_line += sizeof(ftte_spectra_seg) * (size_t)most_segments;
-    const int64_t fit = (int64_t)(kSpectraWorkBytes / per_line);
-    return fit < 1 ? 1 : fit < nlines ? fit : nlines;
-}
-
-} // namespace ftte
 
 namespace {
 

@@ -76,7 +76,16 @@ struct SpectraState {
 
 // Sightlines per launch so that what a batch stages stays under kSpectraWorkBytes: nvel doubles of tau per line where tau is
 // staged, most_segments records per line where a line exceeds a chunk.  At least 1 (a single line may exceed the budget), at most nlines.
-int64_t spectra_batch_lines(int64_t nlines, int64_t nvel, bool stage_tau, int64_t most_segments);
+// (inline: tests/host/spectra_batch_check.cpp holds it without the context)
+inline int64_t spectra_batch_lines(int64_t nlines, int64_t nvel, bool stage_tau, int64_t most_segments)
+{
+    if (nlines < 1) return 1;
+    size_t per_line = 3 * sizeof(double);
+    if (stage_tau) per_line += sizeof(double) * (size_t)(nvel > 0 ? nvel : 0);
+    if (most_segments > kSpectraChunk) per_line += sizeof(ftte_spectra_seg) * (size_t)most_segments;
+    const int64_t fit = (int64_t)(kSpectraWorkBytes / per_line);
+    return fit < 1 ? 1 : fit < nlines ? fit : nlines;
+}
 
 // asynchronous on `stream`; 0, -1 bad argument, -2 launch failure
 int launch_spectra_check(const SpectraRec &R, void *stream);

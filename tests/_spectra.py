@@ -6,7 +6,11 @@
   lines         the g++ evaluation of csrc/ftte_spectra_math.h over such lists (tests/host/spectra_check.cpp through _hostlib.HostLib):
                 tau, N, W, dv90 -- what the GPU is compared with bit for bit;
   profile       H(a, x) of the header;
-  numpy_tau     the same formula in plain numpy (np.exp), the same order, for a = 0.
+  numpy_tau     the same formula in plain numpy (np.exp), the same order, for a = 0;
+  uniform_segments  the segments of a uniform grid too large for the walk's Tree;
+  batch_lines   the host's batch rule restated, for the GPU tests to place their seams by (held to the library's by
+                tests/host/spectra_batch_check.cpp);
+  deep_levels   level lists whose chosen sightlines cross a wanted number of leaves.
 """
 import ctypes as C
 
@@ -97,6 +101,131 @@ class Segments:
         a, mirrored = depth_axis(self.izone)
         u = _f64(vel[a])[self.leaf]
         return -u if mirrored else u
+
+
+class _Lists:
+    """what map_lines reads of a Segments, from arrays"""
+    velocity = Segments.velocity
+
+    def __init__(self, off, leaf, size, s, shape, izone):
+        self.off, self.leaf, self.size, self.s = off, leaf, size, s
+        self.shape, self.npix, self.izone = tuple(shape), off.size - 1, izone
+
+
+def uniform_segments(n, box, izone, shape, centre=(0.5, 0.5, 0.5), zoom=1.0):
+    """Segments of a uniform grid without its Tree (a Python loop over base cells): a base cell is its own leaf, its size the
+    cell's, its centre half a cell behind its entry face.  Held to Segments(Tree(n, zeros)) by test_spectra_host.py."""
+    i0, _ = A.map_axis(n, shape[0], centre[0], zoom)
+    j0, _ = A.map_axis(n, shape[1], centre[1], zoom)
+    kstart, kend = A.map_depth(n, centre[2], zoom)
+    depth = kend - kstart + 1
+    I0, J0 = (a.ravel() for a in np.meshgrid(i0, j0, indexing="ij"))
+    k0 = np.arange(kstart, kend + 1, dtype=np.int64)
+    leaf = A._base_nodes(izone, n, I0[:, None], J0[:, None], k0[None, :]).ravel()
+    cell = box / float(n)
+    s = np.tile((k0 - kstart).astype(np.float64) + 0.5, I0.size) * cell
+    return _Lists(np.arange(I0.size + 1, dtype=np.int64) * depth, leaf, np.full(leaf.size, cell), s, shape, izone)
+
+
+# ---- the batch rule and the kernel's sizes, restated (held to csrc/ftte_spectra.h by tests/host/spectra_batch_check.cpp)
+
+WORK_BYTES, CHUNK, LANES, PASS_PIXELS = 1 << 26, 512, 256, 1024
+
+
+def batch_lines(nlines, nvel, stage_tau, most):
+    """sightlines per launch: ftte::spectra_batch_lines"""
+    per_line = 24 + (8 * max(nvel, 0) if stage_tau else 0) + (32 * most if most > CHUNK else 0)
+    return 1 if nlines < 1 else max(1, min(WORK_BYTES // per_line, nlines))
+
+
+def batches(nlines, nvel, stage_tau, most):
+    """[(line0, lines)] of the launches of one call"""
+    step = batch_lines(nlines, nvel, stage_tau, most)
+    return [(at, min(step, nlines - at)) for at in range(0, nlines, step)]
+
+
+def line_counts(seg):
+    """segments per sightline in the order the kernel numbers them: line = i + nxmap j"""
+    return np.diff(seg.off).reshape(seg.shape).T.ravel()
+
+
+# ---- trees with sightlines of a wanted length
+
+def deep_column(crossings, level, first):
+    """the depth-first level list of a cell the sightline crosses `crossings` times: the two depth children on the line (the upper
+    children along the map axes below a base cell, the lower ones further down: a pixel at the centre of its base cell) share them"""
+    if crossings == 1:
+        return [level]
+    a = b = 1 if first else 0
+    out = []
+    for child in range(8):
+        ca, cb, cc = child >> 2, (child >> 1) & 1, child & 1
+        if (ca, cb) == (a, b):
+            out += deep_column(crossings // 2 if cc == 0 else crossings - crossings // 2, level + 1, False)
+        else:
+            out.append(level + 1)
+    return out
+
+
+def deep_levels(n, columns):
+    """the level list of an n^3 base grid whose storage columns (icell, jcell) of `columns` = {(i, j): crossings} are refined until a
+    sightline along storage k through the centre of the column crosses that many leaves, dealt over the column's n base cells;
+    every other base cell is a leaf.  For the izones whose depth is storage k and whose map axes are not mirrored (1 and 5)."""
+    parts = []
+    plain = np.zeros(n, dtype=np.int32)
+    for i in range(n):
+        for j in range(n):
+            want = columns.get((i, j))
+            if want is None:
+                parts.append(plain)
+            else:
+                assert want >= n
+                for k in range(n):
+                    parts.append(np.array(deep_column(want // n + (1 if k < want % n else 0), 0, True), dtype=np.int32))
+    return np.concatenate(parts)
+
+
+def seam_lines(fit, most):
+    """{line: segments} that puts spilled sightlines of differing lengths on both sides of the seams of batches of `fit` lines in a
+    map of 4096, at its first and last line, and three lengths above a chunk into the first batch"""
+    return {0: most, 330: CHUNK, 700: 700, fit - 1: CHUNK + 1, fit: most, 2 * fit - 1: 700, 2 * fit: 2 * CHUNK, 4095: most}
+
+
+def seam_columns(n, nvel, most):
+    """deep_levels' columns of an n x n map over an n^3 grid for the seams of both paths -- tau staged (host arrays, tau absent) and
+    not (tau to the caller's device array: the spill alone decides) -- under izone 1 (map pixel (i, j) is storage column (i, j)) and
+    under izone 5 (it is column (j, i))"""
+    columns = {}
+    for stage_tau in (False, True):
+        fit = batch_lines(n * n, nvel, stage_tau, most)
+        for line, count in seam_lines(fit, most).items():
+            i, j = line % n, line // n
+            for at in ((i, j), (j, i)):
+                assert columns.setdefault(at, count) == count, "two lengths asked of one column"
+    return columns
+
+
+def seam_conditions(counts, nvel, stage_tau):
+    """what makes a call a test of the batch loop, asserted of the reference's segment counts per line (line_counts): at least three
+    batches, the last one short, a spilled line in the first, a middle and the last, spilled lines on both sides of every seam,
+    three lengths above a chunk in one launch.  Returns the batches."""
+    bs = batches(counts.size, nvel, stage_tau, int(counts.max()))
+    assert len(bs) >= 3 and bs[-1][1] < bs[0][1] and all(b[1] == bs[0][1] for b in bs[:-1]), bs
+    deep = counts > CHUNK
+    for at, nl in (bs[0], bs[len(bs) // 2], bs[-1]):
+        assert deep[at:at + nl].any(), (at, nl)
+    for at, _ in bs[1:]:
+        assert deep[at - 1] and deep[at] and counts[at - 1] != counts[at], at
+    assert max(len(set(counts[at:at + nl][deep[at:at + nl]].tolist())) for at, nl in bs) >= 3
+    assert (counts == CHUNK).any() and (counts == CHUNK + 1).any()
+    return bs
+
+
+def random_medium(ncell, seed, box=3.0e24):
+    """HI, tgas and three velocity components per leaf"""
+    rng = np.random.default_rng(seed)
+    return dict(box=box, HI=10.0 ** rng.uniform(-9, -5, ncell), tgas=10.0 ** rng.uniform(3.5, 5.0, ncell),
+                vel=[rng.uniform(-2e7, 2e7, ncell) for _ in range(3)])
 
 
 def lines(off, dens, size, tgas, s, u, nvel, v0, dv, line, hubble=0.0, period=0.0, want_tau=True):

@@ -1,7 +1,9 @@
 """The sightline spectra on the GPU against the g++ evaluation of csrc/ftte_spectra_math.h on the segments the numpy walk finds
 (tests/_spectra.py; held against an independent Voigt function, plain numpy and the projected map by test_spectra_host.py): tau, N, W
 and dv90 bit for bit -- on the ingest golden under all 24 izones, on a uniform grid, on a tree whose one sightline spills over two
-chunks and one pass of pixels; the _device variants, absent outputs, freshness, the refusals, the owner."""
+chunks and one pass of pixels; the _device variants, absent outputs, freshness, the refusals, the owner; and what a production map
+runs: three batches with spilled lines on both sides of their seams, three batches by tau alone, lines at and around every chunk
+edge over one, two and three passes of pixels, a window deeper than one round of the gather."""
 import ctypes as C
 
 import numpy as np
@@ -103,22 +105,6 @@ def test_uniform_grid_and_no_velocity(stellar, golden):
         assert_same(stellar.sightline_spectra(izone, shape, nvel, v0, dv, rt.LYMAN_ALPHA, hubble=1e-17), still, "the field dropped")
 
 
-def _deep_column(crossings, level, first):
-    """the depth-first level list of a cell the sightline crosses `crossings` times: the two depth children on the line (the upper
-    children along the map axes below a base cell, the lower ones further down: a pixel at the centre of its base cell) share them"""
-    if crossings == 1:
-        return [level]
-    a = b = 1 if first else 0
-    out = []
-    for child in range(8):
-        ca, cb, cc = child >> 2, (child >> 1) & 1, child & 1
-        if (ca, cb) == (a, b):
-            out += _deep_column(crossings // 2 if cc == 0 else crossings - crossings // 2, level + 1, False)
-        else:
-            out.append(level + 1)
-    return out
-
-
 def test_a_sightline_beyond_two_chunks_and_one_pass(stellar):
     """a 4^3 base grid whose cells under pixel (0, 0) of izone 1 are refined level by level until that line holds 2 chunk + 3
     segments (the spill, three chunks, the last one of three records); its neighbours see 4; nvel one more than a pass holds"""
@@ -130,7 +116,7 @@ def test_a_sightline_beyond_two_chunks_and_one_pass(stellar):
     for i in range(n):
         for j in range(n):
             for k in range(n):
-                level += _deep_column(share[k], 0, True) if (i, j) == (0, 0) else [0]
+                level += S.deep_column(share[k], 0, True) if (i, j) == (0, 0) else [0]
     level = np.array(level, dtype=np.int32)
     rng = np.random.default_rng(chunk)
     nc = level.size
@@ -297,3 +283,190 @@ def test_multi_device_context_refuses(golden):
             with pytest.raises(rt.FtteError) as err:
                 call()
             assert err.value.status == "FTTE_ERR_UNSUPPORTED", str(err.value)
+
+
+# ---- the batch loop, the chunk edges, the pixel passes and the second round of the gather: what a production map runs
+
+LYA = rt.LYMAN_ALPHA
+
+
+def assert_same_summaries(got, want, what=""):
+    for key in ("N", "W", "dv90"):
+        assert S.same_bits(got[key], want[key]), f"{what}: {key} differs"
+
+
+def _sizes_are_the_restated_ones(st):
+    """the tests below place their seams and edges by S.CHUNK and S.PASS_PIXELS (and, through tests/host/spectra_batch_check.cpp, by
+    the budget of a batch and the lanes of a workgroup): another constant in the library fails here"""
+    assert st.counter("spectra_chunk_segments") == S.CHUNK and st.counter("spectra_pass_pixels") == S.PASS_PIXELS
+
+
+def _on_device(st, args, shape, nvel, with_tau, **more):
+    """the _device variant into tensors filled with -7, as the host variant's dict"""
+    import torch
+    dev = torch.device("cuda", 0)
+    tau = torch.full((shape[1], shape[0], nvel), -7.0, dtype=torch.float64, device=dev) if with_tau else None
+    summary = torch.full((shape[1], shape[0], 3), -7.0, dtype=torch.float64, device=dev)
+    torch.cuda.synchronize()
+    st.sightline_spectra(*args, tau_device_ptr=tau.data_ptr() if with_tau else 0, summary_device_ptr=summary.data_ptr(), **more)
+    torch.cuda.synchronize()
+    out = {k: summary.cpu().numpy()[:, :, q].T for q, k in enumerate(("N", "W", "dv90"))}
+    out["tau"] = tau.cpu().numpy().transpose(1, 0, 2) if with_tau else None
+    return out
+
+
+SEAM_N, SEAM_NVEL, SEAM_MOST = 64, 70, 2 * S.CHUNK + 3
+
+
+@pytest.fixture(scope="module")
+def seam_case():
+    level = S.deep_levels(SEAM_N, S.seam_columns(SEAM_N, SEAM_NVEL, SEAM_MOST))
+    case = dict(n=SEAM_N, level=level, **S.random_medium(level.size, SEAM_N))
+    case["tree"] = A.Tree(SEAM_N, level)
+    return case
+
+
+@pytest.mark.parametrize("izone", [1, 5])
+def test_batch_seams_with_spilled_lines_on_either_side(stellar, seam_case, izone):
+    """a 64 x 64 map over a 64^3 grid whose lines hold 64 segments, but for columns refined (S.seam_columns) until the lines at the
+    first and the last line of the map and on both sides of every batch seam hold 513 to 1027: three launches, the last one short,
+    each with spilled lines of differing lengths in slots other than 0, and the working memory used again by the next.  The seams lie
+    elsewhere where tau is staged (host arrays; tau absent: fit 2006) and where the spill alone decides (tau to a device array: fit
+    2040), and the tree has columns for both.  izone 5 is the same tree with the depth mirrored and the map axes swapped (the check
+    pass then numbers its lanes along the other axis)."""
+    _sizes_are_the_restated_ones(stellar)
+    case = seam_case
+    load(stellar, case)
+    shape, nvel, v0, dv, hubble = (SEAM_N, SEAM_N), SEAM_NVEL, -5.0e7, 1.0e8 / SEAM_NVEL, 1.0e-17
+    seg = S.Segments(case["tree"], case["box"], izone, shape)
+    counts = S.line_counts(seg)
+    assert counts.max() == SEAM_MOST and counts.min() == SEAM_N
+    staged, direct = S.seam_conditions(counts, nvel, True), S.seam_conditions(counts, nvel, False)
+    assert len(staged) == len(direct) == 3 and staged[1][0] != direct[1][0]
+    want = {line[1] > 0: S.map_lines(seg, case["HI"], case["tgas"], case["vel"], nvel, v0, dv, line, hubble) for line in (LYA, DOPPLER)}
+    host = lambda line, **more: stellar.sightline_spectra(izone, shape, nvel, v0, dv, line, hubble=hubble, **more)  # noqa: E731
+    device = lambda line, with_tau: _on_device(stellar, (izone, shape, nvel, v0, dv, line), shape, nvel, with_tau, hubble=hubble)  # noqa: E731
+    runs = (("host arrays", LYA, True, lambda: host(LYA)),
+            ("host arrays, tau staged and not asked for", DOPPLER, False, lambda: host(DOPPLER, want_tau=False)),
+            ("_device, tau and summaries", DOPPLER, True, lambda: device(DOPPLER, True)),
+            ("_device, summaries alone", LYA, False, lambda: device(LYA, False)))
+    for what, line, with_tau, call in runs:
+        for name in (what, what + ", the second call"):
+            got = call()
+            if with_tau:
+                assert_same(got, want[line[1] > 0], f"izone {izone}, {name}")
+            else:
+                assert got["tau"] is None
+                assert_same_summaries(got, want[line[1] > 0], f"izone {izone}, {name}")
+
+
+def test_batch_seams_by_tau_alone(stellar):
+    """no line beyond a chunk: 72 x 64 lines of four full pixel passes each stage 144 MiB of tau, in batches of 2046, 2046 and 516
+    (the smallest map with three: the size is the budget's, not the grid's); a period equal to the span wraps every line's wings and
+    the cores Hubble flow carries beyond the window"""
+    _sizes_are_the_restated_ones(stellar)
+    n, shape, nvel, izone = 4, (72, 64), 4 * S.PASS_PIXELS, 14
+    bs = S.batches(shape[0] * shape[1], nvel, True, n)
+    assert len(bs) == 3 and bs[0][1] == bs[1][1] > bs[2][1] and bs[0][1] % shape[0] != 0  # (a seam inside a row of the map)
+    case = dict(n=n, level=np.zeros(n ** 3, dtype=np.int32), **S.random_medium(n ** 3, 72))
+    load(stellar, case)
+    span, hubble = 1.0e8, 2.0e-17
+    v0, dv = -0.5 * span, span / nvel
+    seg = S.Segments(A.Tree(n, case["level"]), case["box"], izone, shape)
+    assert np.all(S.line_counts(seg) == n) and (hubble * seg.s + seg.velocity(case["vel"]) > v0 + span).any()
+    want = S.map_lines(seg, case["HI"], case["tgas"], case["vel"], nvel, v0, dv, LYA, hubble, span)
+    got = stellar.sightline_spectra(izone, shape, nvel, v0, dv, LYA, hubble=hubble, period=span)
+    assert_same(got, want, "three batches of tau")
+    assert got["tau"][:, :, -S.PASS_PIXELS:].min() > 0
+    assert_same_summaries(stellar.sightline_spectra(izone, shape, nvel, v0, dv, LYA, hubble=hubble, period=span, want_tau=False), want, "the second call")
+
+
+EDGE_NVEL = 2 * S.PASS_PIXELS + 17
+
+
+@pytest.fixture(scope="module")
+def edge_case():
+    """a 4^3 grid with five refined columns: lines of a chunk, a chunk and one, two chunks, two and three, three and one.  The leaves of
+    two of them move so that a tenth of the column absorbs at -3e7 cm/s and the rest five pixels from the upper end of a spectrum of
+    EDGE_NVEL pixels over +-5e7 (the second line mirrored, for the izone that mirrors the depth): dv90 then spans all three passes"""
+    n = 4
+    columns = {(1, 2): S.CHUNK, (2, 1): S.CHUNK + 1, (3, 3): 2 * S.CHUNK, (0, 3): 2 * S.CHUNK + 3, (0, 0): 3 * S.CHUNK + 1}
+    level = S.deep_levels(n, columns)
+    case = dict(n=n, level=level, counts=sorted([n] * (n * n - len(columns)) + list(columns.values())), **S.random_medium(level.size, S.CHUNK))
+    case["tree"] = A.Tree(n, level)
+    seg = S.Segments(case["tree"], case["box"], 1, (n, n))
+    far = -5.0e7 + (EDGE_NVEL - 4.5) * (1.0e8 / EDGE_NVEL)
+    for (i, j), sign in (((0, 0), 1.0), ((0, 3), -1.0)):
+        q = i * n + j
+        leaves = seg.leaf[seg.off[q]:seg.off[q + 1]]
+        column = case["HI"][leaves] * seg.size[seg.off[q]:seg.off[q + 1]]
+        case["vel"][2][leaves] = sign * np.where(np.cumsum(column) <= 0.1 * column.sum(), -3.0e7, far)
+    return case
+
+
+@pytest.mark.parametrize("nvel", [S.PASS_PIXELS, 2 * S.PASS_PIXELS, EDGE_NVEL])
+def test_chunk_edges_and_pixel_passes(stellar, edge_case, nvel):
+    """one launch with lines of 4, 512 (the last count that stays in LDS), 513 (a second chunk of one record), 1024 (two full chunks:
+    no remainder), 1027 and 1537 (a fourth chunk) segments, in slots other than 0, under izone 1 and under 5 (depth mirrored, map axes
+    swapped); one full pass of pixels, two full passes, and two passes and 17 pixels, where dv90 of one line runs from the first pass
+    into the third"""
+    _sizes_are_the_restated_ones(stellar)
+    case = edge_case
+    load(stellar, case)
+    shape, v0, dv = (4, 4), -5.0e7, 1.0e8 / nvel
+    three_passes = nvel > 2 * S.PASS_PIXELS
+    assert three_passes or nvel % S.PASS_PIXELS == 0
+    hubble = 0.0 if three_passes else 2.0e-17
+    for izone in (1, 5):
+        seg = S.Segments(case["tree"], case["box"], izone, shape)
+        counts = S.line_counts(seg)
+        assert sorted(counts.tolist()) == case["counts"] and counts[0] > 3 * S.CHUNK and (counts[1:] > S.CHUNK).sum() == 3
+        assert (counts == S.CHUNK).sum() == 1 and (counts == S.CHUNK + 1).sum() == 1 and (counts == 2 * S.CHUNK).sum() == 1
+        for line in (LYA, DOPPLER):
+            want = S.map_lines(seg, case["HI"], case["tgas"], case["vel"], nvel, v0, dv, line, hubble)
+            got = stellar.sightline_spectra(izone, shape, nvel, v0, dv, line, hubble=hubble)
+            if three_passes:
+                run = np.cumsum(want["tau"].reshape(-1, nvel), axis=1)
+                p_lo, p_hi = (run >= 0.05 * run[:, -1:]).argmax(axis=1), (run >= 0.95 * run[:, -1:]).argmax(axis=1)
+                split = (p_lo < S.PASS_PIXELS) & (p_hi >= 2 * S.PASS_PIXELS)
+                assert split.any() and np.diff(seg.off)[split].max() > S.CHUNK, (p_lo, p_hi)
+                assert np.array_equal(want["dv90"].ravel()[split], (p_hi - p_lo)[split] * dv)
+            assert_same(got, want, f"izone {izone} nvel {nvel} damping {line[1]}")
+            assert_same(stellar.sightline_spectra(izone, shape, nvel, v0, dv, line, hubble=hubble), got, "the second call")
+
+
+@pytest.mark.parametrize("most", [S.CHUNK, S.CHUNK + 1])
+def test_the_longest_line_of_a_map_at_the_chunk_and_one_beyond(stellar, most):
+    """the host gives a call a spill where its longest line exceeds a chunk, and the kernel spills a line that does: the two draw the
+    line at the same count.  A map whose longest line holds exactly a chunk has no spill; with one record more the spill's stride is
+    a chunk and one"""
+    _sizes_are_the_restated_ones(stellar)
+    n, shape, nvel, v0, dv = 4, (4, 4), 70, -5.0e7, 1.0e8 / 70
+    level = S.deep_levels(n, {(2, 1): most})
+    case = dict(n=n, level=level, **S.random_medium(level.size, most))
+    load(stellar, case)
+    T = A.Tree(n, level)
+    for izone, line in ((1, LYA), (5, DOPPLER)):
+        seg = S.Segments(T, case["box"], izone, shape)
+        counts = S.line_counts(seg)
+        assert counts.max() == most and (counts == n).sum() == n * n - 1 and counts[0] == n
+        got = stellar.sightline_spectra(izone, shape, nvel, v0, dv, line, hubble=1.0e-17)
+        assert_same(got, S.map_lines(seg, case["HI"], case["tgas"], case["vel"], nvel, v0, dv, line, 1.0e-17), f"izone {izone}")
+
+
+def test_the_second_round_of_the_gather(stellar):
+    """a uniform 257^3 grid, the whole depth: a workgroup's 256 lanes take the line's base cells 256 at a time, the grid is a cube and
+    the window no deeper than it, so this is the smallest grid at which the gather takes a second round (one lane of it: the slots go
+    on from the first round's total, the scan's buffers are used again).  Its time is the upload's: 17 million leaves, five fields."""
+    _sizes_are_the_restated_ones(stellar)
+    n, shape, nvel, v0, dv, hubble = S.LANES + 1, (3, 2), 64, -5.0e7, 1.0e8 / 64, 1.0e-17
+    kstart, kend = A.map_depth(n)
+    assert kend - kstart + 1 > S.LANES
+    case = dict(n=n, level=np.zeros(n ** 3, dtype=np.int32), **S.random_medium(n ** 3, n))
+    load(stellar, case)
+    for izone in (1, 5, 15):  # (5: the depth against storage k; 15: against storage i, base cells n^2 leaves apart)
+        seg = S.uniform_segments(n, case["box"], izone, shape)
+        assert np.all(np.diff(seg.off) == n) and np.unique(seg.leaf).size == seg.leaf.size
+        want = S.map_lines(seg, case["HI"], case["tgas"], case["vel"], nvel, v0, dv, LYA, hubble)
+        assert_same(stellar.sightline_spectra(izone, shape, nvel, v0, dv, LYA, hubble=hubble), want, f"izone {izone}")
+    stellar.set_grid(4, np.zeros(64, dtype=np.int32), case["box"])  # (the fixture does not hold 17 million leaves for the tests after this one)

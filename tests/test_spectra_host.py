@@ -1,7 +1,9 @@
 """The absorption line of csrc/ftte_spectra_math.h on the host (g++ through tests/_spectra.py; no GPU): the profile against an
 independent Voigt function (tests/golden/voigt_table.npz: scipy's Faddeeva function, make_golden_voigt.py), the line against plain
-numpy, known answers, the geometry of the sightlines against the numpy restatement of the projected map, and the whole under the
-sanitizers as a program of its own."""
+numpy, known answers, the geometry of the sightlines against the numpy restatement of the projected map, the helpers of the GPU tests (the
+segments of a uniform grid, trees with sightlines of a wanted length), the host's batch rule (csrc/ftte_spectra.h, against a stub of
+the HIP runtime) with the tests' restatement of it, and the whole under the sanitizers as programs of their own."""
+import os
 import shutil
 import subprocess
 
@@ -215,7 +217,78 @@ def test_mirrored_depth_reverses_the_spectrum(refined):
             assert np.all(np.abs(two["tau"] - one["tau"][:, :, ::-1]) <= 1e-13 * one["tau"][:, :, ::-1])
 
 
-# ---- 5. under the sanitizers
+def test_uniform_segments_are_the_walk_of_a_uniform_tree():
+    """what the GPU test of a 257^3 grid takes for its segments, at a size the Tree can be built at"""
+    n, box = 16, 2.5e24
+    T = A.Tree(n, np.zeros(n ** 3, dtype=np.int64))
+    vel = [np.random.default_rng(q).uniform(-1e7, 1e7, n ** 3) for q in range(3)]
+    for izone in (1, 5, 8, 15, 24):
+        for shape, centre, zoom in (((3, 2), (0.5, 0.5, 0.5), 1.0), ((7, 5), (0.5, 0.5, 0.5), 1.0), ((13, 11), (0.3, 0.7, 0.9), 2.5)):
+            want, got = S.Segments(T, box, izone, shape, centre, zoom), S.uniform_segments(n, box, izone, shape, centre, zoom)
+            assert got.shape == want.shape and got.npix == want.npix and got.izone == want.izone
+            for key in ("off", "leaf", "size", "s"):
+                a, b = getattr(got, key), getattr(want, key)
+                assert a.dtype == b.dtype and np.array_equal(a, b), (izone, shape, key)
+            assert np.array_equal(got.velocity(vel), want.velocity(vel)) and np.array_equal(got.velocity(None), want.velocity(None))
+            assert np.array_equal(S.line_counts(got), S.line_counts(want))
+    assert np.diff(S.uniform_segments(n, box, 3, (13, 11), (0.3, 0.7, 0.9), 2.5).off).max() < n  # (the zoomed window is shallower)
+
+
+def test_deep_levels_give_the_wanted_counts():
+    """the trees of the GPU tests' chunk edges: the counts asked for, at the columns asked for, under the two izones they are for"""
+    columns = {(1, 2): 512, (2, 1): 513, (0, 3): 1027, (3, 3): 4, (0, 0): 9}
+    level = S.deep_levels(4, columns)
+    T = A.Tree(4, level)
+    for izone in (1, 5):
+        counts = np.diff(S.Segments(T, 3.0e24, izone, (4, 4)).off).reshape(4, 4)
+        for i in range(4):
+            for j in range(4):
+                at = (i, j) if izone == 1 else (j, i)  # (izone 5: map axis i is storage j)
+                assert counts[i, j] == columns.get(at, 4), (izone, i, j)
+    assert S.line_counts(S.Segments(T, 3.0e24, 1, (4, 4)))[1 + 4 * 2] == 512
+
+
+# ---- 5. the batch rule
+
+BATCH_CASES = [((4096, 70, False, 1027), 2040), ((4096, 70, True, 1027), 2006), ((65536, 1024, True, 512), 8168), ((100, 1024, True, 4), 100),
+               ((5, 1 << 24, True, 4), 1), ((0, 1024, True, 4), 1), ((4608, 4096, True, 4), 2046), ((1280, 16384, True, 4), 511)]
+
+
+def _batch_check(tmp_path, flags, name):
+    gxx = shutil.which("g++")
+    assert gxx, "no g++"
+    exe = str(tmp_path / name)
+    # the stub's directory comes first: <hip/hip_runtime_api.h> is the stub even where ROCm is installed
+    subprocess.check_call([gxx, *flags, "-I" + os.path.join(S.ROOT, "tests", "host", "stub"), "-I" + S.CSRC,
+                           os.path.join(S.ROOT, "tests", "host", "spectra_batch_check.cpp"), "-o", exe])
+    return exe
+
+
+@pytest.mark.parametrize("sanitized", [False, True])
+def test_batch_rule(tmp_path, sanitized):
+    """ftte::spectra_batch_lines as a program of its own (tests/host/spectra_batch_check.cpp): its known values and its property;
+    and the restatement the GPU tests place their seams by, against the same values and against the function over random arguments"""
+    exe = _batch_check(tmp_path, S.SANITIZE if sanitized else ["-std=c++17", "-O2", "-Wall", "-Werror"], "batch")
+    res = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0 and "spectra batch rule: ok" in res.stdout and "ERROR" not in res.stderr, res.stdout[-2000:] + res.stderr[-4000:]
+    for args, want in BATCH_CASES:
+        assert S.batch_lines(*args) == want, args
+    assert [b[1] for b in S.batches(4096, 70, False, 1027)] == [2040, 2040, 16] and [b[1] for b in S.batches(4096, 70, True, 1027)] == [2006, 2006, 84]
+    assert S.batches(4608, 4096, True, 4) == [(0, 2046), (2046, 2046), (4092, 516)]
+    rng = np.random.default_rng(26)
+    rows = [(int(rng.integers(0, 100000)), int(rng.integers(0, 40000)), int(rng.integers(0, 2)), int(rng.integers(0, 3000))) for _ in range(300)]
+    rows += [(int(rng.integers(0, 40)), int(rng.integers(0, 1 << 25)), 1, int(rng.integers(0, 4000000))) for _ in range(60)]
+    rows += [(n, v, t, m) for n in (1, 7, 65536) for v in (1, 1024) for t in (0, 1) for m in (511, 512, 513)]
+    case = tmp_path / "rows.txt"
+    case.write_text("".join("%d %d %d %d\n" % r for r in rows))
+    res = subprocess.run([exe, str(case)], capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0 and "ERROR" not in res.stderr, res.stderr[-4000:]
+    got = [int(v) for v in res.stdout.split()]
+    assert got == [S.batch_lines(n, v, bool(t), m) for n, v, t, m in rows]
+    assert len({g == r[0] for g, r in zip(got, rows)}) == 2 and 1 in got  # whole maps, cut maps and single lines among them
+
+
+# ---- 6. under the sanitizers
 
 def test_statement_under_the_sanitizers(refined, golden, tmp_path):
     """tests/host/spectra_check.cpp's main() over the goldens' segment lists, with AddressSanitizer and UBSan, as a program of its own"""
