@@ -611,6 +611,47 @@ module ftte_binding
        type(c_ptr), value :: value, tau, summary ! device arrays
      end function ftte_sightline_spectra_device
 
+     ! the same along rays of any origin and direction: origin(3,nray), dir(3,nray) unit vectors in the storage frame, base cells;
+     ! tmax(nray) as c_loc or c_null_ptr (to the box's far side); tau(nvel,nray), summary(3,nray); the rays are host arrays in both
+     integer(c_int) function ftte_ray_spectra(ctx, nray, origin, dir, tmax, nvel, v0, dv, hubble, period, line, &
+          value, tau, summary) bind(C, name='ftte_ray_spectra')
+       import :: c_ptr, c_int, c_int64_t, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: nray
+       real(c_double), intent(in) :: origin(3, *), dir(3, *)
+       type(c_ptr), value :: tmax
+       integer(c_int), value :: nvel
+       real(c_double), value :: v0, dv, hubble, period
+       real(c_double), intent(in) :: line(4)
+       type(c_ptr), value :: value, tau, summary ! host arrays
+     end function ftte_ray_spectra
+
+     integer(c_int) function ftte_ray_spectra_device(ctx, nray, origin, dir, tmax, nvel, v0, dv, hubble, period, line, &
+          value, tau, summary) bind(C, name='ftte_ray_spectra_device')
+       import :: c_ptr, c_int, c_int64_t, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: nray
+       real(c_double), intent(in) :: origin(3, *), dir(3, *)
+       type(c_ptr), value :: tmax
+       integer(c_int), value :: nvel
+       real(c_double), value :: v0, dv, hubble, period
+       real(c_double), intent(in) :: line(4)
+       type(c_ptr), value :: value, tau, summary ! device arrays
+     end function ftte_ray_spectra_device
+
+     ! the rays' segment lists: offset(nray+1); leaf, t_in, t_out (capacity) as c_loc, or capacity 0 and c_null_ptr: the offsets alone
+     integer(c_int) function ftte_ray_segments(ctx, nray, origin, dir, tmax, offset, capacity, leaf, t_in, t_out) &
+          bind(C, name='ftte_ray_segments')
+       import :: c_ptr, c_int, c_int64_t, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: nray
+       real(c_double), intent(in) :: origin(3, *), dir(3, *)
+       type(c_ptr), value :: tmax
+       integer(c_int64_t), intent(out) :: offset(*)
+       integer(c_int64_t), value :: capacity
+       type(c_ptr), value :: leaf, t_in, t_out
+     end function ftte_ray_segments
+
      integer(c_int) function ftte_compute_opacities(ctx, nnu, beta) bind(C, name='ftte_compute_opacities')
        import :: c_ptr, c_int, c_double
        type(c_ptr), value :: ctx

@@ -51,7 +51,8 @@ typedef enum {
     FTTE_ERR_PIXEL = -12,         /* equiSources.f90:2152-2160 'nside/ipix out of range'           */
     FTTE_ERR_RATES = -13,         /* equiSources.f90:3637-3654: a species fraction left [0, 1]     */
     FTTE_ERR_MEMORY = -14,        /* not enough device memory for the request (see message)         */
-    FTTE_ERR_STALLED = -15        /* a one-launch sweep (option "dataflow") stopped making progress; its J is not valid */
+    FTTE_ERR_STALLED = -15,       /* a one-launch sweep (option "dataflow") stopped making progress; its J is not valid */
+    FTTE_ERR_INTERNAL = -16       /* the library caught itself breaking one of its own bounds (see message); outputs untouched */
 } ftte_status;
 
 /* ---- lifetime ------------------------------------------------------------------------------ */
@@ -663,6 +664,33 @@ int ftte_sightline_spectra(ftte_ctx *ctx, int izone, int nxmap, int nymap, const
 int ftte_sightline_spectra_device(ftte_ctx *ctx, int izone, int nxmap, int nymap, const double centre[3], double zoom, int nvel,
                                   double v0, double dv, double hubble, double period, const double line[4], const double *value_dev,
                                   double *tau_dev, double *summary_dev);
+/* The same line along rays of any origin and direction (the walk is stated in full in csrc/ftte_ray_math.h).  Frame and units: the
+ * storage frame of ftte_set_velocity (x along storage-i, y along j, z along k), lengths in base cells: the box is [0, n]^3.
+ *   origin[nray][3], dir[nray][3] the caller's unit vectors (| |dir|^2 - 1 | <= 1e-9), tmax[nray] the rays' ends in base cells from
+ *   their origins, or NULL; a tmax <= 0 means "to the box's far side".  A ray starts where it enters the box, or at its origin inside.
+ * The ray's leaves in the order it crosses them, each with its chord: leaf l has D_l = chord cell size [cm], s_l [cm] the distance
+ * of the chord's midpoint from the ray's origin, u_l = (d_0 velx + d_1 vely) + d_2 velz.  Everything else is as above:
+ *   tau[r nvel + p];  summary[3 r + {0, 1, 2}] = N, W, dv90.
+ * A ray along +-e_a from a base cell's face through dyadic transverse coordinates equals the matching pixel column of
+ * ftte_sightline_spectra bit for bit.  A ray that misses the box is no error: N = 0, tau = 0, W = 0, dv90 = 0.  The rays are host
+ * arrays in both variants; _device: value_dev, tau_dev and summary_dev are device pointers.  Rays go in batches so that their
+ * segment records and staged tau stay under 64 MiB (beyond that only where a single ray needs more); the same bits call after call.
+ * Refusals: those of ftte_sightline_spectra; FTTE_ERR_ARG for nray < 1, an origin, direction or tmax that is not finite, a
+ * direction that is no unit vector; FTTE_ERR_UNSUPPORTED on a multi-device context or a tree deeper than 40 levels;
+ * FTTE_ERR_INTERNAL where a walk took more than 3 n 2^maxlevel + 3 steps.  All decided, the leaves' line widths included, before
+ * anything of the caller's is written: on a refusal the outputs are untouched.  No periodic wrap of a ray; a leaf has one velocity.
+ * ftte_counter: "ray_chunk_segments" (records of a ray held in LDS at a time), "ray_work_bytes" (the budget of a batch). */
+int ftte_ray_spectra(ftte_ctx *ctx, int64_t nray, const double *origin, const double *dir, const double *tmax, int nvel, double v0,
+                     double dv, double hubble, double period, const double line[4], const double *value, double *tau, double *summary);
+int ftte_ray_spectra_device(ftte_ctx *ctx, int64_t nray, const double *origin, const double *dir, const double *tmax, int nvel,
+                            double v0, double dv, double hubble, double period, const double line[4], const double *value_dev,
+                            double *tau_dev, double *summary_dev);
+/* The rays' segment lists: ray r's segments are offset[r] .. offset[r + 1] - 1 (offset[nray + 1]), each the leaf's cell-array index
+ * and its [t_in, t_out] in base cells from the ray's origin; a ray's segments tile [its start, its end] without a gap.  Needs a
+ * grid only.  capacity: the room of leaf, t_in and t_out; 0 returns the offsets alone (the three may be NULL), a capacity below
+ * offset[nray] is FTTE_ERR_ARG with everything untouched. */
+int ftte_ray_segments(ftte_ctx *ctx, int64_t nray, const double *origin, const double *dir, const double *tmax, int64_t *offset,
+                      int64_t capacity, int64_t *leaf, double *t_in, double *t_out);
 
 /* ---- host arrays ------------------------------------------------------------------------------
  * The reference keeps its fields in host memory (the zoneType tree, definitionsModule.f90:163-180); the drop-ins

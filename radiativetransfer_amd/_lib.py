@@ -11,6 +11,7 @@ STATUS = {
     0: "FTTE_OK", -1: "FTTE_ERR_ARG", -2: "FTTE_ERR_STATE", -3: "FTTE_ERR_NO_DEVICE", -4: "FTTE_ERR_UNSUPPORTED",
     -5: "FTTE_ERR_NOT_CUBIC", -6: "FTTE_ERR_LEVELS", -7: "FTTE_ERR_PHI", -8: "FTTE_ERR_THETA",
     -9: "FTTE_ERR_DOMINANT_AXIS", -10: "FTTE_ERR_PATTERN", -11: "FTTE_ERR_IZONE", -12: "FTTE_ERR_PIXEL", -13: "FTTE_ERR_RATES", -14: "FTTE_ERR_MEMORY", -15: "FTTE_ERR_STALLED",
+    -16: "FTTE_ERR_INTERNAL",
 }
 
 
@@ -126,6 +127,9 @@ SIGNATURES = {
                                          _dp, _dp, _dp, _dp]),
     "ftte_sightline_spectra_device": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double,
                                                 C.c_double, _dp, _vp, _vp, _vp]),
+    "ftte_ray_spectra": (C.c_int, [_vp, C.c_int64, _dp, _dp, _dp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _dp, _dp, _dp, _dp]),
+    "ftte_ray_spectra_device": (C.c_int, [_vp, C.c_int64, _dp, _dp, _dp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _dp, _vp, _vp, _vp]),
+    "ftte_ray_segments": (C.c_int, [_vp, C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64), _dp, _dp]),
     "ftte_point_ray_steps": (C.c_longlong, [_vp]),
     "ftte_rmax": (C.c_int, [_dp]),
     "ftte_uvb_beta_table": (C.c_int, [C.c_int, C.c_double, _dp, _dp, _dp, _dp]),

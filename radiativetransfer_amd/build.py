@@ -17,7 +17,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libftte.so")
 # the two long compiles first: the pool starts them at once
-SOURCES = ["ftte_tile.hip", "ftte_brick.hip", "ftte_layout.hip", "ftte_forest.hip", "ftte_point.hip", "ftte_chem.hip", "ftte_thermal.hip", "ftte_thermochem.hip", "ftte_recombination.hip", "ftte_recombination.cpp", "ftte_lambda.hip", "ftte_expansion.hip", "ftte_catalogue.hip", "ftte_catalogue.cpp", "ftte_analysis.hip", "ftte_analysis.cpp", "ftte_spectra.hip", "ftte_spectra.cpp", "ftte_lambda_host.cpp", "ftte_api.cpp", "ftte_chem.cpp", "ftte_leaf_pass.cpp", "ftte_plan.cpp", "ftte_planner.cpp", "ftte_sweeps.cpp", "ftte_hybrid.cpp", "ftte_multi.cpp", "ftte_host_arrays.cpp",
+SOURCES = ["ftte_tile.hip", "ftte_brick.hip", "ftte_layout.hip", "ftte_forest.hip", "ftte_point.hip", "ftte_chem.hip", "ftte_thermal.hip", "ftte_thermochem.hip", "ftte_recombination.hip", "ftte_recombination.cpp", "ftte_lambda.hip", "ftte_expansion.hip", "ftte_catalogue.hip", "ftte_catalogue.cpp", "ftte_analysis.hip", "ftte_analysis.cpp", "ftte_spectra.hip", "ftte_spectra.cpp", "ftte_rays.hip", "ftte_rays.cpp", "ftte_lambda_host.cpp", "ftte_api.cpp", "ftte_chem.cpp", "ftte_leaf_pass.cpp", "ftte_plan.cpp", "ftte_planner.cpp", "ftte_sweeps.cpp", "ftte_hybrid.cpp", "ftte_multi.cpp", "ftte_host_arrays.cpp",
            "ftte_geometry.cpp", "ftte_amr.cpp", "ftte_point.cpp", "ftte_tables.cpp", "ftte_ingest.cpp"]
 # -ffp-contract=off: the sweep arithmetic spells out its fused multiply-adds (ftte_math.h); nothing else may be fused,
 # so that the device rounds exactly like the host evaluation the parity tests compare against.

@@ -343,6 +343,8 @@ long long ftte_counter(const ftte_ctx *c, const char *name)
     if (!std::strcmp(name, "spectra_chunk_segments")) return kSpectraChunk;     // segments of a sightline in LDS at a time
     if (!std::strcmp(name, "spectra_pass_pixels")) return kSpectraPassPixels;   // pixels of a sightline a workgroup holds in registers in one pass
     if (!std::strcmp(name, "spectra_velocity")) return c->spectra.velocity_set ? 1 : 0;
+    if (!std::strcmp(name, "ray_chunk_segments")) return kSpectraChunk;         // records of a ray in LDS at a time (ftte_rays.hip)
+    if (!std::strcmp(name, "ray_work_bytes")) return (long long)kSpectraWorkBytes; // what a batch of rays keeps stays below this
     if (!std::strcmp(name, "population_slots")) return c->point.tables.slot_count();
     if (!std::strcmp(name, "expansion_exact_tests")) return c->chem.expansion_tests;
     if (!std::strcmp(name, "medium_abun2")) return c->gas.ready_with_abundance(c->ncell) ? 1 : 0; // the medium came with an abun2

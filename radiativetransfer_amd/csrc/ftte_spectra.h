@@ -64,6 +64,10 @@ struct SpectraState {
     DeviceBuffer<double> column;
     DeviceBuffer<double> tau, summary; // of a batch, where the caller's are on the host or absent
     DeviceBuffer<ftte_spectra_seg> spill;
+    // the oblique rays (ftte_rays.cpp): a call's rays and their offsets, and a batch's records or segment list
+    DeviceBuffer<double> ray_origin, ray_dir, ray_tmax, ray_tin, ray_tout;
+    DeviceBuffer<int64_t> ray_offset, ray_leaf;
+    DeviceBuffer<ftte_spectra_seg> ray_rec;
 
     void drop_velocity() { for (auto &v : vel) v.reset(); velocity_set = false; }
     void drop_grid()
@@ -71,6 +75,7 @@ struct SpectraState {
         drop_velocity();
         value.reset(); nseg.reset(); flags.reset(); column.reset(); tau.reset(); summary.reset(); spill.reset();
         for (int a = 0; a < 2; ++a) { base[a].reset(); frac[a].reset(); }
+        ray_origin.reset(); ray_dir.reset(); ray_tmax.reset(); ray_tin.reset(); ray_tout.reset(); ray_offset.reset(); ray_leaf.reset(); ray_rec.reset();
     }
 };
 
