@@ -652,6 +652,46 @@ module ftte_binding
        type(c_ptr), value :: leaf, t_in, t_out
      end function ftte_ray_segments
 
+     ! the periodic namesakes: the box tiles space and a ray goes on through the opposite face from its origin (anywhere) to
+     ! tmax(nray), which is required (c_loc) and > 0; t and s are measured from the caller's origin across images
+     integer(c_int) function ftte_ray_spectra_periodic(ctx, nray, origin, dir, tmax, nvel, v0, dv, hubble, period, line, &
+          value, tau, summary) bind(C, name='ftte_ray_spectra_periodic')
+       import :: c_ptr, c_int, c_int64_t, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: nray
+       real(c_double), intent(in) :: origin(3, *), dir(3, *)
+       type(c_ptr), value :: tmax
+       integer(c_int), value :: nvel
+       real(c_double), value :: v0, dv, hubble, period
+       real(c_double), intent(in) :: line(4)
+       type(c_ptr), value :: value, tau, summary ! host arrays
+     end function ftte_ray_spectra_periodic
+
+     integer(c_int) function ftte_ray_spectra_periodic_device(ctx, nray, origin, dir, tmax, nvel, v0, dv, hubble, period, line, &
+          value, tau, summary) bind(C, name='ftte_ray_spectra_periodic_device')
+       import :: c_ptr, c_int, c_int64_t, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: nray
+       real(c_double), intent(in) :: origin(3, *), dir(3, *)
+       type(c_ptr), value :: tmax
+       integer(c_int), value :: nvel
+       real(c_double), value :: v0, dv, hubble, period
+       real(c_double), intent(in) :: line(4)
+       type(c_ptr), value :: value, tau, summary ! device arrays
+     end function ftte_ray_spectra_periodic_device
+
+     integer(c_int) function ftte_ray_segments_periodic(ctx, nray, origin, dir, tmax, offset, capacity, leaf, t_in, t_out) &
+          bind(C, name='ftte_ray_segments_periodic')
+       import :: c_ptr, c_int, c_int64_t, c_double
+       type(c_ptr), value :: ctx
+       integer(c_int64_t), value :: nray
+       real(c_double), intent(in) :: origin(3, *), dir(3, *)
+       type(c_ptr), value :: tmax
+       integer(c_int64_t), intent(out) :: offset(*)
+       integer(c_int64_t), value :: capacity
+       type(c_ptr), value :: leaf, t_in, t_out
+     end function ftte_ray_segments_periodic
+
      integer(c_int) function ftte_compute_opacities(ctx, nnu, beta) bind(C, name='ftte_compute_opacities')
        import :: c_ptr, c_int, c_double
        type(c_ptr), value :: ctx

@@ -678,7 +678,8 @@ int ftte_sightline_spectra_device(ftte_ctx *ctx, int izone, int nxmap, int nymap
  * Refusals: those of ftte_sightline_spectra; FTTE_ERR_ARG for nray < 1, an origin, direction or tmax that is not finite, a
  * direction that is no unit vector; FTTE_ERR_UNSUPPORTED on a multi-device context or a tree deeper than 40 levels;
  * FTTE_ERR_INTERNAL where a walk took more than 3 n 2^maxlevel + 3 steps.  All decided, the leaves' line widths included, before
- * anything of the caller's is written: on a refusal the outputs are untouched.  No periodic wrap of a ray; a leaf has one velocity.
+ * anything of the caller's is written: on a refusal the outputs are untouched.  These three calls end a ray at the box's far side;
+ * their _periodic namesakes below wrap it through the opposite face.  A leaf has one velocity.
  * ftte_counter: "ray_chunk_segments" (records of a ray held in LDS at a time), "ray_work_bytes" (the budget of a batch). */
 int ftte_ray_spectra(ftte_ctx *ctx, int64_t nray, const double *origin, const double *dir, const double *tmax, int nvel, double v0,
                      double dv, double hubble, double period, const double line[4], const double *value, double *tau, double *summary);
@@ -691,6 +692,23 @@ int ftte_ray_spectra_device(ftte_ctx *ctx, int64_t nray, const double *origin, c
  * offset[nray] is FTTE_ERR_ARG with everything untouched. */
 int ftte_ray_segments(ftte_ctx *ctx, int64_t nray, const double *origin, const double *dir, const double *tmax, int64_t *offset,
                       int64_t capacity, int64_t *leaf, double *t_in, double *t_out);
+/* Periodic rays: the box tiles space with period n on every axis and a ray goes on through the box's opposite face (the statement is
+ * in csrc/ftte_ray_math.h).  The arguments are those of the namesakes above, except that tmax[nray] is required and every entry is
+ * the ray's length in base cells, finite and > 0: a periodic ray always hits, runs from t = 0 at its origin (any finite point, in
+ * the box or not) to t = tmax, and its segments tile [0, tmax].  t and s_l are measured from the caller's origin along the whole ray,
+ * across images, so the Hubble velocity keeps growing; `period` folds velocities as before, not positions.  A ray along +-e_a of
+ * length k n from a base cell's face gives the one-box list k times with t shifted by exactly j n; a ray that ends before its first
+ * wrap equals the non-periodic ray of that tmax bit for bit.  Refusals beyond the namesakes': FTTE_ERR_ARG for tmax == NULL or a
+ * tmax <= 0 (the message names the first such ray); FTTE_ERR_UNSUPPORTED for a tmax above 2^20 boxes, an origin more than 2^20
+ * boxes away or a step bound 3 (n 2^maxlevel) (ceil(tmax / n) + 1) + 3 beyond 2^62, the reason in the message. */
+int ftte_ray_spectra_periodic(ftte_ctx *ctx, int64_t nray, const double *origin, const double *dir, const double *tmax, int nvel, double v0,
+                              double dv, double hubble, double period, const double line[4], const double *value, double *tau,
+                              double *summary);
+int ftte_ray_spectra_periodic_device(ftte_ctx *ctx, int64_t nray, const double *origin, const double *dir, const double *tmax, int nvel,
+                                     double v0, double dv, double hubble, double period, const double line[4], const double *value_dev,
+                                     double *tau_dev, double *summary_dev);
+int ftte_ray_segments_periodic(ftte_ctx *ctx, int64_t nray, const double *origin, const double *dir, const double *tmax, int64_t *offset,
+                               int64_t capacity, int64_t *leaf, double *t_in, double *t_out);
 
 /* ---- host arrays ------------------------------------------------------------------------------
  * The reference keeps its fields in host memory (the zoneType tree, definitionsModule.f90:163-180); the drop-ins

@@ -130,6 +130,9 @@ SIGNATURES = {
     "ftte_ray_spectra": (C.c_int, [_vp, C.c_int64, _dp, _dp, _dp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _dp, _dp, _dp, _dp]),
     "ftte_ray_spectra_device": (C.c_int, [_vp, C.c_int64, _dp, _dp, _dp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _dp, _vp, _vp, _vp]),
     "ftte_ray_segments": (C.c_int, [_vp, C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64), _dp, _dp]),
+    "ftte_ray_spectra_periodic": (C.c_int, [_vp, C.c_int64, _dp, _dp, _dp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _dp, _dp, _dp, _dp]),
+    "ftte_ray_spectra_periodic_device": (C.c_int, [_vp, C.c_int64, _dp, _dp, _dp, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, _dp, _vp, _vp, _vp]),
+    "ftte_ray_segments_periodic": (C.c_int, [_vp, C.c_int64, _dp, _dp, _dp, C.POINTER(C.c_int64), C.c_int64, C.POINTER(C.c_int64), _dp, _dp]),
     "ftte_point_ray_steps": (C.c_longlong, [_vp]),
     "ftte_rmax": (C.c_int, [_dp]),
     "ftte_uvb_beta_table": (C.c_int, [C.c_int, C.c_double, _dp, _dp, _dp, _dp]),

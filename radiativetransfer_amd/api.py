@@ -996,10 +996,12 @@ class StellarTransfer(DiffuseTransfer):
 
     # -- the same along rays of any origin and direction (include/ftte.h, csrc/ftte_ray_math.h)
     @staticmethod
-    def _rays(origins, directions, tmax):
+    def _rays(origins, directions, tmax, periodic=False):
         o, d = _f64(origins).reshape(-1, 3), _f64(directions).reshape(-1, 3)
         if o.shape != d.shape:
             raise ValueError("origins and directions must both be [nray][3]")
+        if periodic and tmax is None:
+            raise ValueError("a periodic ray needs its tmax")
         if tmax is not None:
             tmax = _f64(tmax).reshape(-1)
             if tmax.size != o.shape[0]:
@@ -1008,14 +1010,17 @@ class StellarTransfer(DiffuseTransfer):
 
     def ray_spectra(self, origins, directions, nvel: int, v0: float, dv: float, line, tmax=None, hubble: float = 0.0, period: float = 0.0,
                     value=None, want_tau: bool = True, want_summary: bool = True, tau_device_ptr=None, summary_device_ptr=None,
-                    value_device_ptr=None) -> dict:
+                    value_device_ptr=None, periodic: bool = False) -> dict:
         """tau(v) of one line along rays through the refined grid: dict(tau [nray][nvel] (None unless want_tau), N, W, dv90 [nray]
         (None unless want_summary), velocity [nvel]).  origins, directions [nray][3] in the storage frame, base cells (the box is
         [0, n]^3), directions unit vectors; tmax [nray] the rays' ends from their origins (None or <= 0: the box's far side).  A ray
         that misses the box has N = 0 and tau = 0.  line, value, hubble, period as sightline_spectra.  With tau_device_ptr or
         summary_device_ptr the _device variant writes there ([nray][nvel] and [nray][3] doubles) and the dict holds None for what
-        went to the device."""
-        o, d, tmax = self._rays(origins, directions, tmax)
+        went to the device.  periodic: the box tiles space and every ray goes on through the opposite face from its origin (anywhere)
+        to its tmax, which is then required and > 0; s, and with it the Hubble velocity, keeps growing across images."""
+        o, d, tmax = self._rays(origins, directions, tmax, periodic)
+        host, device = (self._lib.ftte_ray_spectra_periodic, self._lib.ftte_ray_spectra_periodic_device) if periodic else \
+            (self._lib.ftte_ray_spectra, self._lib.ftte_ray_spectra_device)
         nray, nvel = o.shape[0], int(nvel)
         line = _f64(line).reshape(-1)
         if line.size != 4:
@@ -1027,8 +1032,8 @@ class StellarTransfer(DiffuseTransfer):
                 raise ValueError("the device variant takes value_device_ptr, not a host value array")
             if not tau_device_ptr and not summary_device_ptr:
                 raise ValueError("the device variant writes to tau_device_ptr or summary_device_ptr")
-            self._ok(self._lib.ftte_ray_spectra_device(*head, C.c_void_p(int(value_device_ptr or 0) or None), C.c_void_p(int(tau_device_ptr or 0) or None),
-                                                       C.c_void_p(int(summary_device_ptr or 0) or None)))
+            self._ok(device(*head, C.c_void_p(int(value_device_ptr or 0) or None), C.c_void_p(int(tau_device_ptr or 0) or None),
+                            C.c_void_p(int(summary_device_ptr or 0) or None)))
         else:
             if value is not None:
                 value = _f64(value).reshape(-1)
@@ -1036,26 +1041,26 @@ class StellarTransfer(DiffuseTransfer):
                     raise ValueError("value must have one entry per leaf")
             tau = np.empty((max(nray, 1), max(nvel, 1))) if want_tau else None
             summary = np.empty((max(nray, 1), 3)) if want_summary else None
-            self._ok(self._lib.ftte_ray_spectra(*head, None if value is None else _dp(value), None if tau is None else _dp(tau),
-                                                None if summary is None else _dp(summary)))
+            self._ok(host(*head, None if value is None else _dp(value), None if tau is None else _dp(tau), None if summary is None else _dp(summary)))
         out = dict(tau=tau, N=None, W=None, dv90=None, velocity=float(v0) + (np.arange(max(nvel, 0)) + 0.5) * float(dv))
         if summary is not None:
             out.update(N=summary[:, 0].copy(), W=summary[:, 1].copy(), dv90=summary[:, 2].copy())
         return out
 
-    def ray_segments(self, origins, directions, tmax=None) -> dict:
+    def ray_segments(self, origins, directions, tmax=None, periodic: bool = False) -> dict:
         """The leaves the rays cross, in their order: dict(offset [nray + 1], leaf, t_in, t_out per segment); ray r's segments are
-        offset[r] .. offset[r + 1] - 1, t in base cells from the ray's origin."""
-        o, d, tmax = self._rays(origins, directions, tmax)
+        offset[r] .. offset[r + 1] - 1, t in base cells from the ray's origin.  periodic: as ray_spectra; the segments tile [0, tmax]."""
+        o, d, tmax = self._rays(origins, directions, tmax, periodic)
+        segments = self._lib.ftte_ray_segments_periodic if periodic else self._lib.ftte_ray_segments
         nray = o.shape[0]
         lp = C.POINTER(C.c_int64)
         offset = np.zeros(max(nray, 1) + 1, dtype=np.int64)
         head = (self._ctx, nray, _dp(o), _dp(d), None if tmax is None else _dp(tmax), offset.ctypes.data_as(lp))
-        self._ok(self._lib.ftte_ray_segments(*head, 0, None, None, None))
+        self._ok(segments(*head, 0, None, None, None))
         total = int(offset[-1])
         leaf, t_in, t_out = np.zeros(total, dtype=np.int64), np.zeros(total), np.zeros(total)
         if total:
-            self._ok(self._lib.ftte_ray_segments(*head, total, leaf.ctypes.data_as(lp), _dp(t_in), _dp(t_out)))
+            self._ok(segments(*head, total, leaf.ctypes.data_as(lp), _dp(t_in), _dp(t_out)))
         return dict(offset=offset, leaf=leaf, t_in=t_in, t_out=t_out)
 
 

@@ -209,4 +209,118 @@ FTTE_HD int ray_cross(const ftte_ray *R, ftte_ray_walk *W, int n, double *t_in, 
 FTTE_HD double ray_segment_s(double t_in, double t_out) { return (t_in + t_out) * 0.5; }
 FTTE_HD double ray_segment_u(const ftte_ray *R, double vx, double vy, double vz) { return (R->dx * vx + R->dy * vy) + R->dz * vz; }
 
+/* ---- The periodic ray: the box tiles space with period n on every axis and the ray goes on through the opposite face.
+ *
+ * A periodic ray is an origin o (any finite point), the caller's unit vector d and a length tmax, finite and > 0: it always hits,
+ * t_start = 0 at the origin, t_end = tmax, and t is measured from the caller's origin along the whole ray, across images.
+ *
+ * Image and local origin: per axis an integer image w_a = floor(o_a / n), one lower where d_a < 0 and o_a == w_a n exactly (a
+ * coordinate on a face belongs to the side the ray moves to; with d_a == 0 the half-open cell holds), and the local origin
+ * o'_a = o_a - w_a n clamped into [0, n].  The walk runs in local coordinates with o' in the place of R->o: ray_locate, ray_exit,
+ * ray_far, the clamp of the transverse coordinates and the "chord <= 0 gives nothing" rule are used as they stand.
+ *
+ * The wrap: where the non-periodic walk leaves the box (the exit axis's far face is >= n or <= 0) the periodic one steps w_a by
+ * +-1, recomputes o'_a = o_a - w_a n from the caller's o_a and the integer image -- never from the previous o'_a, so nothing drifts
+ * however many boxes are crossed -- and puts the point on the exit axis on the opposite face, 0 for d_a > 0 and n for d_a < 0; the
+ * transverse coordinates are carried as in ray_cross.  The one-ulp disorder of t between two images of an axis is absorbed by the
+ * chord rule.  The segments tile [0, tmax] by construction.  Every step still crosses a leaf face forwards on its exit axis:
+ * ray_step_bound_periodic.
+ *
+ * What a segment gives the line is as above: s is the midpoint's distance from the caller's origin, so the Hubble velocity keeps
+ * growing across images (the line's period folds velocities, not positions).  For d = +-e_a, an origin on a base cell's face and
+ * dyadic transverse coordinates every t is exact: a ray of length k n gives the one-box list k times, t shifted by exactly j n. */
+#define FTTE_RAY_MAX_BOXES 0x1p20 /* tmax / n a periodic call may ask for */
+
+/* the caller's origin and the image the walk is in */
+typedef struct {
+    double cox, coy, coz;
+    int32_t wx, wy, wz; /* (inside +-(2^21 + 1): ray_periodic_refusal, ray_step_bound_periodic) */
+} ftte_ray_image;
+
+/* 3 (n 2^maxlevel) (ceil(tmax / n) + 1) + 3, or 0 where the tree is deeper than the walk goes, tmax / n is above 2^20 (or tmax
+ * is not > 0) or the product would leave 2^62 */
+FTTE_HD int64_t ray_step_bound_periodic(int n, int max_level, double tmax)
+{
+    if (max_level < 0 || max_level > FTTE_RAY_MAX_LEVEL || n < 1) return 0;
+    const double boxes = tmax / (double)n;
+    if (!(tmax > 0.0) || !(boxes <= FTTE_RAY_MAX_BOXES)) return 0;
+    const double images = __builtin_ceil(boxes) + 1.0, fine = (double)n * (double)((int64_t)1 << max_level);
+    if (!(3.0 * fine * images + 3.0 < 0x1p62)) return 0;
+    return 3 * ((int64_t)n << max_level) * (int64_t)images + 3;
+}
+
+/* What a periodic call refuses beyond ray_arguments_ok: 1 a tmax that is absent or not > 0; 2 an origin more than 2^20 boxes from
+ * the box on an axis (the image counters and w_a n stay exact integers far inside 2^53).  0: a good ray. */
+FTTE_HD int ray_periodic_refusal(const double *o, const double *tmax, int n)
+{
+    if (!tmax || !(*tmax > 0.0)) return 1;
+    const double far = FTTE_RAY_MAX_BOXES * (double)n;
+    if (!(o[0] >= -far && o[0] <= far && o[1] >= -far && o[1] <= far && o[2] >= -far && o[2] <= far)) return 2;
+    return 0;
+}
+
+/* one axis of the image and of the local origin */
+FTTE_HD double ray_image_axis(double o, double d, double dn, int32_t *w)
+{
+    double fl = __builtin_floor(o / dn);
+    if (d < 0.0 && o == fl * dn) fl = fl - 1.0;
+    *w = (int32_t)fl;
+    return ray_clamp(o - fl * dn, 0.0, dn);
+}
+
+/* The periodic ray and the point its walk starts from: its origin, in the image that holds it. */
+FTTE_HD void ray_begin_periodic(ftte_ray *R, ftte_ray_walk *W, ftte_ray_image *I, int n, const double *o, const double *d, double tmax)
+{
+    const double dn = (double)n;
+    I->cox = o[0]; I->coy = o[1]; I->coz = o[2];
+    R->dx = d[0]; R->dy = d[1]; R->dz = d[2];
+    R->ix = d[0] != 0.0 ? 1.0 / d[0] : 0.0;
+    R->iy = d[1] != 0.0 ? 1.0 / d[1] : 0.0;
+    R->iz = d[2] != 0.0 ? 1.0 / d[2] : 0.0;
+    R->ox = ray_image_axis(o[0], d[0], dn, &I->wx);
+    R->oy = ray_image_axis(o[1], d[1], dn, &I->wy);
+    R->oz = ray_image_axis(o[2], d[2], dn, &I->wz);
+    R->t_start = 0.0;
+    R->t_end = tmax;
+    R->hit = tmax > 0.0 && (R->dx != 0.0 || R->dy != 0.0 || R->dz != 0.0);
+    W->t = 0.0; W->px = R->ox; W->py = R->oy; W->pz = R->oz;
+    W->lox = W->loy = W->loz = 0.0; W->h = 1.0;
+    W->leaf = -1;
+    W->done = !R->hit;
+}
+
+/* ray_cross with the wrap: through the leaf found, its segment where the return is 1, and on to the point the next leaf is found
+ * from -- across the box's face that is the opposite face of the next image -- or W->done at tmax. */
+FTTE_HD int ray_cross_periodic(ftte_ray *R, ftte_ray_walk *W, ftte_ray_image *I, int n, double *t_in, double *t_out)
+{
+    const double h = W->h, dn = (double)n;
+    int axis;
+    const double t = ray_exit(R, W, &axis);
+    const double cut = t < R->t_end ? t : R->t_end;
+    const int some = cut - W->t > 0.0;
+    if (some) { *t_in = W->t; *t_out = cut; W->t = cut; }
+    if (!(t < R->t_end)) { W->done = 1; return some; }
+    /* (values first, then the selects, as in ray_cross) */
+    const double farx = ray_far(W->lox, h, R->dx), fary = ray_far(W->loy, h, R->dy), farz = ray_far(W->loz, h, R->dz);
+    const double far = axis == 0 ? farx : axis == 1 ? fary : farz, d = axis == 0 ? R->dx : axis == 1 ? R->dy : R->dz;
+    const int wrap = d > 0.0 ? far >= dn : far <= 0.0;
+    const double px = ray_clamp(R->ox + t * R->dx, W->lox, W->lox + h);
+    const double py = ray_clamp(R->oy + t * R->dy, W->loy, W->loy + h);
+    const double pz = ray_clamp(R->oz + t * R->dz, W->loz, W->loz + h);
+    const double face = !wrap ? far : d > 0.0 ? 0.0 : dn;
+    const int32_t step = !wrap ? 0 : d > 0.0 ? 1 : -1;
+    I->wx = axis == 0 ? I->wx + step : I->wx;
+    I->wy = axis == 1 ? I->wy + step : I->wy;
+    I->wz = axis == 2 ? I->wz + step : I->wz;
+    /* the exit axis's local origin from the caller's origin and the integer image */
+    const double ox = I->cox - (double)I->wx * dn, oy = I->coy - (double)I->wy * dn, oz = I->coz - (double)I->wz * dn;
+    R->ox = wrap && axis == 0 ? ox : R->ox;
+    R->oy = wrap && axis == 1 ? oy : R->oy;
+    R->oz = wrap && axis == 2 ? oz : R->oz;
+    W->px = axis == 0 ? face : px;
+    W->py = axis == 1 ? face : py;
+    W->pz = axis == 2 ? face : pz;
+    return some;
+}
+
 #endif /* FTTE_RAY_MATH_H */

@@ -14,6 +14,7 @@ struct RayCall {
     const char *who;
     int64_t nray;
     const double *origin, *dir, *tmax; // host arrays
+    bool periodic;                     // the rays go on through the box's opposite face up to tmax
     // the spectra
     bool spectra;
     int nvel;
@@ -57,12 +58,27 @@ int run_rays(ftte_ctx *c, const RayCall &M)
     for (int64_t r = 0; r < M.nray; ++r)
         if (!ray_arguments_ok(M.origin + 3 * r, M.dir + 3 * r, M.tmax ? M.tmax + r : nullptr))
             return fail(c, FTTE_ERR_ARG, who + "ray " + std::to_string(r) + ": origin, direction and tmax must be finite and | |dir|^2 - 1 | <= 1e-9");
+    double longest = 0.0;
+    if (M.periodic) {
+        if (!M.tmax) return fail(c, FTTE_ERR_ARG, who + "ray 0: a periodic ray needs its tmax");
+        for (int64_t r = 0; r < M.nray; ++r) {
+            const int refusal = ray_periodic_refusal(M.origin + 3 * r, M.tmax + r, c->n);
+            if (refusal == 1) return fail(c, FTTE_ERR_ARG, who + "ray " + std::to_string(r) + ": the tmax of a periodic ray must be greater than 0");
+            if (refusal) return fail(c, FTTE_ERR_UNSUPPORTED, who + "ray " + std::to_string(r) + ": origin more than 2^20 boxes away");
+            if (M.tmax[r] > longest) longest = M.tmax[r];
+        }
+    }
     if (M.spectra) {
         if (!c->gas.ready(c->ncell)) return fail(c, FTTE_ERR_STATE, who + "no medium: call ftte_set_medium first");
         if (!c->chem.temperature_set) return fail(c, FTTE_ERR_STATE, who + "no temperature (ftte_set_temperature)");
     }
-    R.max_steps = ray_step_bound(c->n, c->tree.max_level);
-    if (R.max_steps < 1) return fail(c, FTTE_ERR_UNSUPPORTED, who + "tree deeper than 40 levels");
+    R.max_steps = M.periodic ? ray_step_bound_periodic(c->n, c->tree.max_level, longest) : ray_step_bound(c->n, c->tree.max_level);
+    if (R.max_steps < 1) {
+        if (c->tree.max_level > FTTE_RAY_MAX_LEVEL || !M.periodic) return fail(c, FTTE_ERR_UNSUPPORTED, who + "tree deeper than 40 levels");
+        if (longest / (double)c->n > FTTE_RAY_MAX_BOXES) return fail(c, FTTE_ERR_UNSUPPORTED, who + "a periodic ray longer than 2^20 boxes");
+        return fail(c, FTTE_ERR_UNSUPPORTED, who + "the step bound of the longest periodic ray is beyond 2^62");
+    }
+    R.periodic = M.periodic ? 1 : 0;
 
     FTTE_HIP(c, hipSetDevice(c->device));
     if ((rc = wait_sweep(c))) return rc;
@@ -170,16 +186,26 @@ int run_rays(ftte_ctx *c, const RayCall &M)
     return FTTE_OK;
 }
 
-RayCall spectra_call(const char *who, int64_t nray, const double *origin, const double *dir, const double *tmax, int nvel, double v0, double dv, double hubble,
-                     double period, const double *line, const double *value, bool on_device, double *tau, double *summary)
+RayCall spectra_call(const char *who, bool periodic, int64_t nray, const double *origin, const double *dir, const double *tmax, int nvel, double v0, double dv,
+                     double hubble, double period, const double *line, const double *value, bool on_device, double *tau, double *summary)
 {
     RayCall M;
     std::memset(&M, 0, sizeof M);
-    M.who = who; M.nray = nray; M.origin = origin; M.dir = dir; M.tmax = tmax;
+    M.who = who; M.nray = nray; M.origin = origin; M.dir = dir; M.tmax = tmax; M.periodic = periodic;
     M.spectra = true;
     M.nvel = nvel; M.v0 = v0; M.dv = dv; M.hubble = hubble; M.period = period; M.line = line; M.value = value;
     M.on_device = on_device; M.tau = tau; M.summary = summary;
     return M;
+}
+
+int segments_call(ftte_ctx *c, const char *who, bool periodic, int64_t nray, const double *origin, const double *dir, const double *tmax, int64_t *offset,
+                  int64_t capacity, int64_t *leaf, double *t_in, double *t_out)
+{
+    RayCall M;
+    std::memset(&M, 0, sizeof M);
+    M.who = who; M.nray = nray; M.origin = origin; M.dir = dir; M.tmax = tmax; M.periodic = periodic;
+    M.offset = offset; M.capacity = capacity; M.leaf = leaf; M.t_in = t_in; M.t_out = t_out;
+    return run_rays(c, M);
 }
 
 } // namespace
@@ -189,23 +215,38 @@ extern "C" {
 int ftte_ray_spectra(ftte_ctx *c, int64_t nray, const double *origin, const double *dir, const double *tmax, int nvel, double v0, double dv, double hubble,
                      double period, const double *line, const double *value, double *tau, double *summary)
 {
-    return run_rays(c, spectra_call("ftte_ray_spectra", nray, origin, dir, tmax, nvel, v0, dv, hubble, period, line, value, false, tau, summary));
+    return run_rays(c, spectra_call("ftte_ray_spectra", false, nray, origin, dir, tmax, nvel, v0, dv, hubble, period, line, value, false, tau, summary));
+}
+
+int ftte_ray_spectra_periodic(ftte_ctx *c, int64_t nray, const double *origin, const double *dir, const double *tmax, int nvel, double v0, double dv, double hubble,
+                              double period, const double *line, const double *value, double *tau, double *summary)
+{
+    return run_rays(c, spectra_call("ftte_ray_spectra_periodic", true, nray, origin, dir, tmax, nvel, v0, dv, hubble, period, line, value, false, tau, summary));
 }
 
 int ftte_ray_spectra_device(ftte_ctx *c, int64_t nray, const double *origin, const double *dir, const double *tmax, int nvel, double v0, double dv,
                             double hubble, double period, const double *line, const double *value_dev, double *tau_dev, double *summary_dev)
 {
-    return run_rays(c, spectra_call("ftte_ray_spectra_device", nray, origin, dir, tmax, nvel, v0, dv, hubble, period, line, value_dev, true, tau_dev, summary_dev));
+    return run_rays(c, spectra_call("ftte_ray_spectra_device", false, nray, origin, dir, tmax, nvel, v0, dv, hubble, period, line, value_dev, true, tau_dev, summary_dev));
+}
+
+int ftte_ray_spectra_periodic_device(ftte_ctx *c, int64_t nray, const double *origin, const double *dir, const double *tmax, int nvel, double v0, double dv,
+                                     double hubble, double period, const double *line, const double *value_dev, double *tau_dev, double *summary_dev)
+{
+    return run_rays(c, spectra_call("ftte_ray_spectra_periodic_device", true, nray, origin, dir, tmax, nvel, v0, dv, hubble, period, line, value_dev, true, tau_dev,
+                                    summary_dev));
 }
 
 int ftte_ray_segments(ftte_ctx *c, int64_t nray, const double *origin, const double *dir, const double *tmax, int64_t *offset, int64_t capacity, int64_t *leaf,
                       double *t_in, double *t_out)
 {
-    RayCall M;
-    std::memset(&M, 0, sizeof M);
-    M.who = "ftte_ray_segments"; M.nray = nray; M.origin = origin; M.dir = dir; M.tmax = tmax;
-    M.offset = offset; M.capacity = capacity; M.leaf = leaf; M.t_in = t_in; M.t_out = t_out;
-    return run_rays(c, M);
+    return segments_call(c, "ftte_ray_segments", false, nray, origin, dir, tmax, offset, capacity, leaf, t_in, t_out);
+}
+
+int ftte_ray_segments_periodic(ftte_ctx *c, int64_t nray, const double *origin, const double *dir, const double *tmax, int64_t *offset, int64_t capacity,
+                               int64_t *leaf, double *t_in, double *t_out)
+{
+    return segments_call(c, "ftte_ray_segments_periodic", true, nray, origin, dir, tmax, offset, capacity, leaf, t_in, t_out);
 }
 
 } // extern "C"

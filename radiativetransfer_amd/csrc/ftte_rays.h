@@ -24,7 +24,7 @@ struct RayRec {
     const double *origin, *dir, *tmax;  // [nray][3], [nray][3], [nray] or nullptr
     int64_t nray;
     int32_t n;
-    int64_t max_steps;                  // ray_step_bound
+    int64_t max_steps;                  // ray_step_bound, or ray_step_bound_periodic of the longest ray
     const double *value, *tgas;         // [ncell], or both nullptr (ftte_ray_segments: the geometry alone)
     const double *velx, *vely, *velz;   // [ncell] each, or nullptr: zero
     double cell_cm;
@@ -44,6 +44,7 @@ struct RayRec {
     double *t_in, *t_out;
     double *tau;                        // [nrays][nvel], ray0's first
     double *summary;                    // [nrays][3] or nullptr
+    int32_t periodic;                   // the walk wraps through the box's opposite face up to tmax (which is then required)
 };
 
 // Rays per launch from ray0 on so that what the batch keeps stays under kSpectraWorkBytes: per_segment bytes for every segment of

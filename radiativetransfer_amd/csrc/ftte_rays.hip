@@ -1,6 +1,7 @@
 // ftte_rays.hip -- the kernels behind ftte_rays.cpp: absorption spectra along oblique rays through the refined grid.
 //
-// ray_walk_kernel, one lane per ray, is the walk of ftte_ray_math.h in two modes from one source:
+// ray_walk_kernel, one lane per ray, is the walk of ftte_ray_math.h in two modes from one source, each of them also periodic (a
+// template parameter, no run-time branch: the walk goes on through the box's opposite face up to the ray's tmax):
 //   count  per ray its segments and its column density N = sum n size in ray order, whether a leaf has no line width, whether the
 //          walk passed its step bound; across rays integer atomicOr / atomicMax only.  Nothing of the caller's is written before
 //          the host has read these;
@@ -19,7 +20,7 @@ namespace ftte {
 
 namespace {
 
-template <bool Fill> __global__ void __launch_bounds__(256) ray_walk_kernel(const RayRec Q)
+template <bool Fill, bool Periodic> __global__ void __launch_bounds__(256) ray_walk_kernel(const RayRec Q)
 {
     __shared__ int s_flags, s_most;
     if (!Fill) {
@@ -31,7 +32,9 @@ template <bool Fill> __global__ void __launch_bounds__(256) ray_walk_kernel(cons
     if (Fill ? lane < Q.nrays : lane < Q.nray) {
         ftte_ray R;
         ftte_ray_walk W;
-        ray_begin(&R, &W, Q.n, Q.origin + 3 * ray, Q.dir + 3 * ray, Q.tmax ? Q.tmax[ray] : 0.0);
+        ftte_ray_image I; // (the periodic modes alone: three image counters and the caller's origin)
+        if (Periodic) ray_begin_periodic(&R, &W, &I, Q.n, Q.origin + 3 * ray, Q.dir + 3 * ray, Q.tmax[ray]);
+        else ray_begin(&R, &W, Q.n, Q.origin + 3 * ray, Q.dir + 3 * ray, Q.tmax ? Q.tmax[ray] : 0.0);
         const ftte_ray_node *const node = reinterpret_cast<const ftte_ray_node *>(Q.node);
         const int32_t room = Fill ? Q.nseg[ray] : 0; // (the count pass walked the same ray)
         const int64_t at0 = Fill ? Q.offset[ray] - Q.offset[Q.ray0] : 0;
@@ -42,7 +45,7 @@ template <bool Fill> __global__ void __launch_bounds__(256) ray_walk_kernel(cons
         while (!W.done) {
             if (++steps > Q.max_steps || !ray_locate(&R, &W, Q.n, node)) { flags |= 2; break; }
             double t_in, t_out;
-            if (!ray_cross(&R, &W, Q.n, &t_in, &t_out)) continue;
+            if (!(Periodic ? ray_cross_periodic(&R, &W, &I, Q.n, &t_in, &t_out) : ray_cross(&R, &W, Q.n, &t_in, &t_out))) continue;
             const int64_t cell = W.leaf;
             if (Q.value) {
                 const double tgas = Q.tgas[cell];
@@ -166,7 +169,7 @@ __global__ void __launch_bounds__(kSpectraLanes) ray_spectra_kernel(const RayRec
 bool rays_ok(const RayRec &Q)
 {
     return Q.n >= 1 && Q.nray >= 1 && Q.origin && Q.dir && Q.max_steps >= 1 && Q.nseg && Q.column && (!Q.value == !Q.tgas) &&
-           (!Q.velx == !Q.vely) && (!Q.velx == !Q.velz);
+           (!Q.velx == !Q.vely) && (!Q.velx == !Q.velz) && (!Q.periodic || Q.tmax);
 }
 
 bool batch_ok(const RayRec &Q) { return Q.offset && Q.ray0 >= 0 && Q.nrays >= 1 && Q.ray0 + Q.nrays <= Q.nray; }
@@ -181,8 +184,11 @@ int launch_ray_walk(const RayRec &Q, bool fill, void *stream)
     } else if (!Q.flags) return -1;
     const int64_t groups = ((fill ? (int64_t)Q.nrays : Q.nray) + 255) / 256;
     if (groups > 0x7fffffff) return -1;
-    if (fill) hipLaunchKernelGGL(ray_walk_kernel<true>, dim3((unsigned)groups), dim3(256), 0, (hipStream_t)stream, Q);
-    else hipLaunchKernelGGL(ray_walk_kernel<false>, dim3((unsigned)groups), dim3(256), 0, (hipStream_t)stream, Q);
+    const dim3 grid((unsigned)groups), block(256);
+    if (fill && Q.periodic) hipLaunchKernelGGL((ray_walk_kernel<true, true>), grid, block, 0, (hipStream_t)stream, Q);
+    else if (fill) hipLaunchKernelGGL((ray_walk_kernel<true, false>), grid, block, 0, (hipStream_t)stream, Q);
+    else if (Q.periodic) hipLaunchKernelGGL((ray_walk_kernel<false, true>), grid, block, 0, (hipStream_t)stream, Q);
+    else hipLaunchKernelGGL((ray_walk_kernel<false, false>), grid, block, 0, (hipStream_t)stream, Q);
     return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 

@@ -3,12 +3,14 @@
 velocity field plus a Hubble flow), HI Lyman alpha, 1024 pixels, tau and the summaries kept on the device:
   (a) the N^2 axis-aligned rays that coincide with izone 1's pixel columns, next to ftte_sightline_spectra over the same columns in
       the same process (the yardstick), and whether the two gave the same bits;
-  (b) 65 536 rays of random direction through random points of the box, from where they enter it to where they leave.
+  (b) 65 536 rays of random direction through random points of the box, from where they enter it to where they leave;
+  (c) the rays of (b) continued periodically from their origins to a fixed length of 4 boxes (--boxes), with the time per segment
+      beside (b)'s from the same process.
 Each call is timed with HIP events on the default stream around it (the library's stream is a blocking one), median of `reps`
 after a warm-up; the offsets-only call of ray_segments (the count launch, the read-back of the counts and the host's prefix sum)
 by the wall clock.  Prints one JSON line; --out FILE writes it.  The kernels alone, and the share of the two walk launches: run it
 under `rocprofv3 --kernel-trace --stats` with reps 1.
-usage: bench_ray_spectra.py N reps [--nvel V] [--rays R] [--out FILE]"""
+usage: bench_ray_spectra.py N reps [--nvel V] [--rays R] [--boxes B] [--out FILE]"""
 import ctypes as C
 import json
 import os
@@ -30,7 +32,7 @@ def option(name, default):
 
 
 n, reps = int(sys.argv[1]), int(sys.argv[2])
-nvel, nrandom, out_path = option("--nvel", 1024), option("--rays", 65536), option("--out", "")
+nvel, nrandom, out_path, boxes = option("--nvel", 1024), option("--rays", 65536), option("--out", ""), option("--boxes", 4.0)
 MSUN, PC = float(np.float32(1.98892e33)), float(np.float32(3.08568025e18))
 
 
@@ -107,6 +109,20 @@ with rt.StellarTransfer() as st:
     r["axis_pairs"], r["random_pairs"] = n * n * n * nvel, int(counts.sum()) * nvel
     s = summary_r.cpu().numpy()
     r["random_mean_W_cm_s"], r["random_mean_dv90_cm_s"] = float(s[:, 1].mean()), float(s[:, 2].mean())
+    # (c) the same rays, periodic: the counts from the offsets-only call (the lists themselves would be gigabytes)
+    length = np.full(nrandom, boxes * n)
+    r["periodic_boxes"] = boxes
+    r["periodic_ray_spectra_ms"] = median_ms(lambda: st.ray_spectra(rand_o, rand_d, nvel, v0, dv, rt.LYMAN_ALPHA, length, hubble=hubble, periodic=True,
+                                                                    tau_device_ptr=tau_r.data_ptr(), summary_device_ptr=summary_r.data_ptr()))
+    offsets = np.zeros(nrandom + 1, dtype=np.int64)
+    st._ok(st._lib.ftte_ray_segments_periodic(st._ctx, nrandom, rand_o.ctypes.data_as(dp), rand_d.ctypes.data_as(dp), length.ctypes.data_as(dp),
+                                              offsets.ctypes.data_as(C.POINTER(C.c_int64)), 0, None, None, None))
+    counts = np.diff(offsets)
+    r["periodic_segments"], r["periodic_most_segments"], r["periodic_pairs"] = int(counts.sum()), int(counts.max()), int(counts.sum()) * nvel
+    r["random_ns_per_segment"] = 1e6 * r["random_ray_spectra_ms"] / r["random_segments"]
+    r["periodic_ns_per_segment"] = 1e6 * r["periodic_ray_spectra_ms"] / r["periodic_segments"]
+    s = summary_r.cpu().numpy()
+    r["periodic_mean_W_cm_s"], r["periodic_mean_dv90_cm_s"] = float(s[:, 1].mean()), float(s[:, 2].mean())
 print(json.dumps(r), flush=True)
 if out_path:
     with open(out_path, "w") as f:
